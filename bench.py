@@ -14,15 +14,19 @@ compiled reference), i.e. synthetic data.
 N>1: BASELINE.json configs[3] -- the same scene and camera at 3840x2160 for EVERY N > 1, rows
 dealt cyclically to the ranks like the reference's MPI_ROW mode (ndt.c:812-820), one RCCL
 gather over xGMI assembling the final 8-bit image on rank 0 (--gather f64: the double
-framebuffer): total work is fixed as N grows, "scaling": "strong"; rank 0 also times the whole
-3840x2160 frame on its one GPU after the run (`strong_reference`), the time the N-GPU frame is
-to be compared with.  `--scaling weak` keeps per-GPU work fixed instead (N x 1080p pixels).
+framebuffer): total work is fixed as N grows, "scaling": "strong"; with --full rank 0 also times
+the whole 3840x2160 frame on its one GPU after the run (`strong_reference`), the time the N-GPU
+frame is to be compared with.  `--scaling weak` keeps per-GPU work fixed instead (N x 1080p pixels).
 
 `value` counts rays ACTUALLY traced on the GPUs (one trace_kd query each).  The reference
 re-traces every pixel's identical ray tree k = 3..18 times (adaptive loop, ndt.c:488; SURVEY
 8a row A3); the GPU path traces it once and replays the loop's arithmetic, so the
 reference-equivalent rate (what the CPU baseline's rays/time means) is reported separately as
 `mray_s_ref_equiv`, never as `value`.
+
+A plain run sets up, warms up, times the steps and prints the line.  `--full` adds what the headline does not
+need: the CPU baseline (N=1), the host-memory and two-frames-in-flight timings (N=1) and the one-GPU time of the
+same frame (N>1, strong).  `--dump-outputs DIR` writes what the last timed step computed as DIR/<name>.npy.
 """
 import argparse
 import ctypes as C
@@ -63,6 +67,27 @@ def frame_size(n_gpus, scaling="strong"):
     w = int(round(1920 * s / 8.0)) * 8
     h = int(round(1080 * s / 8.0)) * 8
     return w, h
+
+
+DUMP_BYTES = 60 * 10 ** 6     # --dump-outputs: what one run writes stays under 64 MB
+DUMP_SEED = 0
+
+
+def dump_outputs(out_dir, frame, st):
+    """--dump-outputs: the last timed step's image (height x width x 4) as float32 and its ray counts as float64.  An image
+    larger than DUMP_BYTES at float32 is written as a fixed sample of whole rows (seed DUMP_SEED), the row numbers beside it."""
+    os.makedirs(out_dir, exist_ok=True)
+    frame = np.asarray(frame, dtype=np.float32)
+    row_bytes = frame[0].nbytes
+    if frame.nbytes > DUMP_BYTES:
+        n = DUMP_BYTES // (row_bytes + 8)
+        rows = np.sort(np.random.default_rng(DUMP_SEED).choice(frame.shape[0], n, replace=False))
+        np.save(os.path.join(out_dir, "frame_rows.npy"), rows.astype(np.float64))
+        np.save(os.path.join(out_dir, "frame_sample.npy"), np.ascontiguousarray(frame[rows]))
+    else:
+        np.save(os.path.join(out_dir, "frame.npy"), frame)
+    counts = [st.rays_primary, st.rays_secondary, st.rays_shadow, st.rays_ref_equiv, st.levels]
+    np.save(os.path.join(out_dir, "ray_counts.npy"), np.array(counts, dtype=np.float64))
 
 
 def algorithmic_bytes_per_ray(dims):
@@ -169,7 +194,15 @@ def main():
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
                     help="nccl = RCCL over xGMI (the real thing); gloo = rehearsal of the N>1 code path on a "
                          "one-GPU box (all ranks share device 0, shards staged through host memory)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: the CPU baseline and the host-memory / two-frames-in-"
+                         "flight timings (N=1), the one-GPU time of the same frame (N>1, strong)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write the last step's image (float32; a fixed sample of its rows when it "
+                         "would exceed 60 MB) and ray counts (float64) as DIR/<name>.npy (rank 0)")
     args = ap.parse_args()
+    if args.dump_outputs and args.steps < 1:
+        ap.error("--dump-outputs writes what the last timed step computed: it needs --steps >= 1")
 
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -277,6 +310,7 @@ def main():
             g.start()
             state["pending"] = g
             state["pending_buf"] = b
+        state["st"] = st
         return st
 
     def fence():
@@ -320,6 +354,15 @@ def main():
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
     total_traced, total_ref = counts.tolist()
     elapsed = float(tmax.item())
+
+    if args.dump_outputs and rank == 0:
+        # what a caller of the timed path receives: the gathered image on rank 0 (N>1 or --selftest-gather), else the
+        # double framebuffer the last step rendered into
+        if multi:
+            last = gath[(state["k"] - 1) % n_buf].image
+        else:
+            last = frames64[(state["k"] - 1) % len(frames64)][:height]
+        dump_outputs(args.dump_outputs, last.cpu().numpy(), state["st"])
 
     if rank == 0:
         steps = max(1, args.steps)
@@ -403,7 +446,7 @@ def main():
             "device_frame_ms_rank0": agg["frame_ms"] / max(1, agg["profiled_steps"]),
             "roofline": roofline,
         }
-        if world == 1:
+        if args.full and world == 1:
             # what a caller of ndt_hip_render_rgba8 waits for: render + pixel_d2c on the device + the 4-bytes-per-pixel
             # copy to host memory (the reference's "rendering took" ends with the pixels in host memory)
             gpu.render_rgba8(width, height, depth)
@@ -449,7 +492,7 @@ def main():
             line["ms_per_step_two_frames_in_flight"] = (time.perf_counter() - t1) / 20 * 1e3
             line["two_frames_in_flight_identical"] = bool(torch.equal(pair[0][1], pair[1][1]))
             second.close()
-        elif args.scaling == "strong" and not rehearsal:
+        elif args.full and args.scaling == "strong" and not rehearsal:
             # the time this frame takes on ONE GPU (rank 0's, alone: the other ranks wait at the barrier below)
             whole = torch.zeros((height, width, 4), dtype=torch.float64, device="cuda")
             torch.cuda.synchronize()
@@ -463,7 +506,7 @@ def main():
                                         "what": "the whole %dx%d frame rendered on rank 0's GPU alone (image left in HBM), "
                                                 "5 frames after the timed region" % (width, height)}
             del whole
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(args.workload, width, height, depth, args.cpu_threads)
             line["cpu_baseline_t1"] = cpu_baseline(args.workload, width, height, depth, 1)
         print(json.dumps(line), flush=True)

@@ -5,7 +5,7 @@ for w in random4d balls4d hypercube3d hypercube6d hypercube8d; do
   for pl in levels hybrid; do
     for H in 1 2; do
       [ $pl = levels ] && [ $H = 2 ] && continue
-      NDT_HIP_PIPELINE=$pl NDT_HIP_HYBRID_LEVEL=$H timeout -k 10 200 python bench.py --no-cpu-baseline --workload $w --steps 30 --warmup 3 > $O/bench_${w}_${pl}$H.log 2>&1 || { tail -3 $O/bench_${w}_${pl}$H.log; exit 1; }
+      NDT_HIP_PIPELINE=$pl NDT_HIP_HYBRID_LEVEL=$H timeout -k 10 200 python bench.py --full --no-cpu-baseline --workload $w --steps 30 --warmup 3 > $O/bench_${w}_${pl}$H.log 2>&1 || { tail -3 $O/bench_${w}_${pl}$H.log; exit 1; }
       python - <<PY
 import json
 d = json.loads([l for l in open("$O/bench_${w}_${pl}$H.log") if l.startswith("{")][0])

@@ -9,8 +9,8 @@ rc=$?
 tail -25 $O/tests.log
 [ $rc -ne 0 ] && exit 1
 for w in random4d balls4d hypercube3d hypercube6d hypercube8d; do
-  timeout -k 10 200 python bench.py --no-cpu-baseline --workload $w --steps 20 --warmup 3 > $O/bench_stream_$w.log 2>&1 || { tail -5 $O/bench_stream_$w.log; exit 1; }
-  NDT_HIP_PIPELINE=levels timeout -k 10 200 python bench.py --no-cpu-baseline --workload $w --steps 20 --warmup 3 > $O/bench_levels_$w.log 2>&1 || exit 1
+  timeout -k 10 200 python bench.py --full --no-cpu-baseline --workload $w --steps 20 --warmup 3 > $O/bench_stream_$w.log 2>&1 || { tail -5 $O/bench_stream_$w.log; exit 1; }
+  NDT_HIP_PIPELINE=levels timeout -k 10 200 python bench.py --full --no-cpu-baseline --workload $w --steps 20 --warmup 3 > $O/bench_levels_$w.log 2>&1 || exit 1
   python - <<PY
 import json
 for k in ("stream", "levels"):

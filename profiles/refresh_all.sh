@@ -35,7 +35,7 @@ fi
 for w in hypercube6d hypercube7d hypercube8d; do
   bash profiles/profile_workload.sh $w || exit 1
 done
-timeout -k 10 300 python bench.py --steps 20 --warmup 3 > $O/bench_default.log 2>&1 || exit 1
+timeout -k 10 300 python bench.py --full --steps 20 --warmup 3 > $O/bench_default.log 2>&1 || exit 1
 grep '^{' $O/bench_default.log > profiles/r04_bench_default.json.log
 for w in balls4d hypercube3d hypercube6d hypercube7d hypercube8d; do
   NDT_HIP_PIPELINE=stream timeout -k 10 200 python bench.py --no-cpu-baseline --workload $w --steps 20 --warmup 3 2>/dev/null | grep '^{' > profiles/r04_bench_stream_$w.json.log

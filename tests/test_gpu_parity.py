@@ -871,13 +871,13 @@ def test_frames_in_sequence_leave_nothing_behind(gpu, oracle):
 
 @pytest.mark.gpu
 def test_bench_line_contract():
-    """bench.py prints ONE JSON line with the fields the driver reads, the roofline object and (N=1) the CPU baseline."""
+    """bench.py --full prints ONE JSON line with the fields the driver reads, the roofline object and (N=1) the CPU baseline."""
     import json
     import subprocess
     import sys
     from conftest import ROOT
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
-           "--workload", "hypercube3d"]
+           "--workload", "hypercube3d", "--full"]
     out = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
@@ -902,6 +902,46 @@ def test_bench_line_contract():
     assert d["ms_per_step_host_rgba8"] > 0 and d["ms_per_step_host_rgba8_pipelined"] > 0       # (timings of three steps: no relation asserted)
     assert d["host_rgba8_pipelined_bytes_identical"] is True
     assert d["ms_per_step_two_frames_in_flight"] > 0 and d["two_frames_in_flight_identical"] is True
+
+
+@pytest.mark.gpu
+def test_bench_plain_line_and_dumped_outputs(tmp_path):
+    """A plain bench.py run (no --full) prints the headline line without the extras, and --dump-outputs writes what its
+    last timed step computed: the double framebuffer as float32 (the image the library renders for that frame) and the
+    step's ray counts (the line's per-step counts)."""
+    import json
+    import subprocess
+    import sys
+    from conftest import ROOT
+    from ndt_amd.hip import NdtHip
+    dump = tmp_path / "outputs"
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
+           "--workload", "hypercube3d", "--dump-outputs", str(dump)]
+    out = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    assert d["steps"] == 2 and d["warmup"] == 1 and d["ms_per_step"] > 0 and d["value"] > 0
+    assert d["unit"] == "Mray/s" and d["higher_is_better"] is True and d["dtype"] == "f64"
+    for key in ("cpu_baseline", "cpu_baseline_t1", "ms_per_step_host_rgba8", "ms_per_step_two_frames_in_flight"):
+        assert key not in d, key
+    files = sorted(p.name for p in dump.iterdir())
+    assert files == ["frame.npy", "ray_counts.npy"]
+    assert sum(p.stat().st_size for p in dump.iterdir()) <= 64 * 10 ** 6
+    frame, counts = np.load(dump / "frame.npy"), np.load(dump / "ray_counts.npy")
+    assert frame.dtype == np.float32 and frame.shape == (1080, 1920, 4)
+    assert counts.dtype == np.float64 and counts[0] + counts[1] + counts[2] == d["rays_traced_per_step"]
+    assert counts[3] == d["rays_ref_equiv_per_step"]
+    g = golden("c1_hypercube3d")
+    ctx = NdtHip(0)
+    try:
+        ctx.upload_scene(g.scene)
+        want, st = ctx.render(1920, 1080, 128)
+    finally:
+        ctx.close()
+    assert np.array_equal(frame, want.astype(np.float32))
+    assert list(counts) == [st.rays_primary, st.rays_secondary, st.rays_shadow, st.rays_ref_equiv, st.levels]
 
 
 @pytest.mark.gpu
