@@ -33,7 +33,8 @@ extern "C" {
  * (ndt.c:1450 `-d`); BASELINE.json's configs span 3..8. */
 #define NDT_MIN_DIMS 3
 #define NDT_MAX_DIMS 12
-#define NDT_MAX_LIGHTS 64
+/* Lights of a scene.  The lighting kernels take them in windows of at most 64 (option "light_window"). */
+#define NDT_MAX_LIGHTS 1024
 
 #define NDT_OK              0
 #define NDT_E_INVALID      -1   /* malformed scene / argument */
@@ -321,6 +322,10 @@ int ndt_hip_multi_path_taken(ndt_hip_ctx *ctx);
  *   "multi_path"      ndt_hip_render_multi: 0 auto (stores on the same device, peer stores over xGMI, a staged copy where
  *                     there is no peer access), 1 never staged, 2 always staged -- also between contexts of one device
  *   "shade_pair"      0: lighting of a bounce and shading of the next as two launches
+ *   "light_window"    lights the lighting kernels take per window: 0 (default) auto, windows of 64; k in 1..64 at most k
+ *                     list entries a window (ambient ones included).  A scene of more than one window renders every pass
+ *                     with the per-bounce kernels, whatever "pipeline" says, and pays a shading and a trace launch per
+ *                     bounce and extra window.  Neutral: it exists so that tests can run the window path on any scene
  *   "debug_levels"    profiled renders print the bounces and the duration of every trace launch
  *   "exit_probe" / "shade_probe" / "stream_probe"   profiled renders log the life of every wavefront of the trace
  *                     launches / of the k-th shade launch (value k + 1) / of the frame kernel

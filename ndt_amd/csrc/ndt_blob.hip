@@ -1102,7 +1102,6 @@ int ndt_impl::build_blob(ndt_hip_ctx *ctx, const ndt_flat_scene *fs)
         b.push(o.transparent ? 1.0 : 0.0);
     }
     sd.off_lights = b.words();
-    int n_shadow_lights = 0;
     bool has_area_lights = false;
     for (int i = 0; i < fs->n_lights; ++i) {
         const ndt_flat_light &l = fs->lights[i];
@@ -1115,8 +1114,7 @@ int ndt_impl::build_blob(ndt_hip_ctx *ctx, const ndt_flat_scene *fs)
         const bool want_dir = l.type == NDT_LIGHT_DIRECTIONAL || l.type == NDT_LIGHT_SPOT;
         if (want_pos && !vec_ok(fs, l.pos_off, 1)) return fail(NDT_E_INVALID, "light %d: position missing", i);
         if (want_dir && !vec_ok(fs, l.dir_off, 1)) return fail(NDT_E_INVALID, "light %d: direction missing", i);
-        if (l.type != NDT_LIGHT_AMBIENT) ++n_shadow_lights;
-        else if (i < 64) sd.ambient_bits |= 1ull << i;
+        if (l.type == NDT_LIGHT_AMBIENT && i < 64) sd.ambient_bits |= 1ull << i;
         b.push_ints(l.type, 0);
         b.push(l.red); b.push(l.green); b.push(l.blue);
         b.push(l.angle);
@@ -1229,6 +1227,39 @@ int ndt_impl::build_blob(ndt_hip_ctx *ctx, const ndt_flat_scene *fs)
     }
     ctx->sd = sd;
     ctx->blob.swap(b.w);
-    ctx->n_shadow_lights = n_shadow_lights;
+    ctx->light_types.resize(fs->n_lights);
+    for (int i = 0; i < fs->n_lights; ++i) ctx->light_types[i] = fs->lights[i].type;
+    light_windows(ctx);         // (sets n_shadow_lights: the non-ambient lights of the largest window)
     return NDT_OK;
+}
+
+void ndt_impl::light_windows(ndt_hip_ctx *ctx)
+{
+    const int n_lights = (int)ctx->light_types.size();
+    const int size = ctx->light_window > 0 ? ctx->light_window : 64;
+    ctx->windows.clear();
+    int n_seg_max = 0;
+    for (int first = 0; first == 0 || first < n_lights; first += size) {
+        ndt_hip_ctx::LightWindow w{};
+        w.first = first;
+        w.count = n_lights - first < size ? n_lights - first : size;
+        for (int l = 0; l < w.count; ++l) {
+            if (ctx->light_types[first + l] == NDT_LIGHT_AMBIENT) w.ambient_bits |= 1ull << l;
+            else ++w.n_seg;
+        }
+        if (w.n_seg > n_seg_max) n_seg_max = w.n_seg;
+        ctx->windows.push_back(w);
+    }
+    ctx->n_shadow_lights = n_seg_max;
+}
+
+SceneDesc ndt_impl::window_desc(const ndt_hip_ctx *ctx, const SceneDesc &sd, int k)
+{
+    SceneDesc out = sd;
+    if (ctx->windows.size() <= 1) return out;
+    const ndt_hip_ctx::LightWindow &w = ctx->windows[k];
+    out.off_lights = sd.off_lights + w.first * (6 + 4 * ctx->dims);
+    out.n_lights = w.count;
+    out.ambient_bits = w.ambient_bits;
+    return out;
 }

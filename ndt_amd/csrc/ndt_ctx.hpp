@@ -55,7 +55,19 @@ struct ndt_hip_ctx {
     double *d_blob = nullptr;
     size_t d_blob_words = 0;
     int tier = 0;
-    int n_shadow_lights = 0;
+    int n_shadow_lights = 0;        // segments of the shadow queue: the non-ambient lights of the largest light window
+    // The scene's lights in windows of at most 64 list entries (option "light_window": 0 auto = 64, else 1 .. 64).  The lighting
+    // kernels take one window at a time: a window is the scene description with its light section narrowed to the window
+    // (window_desc), and a node carries its partial colour from one window to the next.  One window:
+    // the scene description as uploaded, and the kernels of a scene of up to 64 lights.
+    struct LightWindow {
+        int first, count;                   // list entries [first, first + count)
+        int n_seg;                          // ... that are not ambient: the window's segments of the shadow queue
+        unsigned long long ambient_bits;    // bit l: entry first + l is ambient
+    };
+    int light_window = 0;
+    std::vector<int> light_types;           // NDT_LIGHT_* of every list entry (build_blob)
+    std::vector<LightWindow> windows;
     // workspace
     Workspace ws{};
     std::vector<void *> ws_allocs;
@@ -170,6 +182,10 @@ void hcube_face_groups(const HullFaces &hf, const std::vector<double> &hull_rows
                        std::vector<int> &face_set, std::vector<int> &members);
 bool scene_item_boxes(const ndt_flat_scene *fs, int n, std::vector<double> &frame, std::vector<double> &rows, std::vector<char> &has);
 int build_blob(ndt_hip_ctx *ctx, const ndt_flat_scene *fs);
+// splits the uploaded scene's lights into windows of ctx->light_window entries; sets ctx->windows and ctx->n_shadow_lights
+void light_windows(ndt_hip_ctx *ctx);
+// the scene description `sd` with its light section narrowed to window k
+SceneDesc window_desc(const ndt_hip_ctx *ctx, const SceneDesc &sd, int k);
 
 // ndt_frame.hip
 void free_workspace(ndt_hip_ctx *ctx);

@@ -102,7 +102,7 @@ int ndt_impl::ensure_workspace(ndt_hip_ctx *ctx, long long cap, long long sh_cap
     if ((rc = ws_alloc(ctx, &ws.slim, (size_t)sh_cap))) return give_up(rc);
     if ((rc = ws_alloc(ctx, &ws.sobj, (size_t)sh_cap))) return give_up(rc);
     if ((rc = ws_alloc(ctx, &ws.sprim, (size_t)sh_cap))) return give_up(rc);
-    if ((rc = ws_alloc(ctx, &ws.counters, NDT_CNT_TOTAL))) return give_up(rc);
+    if ((rc = ws_alloc(ctx, &ws.counters, NDT_CNT_ALLOC))) return give_up(rc);
     if ((rc = ws_alloc(ctx, &ws.ref_rays, 64 * 8))) return give_up(rc);
     if ((rc = ws_alloc(ctx, &ws.dbg, 160))) return give_up(rc);
     if ((rc = ws_alloc(ctx, &ws.exit_log, (size_t)NDT_EXIT_LOG_LAUNCHES * NDT_EXIT_LOG_WORDS))) return give_up(rc);
@@ -468,8 +468,12 @@ int ndt_impl::render_pass(ndt_hip_ctx *ctx, RenderGeom rg, bool prof, void *d_rg
     // (a pass over a LIST of image positions -- recursive anti-aliasing's samples, all of them on the edges the first pass found:
     // 15 rays a sample where a frame has 2.4 a pixel -- crosses over much earlier: profiles/r03_modes_1080p.txt)
     const long long stream_upto = rg.samples ? ctx->stream_below_list : ctx->stream_below;
-    ctx->use_stream = ctx->pipeline == 2 || (ctx->pipeline == 0 && n_primary <= stream_upto);
-    const bool hybrid = !ctx->use_stream && ctx->pipeline == 3 && ctx->hybrid_level >= 1 && rg.max_depth > ctx->hybrid_level;
+    // (a scene of more than one light window: the per-bounce kernels, whatever the pipeline -- the frame kernel keeps one 64-bit
+    // mask of fired lights per node)
+    const int n_win = (int)ctx->windows.size();
+    const bool windowed = n_win > 1;
+    ctx->use_stream = !windowed && (ctx->pipeline == 2 || (ctx->pipeline == 0 && n_primary <= stream_upto));
+    const bool hybrid = !windowed && !ctx->use_stream && ctx->pipeline == 3 && ctx->hybrid_level >= 1 && rg.max_depth > ctx->hybrid_level;
     // (auto only) the frame kernel keeps one shadow slot per node AND light for the whole frame: with many lights that can
     // exceed what the per-bounce pipeline, which sizes its segments bounce by bounce, needs by far.  When it does not fit --
     // 2^31 slots, or the allocation fails -- auto renders the pass per bounce instead of failing.
@@ -606,13 +610,15 @@ int ndt_impl::render_pass(ndt_hip_ctx *ctx, RenderGeom rg, bool prof, void *d_rg
             sh_cap = (long long)n_seg * hl[0].seg_stride;
             continue;
         }
+        // one trace launch per bounce and light window + the primaries' own (more than NDT_QUEUE_SLOTS: see traced below)
+        long long want_slots = (long long)n_levels * (windowed ? n_win : 1) + 2;
+        const int slots = want_slots > NDT_QUEUE_SLOTS ? NDT_QUEUE_SLOTS : (int)want_slots;
         {
-            int slots = n_levels + 2;               // one trace launch per bounce + the primaries' own
-            if (slots > NDT_QUEUE_SLOTS) slots = NDT_QUEUE_SLOTS;
             if (prof)
                 hipExtLaunchKernelGGL(k_frame_init, dim3(8), dim3(256), 0, s, ev_begin, nullptr, 0u, ws, rg.n_primary, hl[0], slots * NDT_QUEUE_INTS);
             else
                 hipLaunchKernelGGL(k_frame_init, dim3(8), dim3(256), 0, s, ws, rg.n_primary, hl[0], slots * NDT_QUEUE_INTS);
+            if (windowed) HIP_TRY(hipMemsetAsync(ws.counters + NDT_CNT_WIN, 0, (NDT_CNT_ALLOC - NDT_CNT_WIN) * sizeof(int), s));
         }
         int queue_slot = 0;
         int launches = 0;
@@ -620,18 +626,22 @@ int ndt_impl::render_pass(ndt_hip_ctx *ctx, RenderGeom rg, bool prof, void *d_rg
         const bool fuse_primaries = (ctx->fuse_primaries < 0 ? ctx->dims >= 4 : ctx->fuse_primaries != 0) && !ctx->coop && ctx->cam_type == 0;
         // (no k_primary: the first trace launch makes the primaries it traces, TraceJob::make_primaries)
         if (!fuse_primaries) kt->primary(s, ctx->d_blob, sd_pass, ws, rg);
-        auto traced = [&](TraceJob &tj, const std::string &what) -> int {
-            tj.queue = ws.counters + NDT_CNT_QUEUE + (queue_slot++) * NDT_QUEUE_INTS;
+        auto traced = [&](TraceJob &tj, const std::string &what, const SceneDesc *sd_job = nullptr) -> int {
+            // (more trace launches than work queues -- light windows: a queue is used again once the stream has passed the launch
+            // that used it before, zeroed on the stream first)
+            tj.queue = ws.counters + NDT_CNT_QUEUE + (queue_slot % NDT_QUEUE_SLOTS) * NDT_QUEUE_INTS;
+            if (queue_slot++ >= slots) HIP_TRY(hipMemsetAsync(tj.queue, 0, NDT_QUEUE_INTS * sizeof(int), s));
+            const SceneDesc &sdj = sd_job ? *sd_job : sd_pass;
             const bool exit_probe = ctx->exit_probe;
             tj.exit_log = (exit_probe && prof && launches < NDT_EXIT_LOG_LAUNCHES) ? ws.exit_log + (size_t)launches * NDT_EXIT_LOG_WORDS : nullptr;
             coop_setup(ctx, tj, tj.exit_log ? reinterpret_cast<unsigned int *>(ws.dbg + 100 + 2 * launches) : nullptr);
             if (prof) {
                 hipEvent_t a = get_event(ctx, ev_n++), b2 = get_event(ctx, ev_n++);
-                kt->trace(s, ctx->d_blob, sd_pass, ws, tj, ctx->tier, ctx->sd.mask_words, a, b2);
+                kt->trace(s, ctx->d_blob, sdj, ws, tj, ctx->tier, ctx->sd.mask_words, a, b2);
                 trace_ev.push_back({ a, b2 });
                 trace_dbg.push_back(what);
             } else {
-                kt->trace(s, ctx->d_blob, sd_pass, ws, tj, ctx->tier, ctx->sd.mask_words, nullptr, nullptr);
+                kt->trace(s, ctx->d_blob, sdj, ws, tj, ctx->tier, ctx->sd.mask_words, nullptr, nullptr);
             }
             ++launches;
             return NDT_OK;
@@ -669,6 +679,11 @@ int ndt_impl::render_pass(ndt_hip_ctx *ctx, RenderGeom rg, bool prof, void *d_rg
             return w;
         };
         const bool fuse_shade = ctx->shade_pair;
+        // light windows: window k's scene description, and how many window emits the frame has had (they take the two banks of
+        // window counters in turn)
+        std::vector<SceneDesc> sd_win;
+        for (int k = 0; windowed && k < n_win; ++k) sd_win.push_back(window_desc(ctx, sd_pass, k));
+        int win_emits = 0;
         int pending_finish = -1;                // bounce whose lighting has not been launched yet
         long long pending_upper = 0;
         // Hybrid pipeline: the first `hand` bounces -- where the rays are -- go through the per-bounce kernels (three
@@ -679,7 +694,9 @@ int ndt_impl::render_pass(ndt_hip_ctx *ctx, RenderGeom rg, bool prof, void *d_rg
         const int hand = hybrid ? ctx->hybrid_level : n_levels + 1;
         bool streamed = false;
         for (int b = 0; b < n_levels && b < hand; ++b) {
-            if (queue_slot + 1 > NDT_QUEUE_SLOTS || b + 1 > NDT_MAX_LEVELS)
+            // (the same bounce limit whatever the light windows: a windowed pass uses its work queues again, but light_window must
+            // not change what renders)
+            if ((windowed ? b + 2 : queue_slot + 1) > NDT_QUEUE_SLOTS || b + 1 > NDT_MAX_LEVELS)
                 return fail(NDT_E_UNSUPPORTED, "more than %d bounces", NDT_QUEUE_SLOTS - 1);
             if (b > 0) {
                 // posted by k_level_step(b-1), which ran right after shade_emit(b-1)
@@ -699,7 +716,15 @@ int ndt_impl::render_pass(ndt_hip_ctx *ctx, RenderGeom rg, bool prof, void *d_rg
             level_nodes.push_back(upper);
             // hit points, shadow rays of this bounce, and the rays of the next bounce -- in the same launch as the
             // lighting of the previous bounce, which is waiting for the shadow answers the last trace launch produced
-            if (pending_finish >= 0 && fuse_shade) {
+            if (windowed) {
+                // (the lighting of the last window of bounce b-1 and the shading of bounce b see different lights: two launches)
+                if (pending_finish >= 0) {
+                    kt->shade_last(s, ctx->d_blob, sd_win[n_win - 1], shade_ws(pending_upper), rg, pending_finish, pending_upper, 0,
+                                   ctx->windows[n_win - 1].first);
+                    pending_finish = -1;
+                }
+                kt->shade_emit(s, ctx->d_blob, sd_win[0], shade_ws(0), rg, b, upper);
+            } else if (pending_finish >= 0 && fuse_shade) {
                 kt->shade_pair(s, ctx->d_blob, sd_pass, shade_ws(pending_upper, upper), rg, pending_finish, pending_upper, upper);
                 pending_finish = -1;
             } else {
@@ -715,7 +740,7 @@ int ndt_impl::render_pass(ndt_hip_ctx *ctx, RenderGeom rg, bool prof, void *d_rg
             {
                 // ONE launch: shadow rays of bounce b + closest-hit rays of bounce b+1
                 TraceJob tj{};
-                tj.n_seg = n_seg;
+                tj.n_seg = windowed ? ctx->windows[0].n_seg : n_seg;
                 tj.seg.o = ws.so; tj.seg.v = ws.sv; tj.seg.stride = ws.sh_cap; tj.seg.lim = ws.slim; tj.seg.valid = nullptr;
                 tj.seg_light_origins = sd_pass.light_origins;      // (what shade_emit_node left out: ndt_kernels.hip)
                 tj.seg.out_obj = ws.sobj; tj.seg.out_prim = ws.sprim;
@@ -728,7 +753,31 @@ int ndt_impl::render_pass(ndt_hip_ctx *ctx, RenderGeom rg, bool prof, void *d_rg
                 tj.levels = ws.levels; tj.seg_level = b; tj.dense_level = (b + 1 == hand) ? -1 : b + 1;     // the frame kernel traces bounce `hand`
                 tj.publish_level = b;
                 tj.publish_tag = tag;
-                if ((rc = traced(tj, "shadow " + std::to_string(b) + (b + 1 == hand ? "" : " + closest " + std::to_string(b + 1))))) return rc;
+                if ((rc = traced(tj, "shadow " + std::to_string(b) + (b + 1 == hand ? "" : " + closest " + std::to_string(b + 1)),
+                                 windowed ? &sd_win[0] : nullptr)))
+                    return rc;
+            }
+            for (int k = 1; windowed && k < n_win; ++k) {
+                // window k: fold the answers of window k-1 into the nodes' colours and emit their shadow rays of window k, then trace them
+                const ndt_hip_ctx::LightWindow &w = ctx->windows[k];
+                int *bank = ws.counters + NDT_CNT_WIN + 64 * (win_emits & 1);
+                int *next_bank = ws.counters + NDT_CNT_WIN + 64 * ((win_emits + 1) & 1);
+                ++win_emits;
+                kt->shade_window(s, ctx->d_blob, sd_win[k - 1], sd_win[k], shade_ws(upper), rg, b, upper, ctx->windows[k - 1].first, w.first,
+                                 bank, next_bank, w.n_seg, k > 1 ? 1 : 0);
+                if (w.n_seg == 0) continue;
+                TraceJob tj{};
+                tj.n_seg = w.n_seg;
+                tj.seg.o = ws.so; tj.seg.v = ws.sv; tj.seg.stride = ws.sh_cap; tj.seg.lim = ws.slim; tj.seg.valid = nullptr;
+                tj.seg_light_origins = sd_pass.light_origins;
+                tj.seg.out_obj = ws.sobj; tj.seg.out_prim = ws.sprim;
+                tj.seg_count = bank;
+                tj.seg_stride = (upper + 63) & ~63LL;           // sizes the grid only
+                tj.begin = 0;
+                tj.count = 0;                                   // shadow rays only
+                tj.levels = ws.levels; tj.seg_level = b; tj.dense_level = -1;
+                tj.publish_level = -1;
+                if ((rc = traced(tj, "shadow " + std::to_string(b) + " window " + std::to_string(k), &sd_win[k]))) return rc;
             }
             pending_finish = b;
             pending_upper = upper;
@@ -736,7 +785,10 @@ int ndt_impl::render_pass(ndt_hip_ctx *ctx, RenderGeom rg, bool prof, void *d_rg
         // the lighting of the deepest bounce that has nodes: blended on the spot (its nodes have no child nodes), unless the frame
         // kernel renders deeper bounces behind it (hybrid)
         const bool resolve_with_finish = pending_finish >= 0 && !hybrid && pending_finish >= 1 && pending_finish == n_run - 1;
-        if (pending_finish >= 0)
+        if (pending_finish >= 0 && windowed)
+            kt->shade_last(s, ctx->d_blob, sd_win[n_win - 1], shade_ws(pending_upper), rg, pending_finish, pending_upper, resolve_with_finish ? 1 : 0,
+                           ctx->windows[n_win - 1].first);
+        else if (pending_finish >= 0)
             kt->shade_finish(s, ctx->d_blob, sd_pass, shade_ws(pending_upper), rg, pending_finish, pending_upper, resolve_with_finish ? 1 : 0);
         StreamArgs sa = ctx->sa;
         hipEvent_t ev_k0 = nullptr, ev_k1 = nullptr;

@@ -980,7 +980,8 @@ struct ShadowSetup {
 };
 NDT_DEV bool light_setup(const double *blob, const SceneDesc &sd, int li, const double (&src)[N], const double (&hit)[N],
                          const double (&hit_normal)[N], int &type, double (&lgt_pos)[N], double (&rev_light)[N],
-                         double (&light_vec)[N], double (&shadow_o)[N], ShadowSetup &ss, unsigned long long key = 0ull)
+                         double (&light_vec)[N], double (&shadow_o)[N], ShadowSetup &ss, unsigned long long key = 0ull,
+                         int li_base = 0)
 {
     const int w = light_word(sd, li);
     type = blob_int(blob, w, 0);
@@ -988,8 +989,9 @@ NDT_DEV bool light_setup(const double *blob, const SceneDesc &sd, int li, const 
     blob_vec<N>(blob, w + 5, lgt_pos);
     if (type == 4 || type == 5) {
         // LIGHT_DISK / LIGHT_RECT: a random point of the light, then a point light (ndt.c:116-147).
-        // shade_emit and shade_finish call this with the same node key and so see the same point.
-        const unsigned long long lk = ndt_rng_mix(key ^ (0x51ed270b27b4f3cfull * (unsigned long long)(li + 1)));
+        // shade_emit and shade_finish call this with the same node key and so see the same point.  (li_base: where the light
+        // window starts -- the key takes the light's place in the whole list, so that the draw does not depend on the windows)
+        const unsigned long long lk = ndt_rng_mix(key ^ (0x51ed270b27b4f3cfull * (unsigned long long)(li_base + li + 1)));
         double x, y;
         unsigned int k = 0;
         do {
@@ -1314,8 +1316,11 @@ __global__ void __launch_bounds__(NDT_EMIT_BLOCK) k_shade_emit(const double *blo
 
 // ------------------------------------------------------------------ shading, second half
 
+// CONT: a light window after the first: the sum continues from the partial colour and count the window
+// before stored, instead of starting from the scene's ambient light; li_base = the window's first light in the whole list.
+template <bool CONT = false>
 NDT_DEV void shade_finish_node(const double *blob, const SceneDesc &sd, const Workspace &ws, const RenderGeom &rg,
-                               const LevelRange &lr, int level, long long r, const bool resolve_here = false)
+                               const LevelRange &lr, int level, long long r, const bool resolve_here = false, int li_base = 0)
 {
     const bool in_range = r < lr.count;
     const long long g = lr.begin + (in_range ? r : 0);
@@ -1359,9 +1364,16 @@ NDT_DEV void shade_finish_node(const double *blob, const SceneDesc &sd, const Wo
             hitr_r = refl_r; hitr_g = refl_g; hitr_b = refl_b;
         }
         // apply_lights, ndt.c:88-92: scn->ambient first
-        double cr = hit_r * blob[sd.off_cam + 4 * N + 1];
-        double cg = hit_g * blob[sd.off_cam + 4 * N + 2];
-        double cb = hit_b * blob[sd.off_cam + 4 * N + 3];
+        double cr, cg, cb;
+        if (CONT) {
+            cr = ws.clr[0 * ws.cap + g];
+            cg = ws.clr[1 * ws.cap + g];
+            cb = ws.clr[2 * ws.cap + g];
+        } else {
+            cr = hit_r * blob[sd.off_cam + 4 * N + 1];
+            cg = hit_g * blob[sd.off_cam + 4 * N + 2];
+            cb = hit_b * blob[sd.off_cam + 4 * N + 3];
+        }
         int n_shadow = 0;
         // Every lane walks ITS lights -- the ones that fired a shadow ray for this hit, and the ambient ones, in the list's
         // order (the sums below are taken in that order, ndt.c:98) -- not the whole list: on the benchmark scene a hit fires
@@ -1383,7 +1395,7 @@ NDT_DEV void shade_finish_node(const double *blob, const SceneDesc &sd, const Wo
             double lgt_pos[N], rev_light[N], light_vec[N], so[N], light_hit_normal[N];
             ShadowSetup ss;
             light_setup(blob, sd, li, src, hit, nrm, type, lgt_pos, rev_light, light_vec, so, ss,
-                        rg.sample_keys ? ws.rng_key[g] : 0ull);
+                        rg.sample_keys ? ws.rng_key[g] : 0ull, li_base);
             const int sobj = (li == li_first) ? sobj_first : ws.sobj[slot];
             const int sprim = (li == li_first) ? sprim_first : ws.sprim[slot];
             ++n_shadow;
@@ -1450,7 +1462,7 @@ NDT_DEV void shade_finish_node(const double *blob, const SceneDesc &sd, const Wo
         ws.clr[0 * ws.cap + g] = cr;
         ws.clr[1 * ws.cap + g] = cg;
         ws.clr[2 * ws.cap + g] = cb;
-        ws.count[g] = 1 + n_shadow;
+        ws.count[g] = (CONT ? ws.count[g] : 1) + n_shadow;
 
     }
 }
@@ -1493,6 +1505,143 @@ __global__ void __launch_bounds__(256, NDT_SHADE_WAVES) k_shade_pair(const doubl
             shade_emit_node(blob, sd, ws, rg, lr, level + 1, base + threadIdx.x, &sh);
             NDT_SHADE_LOG_END();
         }
+    }
+}
+
+// ------------------------------------------------------------------ light windows (scenes of more than one window)
+//
+// A scene whose lights do not fit in one window of 64 (or of option light_window) is lit window by window:
+// shade_emit(b) as for any scene, with the window-0 scene description; then, per later window k, ONE launch that folds the
+// answers of window k-1 into the node's running colour (stored exactly, as the doubles apply_lights sums into, ndt.c:98) and
+// emits the node's shadow rays of window k; then the lighting of the last window (k_shade_last).  These are kernels of their
+// own: the ones a scene of one window launches are not touched.
+
+// The shadow rays of one node for window k: the light tests, the segment reservations and the stores of shade_emit_node, and
+// nothing that happens once per node (hit point bookkeeping, depth map, background, children: shade_emit did those).
+// `seg_cnt`: the window's segment counters (zero on entry); `room`: the shadow queue holds n_seg segments of this bounce
+// (else nothing is emitted and the overflow is flagged: the host grows the queue and renders again).
+// (every thread of the workgroup calls this: it holds two workgroup barriers)
+NDT_DEV void window_emit_node(const double *blob, const SceneDesc &sd, const Workspace &ws, const RenderGeom &rg,
+                              const LevelRange &lr, int level, long long r, EmitShared *sh, int *seg_cnt, bool room, int li_base)
+{
+    const bool in_range = r < lr.count;
+    const long long g = lr.begin + (in_range ? r : 0);
+    int dl = 0, obj = -1, prim = -1;
+    if (in_range) {
+        dl = ws.depth_left[g];
+        obj = ws.hit_obj[g];
+        prim = ws.hit_prim[g];
+    }
+    // (shade_emit set hit_obj to -1 for the nodes it did not shade)
+    const bool shaded = in_range && dl > 0 && obj >= 0;
+    double src[N], look[N], hit[N], nrm[N];
+    if (shaded) {
+        load_soa<N>(ws.ray_o, ws.cap, g, src);
+        load_soa<N>(ws.ray_v, ws.cap, g, look);
+        isect_full(blob, &sd, prim, src, look, hit, nrm);
+    }
+    const bool live = __ballot(shaded) != 0ull;
+    const int lane = __lane_id();
+    unsigned long long fire = 0ull;
+    const unsigned long long node_key = (rg.sample_keys && in_range) ? ws.rng_key[g] : 0ull;
+    if (shaded && room) {
+        for (int li = 0; li < sd.n_lights; ++li) {
+            int type;
+            double lgt_pos[N], rev_light[N], light_vec[N], so[N];
+            ShadowSetup ss;
+            if (light_setup(blob, sd, li, src, hit, nrm, type, lgt_pos, rev_light, light_vec, so, ss, node_key, li_base)) fire |= 1ull << li;
+        }
+    }
+    int my_total = 0, seg = 0;
+    if (live) {
+        for (int li = 0; li < sd.n_lights; ++li) {
+            if (blob_int(blob, light_word(sd, li), 0) == NDT_LIGHT_AMBIENT_) continue;     // wave-uniform
+            const unsigned long long vote = __ballot((fire >> li) & 1ull);
+            if (lane == seg) my_total = __popcll(vote);
+            ++seg;
+        }
+    }
+    if (shaded) ws.sh_mask[g] = fire;
+    int my_off = 0;
+    if (my_total > 0) my_off = atomicAdd(&sh->seg_total[lane], my_total);
+    __syncthreads();
+    if (threadIdx.x < 64) {
+        const int want = sh->seg_total[threadIdx.x];
+        if (want > 0) sh->seg_base[threadIdx.x] = atomicAdd(&seg_cnt[threadIdx.x], want);
+        // the bounce's shadow-ray count (statistics): window 0's was stored by the trace launch that published the bounce
+        int sum = want;
+        for (int d = 32; d > 0; d >>= 1) sum += __shfl_xor(sum, d, 64);
+        if (threadIdx.x == 0 && sum > 0) atomicAdd(reinterpret_cast<unsigned long long *>(&ws.levels[level].n_shadow), (unsigned long long)sum);
+    }
+    __syncthreads();
+    const int my_base = (my_total > 0) ? sh->seg_base[lane] + my_off : 0;
+    seg = 0;
+    for (int li = 0; live && li < sd.n_lights; ++li) {
+        const int list_type = blob_int(blob, light_word(sd, li), 0);        // (wave-uniform)
+        if (list_type == NDT_LIGHT_AMBIENT_) continue;
+        const bool origin_known = sd.light_origins && (list_type == NDT_LIGHT_POINT_ || list_type == NDT_LIGHT_SPOT_);
+        const bool fires = (fire >> li) & 1ull;
+        const unsigned long long vote = __ballot(fires);
+        const int base = __shfl(my_base, seg, 64);
+        if (fires) {
+            int type;
+            double lgt_pos[N], rev_light[N], light_vec[N], so[N];
+            ShadowSetup ss;
+            light_setup(blob, sd, li, src, hit, nrm, type, lgt_pos, rev_light, light_vec, so, ss, node_key, li_base);
+            const int idx = base + __popcll(vote & ((1ull << lane) - 1ull));
+            const long long slot = (long long)seg * lr.seg_stride + idx;
+            ws.sh_idx[(long long)seg * ws.cap + g] = idx;
+            if (!origin_known) store_soa<N>(ws.so, ws.sh_cap, slot, so);
+            double dir[N];
+#pragma unroll
+            for (int c = 0; c < N; ++c) dir[c] = (type == NDT_LIGHT_DIRECTIONAL_) ? rev_light[c] : light_vec[c];
+            store_soa<N>(ws.sv, ws.sh_cap, slot, dir);
+            ws.slim[slot] = ss.dist_limit;
+        }
+        ++seg;
+    }
+}
+
+// Fold window k-1 (sd_fold; CONT: k-1 > 0) and emit window k (sd_emit, n_seg_emit segments counted in seg_cnt) of bounce `level`.
+// seg_clear: the other bank of window counters -- the one the NEXT window emit of the frame uses, whose last reader (the trace
+// launch of the window emit before this one) has finished: zeroed here, so that it is zero when that emit runs.
+template <bool CONT>
+__global__ void __launch_bounds__(256, NDT_SHADE_WAVES) k_shade_window(const double *blob, SceneDesc sd_fold, SceneDesc sd_emit, Workspace ws,
+                                                                       RenderGeom rg, int level, int li_base_fold, int li_base_emit,
+                                                                       int *seg_cnt, int *seg_clear, int n_seg_emit)
+{
+    __shared__ EmitShared sh;
+    const LevelRange lr = ws.levels[level];
+    const bool room = (long long)n_seg_emit * lr.seg_stride <= ws.sh_cap;
+    if (blockIdx.x == 0 && threadIdx.x < 64) {
+        seg_clear[threadIdx.x] = 0;
+        if (threadIdx.x == 0 && !room) {
+            atomicOr(&ws.counters[2], 2);
+            const long long need = (long long)n_seg_emit * lr.seg_stride;
+            atomicMax(&ws.counters[3], need > 0x7fffffffLL ? 0x7fffffff : (int)need);
+        }
+    }
+    const long long base = (long long)blockIdx.x * blockDim.x;
+    if (base < lr.count) {
+        NDT_SHADE_LOG_BEGIN();
+        shade_finish_node<CONT>(blob, sd_fold, ws, rg, lr, level, base + threadIdx.x, false, li_base_fold);
+        if (threadIdx.x < 64) sh.seg_total[threadIdx.x] = 0;
+        __syncthreads();
+        window_emit_node(blob, sd_emit, ws, rg, lr, level, base + threadIdx.x, &sh, seg_cnt, room, li_base_emit);
+        NDT_SHADE_LOG_END();
+    }
+}
+
+// The lighting of the last window of bounce `level`: what k_shade_finish does, continuing the partial colour and count
+__global__ void __launch_bounds__(256, NDT_SHADE_WAVES) k_shade_last(const double *blob, SceneDesc sd, Workspace ws, RenderGeom rg, int level,
+                                                                     int resolve_here, int li_base)
+{
+    const LevelRange lr = ws.levels[level];
+    const long long base = (long long)blockIdx.x * blockDim.x;
+    if (base < lr.count) {
+        NDT_SHADE_LOG_BEGIN();
+        shade_finish_node<true>(blob, sd, ws, rg, lr, level, base + threadIdx.x, resolve_here != 0, li_base);
+        NDT_SHADE_LOG_END();
     }
 }
 
@@ -1548,6 +1697,24 @@ static void launch_shade_pair(hipStream_t s, const double *blob, SceneDesc sd, W
     if (nf + ne == 0) return;
     hipLaunchKernelGGL(k_shade_pair, dim3(nf + ne), dim3(256), 0, s, blob, sd, ws, rg, level, nf);
 }
+static void launch_shade_window(hipStream_t s, const double *blob, SceneDesc sd_fold, SceneDesc sd_emit, Workspace ws, RenderGeom rg,
+                                int level, long long upper, int li_base_fold, int li_base_emit, int *seg_cnt, int *seg_clear,
+                                int n_seg_emit, int cont)
+{
+    if (upper <= 0) return;
+    if (cont)
+        hipLaunchKernelGGL(k_shade_window<true>, dim3(shade_grid(upper)), dim3(256), 0, s, blob, sd_fold, sd_emit, ws, rg, level,
+                           li_base_fold, li_base_emit, seg_cnt, seg_clear, n_seg_emit);
+    else
+        hipLaunchKernelGGL(k_shade_window<false>, dim3(shade_grid(upper)), dim3(256), 0, s, blob, sd_fold, sd_emit, ws, rg, level,
+                           li_base_fold, li_base_emit, seg_cnt, seg_clear, n_seg_emit);
+}
+static void launch_shade_last(hipStream_t s, const double *blob, SceneDesc sd, Workspace ws, RenderGeom rg, int level, long long upper,
+                              int resolve_here, int li_base)
+{
+    if (upper <= 0) return;
+    hipLaunchKernelGGL(k_shade_last, dim3(shade_grid(upper)), dim3(256), 0, s, blob, sd, ws, rg, level, resolve_here, li_base);
+}
 static void launch_hitpoints(hipStream_t s, const double *blob, SceneDesc sd, const double *o, const double *v,
                              long long stride, const int *prim, double *hit, double *nrm, long long count)
 {
@@ -1561,6 +1728,7 @@ extern "C" const NdtKernelTable *NDT_CAT(ndt_kernel_table_, NDT_DIMS)()
 {
     using namespace NDT_CAT(ndt_d, NDT_DIMS);
     static const NdtKernelTable table = { NDT_DIMS, launch_primary, launch_trace, launch_shade_emit, launch_shade_finish,
-                                          launch_shade_pair, launch_hitpoints, launch_frame_stream };
+                                          launch_shade_pair, launch_hitpoints, launch_frame_stream, launch_shade_window,
+                                          launch_shade_last };
     return &table;
 }

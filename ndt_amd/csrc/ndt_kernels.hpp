@@ -230,6 +230,13 @@ struct NdtKernelTable {
     // the whole ray tree of a frame in one persistent launch (ndt_stream.hpp); primaries already in the pool
     void (*frame_stream)(hipStream_t, const double *blob, SceneDesc, Workspace, RenderGeom, StreamArgs, int tier, int mask_words,
                          hipEvent_t ev_start, hipEvent_t ev_stop);
+    // scenes of more than one light window (ndt_hip_ctx::windows): fold window k-1 of bounce `level` into the nodes' running colour
+    // and emit their shadow rays of window k (cont: k-1 > 0), counted in seg_cnt; seg_clear is zeroed for the next window emit
+    void (*shade_window)(hipStream_t, const double *blob, SceneDesc sd_fold, SceneDesc sd_emit, Workspace, RenderGeom, int level,
+                         long long upper, int li_base_fold, int li_base_emit, int *seg_cnt, int *seg_clear, int n_seg_emit, int cont);
+    // ... and the lighting of the last window (what shade_finish is for a scene of one window)
+    void (*shade_last)(hipStream_t, const double *blob, SceneDesc, Workspace, RenderGeom, int level, long long upper, int resolve_here,
+                       int li_base);
 };
 
 extern "C" const NdtKernelTable *ndt_kernel_table_3();
@@ -275,6 +282,9 @@ extern "C" const NdtKernelTable *ndt_kernel_table_12();
 #define NDT_CNT_SEG (NDT_CNT_QUEUE + NDT_QUEUE_SLOTS * NDT_QUEUE_INTS)
 #define NDT_CNT_TOTAL (NDT_CNT_SEG + 128)         /* shadow-segment counters, double-buffered by bounce parity */
 #define NDT_SEG_COUNTERS(ws, level) ((ws).counters + NDT_CNT_SEG + 64 * ((level) & 1))
+/* scenes of more than one light window: two more banks behind them, used in turn by the window emits (k_shade_window) of a frame */
+#define NDT_CNT_WIN NDT_CNT_TOTAL
+#define NDT_CNT_ALLOC (NDT_CNT_WIN + 128)
 #define NDT_SHADE_MAX_BLOCKS 8192            /* shade kernels walk longer bounces with a grid-stride loop */
 #define NDT_TRACE_LDS_LIMIT (64 * 1024)     /* bytes of scene staged per workgroup: two workgroups per CU */
 #define NDT_MASK_REG_WORDS 4                /* 64-bit words of visit mask kept in registers (256 items) */
