@@ -104,7 +104,12 @@ NDT_DEV double ndt_rng_uniform(unsigned long long key, unsigned int k)
 // (measured per dimension, bounce-synchronous pipeline, 1080p: out of line 3-D 0.67 / 4-D 1.65 ms against 0.63 / 1.62 inlined --
 // the small-vector kernels have the registers, a call costs them more than it saves -- but 6-D 2.16 / 8-D 6.80 ms against
 // 2.24 / 6.95: ndt_kernels.hip compiles the 3-D .. 5-D kernels with NDT_INLINE_LIBM)
-NDT_LIBM double nd_acos(double x) { return acos(x); }
+// acos stays out of line for every dimension (round 5): inlined, its eleven polynomial coefficients are loop-invariant 64-bit
+// constants that the compiler hoists into VGPR pairs ahead of the trace kernel's batch loop, where they are what spills --
+// the three blocks of scratch reloads inside the traversal loop of the 4-D trace kernels (one per facet intersection path).
+// Out of line: 4-D benchmark trace kernel 27 -> 4 spilled VGPRs and no scratch access left in the loop; primaries' trace
+// launch 158 -> 145 us (profiles/r05_kernel_resources.txt).
+__device__ __attribute__((noinline)) double nd_acos(double x) { return acos(x); }
 NDT_LIBM double nd_asin(double x) { return asin(x); }
 NDT_LIBM double nd_sin(double x) { return sin(x); }
 NDT_LIBM double nd_cos(double x) { return cos(x); }
