@@ -311,9 +311,8 @@ template <int MW> NDT_DEV void init_visit_mask(VisitMask<MW> &mask, const double
 // queue (one atomic per batch), so a wavefront that drew cheap rays (sky) immediately takes
 // more work instead of idling until the expensive tiles finish.  Every wavefront exits when
 // the queue head passes the ray count.
-// COOPK: the variant with the straggler ring (TraceJob::coop_ring; option `coop`); PRIM: the variant whose dense part is the
-// pass's primaries, made here (TraceJob::make_primaries).  Both are variants, not run-time branches: the code of either in the
-// kernel cost the launches that do not use it 2-3 % (registers and scratch around the traversal loop).
+// PRIM: the variant whose dense part is the pass's primaries, made here (TraceJob::make_primaries).  A variant, not a run-time
+// branch: its code in the kernel cost the launches that do not use it 2-3 % (registers and scratch around the traversal loop).
 // Where the rays of shadow segment s start, when they all start at one point: the position of the s-th light that is not
 // ambient, if it is a point or a spot light (ndt.c:211; light record: ndt_blob.hip) -- else -1 (directional: the nudged hit
 // points; area lights: a point of the light per ray).  s: the same in every lane.
@@ -330,7 +329,7 @@ NDT_DEV int seg_light_origin(const double *gblob, const SceneDesc &sd, int s)
 #ifndef NDT_TICKET_AHEAD
 #define NDT_TICKET_AHEAD 256
 #endif
-template <int MW, bool LDS, bool LSTACK = false, bool COOPK = false, bool PRIM = false>
+template <int MW, bool LDS, bool LSTACK = false, bool PRIM = false>
 __global__ void __launch_bounds__(MW == 0 ? NDT_TRACE_T1_MAX_BLOCK : NDT_TRACE_MAX_BLOCK) k_trace(const double *__restrict__ gblob, SceneDesc sd, Workspace ws, TraceJob job)
 {
     extern __shared__ __attribute__((aligned(16))) double lds_blob[];
@@ -375,9 +374,6 @@ __global__ void __launch_bounds__(MW == 0 ? NDT_TRACE_T1_MAX_BLOCK : NDT_TRACE_M
         }
     }
     const int lane = __lane_id();
-    // cooperative stragglers (TraceJob::coop_ring): the item-set tier only
-    constexpr bool COOP = COOPK && (MW == 1) && LDS;
-    const bool coop_on = COOP && job.coop_ring != nullptr;
     // NDT_HIP_EXIT_PROBE: when does every wavefront start, start its last batch, and run out of work
     const unsigned int probe_start = job.exit_log ? (unsigned int)wall_clock64() : 0u;
     unsigned int probe_batch = probe_start;
@@ -529,18 +525,6 @@ __global__ void __launch_bounds__(MW == 0 ? NDT_TRACE_T1_MAX_BLOCK : NDT_TRACE_M
         }
 #endif
         if (job.exit_log) probe_batch = (unsigned int)wall_clock64();
-        TraceAbandon ab{};
-        if (COOP && coop_on) {
-            ab.tail = job.queue + NDT_COOP_TAIL;
-            ab.deadline = wall_clock64() + (unsigned long long)job.coop_budget;
-            ab.max_live = job.coop_max_live;
-            ab.tail_limit = job.coop_limit;
-            if (job.coop_tail_only) {
-                // the shard this batch came from: dry when its head has passed its last batch
-                ab.dry_word = job.queue + cur * NDT_QUEUE_STRIDE;
-                ab.dry_at = (int)((n_batches - cur + NDT_QUEUE_SHARDS - 1) / NDT_QUEUE_SHARDS);
-            }
-        }
         long long g;
         bool live;
         const bool in_seg = b >= dense_batches;         // wave-uniform
@@ -570,7 +554,6 @@ __global__ void __launch_bounds__(MW == 0 ? NDT_TRACE_T1_MAX_BLOCK : NDT_TRACE_M
         // A lane without a ray.  The LDS tiers leave it out of the batch; in the global-memory tier it stays with the
         // wavefront as a helper of the coherent leaf scan (ndt_device.hpp:cls_scan: all 64 lanes fetch), with a ray that is
         // finished before it starts.
-        bool gave_up = false;
         if (live || MW == 0) {
         const TracePart &part = in_seg ? job.seg : job.dense;
 #ifdef NDT_TRACE_SKIP_KNOB
@@ -640,111 +623,18 @@ __global__ void __launch_bounds__(MW == 0 ? NDT_TRACE_T1_MAX_BLOCK : NDT_TRACE_M
             prim = -1;
         } else
 #endif
-        trace_kd<N, MW, LSTACK, MW == 0>(blob, sd, mask, o, v, lim, obj, prim, kstack, cls, live, box_slot, ab, &gave_up);
+        trace_kd<N, MW, LSTACK, MW == 0>(blob, sd, mask, o, v, lim, obj, prim, kstack, cls, live, box_slot);
 #endif
 #ifdef NDT_TRACE_SKIP_KNOB
         if (job.skip_trace == 2 && obj == -1) live = false;
 #endif
-        if (live && !gave_up) {
+        if (live) {
             part.out_obj[g] = obj;
             part.out_prim[g] = prim;
         }
         }
-        if (COOP && coop_on) {
-            // the rays this batch gave up: into the straggler ring, one reservation per wavefront
-            const unsigned long long gv = __ballot(live && gave_up);
-            if (gv != 0ull) {
-                int base = 0;
-                if (lane == 0) base = atomicAdd(job.queue + NDT_COOP_TAIL, __popcll(gv));
-                base = __shfl(base, 0, 64);
-                if (live && gave_up) {
-                    const unsigned int payload = (unsigned int)g | (in_seg ? 0x80000000u : 0u);
-                    __hip_atomic_store(job.coop_ring + base + __popcll(gv & ((1ull << lane) - 1ull)),
-                                       ((unsigned long long)job.coop_tag << 32) | payload, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                }
-                if (job.coop_log && lane == 0) atomicAdd(job.coop_log, (unsigned int)__popcll(gv));
-            }
-        }
     }
     const unsigned int probe_left = job.exit_log ? (unsigned int)wall_clock64() : 0u;
-    if (COOP && coop_on) {
-        // ---- this wavefront has no batch left.  It says so; the LAST one of the launch to say so closes the straggler ring:
-        // every ray that will ever be given up has been by then (a wavefront's pushes come before its own leaving), and each
-        // consumer holds exactly one ticket beyond the ring's final tail -- a closing entry goes into each of those slots.
-        const int waves_per_block = blockDim.x >> 6;
-        const int consumers_per_block = waves_per_block < job.coop_waves ? waves_per_block : job.coop_waves;
-        const int n_consumers = gridDim.x * consumers_per_block;
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");        // the ring entries above are out
-        int closer = 0;
-        if (lane == 0) {
-            const int grp = blockIdx.x % NDT_COOP_GROUPS;
-            const int grp_blocks = ((int)gridDim.x - grp + NDT_COOP_GROUPS - 1) / NDT_COOP_GROUPS;
-            const int old = atomicAdd(job.queue + NDT_COOP_LEFT + grp * NDT_QUEUE_STRIDE, 1);
-            if (old + 1 == grp_blocks * waves_per_block) {
-                const int n_groups = (int)gridDim.x < NDT_COOP_GROUPS ? (int)gridDim.x : NDT_COOP_GROUPS;
-                closer = atomicAdd(job.queue + NDT_COOP_GROUPS_DONE, 1) + 1 == n_groups;
-            }
-        }
-        closer = __shfl(closer, 0, 64);
-        if (closer) {
-            int tail = 0;
-            if (lane == 0) tail = __hip_atomic_load(job.queue + NDT_COOP_TAIL, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            tail = __shfl(tail, 0, 64);
-            for (int j = lane; j < n_consumers; j += 64)
-                __hip_atomic_store(job.coop_ring + tail + j, ((unsigned long long)job.coop_tag << 32) | NDT_COOP_CLOSE, __ATOMIC_RELAXED,
-                                   __HIP_MEMORY_SCOPE_AGENT);
-        }
-        // ---- consumers: one wavefront per SIMD (the first four of a workgroup) take the stragglers, one ray at a time
-        if ((int)(threadIdx.x >> 6) < consumers_per_block) {
-            const unsigned long long t_enter = wall_clock64();
-            unsigned int n_done = 0, t_coop = 0;
-            int ticket = -1, polls = 0;
-            while (true) {
-                unsigned long long e = 0ull;
-                if (lane == 0) {
-                    if (ticket < 0) ticket = atomicAdd(job.queue + NDT_COOP_HEAD, 1);
-                    e = __hip_atomic_load(job.coop_ring + ticket, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                }
-                ticket = __shfl(ticket, 0, 64);
-                const unsigned int e_tag = (unsigned int)__shfl((int)(e >> 32), 0, 64), payload = (unsigned int)__shfl((int)e, 0, 64);
-                if (e_tag != job.coop_tag) {
-                    // not written yet (a slot beyond the tail is written when the launch closes)
-                    __builtin_amdgcn_s_sleep(4);
-                    if ((++polls & 1023) == 0 && wall_clock64() - t_enter > 200000000ull) break;   // 2 s: never on a healthy launch
-                    continue;
-                }
-                if (payload == NDT_COOP_CLOSE) break;
-                const unsigned long long t0 = job.coop_log ? wall_clock64() : 0ull;
-                const bool in_seg = (payload >> 31) != 0u;
-                const long long g = (long long)(payload & 0x7fffffffu);
-                const TracePart &part = in_seg ? job.seg : job.dense;
-                double o[N], v[N];
-                // (a launch with the ring never makes its own primaries: what it is given up was stored by an earlier kernel)
-                const int origin_word = (in_seg && job.seg_light_origins) ? seg_light_origin(gblob, sd, (int)(g / seg_stride)) : -1;
-                if (origin_word >= 0) blob_vec<N>(gblob, origin_word, o);
-                else load_soa<N>(part.o, part.stride, g, o);
-                load_soa<N>(part.v, part.stride, g, v);
-                const double lim = part.lim ? part.lim[g] : -1.0;
-                // the next ticket travels while this ray is traced (issued behind the ray's loads: memory operations return in order)
-                ticket = 0;
-                if (lane == 0) ticket = atomicAdd(job.queue + NDT_COOP_HEAD, 1);
-                int obj, prim;
-                coop_trace<N>(blob, sd, o, v, lim, obj, prim);
-                if (lane == 0) {
-                    part.out_obj[g] = obj;
-                    part.out_prim[g] = prim;
-                }
-                if (job.coop_log) {
-                    ++n_done;
-                    t_coop += (unsigned int)(wall_clock64() - t0);
-                }
-            }
-            if (job.coop_log && lane == 0 && n_done) {
-                atomicAdd(job.coop_log + 1, n_done);
-                atomicAdd(job.coop_log + 2, t_coop);
-            }
-        }
-    }
     if (job.exit_log && lane == 0) {
         // one private slot per wavefront: shared counters would serialise the very exits they measure
         const unsigned int w = blockIdx.x * (blockDim.x / 64) + threadIdx.x / 64;
@@ -753,7 +643,7 @@ __global__ void __launch_bounds__(MW == 0 ? NDT_TRACE_T1_MAX_BLOCK : NDT_TRACE_M
             job.exit_log[8 * w + 1] = probe_batch;
             job.exit_log[8 * w + 2] = (unsigned int)wall_clock64() | 1u;
             job.exit_log[8 * w + 3] = (__builtin_amdgcn_s_getreg((31 << 11) | 4) & 0xffffffu) | ((blockDim.x / 64) << 24);   // HW_ID: wave slot [3:0], SIMD [5:4], CU [11:8]; [31:24] wavefronts per workgroup
-            job.exit_log[8 * w + 4] = probe_left | 1u;      // out of batches (with a straggler ring the wavefront stays on as a consumer)
+            job.exit_log[8 * w + 4] = probe_left | 1u;      // out of batches
         }
     }
 #ifdef NDT_PHASE_TIMING
@@ -853,37 +743,34 @@ static void launch_trace(hipStream_t s, const double *blob, SceneDesc sd, Worksp
         int lstack_block = lstack_full;
         if (lstack_full >= 256 && upper / job.batch < small_launch) lstack_block = 256;
         const size_t lds_stack = ((size_t)((sd.trace_words + 1) & ~1) * 8) + (size_t)lstack_block * (sd.kd_depth + 1) * 12;
-        // the kernel's variant: with the straggler ring (item sets only), making its own primaries, or plain
-        const bool ring = job.coop_ring != nullptr && mask_words <= 1;
-        if (!ring) job.coop_ring = nullptr;
-        const bool prim = job.make_primaries != 0 && !ring;
+        // the kernel's variant: making its own primaries, or plain
+        const bool prim = job.make_primaries != 0;
         if (lstack_block >= 64 && mask_words <= 1 && lds_stack <= 160 * 1024) {
-            const TraceKernel kern = ring ? k_trace<1, true, true, true, false> : prim ? k_trace<1, true, true, false, true> : k_trace<1, true, true>;
+            const TraceKernel kern = prim ? k_trace<1, true, true, true> : k_trace<1, true, true>;
             const int res = resident_blocks(kern, lstack_block, lds_stack);
             long long nb = (upper + job.batch * (lstack_block / 64) - 1) / (job.batch * (lstack_block / 64));
             if (nb > res) nb = res;
             NDT_LAUNCH_TRACE(kern, nb, lstack_block, lds_stack);
         } else if (lstack_block >= 64 && mask_words > 1 && lds_stack <= 160 * 1024) {
             // scenes of 65 .. 256 objects (a register mask of four words): the same, with the wider mask
-            const TraceKernel kern = prim ? k_trace<NDT_MASK_REG_WORDS, true, true, false, true> : k_trace<NDT_MASK_REG_WORDS, true, true>;
+            const TraceKernel kern = prim ? k_trace<NDT_MASK_REG_WORDS, true, true, true> : k_trace<NDT_MASK_REG_WORDS, true, true>;
             const int res = resident_blocks(kern, lstack_block, lds_stack);
             long long nb = (upper + job.batch * (lstack_block / 64) - 1) / (job.batch * (lstack_block / 64));
             if (nb > res) nb = res;
             NDT_LAUNCH_TRACE(kern, nb, lstack_block, lds_stack);
         } else if (mask_words <= 1) {
-            const TraceKernel kern = ring ? k_trace<1, true, false, true, false> : prim ? k_trace<1, true, false, false, true> : k_trace<1, true>;
+            const TraceKernel kern = prim ? k_trace<1, true, false, true> : k_trace<1, true>;
             const int res = resident_blocks(kern, block, lds);
             if (blocks > res) blocks = res;
             NDT_LAUNCH_TRACE(kern, blocks, block, lds);
         } else {
-            const TraceKernel kern = prim ? k_trace<NDT_MASK_REG_WORDS, true, false, false, true> : k_trace<NDT_MASK_REG_WORDS, true>;
+            const TraceKernel kern = prim ? k_trace<NDT_MASK_REG_WORDS, true, false, true> : k_trace<NDT_MASK_REG_WORDS, true>;
             const int res = resident_blocks(kern, block, lds);
             if (blocks > res) blocks = res;
             NDT_LAUNCH_TRACE(kern, blocks, block, lds);
         }
     } else {
-        job.coop_ring = nullptr;
-        const TraceKernel kern_t1 = job.make_primaries ? k_trace<0, false, false, false, true> : k_trace<0, false>;
+        const TraceKernel kern_t1 = job.make_primaries ? k_trace<0, false, false, true> : k_trace<0, false>;
         // (coherent leaf scan: one LDS window per wavefront)
         const size_t lds = (size_t)(block / 64) * ((sd.off_obox > 0 ? N * 128 : 0) + (sd.cls_par_words > 0 ? cls_window_words<N>(sd.cls_par_words) : 0)) * sizeof(double);
         const int res = resident_blocks(kern_t1, block, lds);
