@@ -246,6 +246,21 @@ int ndt_hip_render_depth(ndt_hip_ctx *ctx, const ndt_render_params *p, double *r
 int ndt_hip_trace_rays(ndt_hip_ctx *ctx, int64_t n, const double *o, const double *v,
                        const double *dist_limit, int32_t *obj, double *hit, double *normal);
 
+/* bounds_list_optimal (bounding.c:177-240) for n_lists point lists at once, on ctx's device and stream: the minimum
+ * enclosing sphere search (Nelder-Mead over the centre, seeded with the centroid) that object_get_bounds (object.c:582-603)
+ * runs per object, and a frame runs per object and per nested hcube face before it can be uploaded.  List i is points
+ * first[i] .. first[i+1] (first: n_lists + 1 entries, ascending) of points[.][dims] and point_radius[.], in the order
+ * bounds_list_optimal walks the list (head first: bounds_list_add prepends).  centers: n_lists x dims, radii: n_lists,
+ * exactly what bounds_list_optimal returns -- object_get_bounds's `+ EPSILON` stays with the caller.
+ * Bit-identical to the host fit.  NDT_E_INVALID: dims outside 3..12, an empty list, a non-finite input
+ * (the caller fits those itself).  Synchronous.  No scene has to be uploaded; the device buffers belong to the context
+ * and are reused by the next call. */
+int ndt_hip_fit_spheres(ndt_hip_ctx *ctx, int32_t dims, int64_t n_lists, const int64_t *first,
+                        const double *points, const double *point_radius,
+                        double *centers, double *radii);
+/* Kernel launches the context's last ndt_hip_fit_spheres call made (one per group of list lengths; 0 for an empty batch). */
+int ndt_hip_fit_launches(ndt_hip_ctx *ctx);
+
 /* Quantise a double image like the reference does at save time: pixel_d2c (image.h:36-39),
  * (unsigned char)(sqrt(clamp01(x))*255) per channel.  d_rgba: device, n_pixels*4 doubles;
  * d_rgba8: device, n_pixels*4 bytes. */

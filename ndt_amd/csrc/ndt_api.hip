@@ -119,6 +119,7 @@ extern "C" int ndt_hip_destroy(ndt_hip_ctx *ctx)
         if (slot.first) (void)hipFree(slot.first);
     if (ctx->d_blob) (void)hipFree(ctx->d_blob);
     if (ctx->d_out) (void)hipFree(ctx->d_out);
+    if (ctx->d_fit) (void)hipFree(ctx->d_fit);
     if (ctx->d_eyes) (void)hipFree(ctx->d_eyes);
     if (ctx->h_counters) (void)hipHostFree(ctx->h_counters);
     if (ctx->h_levels) (void)hipHostFree(ctx->h_levels);
@@ -295,3 +296,31 @@ extern "C" int ndt_hip_trace_rays(ndt_hip_ctx *ctx, int64_t n_rays, const double
         }
     return NDT_OK;
 }
+
+// ------------------------------------------------------------------ bounding-sphere fits
+
+extern "C" int ndt_hip_fit_spheres(ndt_hip_ctx *ctx, int32_t dims, int64_t n_lists, const int64_t *first, const double *points,
+                                   const double *point_radius, double *centers, double *radii)
+{
+    if (dims < NDT_MIN_DIMS || dims > NDT_MAX_DIMS)
+        return fail(NDT_E_INVALID, "ndt_hip_fit_spheres: %d dimensions: the fit kernels are built for %d..%d", dims, NDT_MIN_DIMS, NDT_MAX_DIMS);
+    if (!ctx) return fail(NDT_E_INVALID, "ndt_hip_fit_spheres: ctx is NULL");
+    if (n_lists < 0 || !first || (n_lists > 0 && (!points || !point_radius || !centers || !radii)))
+        return fail(NDT_E_INVALID, "ndt_hip_fit_spheres: bad argument");
+    ctx->fit_launches = 0;
+    if (n_lists == 0) return NDT_OK;
+    if (n_lists > 0x3fffffffLL) return fail(NDT_E_INVALID, "ndt_hip_fit_spheres: too many lists for one call");
+    if (first[0] < 0) return fail(NDT_E_INVALID, "ndt_hip_fit_spheres: first[0] is negative");
+    for (int64_t i = 0; i < n_lists; ++i) {
+        if (first[i + 1] <= first[i]) return fail(NDT_E_INVALID, "ndt_hip_fit_spheres: list %lld is empty", (long long)i);
+        if (first[i + 1] - first[i] > 0x3fffffffLL) return fail(NDT_E_INVALID, "ndt_hip_fit_spheres: list %lld is too long", (long long)i);
+    }
+    // what the lists use of points[]: [first[0], first[n_lists]); the kernel is handed nothing else to read
+    for (int64_t k = first[0] * dims; k < first[n_lists] * dims; ++k)
+        if (!isfinite(points[k])) return fail(NDT_E_INVALID, "ndt_hip_fit_spheres: point %lld has a non-finite coordinate", (long long)(k / dims));
+    for (int64_t k = first[0]; k < first[n_lists]; ++k)
+        if (!isfinite(point_radius[k])) return fail(NDT_E_INVALID, "ndt_hip_fit_spheres: point %lld has a non-finite radius", (long long)k);
+    return fit_spheres_device(ctx, dims, n_lists, first, points, point_radius, centers, radii);
+}
+
+extern "C" int ndt_hip_fit_launches(ndt_hip_ctx *ctx) { return ctx ? ctx->fit_launches : 0; }

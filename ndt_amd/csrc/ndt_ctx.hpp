@@ -8,6 +8,7 @@
 //   ndt_sampled.hip  -n samples > 1, lens, area lights on top of render_pass
 //   ndt_render.hip   ndt_hip_render*: argument checks and the choice between the three
 //   ndt_multi.hip    one frame over several contexts / devices
+//   ndt_fit.hip      ndt_hip_fit_spheres: the bounding-sphere fits of a frame (batched Nelder-Mead), kernel and launcher
 #pragma once
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
@@ -120,6 +121,9 @@ struct ndt_hip_ctx {
     int sa_nseg = 0;
     void *d_eyes = nullptr;         // the two eye images of a stochastic anaglyph render (ndt_sampled.hip)
     size_t d_eyes_bytes = 0;
+    void *d_fit = nullptr;          // ndt_hip_fit_spheres: jobs, points and spheres of a batch (grow-only, reused across frames)
+    size_t d_fit_bytes = 0;
+    int fit_launches = 0;           // kernel launches of the last ndt_hip_fit_spheres call
     void *d_out = nullptr;          // staging for ndt_hip_render (host output)
     size_t d_out_bytes = 0;
     void *d_shard = nullptr;        // ndt_hip_render_multi: this context's rows before they are pushed into the frame
@@ -188,6 +192,10 @@ void add_stats(ndt_render_stats &acc, const ndt_render_stats &st);
 void worker_stop(ndt_hip_ctx *ctx);
 void free_stage(ndt_hip_ctx *ctx);
 void free_async(ndt_hip_ctx *ctx);
+
+// ndt_fit.hip: bounds_list_optimal for n_lists checked point lists (first[n_lists] = number of points); synchronous
+int fit_spheres_device(ndt_hip_ctx *ctx, int dims, long long n_lists, const int64_t *first, const double *points, const double *point_radius,
+                       double *centers, double *radii);
 
 // ndt_aa.hip / ndt_sampled.hip
 int render_antialiased(ndt_hip_ctx *ctx, const ndt_render_params *p, void *d_rgba, ndt_render_stats &total, void *d_depth = nullptr);

@@ -22,6 +22,7 @@ API_SYMBOLS = [
     "ndt_hip_render_depth_device", "ndt_hip_render_depth", "ndt_hip_render_rgba8", "ndt_hip_render_multi_device",
     "ndt_hip_render_multi", "ndt_hip_device_count", "ndt_hip_device", "ndt_hip_set_option", "ndt_hip_multi_path_taken",
     "ndt_hip_item_boxes", "ndt_hip_render_rgba8_async", "ndt_hip_render_rgba8_wait",
+    "ndt_hip_fit_spheres", "ndt_hip_fit_launches",
 ]
 
 IMAGE_F64, IMAGE_RGBA8 = 0, 1      # enum ndt_image_format
@@ -88,8 +89,28 @@ def load_library():
     lib.ndt_hip_render_rgba8_async.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.ndt_hip_render_rgba8_wait.argtypes = [C.c_void_p]
     lib.ndt_hip_set_option.argtypes = [C.c_void_p, C.c_char_p, C.c_int64]
+    if hasattr(lib, "ndt_hip_fit_spheres"):         # (absent from earlier builds, which profiles/ab_libs.sh loads to compare)
+        lib.ndt_hip_fit_spheres.argtypes = [C.c_void_p, C.c_int32, C.c_int64] + [C.c_void_p] * 5
+        lib.ndt_hip_fit_launches.argtypes = [C.c_void_p]
     _lib = lib
     return lib
+
+
+def pack_point_lists(dims, lists):
+    """The flat arrays ndt_hip_fit_spheres / ndt_host_fit_spheres take, from a sequence of (points [k, dims], radii [k]) pairs
+    in the order bounds_list_optimal walks each list: (first int64 [n + 1], points float64 [total, dims], radii float64 [total])."""
+    first = np.zeros(len(lists) + 1, dtype=np.int64)
+    for i, (pts, rad) in enumerate(lists):
+        pts = np.asarray(pts, dtype=np.float64)
+        if pts.ndim != 2 or pts.shape[1] != dims or np.asarray(rad).shape != (pts.shape[0],):
+            raise ValueError("list %d: points must be [k, %d] and radii [k]" % (i, dims))
+        first[i + 1] = first[i] + pts.shape[0]
+    points = np.zeros((int(first[-1]), dims), dtype=np.float64)
+    radii = np.zeros(int(first[-1]), dtype=np.float64)
+    for i, (pts, rad) in enumerate(lists):
+        points[first[i]:first[i + 1]] = pts
+        radii[first[i]:first[i + 1]] = rad
+    return first, points, radii
 
 
 def hcube_hull_box(fs, obj):
@@ -286,6 +307,20 @@ class NdtHip:
     def quantize_device(self, d_rgba_ptr, d_rgba8_ptr, n_pixels):
         self._check(self.lib.ndt_hip_quantize_device(self.ctx, C.c_void_p(d_rgba_ptr), C.c_void_p(d_rgba8_ptr),
                                                      int(n_pixels)))
+
+    def fit_spheres(self, dims, lists):
+        """ndt_hip_fit_spheres: bounds_list_optimal (bounding.c:177-240) for every (points [k, dims], radii [k]) pair of `lists`
+        on this context's GPU, bit-identical to the host fit.  Returns (centers [n, dims], radii [n])."""
+        first, points, radii = pack_point_lists(int(dims), lists)
+        centers = np.zeros((len(lists), int(dims)), dtype=np.float64)
+        out = np.zeros(len(lists), dtype=np.float64)
+        self._check(self.lib.ndt_hip_fit_spheres(self.ctx, int(dims), len(lists), first.ctypes.data, points.ctypes.data,
+                                                 radii.ctypes.data, centers.ctypes.data, out.ctypes.data))
+        return centers, out
+
+    def fit_launches(self):
+        """ndt_hip_fit_launches: kernel launches of the last fit_spheres call."""
+        return int(self.lib.ndt_hip_fit_launches(self.ctx))
 
     def trace_rays(self, rays):
         """Batch of trace_kd queries; rays: (n, 2*dims+1) = o, v, dist_limit per row."""

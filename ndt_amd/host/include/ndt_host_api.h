@@ -20,6 +20,7 @@
 #define NDT_HOST_API_H
 
 #include <math.h>
+#include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -235,6 +236,11 @@ int bounds_list_centroid(bounds_list *list, vectNd *centroid);
 int bounds_list_radius(bounds_list *list, vectNd *centroid, double *radius);
 int bounds_list_optimal(bounds_list *list, vectNd *centroid, double *radius);
 int vect_bounding_sphere_intersect(bounding_sphere *sph, vectNd *o, vectNd *v, double min_dist);
+/* not in the reference: bounds_list_optimal over flat arrays, the CPU twin of ndt_hip_fit_spheres (ndt_bounding.c) */
+int ndt_host_fit_spheres(int dims, int64_t n_lists, const int64_t *first, const double *points, const double *point_radius,
+                         double *centers, double *radii);
+int ndt_host_fit_spheres_traced(int dims, int64_t n_lists, const int64_t *first, const double *points, const double *point_radius,
+                                double *centers, double *radii, int32_t *evaluations, int32_t *centroid_won);
 
 /* ------------------------------------------------------------------ Nelder-Mead (nelder-mead.h) */
 

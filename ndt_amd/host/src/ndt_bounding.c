@@ -74,9 +74,10 @@ int bounds_list_radius(bounds_list *list, vectNd *centroid, double *radius)
 /* bounding.c:177-240: Nelder-Mead over the centre, seeded with the centroid, at most 1000
  * iterations or until the simplex is smaller than EPSILON; the centroid wins if the search
  * ends worse than it started */
-int bounds_list_optimal(bounds_list *list, vectNd *centroid, double *radius)
+static int fit_optimal(bounds_list *list, vectNd *centroid, double *radius, int *evaluations, int *centroid_won)
 {
     int dim = centroid->n;
+    int n_results = 0, won = 0;
     void *nm = NULL;
     double curr_radius = -1.0;
     vectNd curr, initial;
@@ -90,6 +91,7 @@ int bounds_list_optimal(bounds_list *list, vectNd *centroid, double *radius)
     const double initial_radius = curr_radius;
     while (!nm_done(nm, EPSILON, 1000)) {
         nm_add_result(nm, &curr, curr_radius);
+        ++n_results;
         nm_next_point(nm, &curr);
         bounds_list_radius(list, &curr, &curr_radius);
     }
@@ -98,13 +100,60 @@ int bounds_list_optimal(bounds_list *list, vectNd *centroid, double *radius)
     if (curr_radius - initial_radius > EPSILON) {
         vectNd_copy(&curr, &initial);
         bounds_list_radius(list, &curr, &curr_radius);
+        won = 1;
     }
     vectNd_copy(centroid, &curr);
     *radius = curr_radius;
     vectNd_free(&initial);
     vectNd_free(&curr);
     nm_free(nm);
+    if (evaluations) *evaluations = n_results;
+    if (centroid_won) *centroid_won = won;
     return 0;
+}
+
+int bounds_list_optimal(bounds_list *list, vectNd *centroid, double *radius)
+{
+    return fit_optimal(list, centroid, radius, NULL, NULL);
+}
+
+/* bounds_list_optimal for n_lists point lists given flat -- the signature of ndt_hip_fit_spheres (include/ndt_hip.h), run
+ * through the functions above on the CPU: list i is points first[i] .. first[i+1] of points[.][dims] / point_radius[.] in
+ * the order the list is walked, head first.  The twin the device fit is compared against.  Returns 0, or -1 for an
+ * argument the device call refuses as well (dims < 1, an empty list).  _traced also tells, per list (either may be NULL),
+ * how many results the search took (1 001: it ran into the iteration limit) and whether the centroid won in the end. */
+int ndt_host_fit_spheres(int dims, int64_t n_lists, const int64_t *first, const double *points, const double *point_radius,
+                         double *centers, double *radii)
+{
+    return ndt_host_fit_spheres_traced(dims, n_lists, first, points, point_radius, centers, radii, NULL, NULL);
+}
+
+int ndt_host_fit_spheres_traced(int dims, int64_t n_lists, const int64_t *first, const double *points, const double *point_radius,
+                                double *centers, double *radii, int32_t *evaluations, int32_t *centroid_won)
+{
+    if (dims < 1 || n_lists < 0 || !first) return -1;
+    vectNd p, c;
+    vectNd_calloc(&p, dims);
+    vectNd_calloc(&c, dims);
+    int rc = 0;
+    for (int64_t i = 0; i < n_lists && rc == 0; ++i) {
+        if (first[i + 1] <= first[i]) { rc = -1; break; }
+        bounds_list pts;
+        bounds_list_init(&pts);
+        for (int64_t k = first[i + 1] - 1; k >= first[i]; --k) {       /* bounds_list_add prepends: last point first */
+            memcpy(p.v, points + k * dims, (size_t)dims * sizeof(double));
+            bounds_list_add(&pts, &p, point_radius[k]);
+        }
+        int n_results = 0, won = 0;
+        fit_optimal(&pts, &c, &radii[i], &n_results, &won);
+        if (evaluations) evaluations[i] = n_results;
+        if (centroid_won) centroid_won[i] = won;
+        memcpy(centers + i * dims, c.v, (size_t)dims * sizeof(double));
+        bounds_list_free(&pts);
+    }
+    vectNd_free(&p);
+    vectNd_free(&c);
+    return rc;
 }
 
 /* bounding.c:34-85.  Host copy of the gate the device evaluates per ray. */

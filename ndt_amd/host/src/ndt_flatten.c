@@ -7,6 +7,7 @@
  * (object.c:609-615) and build hcube faces (hcube.c:164) with their bounds. */
 #include "ndt_host_internal.h"
 #include <pthread.h>
+#include <time.h>
 
 #define GROW(ptr, n, cap, need, type)                                                  \
     do {                                                                               \
@@ -135,6 +136,139 @@ static void fit_bounds_parallel(object **objs, int n, int threads)
     /* (a thread that could not be started leaves its share to the loops) */
 }
 
+#define PUSH_OBJ(arr, n, cap, o)                                                                       \
+    do {                                                                                               \
+        if ((n) == (cap)) { (cap) = (cap) * 2 + 64; (arr) = (object **)realloc((arr), (size_t)(cap) * sizeof(object *)); } \
+        (arr)[(n)++] = (o);                                                                            \
+    } while (0)
+
+/* ---- the fits of a batch of objects through a fitter that takes flat point lists (ndt_flatten_scene_fit)
+ *
+ * Every object's bounding points are gathered through its bounding_points callback, in the order bounds_list_optimal walks
+ * the list, on `threads` threads (an object's callback reads that object alone; thread k takes a contiguous share, so the
+ * shares concatenate in object order); the fitter gets all lists at once; what object_get_bounds (ndt_objects.c) does around
+ * the fit stays here: an empty list marks an infinite object (radius -1, not fitted), a radius > 0 gets its EPSILON. */
+typedef struct { object **objs; int n, cap; } object_list;     /* the objects a fitter made a sphere for */
+
+typedef struct {
+    object **objs;
+    int begin, end, dims;
+    double *points, *radius;            /* this share's bounding points */
+    int64_t n_points, cap_points;
+    int64_t *count;                     /* the caller's, per object: points of its list (0: infinite) */
+} gather_job;
+
+static void *gather_worker(void *arg)
+{
+    gather_job *j = (gather_job *)arg;
+    const int d = j->dims;
+    for (int i = j->begin; i < j->end; ++i) {
+        bounds_list pts;
+        bounds_list_init(&pts);
+        j->objs[i]->bounding_points(j->objs[i], &pts);
+        int64_t n = 0;
+        for (bounds_node *b = pts.head; b; b = b->next) ++n;
+        if (j->n_points + n > j->cap_points) {
+            j->cap_points = (j->cap_points * 2 > j->n_points + n) ? j->cap_points * 2 : j->n_points + n + 256;
+            j->points = (double *)realloc(j->points, (size_t)j->cap_points * (size_t)d * sizeof(double));
+            j->radius = (double *)realloc(j->radius, (size_t)j->cap_points * sizeof(double));
+        }
+        for (bounds_node *b = pts.head; b; b = b->next) {
+            memcpy(j->points + j->n_points * d, b->bounds.center.v, (size_t)d * sizeof(double));
+            j->radius[j->n_points++] = b->bounds.radius;
+        }
+        j->count[i] = n;
+        bounds_list_free(&pts);
+    }
+    return NULL;
+}
+
+static double ms_since(const struct timespec *t0)
+{
+    struct timespec t1;
+    clock_gettime(CLOCK_MONOTONIC, &t1);
+    return (t1.tv_sec - t0->tv_sec) * 1e3 + (t1.tv_nsec - t0->tv_nsec) * 1e-6;
+}
+
+static int fit_batch(object **objs, int n, int dims, int threads, ndt_fit_fn fit, void *fit_arg, ndt_fit_stats *stats, object_list *fitted,
+                     char *err, int err_len)
+{
+    if (n <= 0) return 0;
+    struct timespec t0;
+    clock_gettime(CLOCK_MONOTONIC, &t0);
+    if (threads > 64) threads = 64;
+    if (threads < 1 || n < 64) threads = 1;
+    int64_t *count = (int64_t *)calloc((size_t)n, sizeof(int64_t));
+    gather_job jobs[64];
+    pthread_t th[64];
+    int started[64];
+    for (int k = 0; k < threads; ++k) {
+        memset(&jobs[k], 0, sizeof(jobs[k]));
+        jobs[k].objs = objs; jobs[k].dims = dims; jobs[k].count = count;
+        jobs[k].begin = (int)((int64_t)n * k / threads);
+        jobs[k].end = (int)((int64_t)n * (k + 1) / threads);
+        started[k] = k > 0 && pthread_create(&th[k], NULL, gather_worker, &jobs[k]) == 0;
+    }
+    for (int k = 0; k < threads; ++k)
+        if (!started[k]) gather_worker(&jobs[k]);         /* share 0, and the share of a thread that could not be started */
+    for (int k = 0; k < threads; ++k)
+        if (started[k]) pthread_join(th[k], NULL);
+    int64_t n_points = 0, n_lists = 0;
+    for (int k = 0; k < threads; ++k) n_points += jobs[k].n_points;
+    for (int i = 0; i < n; ++i) n_lists += count[i] > 0;
+    double *points = (double *)malloc((size_t)(n_points > 0 ? n_points : 1) * (size_t)dims * sizeof(double));
+    double *radius = (double *)malloc((size_t)(n_points > 0 ? n_points : 1) * sizeof(double));
+    int64_t *first = (int64_t *)malloc((size_t)(n_lists + 1) * sizeof(int64_t));
+    double *centers = (double *)malloc((size_t)(n_lists > 0 ? n_lists : 1) * (size_t)dims * sizeof(double));
+    double *radii = (double *)malloc((size_t)(n_lists > 0 ? n_lists : 1) * sizeof(double));
+    int64_t at = 0;
+    for (int k = 0; k < threads; ++k) {
+        if (jobs[k].n_points > 0) {
+            memcpy(points + at * dims, jobs[k].points, (size_t)jobs[k].n_points * (size_t)dims * sizeof(double));
+            memcpy(radius + at, jobs[k].radius, (size_t)jobs[k].n_points * sizeof(double));
+        }
+        at += jobs[k].n_points;
+        free(jobs[k].points);
+        free(jobs[k].radius);
+    }
+    first[0] = 0;
+    for (int i = 0, l = 0; i < n; ++i)
+        if (count[i] > 0) { first[l + 1] = first[l] + count[i]; ++l; }
+    const double gathered = ms_since(&t0);
+    int rc = 0;
+    if (n_lists > 0) {
+        clock_gettime(CLOCK_MONOTONIC, &t0);
+        rc = fit(fit_arg, dims, n_lists, first, points, radius, centers, radii, err, err_len);
+        if (stats) { stats->fit_ms += ms_since(&t0); stats->calls += 1; }
+    }
+    if (stats) { stats->gather_ms += gathered; stats->points += n_points; }
+    if (rc == 0) {
+        for (int i = 0, l = 0; i < n; ++i) {
+            object *o = objs[i];
+            if (count[i] == 0) {                        /* object_get_bounds: an empty point list marks an infinite object */
+                o->bounds.radius = -1.0;
+                continue;
+            }
+            memcpy(o->bounds.center.v, centers + (int64_t)l * dims, (size_t)dims * sizeof(double));
+            o->bounds.radius = radii[l];
+            if (o->bounds.radius > 0.0) o->bounds.radius += EPSILON;
+            PUSH_OBJ(fitted->objs, fitted->n, fitted->cap, o);
+            ++l;
+        }
+    }
+    free(points); free(radius); free(first); free(centers); free(radii); free(count);
+    return rc ? -1 : 0;
+}
+
+/* the objects of `fitted` counted once each */
+static int64_t count_distinct(object **fitted, int n)
+{
+    qsort(fitted, (size_t)n, sizeof(object *), cmp_object_ptr);
+    int64_t k = 0;
+    for (int i = 0; i < n; ++i) k += (i == 0 || fitted[i] != fitted[i - 1]);
+    return k;
+}
+
 int ndt_flatten_scene(scene *scn, ndt_flat_builder *fb, char *err, int err_len)
 {
     return ndt_flatten_scene_mt(scn, fb, err, err_len, 1);
@@ -142,18 +276,50 @@ int ndt_flatten_scene(scene *scn, ndt_flat_builder *fb, char *err, int err_len)
 
 int ndt_flatten_scene_mt(scene *scn, ndt_flat_builder *fb, char *err, int err_len, int threads)
 {
+    return ndt_flatten_scene_fit(scn, fb, err, err_len, threads, NULL, NULL, NULL);
+}
+
+int ndt_flatten_scene_fit(scene *scn, ndt_flat_builder *fb, char *err, int err_len, int threads, ndt_fit_fn fit_fn, void *fit_arg,
+                          ndt_fit_stats *stats)
+{
     const int dims = scn->dimensions;
     memset(fb, 0, sizeof(*fb));
     if (err_len > 0) err[0] = '\0';
+    if (stats) memset(stats, 0, sizeof(*stats));
+    /* with a fitter: every object it fitted this frame (ndt_fit_stats.spheres counts objects, not calls) */
+    object_list fitted = { NULL, 0, 0 };
 
     /* ndt.c:1899-1908 */
     ndt_kd_tree kd;
     ndt_kd_init(&kd, dims);
+    if (fit_fn) {
+        /* (a) the fits of the loop below, ahead of it and in one batch: ndt_kd_add_object looks at an object's bounding points,
+         * not at its sphere, and a fit reads and writes its object alone */
+        int n_top = 0, cap_top = 0;
+        object **top = NULL;
+        for (int i = 0; i < scn->num_objects; ++i)
+            if (ndt_object_type_id(scn->object_ptrs[i]) != NDT_TYPE_CLUSTER) {
+                PUSH_OBJ(top, n_top, cap_top, scn->object_ptrs[i]);
+            }
+        /* (the same object twice in the scene's list is fitted twice by the loop, to the same sphere: once is enough) */
+        qsort(top, (size_t)n_top, sizeof(object *), cmp_object_ptr);
+        int n_uniq = 0;
+        for (int i = 0; i < n_top; ++i)
+            if (n_uniq == 0 || top[n_uniq - 1] != top[i]) top[n_uniq++] = top[i];
+        const int frc = fit_batch(top, n_uniq, dims, threads, fit_fn, fit_arg, stats, &fitted, err, err_len);
+        free(top);
+        if (frc != 0) { free(fitted.objs); ndt_kd_free(&kd); return -1; }
+    }
     for (int i = 0; i < scn->num_objects; ++i) {
         /* (ndt.c:1905 fits every top-level object.  A cluster's own sphere -- one search over the bounding points of all its
          * members, 172 000 of them for the 8-D hypercube -- is never looked at again: the kd-tree takes its members one by
          * one, object.c:633-681, and nothing else of this path reads it.  Not fitted.) */
-        if (ndt_object_type_id(scn->object_ptrs[i]) != NDT_TYPE_CLUSTER) object_get_bounds(scn->object_ptrs[i]);
+        if (!fit_fn && ndt_object_type_id(scn->object_ptrs[i]) != NDT_TYPE_CLUSTER) {
+            struct timespec t0;
+            if (stats) clock_gettime(CLOCK_MONOTONIC, &t0);
+            object_get_bounds(scn->object_ptrs[i]);
+            if (stats) stats->fit_ms += ms_since(&t0);
+        }
         ndt_kd_add_object(&kd, scn->object_ptrs[i]);
     }
     ndt_kd_build(&kd);
@@ -161,7 +327,7 @@ int ndt_flatten_scene_mt(scene *scn, ndt_flat_builder *fb, char *err, int err_le
     camera_aim(&scn->cam);              /* ndt.c:1925 */
 
     int rc = 0;
-    if (threads > 1) {
+    if (threads > 1 || fit_fn) {
         /* the lazy fits of the two loops below, ahead of them and in parallel */
         int n_fit = 0, cap_fit = kd.n_items;
         object **fit = (object **)malloc((size_t)(cap_fit > 0 ? cap_fit : 1) * sizeof(object *));
@@ -186,14 +352,43 @@ int ndt_flatten_scene_mt(scene *scn, ndt_flat_builder *fb, char *err, int err_le
         int n_uniq = 0;
         for (int i = 0; i < n_fit; ++i)
             if (n_uniq == 0 || fit[n_uniq - 1] != fit[i]) fit[n_uniq++] = fit[i];
-        fit_bounds_parallel(fit, n_uniq, threads);
+        if (!fit_fn) {
+            struct timespec t0;
+            if (stats) clock_gettime(CLOCK_MONOTONIC, &t0);
+            fit_bounds_parallel(fit, n_uniq, threads);
+            if (stats) stats->fit_ms += ms_since(&t0);
+        } else {
+            /* (b) what fit_worker takes: the objects of the list that are not fitted yet */
+            int n_lazy = 0;
+            for (int i = 0; i < n_uniq; ++i)
+                if (fit[i]->bounds.radius == 0) fit[n_lazy++] = fit[i];
+            if (fit_batch(fit, n_lazy, dims, threads, fit_fn, fit_arg, stats, &fitted, err, err_len) != 0) rc = -1;
+            /* (c) the hcubes' own spheres, which ndt_hcube_prepare reset when it built the faces */
+            n_lazy = 0;
+            for (int i = 0; i < kd.n_items && rc == 0; ++i)
+                if (ndt_object_type_id(kd.items[i].obj) == NDT_OBJ_HCUBE && kd.items[i].obj->bounds.radius == 0) fit[n_lazy++] = kd.items[i].obj;
+            qsort(fit, (size_t)n_lazy, sizeof(object *), cmp_object_ptr);
+            n_uniq = 0;
+            for (int i = 0; i < n_lazy; ++i)
+                if (n_uniq == 0 || fit[n_uniq - 1] != fit[i]) fit[n_uniq++] = fit[i];
+            if (rc == 0 && fit_batch(fit, n_uniq, dims, threads, fit_fn, fit_arg, stats, &fitted, err, err_len) != 0) rc = -1;
+        }
         free(fit);
     }
+    if (stats && fit_fn) stats->spheres = count_distinct(fitted.objs, fitted.n);
+    free(fitted.objs);
+    /* (with a fitter the two loops below find every radius non-zero, except where a fit returned 0 -- coincident points: that
+     * still reads as "not fitted", and they fit it again on the host, to the same sphere, as they do without a fitter) */
     /* kd items first, in id order: the visit mask is indexed by this position */
     for (int i = 0; i < kd.n_items && rc == 0; ++i) {
         object *o = kd.items[i].obj;
         if (ndt_object_type_id(o) == NDT_OBJ_HCUBE) ndt_hcube_prepare(o);      /* resets its radius to 0 */
-        if (o->bounds.radius == 0) object_get_bounds(o);                        /* object.c:609-615 */
+        if (o->bounds.radius == 0) {                                            /* object.c:609-615 */
+            struct timespec t0;
+            if (stats) clock_gettime(CLOCK_MONOTONIC, &t0);
+            object_get_bounds(o);
+            if (stats) stats->fit_ms += ms_since(&t0);
+        }
         if (add_object(fb, o, -1, dims, err, err_len) < 0) rc = -1;
     }
     /* then the nested primitives */
@@ -204,7 +399,12 @@ int ndt_flatten_scene_mt(scene *scn, ndt_flat_builder *fb, char *err, int err_le
         fb->objects[i].n_obj = o->n_obj;
         for (int k = 0; k < o->n_obj && rc == 0; ++k) {
             object *face = o->obj[k];
-            if (face->bounds.radius == 0) object_get_bounds(face);
+            if (face->bounds.radius == 0) {
+                struct timespec t0;
+                if (stats) clock_gettime(CLOCK_MONOTONIC, &t0);
+                object_get_bounds(face);
+                if (stats) stats->fit_ms += ms_since(&t0);
+            }
             int idx = add_object(fb, face, i, dims, err, err_len);
             if (idx < 0) { rc = -1; break; }
             GROW(fb->refs, fb->n_refs, fb->cap_refs, 1, int);

@@ -58,6 +58,27 @@ typedef struct {
  * flattens.  Returns 0, or -1 with a message in `err` when the scene cannot go to the device. */
 int ndt_flatten_scene(scene *scn, ndt_flat_builder *fb, char *err, int err_len);
 int ndt_flatten_scene_mt(scene *scn, ndt_flat_builder *fb, char *err, int err_len, int threads);
+/* The same with the bounding-sphere fits delegated: `fit` takes a batch of point lists in the flat form of ndt_hip_fit_spheres
+ * (include/ndt_hip.h) and returns 0 or, with the message in `err`, non-zero.  It is called at most three times a frame: (a) the
+ * top-level objects before the kd build, (b) the kd items and hcube faces the loops would fit lazily, (c) the hcubes' own
+ * spheres, which their faces reset.  fit == NULL: ndt_flatten_scene_mt.  `stats` (may be NULL) says what the frame fitted. */
+typedef int (*ndt_fit_fn)(void *arg, int dims, int64_t n_lists, const int64_t *first, const double *points, const double *point_radius,
+                          double *centers, double *radii, char *err, int err_len);
+typedef struct {
+    int64_t spheres;            /* objects whose sphere `fit` made */
+    int64_t points;             /* bounding points handed to it */
+    int calls;
+    double gather_ms, fit_ms;   /* collecting the points (bounding_points of every object) / inside `fit`; without a fitter
+                                 * fit_ms is the time of the host fits (points and search together) */
+} ndt_fit_stats;
+int ndt_flatten_scene_fit(scene *scn, ndt_flat_builder *fb, char *err, int err_len, int threads, ndt_fit_fn fit, void *fit_arg,
+                          ndt_fit_stats *stats);
+/* ndt_render.c: where the bounding spheres of the frames this process flattens for rendering are fitted -- 0 on the host
+ * (default), 1 on the GPU (`ndt_hip --fit gpu`) -- and ndt_flatten_scene_fit with context 0 of the calling thread as the
+ * fitter (the contexts are created first).  It prints `fitted K bounding spheres on GPU D in L launches`; there is no
+ * fallback: without a device, or with a scene the device fit refuses, it fails with the reason in `err`. */
+void ndt_render_fit_on_gpu(int on);
+int ndt_flatten_scene_gpu_fit(scene *scn, ndt_flat_builder *fb, char *err, int err_len, int threads, ndt_fit_stats *stats);
 void ndt_flat_builder_free(ndt_flat_builder *fb);
 int ndt_write_ndtscene(const ndt_flat_scene *fs, const char *name, const char *path);
 

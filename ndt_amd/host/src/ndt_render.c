@@ -48,6 +48,41 @@ static int have_contexts(void)
     return 1;
 }
 
+/* ---- the frame's bounding-sphere fits on the GPU (ndt_hip_fit_spheres) */
+static int g_fit_on_gpu = 0;                /* process-wide, set before any frame: `ndt_hip --fit gpu` */
+static __thread int g_fit_launches = 0;
+
+void ndt_render_fit_on_gpu(int on) { g_fit_on_gpu = on != 0; }
+
+static int device_fit(void *arg, int dims, int64_t n_lists, const int64_t *first, const double *points, const double *point_radius,
+                      double *centers, double *radii, char *err, int err_len)
+{
+    ndt_hip_ctx *ctx = (ndt_hip_ctx *)arg;
+    const int rc = ndt_hip_fit_spheres(ctx, dims, n_lists, first, points, point_radius, centers, radii);
+    if (rc != NDT_OK) {
+        snprintf(err, (size_t)err_len, "bounding spheres on the GPU: %s", ndt_hip_last_error());
+        return rc;
+    }
+    g_fit_launches += ndt_hip_fit_launches(ctx);
+    return 0;
+}
+
+int ndt_flatten_scene_gpu_fit(scene *scn, ndt_flat_builder *fb, char *err, int err_len, int threads, ndt_fit_stats *stats)
+{
+    ndt_fit_stats local;
+    if (!stats) stats = &local;
+    memset(fb, 0, sizeof(*fb));
+    /* the contexts before the scene: context 0 is the fitter (-j K: every worker thread has its own; -g N: the first of N) */
+    if (!have_contexts()) {
+        snprintf(err, (size_t)err_len, "bounding spheres on the GPU: %s", ndt_hip_last_error());
+        return -1;
+    }
+    g_fit_launches = 0;
+    if (ndt_flatten_scene_fit(scn, fb, err, err_len, threads, device_fit, g_ctx[0], stats) != 0) return -1;
+    printf("fitted %lld bounding spheres on GPU %d in %d launches\n", (long long)stats->spheres, ndt_hip_device(g_ctx[0]), g_fit_launches);
+    return 0;
+}
+
 int ndt_render_image(scene *scn, int width, int height, int threads, int max_optic_depth, double *rgba)
 {
     return ndt_render_image_aa(scn, width, height, threads, -1, -1, max_optic_depth, rgba);
@@ -70,7 +105,9 @@ static int render_any(scene *scn, int width, int height, int samples, int aa_dif
     const int timing = getenv("NDT_HOST_TIMING") != NULL;
     struct timespec ts0, ts1, ts2, ts3;
     if (timing) clock_gettime(CLOCK_MONOTONIC, &ts0);
-    if (ndt_flatten_scene_mt(scn, &fb, err, sizeof(err), threads) != 0) {
+    ndt_fit_stats fit;
+    if ((g_fit_on_gpu ? ndt_flatten_scene_gpu_fit(scn, &fb, err, sizeof(err), threads, &fit)
+                      : ndt_flatten_scene_fit(scn, &fb, err, sizeof(err), threads, NULL, NULL, timing ? &fit : NULL)) != 0) {
         fprintf(stderr, "ndt_render_image: %s\n", err);
         ndt_flat_builder_free(&fb);
         return 0;
@@ -110,8 +147,15 @@ static int render_any(scene *scn, int width, int height, int samples, int aa_dif
     if (timing) {
         clock_gettime(CLOCK_MONOTONIC, &ts3);
 #define NDT_MS(a, b) (((b).tv_sec - (a).tv_sec) * 1e3 + ((b).tv_nsec - (a).tv_nsec) * 1e-6)
-        fprintf(stderr, "ndt_render_image: bounds + kd-tree + flatten %.2f ms, upload %.2f ms, render + image to host %.2f ms\n",
-                NDT_MS(ts0, ts1), NDT_MS(ts1, ts2), NDT_MS(ts2, ts3));
+        /* the first figure split: the sphere fits (on the GPU: gathering the bounding points / the fit calls) and the rest */
+        char share[160];
+        if (g_fit_on_gpu)
+            snprintf(share, sizeof(share), "gpu fits: points gathered %.2f + fit %.2f, rest %.2f", fit.gather_ms, fit.fit_ms,
+                     NDT_MS(ts0, ts1) - fit.gather_ms - fit.fit_ms);
+        else
+            snprintf(share, sizeof(share), "host fits %.2f, rest %.2f", fit.fit_ms, NDT_MS(ts0, ts1) - fit.fit_ms);
+        fprintf(stderr, "ndt_render_image: bounds + kd-tree + flatten %.2f ms (%s), upload %.2f ms, render + image to host %.2f ms\n",
+                NDT_MS(ts0, ts1), share, NDT_MS(ts1, ts2), NDT_MS(ts2, ts3));
     }
     ndt_flat_builder_free(&fb);
     return ok;
