@@ -14,6 +14,11 @@ For every case this drives oracle/_ref/ndt_ref_shim (oracle/ref_shim.c) to
   * answer seeded trace_kd queries                           -> <case>.npz : kat_in, kat_out
   * count trace_kd calls during the render                   -> <case>.json
 The fixtures are data (inputs + expected outputs); no reference source text is stored.
+
+The known-answer rays made here are drawn at random in the scene box (make_kat_rays) or aimed into the bounding ball of a kd
+leaf's items (leaf_targets).  Above 5-D neither meets a thin object -- a plate, a triangle, a disk, a face of the hcube -- often
+enough to test its intersector: in 10-D .. 12-D they are answered by the hyperplane or by nothing.  The rays that are aimed at
+the objects themselves, class by class, are made by make_golden_aimed.py (aim_zoo3d .. aim_zoo12d, on the zoo scenes stored here).
 """
 import gzip
 import json
@@ -64,6 +69,9 @@ CASES = {
     "zoo3d_mirror": dict(scene="parity_zoo", dims=3, res=(64, 48), depth=128, fb=True, kat=512, config="mirror"),
     "zoo5d_f2": dict(scene="parity_zoo", dims=5, res=(48, 27), depth=8, fb=True, kat=512, frame=2),
     "zoo6d": dict(scene="parity_zoo", dims=6, res=(40, 24), depth=5, fb=True, kat=256),
+    # the two dimensions that had no zoo: their known-answer rays are the aimed ones (make_golden_aimed.py: aim_zoo7d, aim_zoo8d)
+    "zoo7d": dict(scene="parity_zoo", dims=7, res=(40, 24), depth=5, fb=True, kat=0),
+    "zoo8d": dict(scene="parity_zoo", dims=8, res=(40, 24), depth=5, fb=True, kat=0),
     # an animated frame: rotated hypercube, different tree
     "c1_hypercube3d_f37": dict(scene="hypercube", dims=3, res=(64, 64), depth=128, fb=True, kat=0, frame=37),
     # full BASELINE resolution, 8-bit (what the reference writes to PNG)
