@@ -261,6 +261,38 @@ int ndt_hip_fit_spheres(ndt_hip_ctx *ctx, int32_t dims, int64_t n_lists, const i
 /* Kernel launches the context's last ndt_hip_fit_spheres call made (one per group of list lengths; 0 for an empty batch). */
 int ndt_hip_fit_launches(ndt_hip_ctx *ctx);
 
+/* kd_tree_build (kd-tree.c:421-477) for the item boxes of a frame, on ctx's device and stream: the exhaustive split search of
+ * kd_tree_split_node (kd-tree.c:294-419) level by level, every candidate of every open node scored at once.  Input: the boxes
+ * object_kdlist_add makes (object.c:633-681), lower / upper: n_items x dims, and one byte per item, finite != 0 for the
+ * reference's `bounds.radius >= 0` (kd-tree.c:448-463).  Inverted boxes (lower = DBL_MAX, upper = -DBL_MAX) are legal and go
+ * through the search's own comparisons.  The tree is the host builder's, byte for byte, in the arrays an ndt_flat_scene
+ * carries: nodes in preorder (left = node + 1; a leaf's items are leaf_refs[first .. first + num), in list order), inf_refs
+ * (the other items, ascending) and the root box (DBL_MAX / -DBL_MAX without a finite item).  No item, or no finite one: one
+ * empty leaf.
+ * Two calls, because the tree's size is not known in advance: the build leaves the tree in the context and fills *counts;
+ * the fetch copies it into arrays of those sizes (nodes: n_kd_nodes, leaf_refs: n_leaf_refs, inf_refs: n_inf, bb_*: dims).
+ * The tree stays fetchable until the context's next build.  Synchronous.  No scene has to be uploaded.
+ * Device buffers belong to the context, only grow and are reused.  Growth policy: a level's node, reference and candidate
+ * counts are known before anything of it is written; a buffer that is too small becomes max(what is needed, twice its size),
+ * its contents moved, and nothing is ever written past a buffer.  Upper bound: 2^30 item references over all nodes of the
+ * tree under construction (4 GiB), 2^26 nodes; beyond that, or when the device has no such memory, NDT_E_NOMEM with the size
+ * that was needed -- never a partial tree.
+ * NDT_E_INVALID, before any device call: dims outside 3..12, n_items < 0, a NULL array or context, a NaN bound (the caller
+ * builds those itself).  NDT_E_UNSUPPORTED: the tree is deeper than the traversal stack of the trace kernels holds (40 levels;
+ * the upload refuses such a tree as well). */
+typedef struct ndt_kd_counts {
+    int32_t n_kd_nodes, n_leaf_refs, n_inf;
+    int32_t depth;              /* levels of the tree: 1 for a single leaf */
+    int32_t launches;           /* kernel launches of the build: at most three a level */
+    int32_t grows;              /* device buffers that had to be replaced by larger ones during the build */
+} ndt_kd_counts;
+int ndt_hip_build_kdtree(ndt_hip_ctx *ctx, int32_t dims, int32_t n_items, const double *lower, const double *upper,
+                         const uint8_t *finite, ndt_kd_counts *counts);
+int ndt_hip_kdtree_fetch(ndt_hip_ctx *ctx, ndt_flat_kdnode *nodes, int32_t *leaf_refs, int32_t *inf_refs,
+                         double *bb_lower, double *bb_upper);
+/* Kernel launches the context's last build made. */
+int ndt_hip_kd_launches(ndt_hip_ctx *ctx);
+
 /* Quantise a double image like the reference does at save time: pixel_d2c (image.h:36-39),
  * (unsigned char)(sqrt(clamp01(x))*255) per channel.  d_rgba: device, n_pixels*4 doubles;
  * d_rgba8: device, n_pixels*4 bytes. */

@@ -9,6 +9,7 @@
 //   ndt_render.hip   ndt_hip_render*: argument checks and the choice between the three
 //   ndt_multi.hip    one frame over several contexts / devices
 //   ndt_fit.hip      ndt_hip_fit_spheres: the bounding-sphere fits of a frame (batched Nelder-Mead), kernel and launcher
+//   ndt_kd.hip       ndt_hip_build_kdtree: the kd-tree of a frame's item boxes, level by level; kernels, launcher and C ABI
 #pragma once
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
@@ -40,6 +41,17 @@ using namespace ndt_impl;
         hipError_t e_ = (expr);                                                                    \
         if (e_ != hipSuccess) return fail(NDT_E_DEVICE, "%s: %s", #expr, hipGetErrorString(e_));   \
     } while (0)
+
+// ndt_hip_build_kdtree (ndt_kd.hip): grow-only device buffers, reused by the next build, and the last tree in its final layout
+struct KdState {
+    void *d_bounds = nullptr, *d_refs = nullptr, *d_nodes = nullptr, *d_slices = nullptr, *d_slice_off[2] = { nullptr, nullptr }, *d_totals = nullptr;
+    size_t bounds_bytes = 0, refs_bytes = 0, nodes_bytes = 0, slices_bytes = 0, slice_off_bytes[2] = { 0, 0 }, totals_bytes = 0;
+    std::vector<ndt_flat_kdnode> nodes;         // preorder
+    std::vector<int32_t> leaf_refs, inf_refs;
+    std::vector<double> bb_lower, bb_upper;
+    int dims = 0, depth = 0, launches = 0, grows = 0;
+    bool valid = false;
+};
 
 struct ndt_hip_ctx {
     int device = 0;
@@ -124,6 +136,7 @@ struct ndt_hip_ctx {
     void *d_fit = nullptr;          // ndt_hip_fit_spheres: jobs, points and spheres of a batch (grow-only, reused across frames)
     size_t d_fit_bytes = 0;
     int fit_launches = 0;           // kernel launches of the last ndt_hip_fit_spheres call
+    KdState kd;                     // ndt_hip_build_kdtree
     void *d_out = nullptr;          // staging for ndt_hip_render (host output)
     size_t d_out_bytes = 0;
     void *d_shard = nullptr;        // ndt_hip_render_multi: this context's rows before they are pushed into the frame
@@ -196,6 +209,10 @@ void free_async(ndt_hip_ctx *ctx);
 // ndt_fit.hip: bounds_list_optimal for n_lists checked point lists (first[n_lists] = number of points); synchronous
 int fit_spheres_device(ndt_hip_ctx *ctx, int dims, long long n_lists, const int64_t *first, const double *points, const double *point_radius,
                        double *centers, double *radii);
+
+// ndt_kd.hip: kd_tree_build for checked item boxes (no NaN), into ctx->kd; synchronous
+int build_kdtree_device(ndt_hip_ctx *ctx, int dims, int n_items, const double *lower, const double *upper, const unsigned char *finite);
+void free_kd(ndt_hip_ctx *ctx);
 
 // ndt_aa.hip / ndt_sampled.hip
 int render_antialiased(ndt_hip_ctx *ctx, const ndt_render_params *p, void *d_rgba, ndt_render_stats &total, void *d_depth = nullptr);

@@ -23,6 +23,7 @@ API_SYMBOLS = [
     "ndt_hip_render_multi", "ndt_hip_device_count", "ndt_hip_device", "ndt_hip_set_option", "ndt_hip_multi_path_taken",
     "ndt_hip_item_boxes", "ndt_hip_render_rgba8_async", "ndt_hip_render_rgba8_wait",
     "ndt_hip_fit_spheres", "ndt_hip_fit_launches",
+    "ndt_hip_build_kdtree", "ndt_hip_kdtree_fetch", "ndt_hip_kd_launches",
 ]
 
 IMAGE_F64, IMAGE_RGBA8 = 0, 1      # enum ndt_image_format
@@ -92,8 +93,28 @@ def load_library():
     if hasattr(lib, "ndt_hip_fit_spheres"):         # (absent from earlier builds, which profiles/ab_libs.sh loads to compare)
         lib.ndt_hip_fit_spheres.argtypes = [C.c_void_p, C.c_int32, C.c_int64] + [C.c_void_p] * 5
         lib.ndt_hip_fit_launches.argtypes = [C.c_void_p]
+    if hasattr(lib, "ndt_hip_build_kdtree"):
+        lib.ndt_hip_build_kdtree.argtypes = [C.c_void_p, C.c_int32, C.c_int32] + [C.c_void_p] * 4
+        lib.ndt_hip_kdtree_fetch.argtypes = [C.c_void_p] * 6
+        lib.ndt_hip_kd_launches.argtypes = [C.c_void_p]
     _lib = lib
     return lib
+
+
+class KdCounts(C.Structure):
+    """ndt_kd_counts: what ndt_hip_build_kdtree says about the tree it left in the context"""
+    _fields_ = [("n_kd_nodes", C.c_int32), ("n_leaf_refs", C.c_int32), ("n_inf", C.c_int32), ("depth", C.c_int32),
+                ("launches", C.c_int32), ("grows", C.c_int32)]
+
+
+def pack_boxes(dims, lower, upper, finite):
+    """The flat arrays ndt_hip_build_kdtree / ndt_host_build_kdtree take: (n, lower [n, dims], upper [n, dims], finite uint8 [n])."""
+    lower = np.ascontiguousarray(lower, dtype=np.float64).reshape(-1, int(dims))
+    upper = np.ascontiguousarray(upper, dtype=np.float64).reshape(-1, int(dims))
+    finite = np.ascontiguousarray(np.asarray(finite) != 0, dtype=np.uint8).reshape(-1)
+    if not lower.shape == upper.shape == (finite.shape[0], int(dims)):
+        raise ValueError("lower and upper must be [n, %d] and finite [n]" % dims)
+    return finite.shape[0], lower, upper, finite
 
 
 def pack_point_lists(dims, lists):
@@ -321,6 +342,29 @@ class NdtHip:
     def fit_launches(self):
         """ndt_hip_fit_launches: kernel launches of the last fit_spheres call."""
         return int(self.lib.ndt_hip_fit_launches(self.ctx))
+
+    def build_kdtree(self, dims, lower, upper, finite):
+        """ndt_hip_build_kdtree + ndt_hip_kdtree_fetch: the reference's kd-tree (kd-tree.c:294-477) of the item boxes lower / upper
+        [n, dims] on this context's GPU, byte-identical to the host builder's.  Returns (nodes, leaf_refs, inf_refs, bb_lower,
+        bb_upper): nodes in preorder with the dtype of FlatKdNode, the rest int32 / float64; self.kd_counts keeps the counts."""
+        from .flat_scene import FlatKdNode
+        n, lower, upper, finite = pack_boxes(dims, lower, upper, finite)
+        counts = KdCounts()
+        self._check(self.lib.ndt_hip_build_kdtree(self.ctx, int(dims), n, lower.ctypes.data, upper.ctypes.data, finite.ctypes.data,
+                                                  C.addressof(counts)))
+        self.kd_counts = counts
+        nodes = np.zeros(counts.n_kd_nodes, dtype=np.dtype(FlatKdNode))
+        leaf_refs = np.zeros(counts.n_leaf_refs, dtype=np.int32)
+        inf_refs = np.zeros(counts.n_inf, dtype=np.int32)
+        bb_lower, bb_upper = np.zeros(int(dims)), np.zeros(int(dims))
+        # (an empty array's buffer is still a valid address: the library copies nothing into it)
+        self._check(self.lib.ndt_hip_kdtree_fetch(self.ctx, nodes.ctypes.data, leaf_refs.ctypes.data, inf_refs.ctypes.data,
+                                                  bb_lower.ctypes.data, bb_upper.ctypes.data))
+        return nodes, leaf_refs, inf_refs, bb_lower, bb_upper
+
+    def kd_launches(self):
+        """ndt_hip_kd_launches: kernel launches of the last build_kdtree call."""
+        return int(self.lib.ndt_hip_kd_launches(self.ctx))
 
     def trace_rays(self, rays):
         """Batch of trace_kd queries; rays: (n, 2*dims+1) = o, v, dist_limit per row."""

@@ -282,10 +282,19 @@ int ndt_flatten_scene_mt(scene *scn, ndt_flat_builder *fb, char *err, int err_le
 int ndt_flatten_scene_fit(scene *scn, ndt_flat_builder *fb, char *err, int err_len, int threads, ndt_fit_fn fit_fn, void *fit_arg,
                           ndt_fit_stats *stats)
 {
+    return ndt_flatten_scene_with(scn, fb, err, err_len, threads, fit_fn, fit_arg, stats, NULL, NULL, NULL);
+}
+
+int ndt_flatten_scene_with(scene *scn, ndt_flat_builder *fb, char *err, int err_len, int threads, ndt_fit_fn fit_fn, void *fit_arg,
+                           ndt_fit_stats *stats, ndt_kd_fn kd_fn, void *kd_arg, ndt_kd_stats *kd_stats)
+{
     const int dims = scn->dimensions;
     memset(fb, 0, sizeof(*fb));
     if (err_len > 0) err[0] = '\0';
     if (stats) memset(stats, 0, sizeof(*stats));
+    if (kd_stats) memset(kd_stats, 0, sizeof(*kd_stats));
+    ndt_host_kdtree built;              /* with a builder: the tree it made */
+    memset(&built, 0, sizeof(built));
     /* with a fitter: every object it fitted this frame (ndt_fit_stats.spheres counts objects, not calls) */
     object_list fitted = { NULL, 0, 0 };
 
@@ -322,7 +331,28 @@ int ndt_flatten_scene_fit(scene *scn, ndt_flat_builder *fb, char *err, int err_l
         }
         ndt_kd_add_object(&kd, scn->object_ptrs[i]);
     }
-    ndt_kd_build(&kd);
+    {
+        struct timespec t0;
+        clock_gettime(CLOCK_MONOTONIC, &t0);
+        if (!kd_fn) ndt_kd_build(&kd);
+        else {
+            /* the boxes flat, and what kd_tree_build asks every item's object at this point (kd-tree.c:448-463: cluster members
+             * are not fitted yet, their radius of 0 counts as finite) */
+            const size_t n = (size_t)(kd.n_items > 0 ? kd.n_items : 1);
+            double *lower = (double *)malloc(n * (size_t)dims * sizeof(double)), *upper = (double *)malloc(n * (size_t)dims * sizeof(double));
+            unsigned char *finite = (unsigned char *)malloc(n);
+            for (int i = 0; i < kd.n_items; ++i) {
+                memcpy(lower + (size_t)i * dims, kd.items[i].lower, (size_t)dims * sizeof(double));
+                memcpy(upper + (size_t)i * dims, kd.items[i].upper, (size_t)dims * sizeof(double));
+                finite[i] = kd.items[i].obj->bounds.radius >= 0.0;
+            }
+            const int krc = kd_fn(kd_arg, dims, kd.n_items, lower, upper, finite, &built, err, err_len);
+            free(lower); free(upper); free(finite);
+            if (kd_stats) kd_stats->calls += 1;
+            if (krc != 0) { ndt_host_kdtree_free(&built); free(fitted.objs); ndt_kd_free(&kd); return -1; }
+        }
+        if (kd_stats) kd_stats->build_ms += ms_since(&t0);
+    }
     scene_validate_objects(scn);        /* ndt.c:1913 */
     camera_aim(&scn->cam);              /* ndt.c:1925 */
 
@@ -412,18 +442,26 @@ int ndt_flatten_scene_fit(scene *scn, ndt_flat_builder *fb, char *err, int err_l
         }
     }
     if (rc == 0) {
-        fb->n_nodes = count_nodes(kd.root);
-        fb->nodes = (ndt_flat_kdnode *)calloc((size_t)(fb->n_nodes > 0 ? fb->n_nodes : 1), sizeof(ndt_flat_kdnode));
-        if (kd.root) flatten_node(fb, kd.root, 0);
-        fb->n_inf = kd.n_inf;
-        fb->inf_refs = (int *)malloc((size_t)(kd.n_inf > 0 ? kd.n_inf : 1) * sizeof(int));
-        memcpy(fb->inf_refs, kd.inf_ids, (size_t)kd.n_inf * sizeof(int));
+        if (kd_fn) {
+            /* the builder's arrays are the flat scene's (ndt_flat_builder_free frees them) */
+            fb->n_nodes = built.n_kd_nodes;     fb->nodes = built.nodes;            built.nodes = NULL;
+            fb->n_leaf_refs = fb->cap_leaf_refs = built.n_leaf_refs;
+            fb->leaf_refs = built.leaf_refs;    built.leaf_refs = NULL;
+            fb->n_inf = built.n_inf;            fb->inf_refs = built.inf_refs;      built.inf_refs = NULL;
+        } else {
+            fb->n_nodes = count_nodes(kd.root);
+            fb->nodes = (ndt_flat_kdnode *)calloc((size_t)(fb->n_nodes > 0 ? fb->n_nodes : 1), sizeof(ndt_flat_kdnode));
+            if (kd.root) flatten_node(fb, kd.root, 0);
+            fb->n_inf = kd.n_inf;
+            fb->inf_refs = (int *)malloc((size_t)(kd.n_inf > 0 ? kd.n_inf : 1) * sizeof(int));
+            memcpy(fb->inf_refs, kd.inf_ids, (size_t)kd.n_inf * sizeof(int));
+        }
 
         ndt_flat_scene *fs = &fb->fs;
         fs->abi_version = NDT_HIP_ABI_VERSION;
         fs->dims = dims;
-        fs->bb_lower_off = push_raw(fb, kd.bb_lower, dims);
-        fs->bb_upper_off = push_raw(fb, kd.bb_upper, dims);
+        fs->bb_lower_off = push_raw(fb, kd_fn ? built.bb_lower : kd.bb_lower, dims);
+        fs->bb_upper_off = push_raw(fb, kd_fn ? built.bb_upper : kd.bb_upper, dims);
         fs->cam_type = (int)scn->cam.type;
         fs->cam_focal_distance = scn->cam.focal_distance;
         fs->cam_pos_off = push_vec(fb, &scn->cam.pos, dims);
@@ -472,6 +510,7 @@ int ndt_flatten_scene_fit(scene *scn, ndt_flat_builder *fb, char *err, int err_l
         fs->leaf_refs = fb->leaf_refs; fs->n_leaf_refs = fb->n_leaf_refs;
         fs->inf_refs = fb->inf_refs; fs->n_inf = fb->n_inf;
     }
+    ndt_host_kdtree_free(&built);
     ndt_kd_free(&kd);
     return rc;
 }

@@ -40,6 +40,19 @@ void ndt_kd_add_object(ndt_kd_tree *t, object *obj);        /* object_kdlist_add
 void ndt_kd_build(ndt_kd_tree *t);                          /* kd_tree_build, kd-tree.c:421-477 */
 void ndt_kd_free(ndt_kd_tree *t);
 
+/* kd_tree_build over flat arrays (ndt_kdtree.c): the CPU twin of ndt_hip_build_kdtree, the specification the device build is
+ * compared with.  The arrays are malloc'ed: whoever takes the tree frees them with free() or ndt_host_kdtree_free.
+ * Returns 0, or -1 for arguments the device call refuses as well. */
+typedef struct {
+    int32_t n_kd_nodes, n_leaf_refs, n_inf;
+    int32_t depth;                  /* levels: 1 for a single leaf */
+    ndt_flat_kdnode *nodes;         /* preorder */
+    int32_t *leaf_refs, *inf_refs;
+    double *bb_lower, *bb_upper;    /* dims each */
+} ndt_host_kdtree;
+int ndt_host_build_kdtree(int dims, int n_items, const double *lower, const double *upper, const unsigned char *finite, ndt_host_kdtree *out);
+void ndt_host_kdtree_free(ndt_host_kdtree *t);
+
 /* ---- flattening (the reference-side stub of INTEGRATION.md, against this host model) ---- */
 typedef struct {
     ndt_flat_scene fs;
@@ -73,12 +86,30 @@ typedef struct {
 } ndt_fit_stats;
 int ndt_flatten_scene_fit(scene *scn, ndt_flat_builder *fb, char *err, int err_len, int threads, ndt_fit_fn fit, void *fit_arg,
                           ndt_fit_stats *stats);
+/* The same with the kd-tree build delegated as well: ndt_kd_add_object still makes the item boxes, `kd` gets them flat (the
+ * arguments of ndt_hip_build_kdtree) exactly once a frame and returns the tree in malloc'ed arrays, which become the flat
+ * scene's; 0 or, with the message in `err`, non-zero.  kd == NULL: ndt_kd_build.  The two delegations are independent.
+ * `kd_stats` (may be NULL) says what the build cost, whoever made it. */
+typedef int (*ndt_kd_fn)(void *arg, int dims, int n_items, const double *lower, const double *upper, const unsigned char *finite,
+                         ndt_host_kdtree *out, char *err, int err_len);
+typedef struct {
+    double build_ms;            /* inside ndt_kd_build / inside `kd` */
+    int calls;                  /* of `kd` */
+} ndt_kd_stats;
+int ndt_flatten_scene_with(scene *scn, ndt_flat_builder *fb, char *err, int err_len, int threads, ndt_fit_fn fit, void *fit_arg,
+                           ndt_fit_stats *stats, ndt_kd_fn kd, void *kd_arg, ndt_kd_stats *kd_stats);
 /* ndt_render.c: where the bounding spheres of the frames this process flattens for rendering are fitted -- 0 on the host
  * (default), 1 on the GPU (`ndt_hip --fit gpu`) -- and ndt_flatten_scene_fit with context 0 of the calling thread as the
  * fitter (the contexts are created first).  It prints `fitted K bounding spheres on GPU D in L launches`; there is no
  * fallback: without a device, or with a scene the device fit refuses, it fails with the reason in `err`. */
 void ndt_render_fit_on_gpu(int on);
 int ndt_flatten_scene_gpu_fit(scene *scn, ndt_flat_builder *fb, char *err, int err_len, int threads, ndt_fit_stats *stats);
+/* ... and where their kd-trees are built -- 0 on the host (default), 1 on the GPU (`ndt_hip --kd gpu`, ndt_hip_build_kdtree on
+ * context 0 of the calling thread) -- and the flattening with either piece, both or neither on the GPU.  With the tree on the
+ * GPU it prints `built kd-tree of K nodes on GPU D in L launches`; no fallback either. */
+void ndt_render_kd_on_gpu(int on);
+int ndt_flatten_scene_gpu(scene *scn, ndt_flat_builder *fb, char *err, int err_len, int threads, int fit_on_gpu, int kd_on_gpu,
+                          ndt_fit_stats *stats, ndt_kd_stats *kd_stats);
 void ndt_flat_builder_free(ndt_flat_builder *fb);
 int ndt_write_ndtscene(const ndt_flat_scene *fs, const char *name, const char *path);
 

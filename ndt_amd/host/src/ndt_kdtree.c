@@ -337,3 +337,86 @@ void ndt_kd_free(ndt_kd_tree *t)
     free_node(t->root);
     memset(t, 0, sizeof(*t));
 }
+
+/* ---- kd_tree_build over flat arrays: the CPU twin of ndt_hip_build_kdtree (include/ndt_hip.h), ndt_kd_build above behind
+ * that call's signature.  lower / upper: n_items x dims, the boxes ndt_kd_add_object makes; finite[i] != 0 stands for
+ * `bounds.radius >= 0` (kd-tree.c:448-463).  The result is what ndt_flatten.c puts into an ndt_flat_scene: nodes in preorder,
+ * the leaves' lists in that order, the other items, the root box. */
+static int twin_count(const ndt_kd_node *n) { return n ? 1 + twin_count(n->left) + twin_count(n->right) : 0; }
+static int twin_depth(const ndt_kd_node *n)
+{
+    if (!n) return 0;
+    const int l = twin_depth(n->left), r = twin_depth(n->right);
+    return 1 + (l > r ? l : r);
+}
+/* flatten_node, ndt_flatten.c: a node, its left subtree, its right subtree */
+static int twin_flatten(ndt_host_kdtree *out, const ndt_kd_node *n, int me)
+{
+    ndt_flat_kdnode *k = &out->nodes[me];
+    memset(k, 0, sizeof(*k));
+    k->dim = n->dim;
+    k->boundary = n->boundary;
+    if (n->dim >= 0) {
+        k->left = me + 1;
+        const int after_left = twin_flatten(out, n->left, me + 1);
+        out->nodes[me].right = after_left;
+        return twin_flatten(out, n->right, after_left);
+    }
+    k->left = k->right = -1;
+    k->first = out->n_leaf_refs;
+    k->num = n->num;
+    memcpy(out->leaf_refs + out->n_leaf_refs, n->ids, (size_t)n->num * sizeof(int));
+    out->n_leaf_refs += n->num;
+    return me + 1;
+}
+static int64_t twin_refs(const ndt_kd_node *n) { return !n ? 0 : n->dim < 0 ? n->num : twin_refs(n->left) + twin_refs(n->right); }
+
+int ndt_host_build_kdtree(int dims, int n_items, const double *lower, const double *upper, const unsigned char *finite, ndt_host_kdtree *out)
+{
+    if (dims < 1 || n_items < 0 || !out || (n_items > 0 && (!lower || !upper || !finite))) return -1;
+    memset(out, 0, sizeof(*out));
+    /* ndt_kd_build asks an item's object whether it is finite: two stand-ins */
+    object *stand_in = (object *)calloc(2, sizeof(object));
+    stand_in[1].bounds.radius = -1.0;
+    ndt_kd_tree t;
+    ndt_kd_init(&t, dims);
+    t.items = (ndt_kd_item *)calloc((size_t)(n_items > 0 ? n_items : 1), sizeof(ndt_kd_item));
+    t.n_items = t.cap_items = n_items;
+    for (int i = 0; i < n_items; ++i) {
+        ndt_kd_item *it = &t.items[i];
+        it->lower = (double *)malloc((size_t)dims * sizeof(double));
+        it->upper = (double *)malloc((size_t)dims * sizeof(double));
+        memcpy(it->lower, lower + (size_t)i * dims, (size_t)dims * sizeof(double));
+        memcpy(it->upper, upper + (size_t)i * dims, (size_t)dims * sizeof(double));
+        it->obj = &stand_in[finite[i] ? 0 : 1];
+        it->id = i;
+    }
+    ndt_kd_build(&t);
+    const int64_t n_refs = twin_refs(t.root);
+    int rc = 0;
+    if (n_refs > 0x7fffffff) rc = -1;
+    else {
+        out->n_kd_nodes = twin_count(t.root);
+        out->depth = twin_depth(t.root);
+        out->nodes = (ndt_flat_kdnode *)calloc((size_t)out->n_kd_nodes, sizeof(ndt_flat_kdnode));
+        out->leaf_refs = (int32_t *)malloc((size_t)(n_refs > 0 ? n_refs : 1) * sizeof(int32_t));
+        twin_flatten(out, t.root, 0);
+        out->n_inf = t.n_inf;
+        out->inf_refs = (int32_t *)malloc((size_t)(t.n_inf > 0 ? t.n_inf : 1) * sizeof(int32_t));
+        memcpy(out->inf_refs, t.inf_ids, (size_t)t.n_inf * sizeof(int32_t));
+        out->bb_lower = (double *)malloc((size_t)dims * sizeof(double));
+        out->bb_upper = (double *)malloc((size_t)dims * sizeof(double));
+        memcpy(out->bb_lower, t.bb_lower, (size_t)dims * sizeof(double));
+        memcpy(out->bb_upper, t.bb_upper, (size_t)dims * sizeof(double));
+    }
+    ndt_kd_free(&t);
+    free(stand_in);
+    return rc;
+}
+
+void ndt_host_kdtree_free(ndt_host_kdtree *t)
+{
+    if (!t) return;
+    free(t->nodes); free(t->leaf_refs); free(t->inf_refs); free(t->bb_lower); free(t->bb_upper);
+    memset(t, 0, sizeof(*t));
+}

@@ -5,7 +5,8 @@
  * images/<scene>/<N>d/<WxH>/<scene>_<WxH>_<frame>.ppm (binary PPM of the pixel_d2c bytes; PNG
  * / JPEG encoding is outside this repository's scope).  `--dump-scene F` writes the flattened
  * scene of the last frame as an ndtscene file instead of rendering.  `--fit gpu` fits the frames'
- * bounding spheres on the GPU (ndt_hip_fit_spheres) instead of on the host's `-t` threads. */
+ * bounding spheres on the GPU (ndt_hip_fit_spheres) instead of on the host's `-t` threads; `--kd gpu` builds their kd-trees
+ * there (ndt_hip_build_kdtree) instead of on the host.  Neither falls back: what the device path cannot do ends the run. */
 #include <dlfcn.h>
 #include <getopt.h>
 #include <pthread.h>
@@ -300,10 +301,11 @@ int main(int argc, char **argv)
     int stereo = 0, specular = 1, want_depth = 0;      /* -m, -p, -z (ndt.c:1533-1573, 1581-1589, 1726-1729) */
     char *scene_path = NULL, *config = NULL, *dump_path = NULL, *raw_path = NULL;
     int fit_gpu = 0;        /* --fit host|gpu: where the frames' bounding spheres are fitted (default: host, on the -t threads) */
+    int kd_gpu = 0;         /* --kd host|gpu: where the frames' kd-trees are built (default: host) */
     char *objects_dir = "objects";      /* -o: where object plugins are looked for (object.c:119; ndt.c passes "objects") */
     static struct option longopts[] = { { "dump-scene", required_argument, NULL, 1000 },
                                         { "raw", required_argument, NULL, 1001 }, { "png", no_argument, NULL, 1002 },
-                                        { "fit", required_argument, NULL, 1003 },
+                                        { "fit", required_argument, NULL, 1003 }, { "kd", required_argument, NULL, 1004 },
                                         { NULL, 0, NULL, 0 } };
     int ch;
     while ((ch = getopt_long(argc, argv, "a:d:g:r:f:j:l:m:3:n:ps:t:u:o:zh", longopts, NULL)) != -1) {
@@ -358,9 +360,14 @@ int main(int argc, char **argv)
             else if (!strcmp(optarg, "host")) fit_gpu = 0;
             else { fprintf(stderr, "%s: --fit takes host or gpu, not '%s'\n", argv[0], optarg); return 1; }
             break;
+        case 1004:
+            if (!strcmp(optarg, "gpu")) kd_gpu = 1;
+            else if (!strcmp(optarg, "host")) kd_gpu = 0;
+            else { fprintf(stderr, "%s: --kd takes host or gpu, not '%s'\n", argv[0], optarg); return 1; }
+            break;
         default:
             fprintf(stderr, "usage: %s -s scene.so|builtin:yaml [-d dims] [-r WxH|1080p|4k] [-f last|first:last[:total]] [-l depth]\n"
-                            "          [-a diff,depth] [-n samples] [-m s|o|a|m] [-p] [-z] [-j frames_in_flight] [-g gpus_per_frame] [-u config] [--dump-scene file.ndtscene] [--raw file.f64] [--png] [--fit host|gpu]\n", argv[0]);
+                            "          [-a diff,depth] [-n samples] [-m s|o|a|m] [-p] [-z] [-j frames_in_flight] [-g gpus_per_frame] [-u config] [--dump-scene file.ndtscene] [--raw file.f64] [--png] [--fit host|gpu] [--kd host|gpu]\n", argv[0]);
             return ch == 'h' ? 0 : 1;
         }
     }
@@ -392,6 +399,7 @@ int main(int argc, char **argv)
     job_opts.want_depth = want_depth; job_opts.raw_path = raw_path; job_opts.samples = samples; job_opts.png = png;
     job_opts.gpus = gpus > 1 ? gpus : 1;
     ndt_render_fit_on_gpu(fit_gpu);
+    ndt_render_kd_on_gpu(kd_gpu);
     if (job_opts.gpus > 1) {
         printf("one frame over %d GPU contexts (%d device(s) visible)\n", job_opts.gpus, ndt_hip_device_count());
         ndt_render_use_devices(job_opts.gpus);
@@ -422,9 +430,9 @@ int main(int argc, char **argv)
         if (dump_path) {
             char err[256];
             ndt_flat_builder fb;
-            /* --fit gpu: the dump needs a device then; there is no falling back to the host fit */
-            if ((fit_gpu ? ndt_flatten_scene_gpu_fit(scn, &fb, err, sizeof(err), threads, NULL)
-                         : ndt_flatten_scene_mt(scn, &fb, err, sizeof(err), threads)) != 0) { fprintf(stderr, "%s\n", err); return 1; }
+            /* --fit gpu, --kd gpu: the dump needs a device then; there is no falling back to the host */
+            if (((fit_gpu || kd_gpu) ? ndt_flatten_scene_gpu(scn, &fb, err, sizeof(err), threads, fit_gpu, kd_gpu, NULL, NULL)
+                                     : ndt_flatten_scene_mt(scn, &fb, err, sizeof(err), threads)) != 0) { fprintf(stderr, "%s\n", err); return 1; }
             if (i == last || i == frames - 1) ndt_write_ndtscene(&fb.fs, scn->name, dump_path);
             ndt_flat_builder_free(&fb);
             scene_free(scn);

@@ -67,20 +67,61 @@ static int device_fit(void *arg, int dims, int64_t n_lists, const int64_t *first
     return 0;
 }
 
-int ndt_flatten_scene_gpu_fit(scene *scn, ndt_flat_builder *fb, char *err, int err_len, int threads, ndt_fit_stats *stats)
+/* ---- the frame's kd-tree on the GPU (ndt_hip_build_kdtree) */
+static int g_kd_on_gpu = 0;                 /* process-wide, set before any frame: `ndt_hip --kd gpu` */
+static __thread int g_kd_launches = 0;
+
+void ndt_render_kd_on_gpu(int on) { g_kd_on_gpu = on != 0; }
+
+static int device_kd(void *arg, int dims, int n_items, const double *lower, const double *upper, const unsigned char *finite,
+                     ndt_host_kdtree *out, char *err, int err_len)
+{
+    ndt_hip_ctx *ctx = (ndt_hip_ctx *)arg;
+    ndt_kd_counts c;
+    int rc = ndt_hip_build_kdtree(ctx, dims, n_items, lower, upper, finite, &c);
+    if (rc == NDT_OK) {
+        memset(out, 0, sizeof(*out));
+        out->n_kd_nodes = c.n_kd_nodes; out->n_leaf_refs = c.n_leaf_refs; out->n_inf = c.n_inf; out->depth = c.depth;
+        out->nodes = (ndt_flat_kdnode *)calloc((size_t)c.n_kd_nodes, sizeof(ndt_flat_kdnode));
+        out->leaf_refs = (int32_t *)malloc((size_t)(c.n_leaf_refs > 0 ? c.n_leaf_refs : 1) * sizeof(int32_t));
+        out->inf_refs = (int32_t *)malloc((size_t)(c.n_inf > 0 ? c.n_inf : 1) * sizeof(int32_t));
+        out->bb_lower = (double *)malloc((size_t)dims * sizeof(double));
+        out->bb_upper = (double *)malloc((size_t)dims * sizeof(double));
+        rc = ndt_hip_kdtree_fetch(ctx, out->nodes, out->leaf_refs, out->inf_refs, out->bb_lower, out->bb_upper);
+    }
+    if (rc != NDT_OK) {
+        snprintf(err, (size_t)err_len, "kd-tree on the GPU: %s", ndt_hip_last_error());
+        return rc;
+    }
+    g_kd_launches += c.launches;
+    return 0;
+}
+
+int ndt_flatten_scene_gpu(scene *scn, ndt_flat_builder *fb, char *err, int err_len, int threads, int fit_on_gpu, int kd_on_gpu,
+                          ndt_fit_stats *stats, ndt_kd_stats *kd_stats)
 {
     ndt_fit_stats local;
     if (!stats) stats = &local;
     memset(fb, 0, sizeof(*fb));
-    /* the contexts before the scene: context 0 is the fitter (-j K: every worker thread has its own; -g N: the first of N) */
-    if (!have_contexts()) {
-        snprintf(err, (size_t)err_len, "bounding spheres on the GPU: %s", ndt_hip_last_error());
+    /* the contexts before the scene: context 0 does the work (-j K: every worker thread has its own; -g N: the first of N) */
+    if ((fit_on_gpu || kd_on_gpu) && !have_contexts()) {
+        snprintf(err, (size_t)err_len, "%s on the GPU: %s", fit_on_gpu ? "bounding spheres" : "kd-tree", ndt_hip_last_error());
         return -1;
     }
     g_fit_launches = 0;
-    if (ndt_flatten_scene_fit(scn, fb, err, err_len, threads, device_fit, g_ctx[0], stats) != 0) return -1;
-    printf("fitted %lld bounding spheres on GPU %d in %d launches\n", (long long)stats->spheres, ndt_hip_device(g_ctx[0]), g_fit_launches);
+    g_kd_launches = 0;
+    if (ndt_flatten_scene_with(scn, fb, err, err_len, threads, fit_on_gpu ? device_fit : NULL, fit_on_gpu ? g_ctx[0] : NULL, stats,
+                               kd_on_gpu ? device_kd : NULL, kd_on_gpu ? g_ctx[0] : NULL, kd_stats) != 0) return -1;
+    if (fit_on_gpu)
+        printf("fitted %lld bounding spheres on GPU %d in %d launches\n", (long long)stats->spheres, ndt_hip_device(g_ctx[0]), g_fit_launches);
+    if (kd_on_gpu)
+        printf("built kd-tree of %d nodes on GPU %d in %d launches\n", fb->n_nodes, ndt_hip_device(g_ctx[0]), g_kd_launches);
     return 0;
+}
+
+int ndt_flatten_scene_gpu_fit(scene *scn, ndt_flat_builder *fb, char *err, int err_len, int threads, ndt_fit_stats *stats)
+{
+    return ndt_flatten_scene_gpu(scn, fb, err, err_len, threads, 1, 0, stats, NULL);
 }
 
 int ndt_render_image(scene *scn, int width, int height, int threads, int max_optic_depth, double *rgba)
@@ -106,8 +147,8 @@ static int render_any(scene *scn, int width, int height, int samples, int aa_dif
     struct timespec ts0, ts1, ts2, ts3;
     if (timing) clock_gettime(CLOCK_MONOTONIC, &ts0);
     ndt_fit_stats fit;
-    if ((g_fit_on_gpu ? ndt_flatten_scene_gpu_fit(scn, &fb, err, sizeof(err), threads, &fit)
-                      : ndt_flatten_scene_fit(scn, &fb, err, sizeof(err), threads, NULL, NULL, timing ? &fit : NULL)) != 0) {
+    ndt_kd_stats kds;
+    if (ndt_flatten_scene_gpu(scn, &fb, err, sizeof(err), threads, g_fit_on_gpu, g_kd_on_gpu, &fit, &kds) != 0) {
         fprintf(stderr, "ndt_render_image: %s\n", err);
         ndt_flat_builder_free(&fb);
         return 0;
@@ -148,12 +189,15 @@ static int render_any(scene *scn, int width, int height, int samples, int aa_dif
         clock_gettime(CLOCK_MONOTONIC, &ts3);
 #define NDT_MS(a, b) (((b).tv_sec - (a).tv_sec) * 1e3 + ((b).tv_nsec - (a).tv_nsec) * 1e-6)
         /* the first figure split: the sphere fits (on the GPU: gathering the bounding points / the fit calls) and the rest */
-        char share[160];
+        /* ... and of the rest the kd-tree build on its own, whoever made it */
+        char share[240], tree[64];
+        if (g_kd_on_gpu) snprintf(tree, sizeof(tree), "kd-tree on GPU %.2f in %d launches", kds.build_ms, g_kd_launches);
+        else snprintf(tree, sizeof(tree), "kd-tree %.2f", kds.build_ms);
         if (g_fit_on_gpu)
-            snprintf(share, sizeof(share), "gpu fits: points gathered %.2f + fit %.2f, rest %.2f", fit.gather_ms, fit.fit_ms,
-                     NDT_MS(ts0, ts1) - fit.gather_ms - fit.fit_ms);
+            snprintf(share, sizeof(share), "gpu fits: points gathered %.2f + fit %.2f, %s, rest %.2f", fit.gather_ms, fit.fit_ms, tree,
+                     NDT_MS(ts0, ts1) - fit.gather_ms - fit.fit_ms - kds.build_ms);
         else
-            snprintf(share, sizeof(share), "host fits %.2f, rest %.2f", fit.fit_ms, NDT_MS(ts0, ts1) - fit.fit_ms);
+            snprintf(share, sizeof(share), "host fits %.2f, %s, rest %.2f", fit.fit_ms, tree, NDT_MS(ts0, ts1) - fit.fit_ms - kds.build_ms);
         fprintf(stderr, "ndt_render_image: bounds + kd-tree + flatten %.2f ms (%s), upload %.2f ms, render + image to host %.2f ms\n",
                 NDT_MS(ts0, ts1), share, NDT_MS(ts1, ts2), NDT_MS(ts2, ts3));
     }
