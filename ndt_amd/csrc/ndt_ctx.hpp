@@ -4,6 +4,7 @@
 //   ndt_api.hip      create / destroy / upload / trace_rays / quantize: the plain C ABI of include/ndt_hip.h
 //   ndt_blob.hip     scene validation, the plugins' prepare() data, hull boxes: the scene blob (host code only)
 //   ndt_frame.hip    workspace + one pass of the ray pipeline over a set of primaries (render_pass)
+//   ndt_probe.hip    what the diagnostics of a profiled pass print (stream / shade / exit probes, NDT_PHASE_TIMING)
 //   ndt_aa.hip       Whitted's recursive anti-aliasing on top of render_pass
 //   ndt_sampled.hip  -n samples > 1, lens, area lights on top of render_pass
 //   ndt_render.hip   ndt_hip_render*: argument checks and the choice between the three
@@ -104,7 +105,6 @@ struct ndt_hip_ctx {
     int hybrid_level = 2;           // hybrid: the bounce from which on the frame kernel renders (NDT_HIP_HYBRID_LEVEL)
     long long stream_below = 1000000;       // where the two cross on the benchmark scene (profiles/r03_frame_time_vs_size_*.txt: 1280x720 stream 0.918 / levels 0.965 ms, 1408x792 1.054 / 1.045; the r::8 shard of a 3840x2160 frame, 1.04 M primaries: 0.977 per bounce, 1.00 streamed)
     long long stream_below_list = 30000;    // ... for passes over a list of samples (-a): 1080p -a 20,4 of the benchmark scene 27.6 -> 24.0 ms, balls 14.0 -> 12.7
-    bool use_stream = false;        // the choice for the pass being rendered
     StreamArgs sa{};
     // ndt_hip_set_option / NDT_HIP_* at context creation (include/ndt_hip.h)
     bool stream_probe = false, exit_probe = false, debug_levels = false, test_small_pool = false;
@@ -159,9 +159,9 @@ struct ndt_hip_ctx {
     int multi_path = 0;             // option "multi_path": 0 auto, 1 never staged, 2 always staged
     int multi_path_taken = 0;       // ndt_multi_path of the last multi-context frame (ndt_hip_multi_path_taken)
     ndt_impl::CtxWorker *worker = nullptr;
-    int *h_counters = nullptr;      // pinned
+    int *h_counters = nullptr;      // pinned, 128 ints: the level totals a kd-tree build reads back (ndt_kd.hip)
     LevelRange *h_levels = nullptr; // pinned, NDT_MAX_LEVELS + 1
-    LevelRange *h_mail = nullptr;   // mapped + coherent: bounce ranges posted by k_level_step while the frame runs
+    LevelRange *h_mail = nullptr;   // mapped + coherent: bounce ranges posted by the trace launches' prologue (TraceJob::publish_level) while the frame runs
     unsigned long long *h_mail_tag = nullptr;
     LevelRange *d_mail = nullptr;   // the device's view of the two
     unsigned long long *d_mail_tag = nullptr;
@@ -200,6 +200,12 @@ int ensure_workspace(ndt_hip_ctx *ctx, long long cap, long long sh_cap);
 int render_pass(ndt_hip_ctx *ctx, RenderGeom rg, bool prof, void *d_rgba, ndt_render_stats &st, void *d_depth = nullptr);
 void launch_fill_black(hipStream_t s, double *rgba, long long n_pixels);
 void add_stats(ndt_render_stats &acc, const ndt_render_stats &st);
+
+// ndt_probe.hip: each reads its log back from the device and prints to stderr
+void print_stream_probe(const unsigned int *wave_log, float kernel_ms);
+void print_shade_probe(const unsigned int *shade_log, int shade_probe, long long finish_waves);
+void print_exit_probe(const unsigned int *exit_log, int launches);
+void print_phase_timing(const unsigned long long *dbg);
 
 // ndt_multi.hip
 void worker_stop(ndt_hip_ctx *ctx);

@@ -345,63 +345,6 @@ void ndt_impl::add_stats(ndt_render_stats &acc, const ndt_render_stats &st)
 
 // ------------------------------------------------------------------ render
 
-// NDT_HIP_STREAM_PROBE: what every wavefront of the frame kernel did and when (100 MHz ticks)
-static void print_stream_probe(const unsigned int *wave_log, float km)
-{
-                    std::vector<unsigned int> log((size_t)24 * NDT_STREAM_LOG_WAVES);
-                    if (hipMemcpy(log.data(), wave_log, log.size() * sizeof(unsigned int), hipMemcpyDeviceToHost) == hipSuccess) {
-                        unsigned long long n[4] = { 0, 0, 0, 0 }, t[3] = { 0, 0, 0 }, parts[5] = { 0, 0, 0, 0, 0 };
-                        int waves = 0, busy_waves = 0;
-                        unsigned int t0 = 0, max_items = 0;
-                        bool any = false;
-                        for (int w = 0; w < NDT_STREAM_LOG_WAVES; ++w) {
-                            const unsigned int *q = &log[(size_t)24 * w];
-                            if (!q[9]) continue;
-                            if (!any || (int)(q[10] - t0) < 0) t0 = q[10];
-                            any = true;
-                        }
-                        double first_item = 1e30, last_item = 0, last_exit = 0, start_spread = 0;
-                        int hist[32] = { 0 };
-                        for (int w = 0; w < NDT_STREAM_LOG_WAVES; ++w) {
-                            const unsigned int *q = &log[(size_t)24 * w];
-                            if (!q[9]) continue;
-                            ++waves;
-                            const unsigned int items = q[0] + q[1] + q[2];
-                            if (items) ++busy_waves;
-                            if (items > max_items) max_items = items;
-                            for (int k = 0; k < 4; ++k) n[k] += q[k];
-                            for (int k = 0; k < 3; ++k) t[k] += q[4 + k];
-                            for (int k = 0; k < 5; ++k) parts[k] += q[12 + k];
-                            const double off = (q[10] - t0) / 100.0;
-                            if (off > start_spread) start_spread = off;
-                            if (q[7] && off + q[7] / 100.0 < first_item) first_item = off + q[7] / 100.0;
-                            if (off + q[8] / 100.0 > last_item) last_item = off + q[8] / 100.0;
-                            if (off + q[9] / 100.0 > last_exit) last_exit = off + q[9] / 100.0;
-                            int bin = (int)((off + q[8] / 100.0) / (km * 1000.0 / 32.0 + 1e-9));
-                            ++hist[bin < 0 ? 0 : bin > 31 ? 31 : bin];
-                        }
-                        std::string line;
-                        for (int b = 0; b < 32; ++b) {
-                            char buf[16];
-                            snprintf(buf, sizeof buf, " %d", hist[b]);
-                            line += buf;
-                        }
-                        fprintf(stderr, "ndt_hip: frame kernel %.3f ms: %d wavefronts (%d with work, at most %u items each) started within %.1f us; "
-                                        "node batches %llu (%.1f us each), shadow batches %llu (%.1f us each), lighting batches %llu (%.1f us each), "
-                                        "idle rounds %llu; first item at %.1f us, last item done at %.1f us, last exit at %.1f us; "
-                                        "wavefronts by the 32nd of the kernel in which they finished their last item:%s\n",
-                                km, waves, busy_waves, max_items, start_spread, n[0], n[0] ? t[0] / 100.0 / n[0] : 0.0, n[1],
-                                n[1] ? t[1] / 100.0 / n[1] : 0.0, n[2], n[2] ? t[2] / 100.0 / n[2] : 0.0, n[3], first_item, last_item, last_exit,
-                                line.c_str());
-                        fprintf(stderr, "ndt_hip:    per item: looking for work %.1f us (all kinds); node + shadow items: loading the rays %.1f us; trace_kd: node "
-                                        "batches %.1f us, shadow batches %.1f us; colours up the tree + counters %.1f us (node and lighting batches)\n",
-                                (n[0] + n[1] + n[2]) ? parts[0] / 100.0 / (n[0] + n[1] + n[2]) : 0.0,
-                                (n[0] + n[1]) ? parts[1] / 100.0 / (n[0] + n[1]) : 0.0, n[0] ? (parts[2] - parts[3]) / 100.0 / n[0] : 0.0,
-                                n[1] ? parts[3] / 100.0 / n[1] : 0.0, (n[0] + n[2]) ? parts[4] / 100.0 / (n[0] + n[2]) : 0.0);
-                    }
-}
-
-
 static hipEvent_t get_event(ndt_hip_ctx *ctx, size_t idx)
 {
     while (ctx->ev_pool.size() <= idx) {
@@ -419,26 +362,562 @@ static double wall_s()
     return (double)ts.tv_sec + 1e-9 * (double)ts.tv_nsec;
 }
 
+// The host waits for a kernel of the running frame by polling a word of host-mapped memory for the frame's tag: no stream
+// synchronisation, no read-back.  After 30 s without it the stream is synchronised and the word looked at once more; `what`
+// (a format that may take `bounce`) is the error if it still is not there.
+static int wait_for_tag(ndt_hip_ctx *ctx, const unsigned long long *word, unsigned long long tag, const char *what, int bounce = 0)
+{
+    const double t_wait = wall_s();
+    while (__atomic_load_n(word, __ATOMIC_ACQUIRE) != tag) {
+        if (wall_s() - t_wait > 30.0) {
+            HIP_TRY(hipStreamSynchronize(ctx->stream));
+            if (__atomic_load_n(word, __ATOMIC_ACQUIRE) != tag) return fail(NDT_E_STATE, what, bounce);
+        }
+    }
+    return NDT_OK;
+}
+
+static long long n_pixels(const RenderGeom &rg) { return rg.samples ? (long long)rg.n_samples : (long long)rg.rows * rg.width; }
+
+// A profiled pass takes the frame's begin / end from the dispatch timestamps of its first and last kernel
+template <typename Kernel, typename... Args>
+static void launch_stamped(Kernel k, dim3 grid, dim3 block, hipStream_t s, hipEvent_t ev_start, hipEvent_t ev_stop, Args... args)
+{
+    if (ev_start || ev_stop)
+        hipExtLaunchKernelGGL(k, grid, block, 0, s, ev_start, ev_stop, 0u, args...);
+    else
+        hipLaunchKernelGGL(k, grid, block, 0, s, args...);
+}
+
+static void launch_finish_pixels(ndt_hip_ctx *ctx, const SceneDesc &sd_pass, const Workspace &ws, const RenderGeom &rg, void *d_rgba, void *d_depth,
+                                 int resolve0)
+{
+    hipLaunchKernelGGL(k_finish_pixels, dim3((unsigned)((rg.n_primary + NDT_FINISH_BLOCK - 1) / NDT_FINISH_BLOCK)), dim3(NDT_FINISH_BLOCK), 0, ctx->stream,
+                       ctx->d_blob, sd_pass, ws, rg, ctx->dims, (double *)d_rgba, (double *)d_depth, resolve0);
+}
+
+// The frame kernel's arguments for a forest rooted at node slots [begin, begin + count): the primaries of a whole frame, or the
+// nodes of the bounce at which the hybrid pipeline hands over.  The root range is the 64-aligned cover of the slots (the frame
+// kernel works in batches of 64).
+static int stream_roots(ndt_hip_ctx *ctx, bool prof, long long begin, long long count, int primaries, StreamArgs &sa)
+{
+    sa = ctx->sa;
+    sa.root_begin = (int)(begin & ~63LL);
+    sa.n_primary = (int)(((begin + count + 63) & ~63LL) - sa.root_begin);
+    sa.valid_begin = (int)begin;
+    sa.valid_end = (int)(begin + count);
+    sa.roots_are_primaries = primaries;
+    sa.fused = 0;
+    if (!prof) sa.wave_log = nullptr;
+    else if (sa.wave_log) HIP_TRY(hipMemsetAsync(sa.wave_log, 0, (size_t)24 * NDT_STREAM_LOG_WAVES * sizeof(unsigned int), ctx->stream));
+    return NDT_OK;
+}
+
+static void launch_stream_init(ndt_hip_ctx *ctx, const Workspace &ws, const StreamArgs &sa, int frame_too, hipEvent_t ev_start)
+{
+    const long long sh_batches = (long long)sa.n_seg * (sa.seg_cap / 64) + NDT_STREAM_LOG_WAVES;
+    launch_stamped(k_stream_init, dim3(512), dim3(256), ctx->stream, ev_start, nullptr, ws, sa, (long long)sa.node_batches, sh_batches, frame_too);
+}
+
+// render_pass_levels and one attempt of it: the pools overflowed and have been grown, render the pass again (not an NDT_E_* code)
+static const int PASS_AGAIN = 1;
+
+// ---- the streaming pipeline: one persistent launch for the whole ray tree (ndt_stream.hpp).  no_room: the pools the frame
+// kernel wants cannot be had (auto then renders the pass per bounce).
+static int render_pass_stream(ndt_hip_ctx *ctx, const RenderGeom &rg, const SceneDesc &sd_pass, bool prof, void *d_rgba, void *d_depth, long long cap,
+                              long long sh_cap, ndt_render_stats &st, bool &no_room)
+{
+    hipStream_t s = ctx->stream;
+    const NdtKernelTable *kt = ctx->kt;
+    const int n_seg = ctx->n_shadow_lights > 0 ? ctx->n_shadow_lights : 1;
+    for (int attempt = 0; attempt < 8; ++attempt) {
+        // every light's shadow segment can hold one ray per node
+        if (sh_cap < cap * n_seg) sh_cap = cap * n_seg;
+        int rc = NDT_OK;
+        if (cap > 0x7fffff00LL || sh_cap > 0x7fffff00LL) rc = fail(NDT_E_NOMEM, "ray tree exceeds 2^31 nodes");
+        if (!rc) rc = ensure_workspace(ctx, cap, sh_cap);
+        if (!rc) rc = ensure_stream_args(ctx);
+        no_room = rc == NDT_E_NOMEM;
+        if (rc) return rc;
+        const Workspace ws = ctx->ws;
+        StreamArgs sa;
+        if ((rc = stream_roots(ctx, prof, 0, rg.n_primary, 1, sa))) return rc;
+        // the kernel makes its own primaries and writes its own pixels (option stream_fused, on by default)
+        sa.fused = ctx->stream_fused ? 1 : 0;
+        sa.rgba = (double *)d_rgba;
+        sa.depth_out = (double *)d_depth;
+        hipEvent_t ev_begin = nullptr, ev_end = nullptr, ev_k0 = nullptr, ev_k1 = nullptr;
+        if (prof) {
+            ev_begin = get_event(ctx, 0);
+            ev_end = get_event(ctx, 1);
+            ev_k0 = get_event(ctx, 2);
+            ev_k1 = get_event(ctx, 3);
+        }
+        const unsigned long long tag = ++ctx->frame_tag;
+        launch_stream_init(ctx, ws, sa, 1, ev_begin);
+        if (!sa.fused) kt->primary(s, ctx->d_blob, sd_pass, ws, rg);
+        kt->frame_stream(s, ctx->d_blob, sd_pass, ws, rg, sa, ctx->tier, ctx->sd.mask_words, ev_k0, ev_k1);
+        if (!sa.fused) launch_finish_pixels(ctx, sd_pass, ws, rg, d_rgba, d_depth, 0);
+        launch_stamped(k_stream_done, dim3(1), dim3(64), s, nullptr, ev_end, ws, sa, ctx->d_done, tag);
+        HIP_TRY(hipGetLastError());
+        if ((rc = wait_for_tag(ctx, &ctx->h_done[7], tag, "the frame never completed"))) return rc;
+        if (prof) HIP_TRY(hipEventSynchronize(ev_end));
+        const int overflow = (int)(long long)ctx->h_done[1], aborted = (int)(long long)ctx->h_done[2];
+        if (overflow != 0) {
+            if (overflow & 1) cap *= 2;
+            if (overflow & 2) sh_cap *= 2;
+            continue;
+        }
+        if (aborted != 0)
+            return fail(NDT_E_STATE, "the frame kernel gave up (abort %d, where %d): a work item never arrived", aborted & 0xff, aborted >> 8);
+        st = ndt_render_stats{};
+        st.rays_primary = n_pixels(rg);
+        st.rays_secondary = (long long)ctx->h_done[6];
+        st.rays_shadow = (long long)ctx->h_done[3];
+        st.rays_ref_equiv = (long long)ctx->h_done[5];
+        st.levels = (int)ctx->h_done[4];
+        st.trace_launches = 1;
+        st.node_capacity = ws.cap;
+        if (prof) {
+            float km = 0, fm = 0;
+            HIP_TRY(hipEventElapsedTime(&km, ev_k0, ev_k1));
+            HIP_TRY(hipEventElapsedTime(&fm, ev_begin, ev_end));
+            st.trace_ms = km;
+            st.frame_ms = fm;
+            if (sa.wave_log) print_stream_probe(sa.wave_log, km);
+        }
+        return NDT_OK;
+    }
+    return fail(NDT_E_NOMEM, "ray-tree workspace kept overflowing");
+}
+
+// ---- the per-bounce pipeline.  One attempt at the pass -- a frame in flight: what the pass is, and what the launches of the
+// attempt share.  The stream is never synchronised inside a frame: the range of every bounce is published on the device (by
+// the prologue of the trace launch behind its shading, TraceJob::publish_level) and read there; the host only learns, from
+// the mailbox, whether there is a next bounce to enqueue.  Bounce 0 = the primaries.
+struct FrameInFlight {
+    ndt_hip_ctx *ctx;
+    const RenderGeom &rg;
+    const SceneDesc &sd_pass;
+    const bool prof;
+    // Hybrid pipeline: the first `hand` bounces -- where the rays are -- go through the per-bounce kernels (three
+    // wavefronts per SIMD in the trace kernel, shade kernels with the whole chip's wavefront slots); the deeper
+    // bounces, a few per cent of the rays but a launch latency each (one slow batch: 0.15-0.2 ms per trace launch
+    // and 75 us per shade launch, three times over on the benchmark frame), are ONE launch of the frame kernel
+    // rooted at the nodes of bounce `hand`.
+    const bool hybrid;
+    void *d_rgba, *d_depth;
+    hipStream_t s;
+    const NdtKernelTable *kt;
+    Workspace ws;
+    const int n_levels;             // a node spawns children only while depth_left > 1
+    const int hand;                 // hybrid: the bounce the frame kernel takes over; else none
+    // light windows: window k's scene description, and how many window emits the frame has had (they take the two banks of
+    // window counters in turn)
+    const int n_win;
+    const bool windowed;
+    std::vector<SceneDesc> sd_win;
+    int win_emits = 0;
+    unsigned long long tag = 0;
+    int slots = 0, queue_slot = 0;  // work queues zeroed by frame init / handed out so far
+    int launches = 0;               // trace launches + the frame kernel's
+    size_t ev_n = 0;
+    hipEvent_t ev_begin = nullptr, ev_end = nullptr, ev_k0 = nullptr, ev_k1 = nullptr;
+    std::vector<std::pair<hipEvent_t, hipEvent_t>> trace_ev;
+    std::vector<std::string> trace_dbg;
+    // NDT_HIP_SHADE_PROBE=<k>: the k-th shade launch of the frame logs the life of each of its wavefronts
+    int shade_launch = 0;
+    long long shade_probe_finish_waves = 0;     // wavefronts of the lighting part of the probed launch
+    int n_run;                                  // bounces enqueued (the per-bounce resolve walks them)
+    std::vector<long long> level_nodes;         // node count of every bounce (an upper bound: sizes grids)
+    int pending_finish = -1;                    // bounce whose lighting has not been launched yet
+    long long pending_upper = 0;
+    bool resolve_with_finish = false;           // the deepest bounce was blended by its lighting launch
+    StreamArgs sa{};                            // hybrid: the frame kernel's launch, if there was one
+    bool streamed = false;
+
+    FrameInFlight(ndt_hip_ctx *c, const RenderGeom &g, const SceneDesc &sd, bool p, bool hyb, void *rgba, void *depth)
+        : ctx(c), rg(g), sd_pass(sd), prof(p), hybrid(hyb), d_rgba(rgba), d_depth(depth), s(c->stream), kt(c->kt), ws(c->ws),
+          n_levels(g.max_depth > 1 ? g.max_depth : 1), hand(hyb ? c->hybrid_level : n_levels + 1), n_win((int)c->windows.size()),
+          windowed(n_win > 1), n_run(n_levels)
+    {
+        ws.mail = ctx->d_mail;
+        ws.mail_tag = ctx->d_mail_tag;
+        for (int k = 0; windowed && k < n_win; ++k) sd_win.push_back(window_desc(ctx, sd_pass, k));
+    }
+
+    int render(long long &cap, long long &sh_cap, ndt_render_stats &st);
+    int frame_init(long long &sh_cap);
+    int traced(TraceJob &tj, const std::string &what, const SceneDesc *sd_job = nullptr);
+    Workspace shade_ws(long long finish_nodes);
+    int trace_primaries();
+    void light_and_shade(int b, long long upper);
+    int trace_bounce(int b, long long upper);
+    int trace_windows(int b, long long upper);
+    void light_last();
+    int hand_off(long long &cap);
+    void resolve();
+    int close();
+    int report(long long &cap, long long &sh_cap, ndt_render_stats &st);
+    hipError_t print_debug(int levels_used);
+};
+
+int FrameInFlight::render(long long &cap, long long &sh_cap, ndt_render_stats &st)
+{
+    int rc;
+    if ((rc = frame_init(sh_cap))) return rc;
+    if ((rc = trace_primaries())) return rc;
+    long long upper = rg.n_primary;         // node count of the bounce
+    for (int b = 0; b < n_levels && b < hand; ++b) {
+        // (the same bounce limit whatever the light windows: a windowed pass uses its work queues again, but light_window must
+        // not change what renders)
+        if ((windowed ? b + 2 : queue_slot + 1) > NDT_QUEUE_SLOTS || b + 1 > NDT_MAX_LEVELS)
+            return fail(NDT_E_UNSUPPORTED, "more than %d bounces", NDT_QUEUE_SLOTS - 1);
+        if (b > 0) {
+            // published by the trace launch of bounce b - 1, which ran right after shade_emit(b - 1)
+            if ((rc = wait_for_tag(ctx, &ctx->h_mail_tag[b], tag, "bounce %d was never published", b))) return rc;
+            upper = ctx->h_mail[b].count;
+            if (upper <= 0) {
+                n_run = b;
+                break;
+            }
+        }
+        level_nodes.push_back(upper);
+        light_and_shade(b, upper);
+        if ((rc = trace_bounce(b, upper))) return rc;
+        if (windowed && (rc = trace_windows(b, upper))) return rc;
+        pending_finish = b;
+        pending_upper = upper;
+    }
+    light_last();
+    if (hybrid && n_run >= hand && hand < n_levels && (rc = hand_off(cap))) return rc;
+    resolve();
+    launch_finish_pixels(ctx, sd_pass, ws, rg, d_rgba, d_depth, n_run >= 1 ? 1 : 0);
+    if ((rc = close())) return rc;
+    return report(cap, sh_cap, st);
+}
+
+// Everything the frame needs reset, and the primaries' range (k_frame_init).  PASS_AGAIN: the shadow queue cannot hold the
+// primaries' segments.
+int FrameInFlight::frame_init(long long &sh_cap)
+{
+    if (prof) {
+        // frame time = start of the frame's first kernel .. end of its last (their own dispatch timestamps)
+        ev_begin = get_event(ctx, ev_n++);
+        ev_end = get_event(ctx, ev_n++);
+    }
+    if (prof && ctx->exit_probe)
+        HIP_TRY(hipMemsetAsync(ws.exit_log, 0, (size_t)NDT_EXIT_LOG_LAUNCHES * NDT_EXIT_LOG_WORDS * sizeof(unsigned int), s));
+    tag = ++ctx->frame_tag;
+    LevelRange level0;
+    level0.begin = 0;
+    level0.count = rg.n_primary;
+    level0.seg_stride = (rg.n_primary + 63) & ~63LL;
+    level0.n_shadow = 0;
+    if ((long long)ctx->n_shadow_lights * level0.seg_stride > ws.sh_cap) {
+        sh_cap = (long long)ctx->n_shadow_lights * level0.seg_stride;
+        return PASS_AGAIN;
+    }
+    // one trace launch per bounce and light window + the primaries' own (more than NDT_QUEUE_SLOTS: see traced)
+    const long long want_slots = (long long)n_levels * (windowed ? n_win : 1) + 2;
+    slots = want_slots > NDT_QUEUE_SLOTS ? NDT_QUEUE_SLOTS : (int)want_slots;
+    launch_stamped(k_frame_init, dim3(8), dim3(256), s, ev_begin, nullptr, ws, rg.n_primary, level0, slots * NDT_QUEUE_INTS);
+    if (windowed) HIP_TRY(hipMemsetAsync(ws.counters + NDT_CNT_WIN, 0, (NDT_CNT_ALLOC - NDT_CNT_WIN) * sizeof(int), s));
+    return NDT_OK;
+}
+
+// One trace launch of the frame, on the next work queue
+int FrameInFlight::traced(TraceJob &tj, const std::string &what, const SceneDesc *sd_job)
+{
+    // (more trace launches than work queues -- light windows: a queue is used again once the stream has passed the launch
+    // that used it before, zeroed on the stream first)
+    tj.queue = ws.counters + NDT_CNT_QUEUE + (queue_slot % NDT_QUEUE_SLOTS) * NDT_QUEUE_INTS;
+    if (queue_slot++ >= slots) HIP_TRY(hipMemsetAsync(tj.queue, 0, NDT_QUEUE_INTS * sizeof(int), s));
+    const SceneDesc &sdj = sd_job ? *sd_job : sd_pass;
+    tj.exit_log = (ctx->exit_probe && prof && launches < NDT_EXIT_LOG_LAUNCHES) ? ws.exit_log + (size_t)launches * NDT_EXIT_LOG_WORDS : nullptr;
+    hipEvent_t a = nullptr, b2 = nullptr;
+    if (prof) {
+        a = get_event(ctx, ev_n++);
+        b2 = get_event(ctx, ev_n++);
+        trace_ev.push_back({ a, b2 });
+        trace_dbg.push_back(what);
+    }
+    kt->trace(s, ctx->d_blob, sdj, ws, tj, ctx->tier, ctx->sd.mask_words, a, b2);
+    ++launches;
+    return NDT_OK;
+}
+
+// the workspace a shade launch gets: with the shade probe's log if it is the probed launch (`finish_nodes` of it are lit)
+Workspace FrameInFlight::shade_ws(long long finish_nodes)
+{
+    Workspace w = ws;
+    if (shade_launch++ != ctx->shade_probe || !prof) {
+        w.shade_log = nullptr;
+    } else {
+        shade_probe_finish_waves = (finish_nodes + 255) / 256 * 4;
+        (void)hipMemsetAsync(w.shade_log, 0, (size_t)2 * NDT_SHADE_LOG_WAVES * sizeof(unsigned int), s);
+    }
+    return w;
+}
+
+// the dense half of a trace launch: closest-hit queries of nodes in the pool
+static void job_closest(TraceJob &tj, const Workspace &ws)
+{
+    tj.dense.o = ws.ray_o; tj.dense.v = ws.ray_v; tj.dense.stride = ws.cap; tj.dense.lim = nullptr;
+    tj.dense.valid = ws.depth_left; tj.dense.out_obj = ws.hit_obj; tj.dense.out_prim = ws.hit_prim;
+    tj.begin = 0;
+}
+
+// the segmented half: shadow rays of bounce b (at most `upper` nodes) in n_seg segments of the shadow queue, counted in seg_count
+static void job_shadow(TraceJob &tj, const Workspace &ws, const SceneDesc &sd_pass, int b, long long upper, int n_seg, const int *seg_count)
+{
+    tj.n_seg = n_seg;
+    tj.seg.o = ws.so; tj.seg.v = ws.sv; tj.seg.stride = ws.sh_cap; tj.seg.lim = ws.slim; tj.seg.valid = nullptr;
+    tj.seg_light_origins = sd_pass.light_origins;      // (what shade_emit_node left out: ndt_kernels.hip)
+    tj.seg.out_obj = ws.sobj; tj.seg.out_prim = ws.sprim;
+    tj.seg_count = seg_count;
+    tj.seg_stride = (upper + 63) & ~63LL;           // sizes the grid only
+    tj.levels = ws.levels;
+    tj.seg_level = b;
+}
+
+// closest-hit queries of the primaries: the only launch that is not shared
+int FrameInFlight::trace_primaries()
+{
+    // (the variant is built for the planar camera: VR and panorama frames take k_primary)
+    const bool fuse_primaries = (ctx->fuse_primaries < 0 ? ctx->dims >= 4 : ctx->fuse_primaries != 0) && ctx->cam_type == 0;
+    // (no k_primary: the first trace launch makes the primaries it traces, TraceJob::make_primaries)
+    if (!fuse_primaries) kt->primary(s, ctx->d_blob, sd_pass, ws, rg);
+    TraceJob tj{};
+    job_closest(tj, ws);
+    tj.count = rg.n_primary;
+    tj.publish_level = -1;
+    if (fuse_primaries) {
+        tj.make_primaries = 1;
+        tj.rg = rg;
+    }
+    return traced(tj, "primaries + closest 0");
+}
+
+// Hit points, shadow rays of bounce b, and the rays of the next bounce -- in the same launch as the lighting of the previous
+// bounce, which is waiting for the shadow answers the last trace launch produced
+void FrameInFlight::light_and_shade(int b, long long upper)
+{
+    if (windowed) {
+        // (the lighting of the last window of bounce b-1 and the shading of bounce b see different lights: two launches)
+        if (pending_finish >= 0)
+            kt->shade_last(s, ctx->d_blob, sd_win[n_win - 1], shade_ws(pending_upper), rg, pending_finish, pending_upper, 0, ctx->windows[n_win - 1].first);
+        kt->shade_emit(s, ctx->d_blob, sd_win[0], shade_ws(0), rg, b, upper);
+    } else if (pending_finish >= 0 && ctx->shade_pair) {
+        kt->shade_pair(s, ctx->d_blob, sd_pass, shade_ws(pending_upper), rg, pending_finish, pending_upper, upper);
+    } else {
+        if (pending_finish >= 0) kt->shade_finish(s, ctx->d_blob, sd_pass, shade_ws(pending_upper), rg, pending_finish, pending_upper, 0);
+        kt->shade_emit(s, ctx->d_blob, sd_pass, shade_ws(0), rg, b, upper);
+    }
+    pending_finish = -1;
+}
+
+// ONE launch: shadow rays of bounce b (of its first light window) + closest-hit rays of bounce b + 1, which its prologue publishes
+int FrameInFlight::trace_bounce(int b, long long upper)
+{
+    long long next_upper = 2 * upper;           // each node spawns at most two
+    if (next_upper > ws.cap) next_upper = ws.cap;
+    const bool last = b + 1 == hand;            // the frame kernel traces bounce `hand`
+    TraceJob tj{};
+    job_shadow(tj, ws, sd_pass, b, upper, windowed ? ctx->windows[0].n_seg : ctx->n_shadow_lights, NDT_SEG_COUNTERS(ws, b));
+    job_closest(tj, ws);
+    tj.count = next_upper;                      // sizes the grid only
+    tj.dense_level = last ? -1 : b + 1;
+    tj.publish_level = b;
+    tj.publish_tag = tag;
+    return traced(tj, "shadow " + std::to_string(b) + (last ? "" : " + closest " + std::to_string(b + 1)), windowed ? &sd_win[0] : nullptr);
+}
+
+// Light windows 1 .. of bounce b.  Window k: fold the answers of window k-1 into the nodes' colours and emit their shadow rays of
+// window k, then trace them
+int FrameInFlight::trace_windows(int b, long long upper)
+{
+    for (int k = 1; k < n_win; ++k) {
+        const ndt_hip_ctx::LightWindow &w = ctx->windows[k];
+        int *bank = ws.counters + NDT_CNT_WIN + 64 * (win_emits & 1);
+        int *next_bank = ws.counters + NDT_CNT_WIN + 64 * ((win_emits + 1) & 1);
+        ++win_emits;
+        kt->shade_window(s, ctx->d_blob, sd_win[k - 1], sd_win[k], shade_ws(upper), rg, b, upper, ctx->windows[k - 1].first, w.first, bank, next_bank,
+                         w.n_seg, k > 1 ? 1 : 0);
+        if (w.n_seg == 0) continue;
+        TraceJob tj{};
+        job_shadow(tj, ws, sd_pass, b, upper, w.n_seg, bank);
+        tj.count = 0;                               // shadow rays only
+        tj.dense_level = -1;
+        tj.publish_level = -1;
+        int rc = traced(tj, "shadow " + std::to_string(b) + " window " + std::to_string(k), &sd_win[k]);
+        if (rc) return rc;
+    }
+    return NDT_OK;
+}
+
+// The lighting of the deepest bounce that has nodes: blended on the spot (its nodes have no child nodes), unless the frame
+// kernel renders deeper bounces behind it (hybrid)
+void FrameInFlight::light_last()
+{
+    if (pending_finish < 0) return;
+    resolve_with_finish = !hybrid && pending_finish >= 1 && pending_finish == n_run - 1;
+    if (windowed)
+        kt->shade_last(s, ctx->d_blob, sd_win[n_win - 1], shade_ws(pending_upper), rg, pending_finish, pending_upper, resolve_with_finish ? 1 : 0,
+                       ctx->windows[n_win - 1].first);
+    else
+        kt->shade_finish(s, ctx->d_blob, sd_pass, shade_ws(pending_upper), rg, pending_finish, pending_upper, resolve_with_finish ? 1 : 0);
+}
+
+// Hybrid: the frame kernel renders the forest rooted at the nodes of bounce `hand` (its queues are reset, and it runs).
+// PASS_AGAIN: the 64-aligned cover of the roots does not fit the pool.
+int FrameInFlight::hand_off(long long &cap)
+{
+    int rc;
+    if ((rc = wait_for_tag(ctx, &ctx->h_mail_tag[hand], tag, "bounce %d was never published", hand))) return rc;
+    const LevelRange roots = ctx->h_mail[hand];
+    if (roots.count > 0) {
+        if ((rc = stream_roots(ctx, prof, roots.begin, roots.count, 0, sa))) return rc;
+        if ((long long)sa.root_begin + sa.n_primary > ws.cap) {
+            cap *= 2;
+            return PASS_AGAIN;
+        }
+        launch_stream_init(ctx, ws, sa, 0, nullptr);
+        if (prof) {
+            ev_k0 = get_event(ctx, ev_n++);
+            ev_k1 = get_event(ctx, ev_n++);
+            trace_ev.push_back({ ev_k0, ev_k1 });
+            trace_dbg.push_back("frame kernel, bounces " + std::to_string(hand) + " ..");
+        }
+        kt->frame_stream(s, ctx->d_blob, sd_pass, ws, rg, sa, ctx->tier, ctx->sd.mask_words, ev_k0, ev_k1);
+        ++launches;
+        streamed = true;
+    }
+    n_run = hand;           // the bounces the per-bounce resolve walks
+    return NDT_OK;
+}
+
+// bottom-up colour resolve, deepest bounce first (bounce 0, the primaries: inside k_finish_pixels)
+void FrameInFlight::resolve()
+{
+    for (int b = n_run; b-- > 1;) {
+        if (resolve_with_finish && b == n_run - 1) continue;
+        long long blocks = (level_nodes[b] + 255) / 256;
+        if (blocks > NDT_SHADE_MAX_BLOCKS) blocks = NDT_SHADE_MAX_BLOCKS;
+        hipLaunchKernelGGL(k_resolve, dim3((unsigned)blocks), dim3(256), 0, s, ctx->d_blob, sd_pass, ws, rg.specular, b);
+    }
+}
+
+// k_frame_done is the last kernel of the frame: once its tag is here, the image and the record are complete
+int FrameInFlight::close()
+{
+    launch_stamped(k_frame_done, dim3(1), dim3(64), s, nullptr, ev_end, ws, n_run, ctx->d_done, tag, streamed ? sa.ctl : (const StreamCtl *)nullptr);
+    HIP_TRY(hipGetLastError());
+    int rc = wait_for_tag(ctx, &ctx->h_done[7], tag, "the frame never completed");
+    if (rc) return rc;
+    if (prof) HIP_TRY(hipEventSynchronize(ev_end));     // the closing kernel has run: its completion is at most microseconds away
+    return NDT_OK;
+}
+
+// The closing record (k_frame_done): a pool overflowed somewhere in the frame -- grow it, PASS_AGAIN -- or the pass's statistics
+int FrameInFlight::report(long long &cap, long long &sh_cap, ndt_render_stats &st)
+{
+    const unsigned long long *done = ctx->h_done;
+    const int overflow = (int)(long long)done[1], sh_wanted = (int)(long long)done[2];
+    const int s_overflow = (int)(long long)done[8], s_abort = (int)(long long)done[9];
+    if (overflow != 0 || s_overflow != 0) {
+        if (ctx->debug_levels)
+            fprintf(stderr, "ndt_hip: overflow: per-bounce kernels %d (needs %d), frame kernel %d; pool %lld nodes, %lld shadow slots\n", overflow,
+                    sh_wanted, s_overflow, cap, sh_cap);
+        if ((overflow & 1) || (s_overflow & 1)) cap *= 2;
+        if ((overflow & 2) || (s_overflow & 2)) {
+            sh_cap *= 2;
+            if (sh_cap < sh_wanted) sh_cap = sh_wanted;
+        }
+        // (the frame kernel keeps the shadow rays of ALL its bounces: its segments grow with the node pool, together)
+        const int n_seg = ctx->n_shadow_lights > 0 ? ctx->n_shadow_lights : 1;
+        if (s_overflow != 0 && sh_cap < cap * n_seg) sh_cap = cap * n_seg;
+        return PASS_AGAIN;
+    }
+    if (s_abort != 0)
+        return fail(NDT_E_STATE, "the frame kernel gave up (abort %d, where %d): a work item never arrived", s_abort & 0xff, s_abort >> 8);
+    st = ndt_render_stats{};
+    st.rays_primary = n_pixels(rg);
+    st.rays_secondary = (long long)(int)(long long)done[0] - rg.n_primary + (long long)done[10];
+    st.rays_shadow = (long long)done[3];
+    st.rays_ref_equiv = (long long)done[5];
+    st.levels = (int)done[4];
+    st.trace_launches = launches;
+    st.node_capacity = ws.cap;
+    if (prof) {
+        float ms = 0, fm = 0;
+        for (auto &pr : trace_ev) {
+            float m = 0;
+            HIP_TRY(hipEventElapsedTime(&m, pr.first, pr.second));
+            ms += m;
+        }
+        st.trace_ms = ms;
+        if (streamed && sa.wave_log && ev_k0) {
+            float km = 0;
+            HIP_TRY(hipEventElapsedTime(&km, ev_k0, ev_k1));
+            print_stream_probe(sa.wave_log, km);
+        }
+        if (ctx->debug_levels) HIP_TRY(print_debug(st.levels));
+        HIP_TRY(hipEventElapsedTime(&fm, ev_begin, ev_end));
+        st.frame_ms = fm;
+    }
+    return NDT_OK;
+}
+
+// NDT_HIP_DEBUG_LEVELS of a profiled pass: the bounce table, the probes, every trace launch's time
+hipError_t FrameInFlight::print_debug(int levels_used)
+{
+    LevelRange *hl = ctx->h_levels;
+    const hipError_t e = hipMemcpy(hl, ws.levels, (size_t)(n_run + 1) * sizeof(LevelRange), hipMemcpyDeviceToHost);
+    if (e != hipSuccess) return e;
+    for (int b = 0; b < levels_used; ++b) fprintf(stderr, "ndt_hip: bounce %d: %lld nodes, %lld shadow rays\n", b, hl[b].count, hl[b].n_shadow);
+    if (ctx->shade_probe >= 0 && ws.shade_log) print_shade_probe(ws.shade_log, ctx->shade_probe, shade_probe_finish_waves);
+    if (ctx->exit_probe) print_exit_probe(ws.exit_log, launches);
+    print_phase_timing(ws.dbg);
+    for (size_t i = 0; i < trace_ev.size(); ++i) {
+        float m = 0;
+        (void)hipEventElapsedTime(&m, trace_ev[i].first, trace_ev[i].second);
+        fprintf(stderr, "ndt_hip: trace launch %zu: %.3f ms (%s)\n", i, m, trace_dbg[i].c_str());
+    }
+    return hipSuccess;
+}
+
+// Grows the pools and renders again on overflow, at most 8 times
+static int render_pass_levels(ndt_hip_ctx *ctx, const RenderGeom &rg, const SceneDesc &sd_pass, bool prof, bool hybrid, void *d_rgba, void *d_depth,
+                              long long cap, long long sh_cap, ndt_render_stats &st)
+{
+    for (int attempt = 0; attempt < 8; ++attempt) {
+        if (cap > 0x7fffff00LL || sh_cap > 0x7fffff00LL) return fail(NDT_E_NOMEM, "ray tree exceeds 2^31 nodes");
+        int rc = ensure_workspace(ctx, cap, sh_cap);
+        if (rc) return rc;
+        if (hybrid && (rc = ensure_stream_args(ctx))) return rc;
+        FrameInFlight frame(ctx, rg, sd_pass, prof, hybrid, d_rgba, d_depth);
+        if ((rc = frame.render(cap, sh_cap, st)) != PASS_AGAIN) return rc;
+    }
+    return fail(NDT_E_NOMEM, "ray-tree workspace kept overflowing");
+}
+
 // One pass of the ray pipeline over the primaries `rg` describes: primary rays, the bounce loop,
 // bottom-up resolve, per-primary colour (k_finish_pixels) into d_rgba.  Grid mode writes a
 // rows x width image, list mode one RGBA per sample.  max_depth > 0 (the callers handle -l 0).
 int ndt_impl::render_pass(ndt_hip_ctx *ctx, RenderGeom rg, bool prof, void *d_rgba, ndt_render_stats &st, void *d_depth)
 {
     rg.want_depth = d_depth ? 1 : 0;
-    hipStream_t s = ctx->stream;
     const long long n_primary = rg.n_primary;
-    const long long n_pixels = rg.samples ? (long long)rg.n_samples : (long long)rg.rows * rg.width;
     long long cap = ctx->ws.cap, sh_cap = ctx->ws.sh_cap;
     if (cap < 2 * n_primary + 4096) cap = 2 * n_primary + 4096;
     const long long want_sh = n_primary * (ctx->n_shadow_lights > 0 ? ctx->n_shadow_lights : 1) + 4096;
     if (sh_cap < want_sh) sh_cap = want_sh;
     if (ctx->test_small_pool && ctx->ws.cap == 0) {
         // tests only: a fresh context starts with a node pool that a reflective scene overflows, so that the
-        // overflow -> grow -> render-again path below is exercised (tests/test_gpu_parity.py)
+        // overflow -> grow -> render-again path of the two pipelines is exercised (tests/test_gpu_parity.py)
         cap = ((n_primary + 63) & ~63LL) + 64;
     }
-
-    const NdtKernelTable *kt = ctx->kt;
     // (the gate prepass of trace_kd: the scene description a pass's kernels get carries the gated items only when it is on)
     SceneDesc sd_pass = ctx->sd;
     if (ctx->gate_prepass == 0 || (ctx->gate_prepass == 2 && n_primary > ctx->gate_prepass_below)) sd_pass.gate_bits = 0ull;
@@ -447,578 +926,18 @@ int ndt_impl::render_pass(ndt_hip_ctx *ctx, RenderGeom rg, bool prof, void *d_rg
     const long long stream_upto = rg.samples ? ctx->stream_below_list : ctx->stream_below;
     // (a scene of more than one light window: the per-bounce kernels, whatever the pipeline -- the frame kernel keeps one 64-bit
     // mask of fired lights per node)
-    const int n_win = (int)ctx->windows.size();
-    const bool windowed = n_win > 1;
-    ctx->use_stream = !windowed && (ctx->pipeline == 2 || (ctx->pipeline == 0 && n_primary <= stream_upto));
-    const bool hybrid = !windowed && !ctx->use_stream && ctx->pipeline == 3 && ctx->hybrid_level >= 1 && rg.max_depth > ctx->hybrid_level;
-    // (auto only) the frame kernel keeps one shadow slot per node AND light for the whole frame: with many lights that can
-    // exceed what the per-bounce pipeline, which sizes its segments bounce by bounce, needs by far.  When it does not fit --
-    // 2^31 slots, or the allocation fails -- auto renders the pass per bounce instead of failing.
-    const long long cap_levels = cap, sh_cap_levels = sh_cap;
-    bool stream_gave_up = false;
-    if (ctx->use_stream) {
-        // ---- the streaming pipeline: one persistent launch for the whole ray tree (ndt_stream.hpp)
-        const int n_seg = ctx->n_shadow_lights > 0 ? ctx->n_shadow_lights : 1;
-        for (int attempt = 0; attempt < 8; ++attempt) {
-            // every light's shadow segment can hold one ray per node
-            if (sh_cap < cap * n_seg) sh_cap = cap * n_seg;
-            int rc = NDT_OK;
-            if (cap > 0x7fffff00LL || sh_cap > 0x7fffff00LL) rc = fail(NDT_E_NOMEM, "ray tree exceeds 2^31 nodes");
-            if (!rc) rc = ensure_workspace(ctx, cap, sh_cap);
-            if (!rc) rc = ensure_stream_args(ctx);
-            if (rc == NDT_E_NOMEM && ctx->pipeline == 0) {
-                stream_gave_up = true;
-                break;
-            }
-            if (rc) return rc;
-            Workspace ws = ctx->ws;
-            StreamArgs sa = ctx->sa;
-            sa.root_begin = 0;
-            sa.n_primary = rg.n_primary;
-            sa.roots_are_primaries = 1;
-            sa.valid_begin = 0;
-            sa.valid_end = rg.n_primary;
-            // the kernel makes its own primaries and writes its own pixels (option stream_fused, on by default)
-            sa.fused = ctx->stream_fused ? 1 : 0;
-            sa.rgba = (double *)d_rgba;
-            sa.depth_out = (double *)d_depth;
-            unsigned int *wave_log = sa.wave_log;
-            if (!prof) sa.wave_log = nullptr;
-            else if (wave_log) HIP_TRY(hipMemsetAsync(wave_log, 0, (size_t)24 * NDT_STREAM_LOG_WAVES * sizeof(unsigned int), s));
-            hipEvent_t ev_begin = nullptr, ev_end = nullptr, ev_k0 = nullptr, ev_k1 = nullptr;
-            if (prof) {
-                ev_begin = get_event(ctx, 0);
-                ev_end = get_event(ctx, 1);
-                ev_k0 = get_event(ctx, 2);
-                ev_k1 = get_event(ctx, 3);
-            }
-            const unsigned long long tag = ++ctx->frame_tag;
-            const long long node_batches = sa.node_batches, sh_batches = (long long)sa.n_seg * (sa.seg_cap / 64) + NDT_STREAM_LOG_WAVES;
-            if (prof)
-                hipExtLaunchKernelGGL(k_stream_init, dim3(512), dim3(256), 0, s, ev_begin, nullptr, 0u, ws, sa, node_batches, sh_batches, 1);
-            else
-                hipLaunchKernelGGL(k_stream_init, dim3(512), dim3(256), 0, s, ws, sa, node_batches, sh_batches, 1);
-            if (!sa.fused) kt->primary(s, ctx->d_blob, sd_pass, ws, rg);
-            kt->frame_stream(s, ctx->d_blob, sd_pass, ws, rg, sa, ctx->tier, ctx->sd.mask_words, ev_k0, ev_k1);
-            if (!sa.fused)
-                hipLaunchKernelGGL(k_finish_pixels, dim3((unsigned)((rg.n_primary + NDT_FINISH_BLOCK - 1) / NDT_FINISH_BLOCK)), dim3(NDT_FINISH_BLOCK), 0, s, ctx->d_blob, sd_pass, ws,
-                                   rg, ctx->dims, (double *)d_rgba, (double *)d_depth, 0);
-            if (prof)
-                hipExtLaunchKernelGGL(k_stream_done, dim3(1), dim3(64), 0, s, nullptr, ev_end, 0u, ws, sa, ctx->d_done, tag);
-            else
-                hipLaunchKernelGGL(k_stream_done, dim3(1), dim3(64), 0, s, ws, sa, ctx->d_done, tag);
-            HIP_TRY(hipGetLastError());
-            {
-                const double t_wait = wall_s();
-                while (__atomic_load_n(&ctx->h_done[7], __ATOMIC_ACQUIRE) != tag) {
-                    if (wall_s() - t_wait > 30.0) {
-                        HIP_TRY(hipStreamSynchronize(s));
-                        if (__atomic_load_n(&ctx->h_done[7], __ATOMIC_ACQUIRE) != tag) return fail(NDT_E_STATE, "the frame never completed");
-                    }
-                }
-            }
-            if (prof) HIP_TRY(hipEventSynchronize(ev_end));
-            const int overflow = (int)(long long)ctx->h_done[1], aborted = (int)(long long)ctx->h_done[2];
-            if (overflow != 0) {
-                if (overflow & 1) cap *= 2;
-                if (overflow & 2) sh_cap *= 2;
-                continue;
-            }
-            if (aborted != 0)
-                return fail(NDT_E_STATE, "the frame kernel gave up (abort %d, where %d): a work item never arrived", aborted & 0xff, aborted >> 8);
-            st = ndt_render_stats{};
-            st.rays_primary = n_pixels;
-            st.rays_secondary = (long long)ctx->h_done[6];
-            st.rays_shadow = (long long)ctx->h_done[3];
-            st.rays_ref_equiv = (long long)ctx->h_done[5];
-            st.levels = (int)ctx->h_done[4];
-            st.trace_launches = 1;
-            st.node_capacity = ws.cap;
-            if (prof) {
-                float km = 0, fm = 0;
-                HIP_TRY(hipEventElapsedTime(&km, ev_k0, ev_k1));
-                HIP_TRY(hipEventElapsedTime(&fm, ev_begin, ev_end));
-                st.trace_ms = km;
-                st.frame_ms = fm;
-                if (wave_log) print_stream_probe(wave_log, km);
-            }
-            return NDT_OK;
-        }
-        if (!stream_gave_up) return fail(NDT_E_NOMEM, "ray-tree workspace kept overflowing");
-        ctx->use_stream = false;
-        cap = cap_levels;
-        sh_cap = sh_cap_levels;
+    const bool windowed = ctx->windows.size() > 1;
+    const bool use_stream = !windowed && (ctx->pipeline == 2 || (ctx->pipeline == 0 && n_primary <= stream_upto));
+    const bool hybrid = !windowed && !use_stream && ctx->pipeline == 3 && ctx->hybrid_level >= 1 && rg.max_depth > ctx->hybrid_level;
+    if (use_stream) {
+        bool no_room = false;
+        const int rc = render_pass_stream(ctx, rg, sd_pass, prof, d_rgba, d_depth, cap, sh_cap, st, no_room);
+        // (auto only) the frame kernel keeps one shadow slot per node AND light for the whole frame: with many lights that can
+        // exceed what the per-bounce pipeline, which sizes its segments bounce by bounce, needs by far.  When it does not fit --
+        // 2^31 slots, or the allocation fails -- auto renders the pass per bounce instead of failing.
+        if (!(no_room && ctx->pipeline == 0)) return rc;
         if (cap < ctx->ws.cap) cap = ctx->ws.cap;
         if (sh_cap < ctx->ws.sh_cap) sh_cap = ctx->ws.sh_cap;
     }
-    for (int attempt = 0; attempt < 8; ++attempt) {
-        if (cap > 0x7fffff00LL || sh_cap > 0x7fffff00LL) return fail(NDT_E_NOMEM, "ray tree exceeds 2^31 nodes");
-        int rc = ensure_workspace(ctx, cap, sh_cap);
-        if (rc) return rc;
-        if (hybrid && (rc = ensure_stream_args(ctx))) return rc;
-        Workspace ws = ctx->ws;
-        size_t ev_n = 0;
-        hipEvent_t ev_begin = nullptr, ev_end = nullptr;
-        std::vector<std::pair<hipEvent_t, hipEvent_t>> trace_ev;
-        std::vector<std::string> trace_dbg;
-        if (prof) {
-            // frame time = start of the frame's first kernel .. end of its last (their own dispatch timestamps)
-            ev_begin = get_event(ctx, ev_n++);
-            ev_end = get_event(ctx, ev_n++);
-        }
-        int *hc = ctx->h_counters;
-        if (prof && ctx->exit_probe)
-            HIP_TRY(hipMemsetAsync(ws.exit_log, 0, (size_t)NDT_EXIT_LOG_LAUNCHES * NDT_EXIT_LOG_WORDS * sizeof(unsigned int), s));
-        // The stream is never synchronised inside a frame: the range of every bounce is published
-        // on the device (k_level_step) and read there; the host only learns, from the mailbox,
-        // whether there is a next bounce to enqueue.  Bounce 0 = the primaries.
-        ws.mail = ctx->d_mail;
-        ws.mail_tag = ctx->d_mail_tag;
-        const unsigned long long tag = ++ctx->frame_tag;
-        const int n_seg = ctx->n_shadow_lights;
-        const int n_levels = rg.max_depth > 1 ? rg.max_depth : 1;      // a node spawns children only while depth_left > 1
-        int n_run = n_levels;                                           // bounces actually enqueued
-        LevelRange *hl = ctx->h_levels;
-        hl[0].begin = 0;
-        hl[0].count = rg.n_primary;
-        hl[0].seg_stride = (rg.n_primary + 63) & ~63LL;
-        hl[0].n_shadow = 0;
-        if ((long long)n_seg * hl[0].seg_stride > ws.sh_cap) {
-            sh_cap = (long long)n_seg * hl[0].seg_stride;
-            continue;
-        }
-        // one trace launch per bounce and light window + the primaries' own (more than NDT_QUEUE_SLOTS: see traced below)
-        long long want_slots = (long long)n_levels * (windowed ? n_win : 1) + 2;
-        const int slots = want_slots > NDT_QUEUE_SLOTS ? NDT_QUEUE_SLOTS : (int)want_slots;
-        {
-            if (prof)
-                hipExtLaunchKernelGGL(k_frame_init, dim3(8), dim3(256), 0, s, ev_begin, nullptr, 0u, ws, rg.n_primary, hl[0], slots * NDT_QUEUE_INTS);
-            else
-                hipLaunchKernelGGL(k_frame_init, dim3(8), dim3(256), 0, s, ws, rg.n_primary, hl[0], slots * NDT_QUEUE_INTS);
-            if (windowed) HIP_TRY(hipMemsetAsync(ws.counters + NDT_CNT_WIN, 0, (NDT_CNT_ALLOC - NDT_CNT_WIN) * sizeof(int), s));
-        }
-        int queue_slot = 0;
-        int launches = 0;
-        // (the variant is built for the planar camera: VR and panorama frames take k_primary)
-        const bool fuse_primaries = (ctx->fuse_primaries < 0 ? ctx->dims >= 4 : ctx->fuse_primaries != 0) && ctx->cam_type == 0;
-        // (no k_primary: the first trace launch makes the primaries it traces, TraceJob::make_primaries)
-        if (!fuse_primaries) kt->primary(s, ctx->d_blob, sd_pass, ws, rg);
-        auto traced = [&](TraceJob &tj, const std::string &what, const SceneDesc *sd_job = nullptr) -> int {
-            // (more trace launches than work queues -- light windows: a queue is used again once the stream has passed the launch
-            // that used it before, zeroed on the stream first)
-            tj.queue = ws.counters + NDT_CNT_QUEUE + (queue_slot % NDT_QUEUE_SLOTS) * NDT_QUEUE_INTS;
-            if (queue_slot++ >= slots) HIP_TRY(hipMemsetAsync(tj.queue, 0, NDT_QUEUE_INTS * sizeof(int), s));
-            const SceneDesc &sdj = sd_job ? *sd_job : sd_pass;
-            const bool exit_probe = ctx->exit_probe;
-            tj.exit_log = (exit_probe && prof && launches < NDT_EXIT_LOG_LAUNCHES) ? ws.exit_log + (size_t)launches * NDT_EXIT_LOG_WORDS : nullptr;
-            if (prof) {
-                hipEvent_t a = get_event(ctx, ev_n++), b2 = get_event(ctx, ev_n++);
-                kt->trace(s, ctx->d_blob, sdj, ws, tj, ctx->tier, ctx->sd.mask_words, a, b2);
-                trace_ev.push_back({ a, b2 });
-                trace_dbg.push_back(what);
-            } else {
-                kt->trace(s, ctx->d_blob, sdj, ws, tj, ctx->tier, ctx->sd.mask_words, nullptr, nullptr);
-            }
-            ++launches;
-            return NDT_OK;
-        };
-        // closest-hit queries of the primaries: the only launch that is not shared
-        {
-            TraceJob tj{};
-            tj.n_seg = 0;
-            tj.dense.o = ws.ray_o; tj.dense.v = ws.ray_v; tj.dense.stride = ws.cap; tj.dense.lim = nullptr;
-            tj.dense.valid = ws.depth_left; tj.dense.out_obj = ws.hit_obj; tj.dense.out_prim = ws.hit_prim;
-            tj.begin = 0; tj.count = rg.n_primary; tj.levels = nullptr;
-            tj.publish_level = -1;
-            if (fuse_primaries) {
-                tj.make_primaries = 1;
-                tj.rg = rg;
-            }
-            if ((rc = traced(tj, "primaries + closest 0"))) return rc;
-        }
-        long long upper = rg.n_primary;         // node count of the bounce
-        std::vector<long long> level_nodes;
-        // NDT_HIP_SHADE_PROBE=<k>: the k-th shade launch of the frame logs the life of each of its wavefronts
-        const int shade_probe = ctx->shade_probe;
-        int shade_launch = 0;
-        long long shade_probe_finish_waves = 0;         // wavefronts of the lighting part of the probed launch
-        long long shade_probe_emit_waves = 0;           // ... and of the shading part behind it (pair launches)
-        auto shade_ws = [&](long long finish_nodes, long long emit_nodes_behind = 0) {
-            Workspace w = ws;
-            if (shade_launch++ != shade_probe || !prof) {
-                w.shade_log = nullptr;
-            } else {
-                shade_probe_finish_waves = (finish_nodes + 255) / 256 * 4;
-                shade_probe_emit_waves = (emit_nodes_behind + 255) / 256 * 4;
-                (void)hipMemsetAsync(w.shade_log, 0, (size_t)2 * NDT_SHADE_LOG_WAVES * sizeof(unsigned int), s);
-            }
-            return w;
-        };
-        const bool fuse_shade = ctx->shade_pair;
-        // light windows: window k's scene description, and how many window emits the frame has had (they take the two banks of
-        // window counters in turn)
-        std::vector<SceneDesc> sd_win;
-        for (int k = 0; windowed && k < n_win; ++k) sd_win.push_back(window_desc(ctx, sd_pass, k));
-        int win_emits = 0;
-        int pending_finish = -1;                // bounce whose lighting has not been launched yet
-        long long pending_upper = 0;
-        // Hybrid pipeline: the first `hand` bounces -- where the rays are -- go through the per-bounce kernels (three
-        // wavefronts per SIMD in the trace kernel, shade kernels with the whole chip's wavefront slots); the deeper
-        // bounces, a few per cent of the rays but a launch latency each (one slow batch: 0.15-0.2 ms per trace launch
-        // and 75 us per shade launch, three times over on the benchmark frame), are ONE launch of the frame kernel
-        // rooted at the nodes of bounce `hand`.
-        const int hand = hybrid ? ctx->hybrid_level : n_levels + 1;
-        bool streamed = false;
-        for (int b = 0; b < n_levels && b < hand; ++b) {
-            // (the same bounce limit whatever the light windows: a windowed pass uses its work queues again, but light_window must
-            // not change what renders)
-            if ((windowed ? b + 2 : queue_slot + 1) > NDT_QUEUE_SLOTS || b + 1 > NDT_MAX_LEVELS)
-                return fail(NDT_E_UNSUPPORTED, "more than %d bounces", NDT_QUEUE_SLOTS - 1);
-            if (b > 0) {
-                // posted by k_level_step(b-1), which ran right after shade_emit(b-1)
-                const double t_wait = wall_s();
-                while (__atomic_load_n(&ctx->h_mail_tag[b], __ATOMIC_ACQUIRE) != tag) {
-                    if (wall_s() - t_wait > 30.0) {
-                        HIP_TRY(hipStreamSynchronize(s));
-                        if (__atomic_load_n(&ctx->h_mail_tag[b], __ATOMIC_ACQUIRE) != tag) return fail(NDT_E_STATE, "bounce %d was never published", b);
-                    }
-                }
-                upper = ctx->h_mail[b].count;
-                if (upper <= 0) {
-                    n_run = b;
-                    break;
-                }
-            }
-            level_nodes.push_back(upper);
-            // hit points, shadow rays of this bounce, and the rays of the next bounce -- in the same launch as the
-            // lighting of the previous bounce, which is waiting for the shadow answers the last trace launch produced
-            if (windowed) {
-                // (the lighting of the last window of bounce b-1 and the shading of bounce b see different lights: two launches)
-                if (pending_finish >= 0) {
-                    kt->shade_last(s, ctx->d_blob, sd_win[n_win - 1], shade_ws(pending_upper), rg, pending_finish, pending_upper, 0,
-                                   ctx->windows[n_win - 1].first);
-                    pending_finish = -1;
-                }
-                kt->shade_emit(s, ctx->d_blob, sd_win[0], shade_ws(0), rg, b, upper);
-            } else if (pending_finish >= 0 && fuse_shade) {
-                kt->shade_pair(s, ctx->d_blob, sd_pass, shade_ws(pending_upper, upper), rg, pending_finish, pending_upper, upper);
-                pending_finish = -1;
-            } else {
-                if (pending_finish >= 0) {
-                    kt->shade_finish(s, ctx->d_blob, sd_pass, shade_ws(pending_upper), rg, pending_finish, pending_upper, 0);
-                    pending_finish = -1;
-                }
-                kt->shade_emit(s, ctx->d_blob, sd_pass, shade_ws(0), rg, b, upper);
-            }
-            // (no k_level_step: the trace launch below publishes bounce b + 1, TraceJob::publish_level)
-            long long next_upper = 2 * upper;           // each node spawns at most two
-            if (next_upper > ws.cap) next_upper = ws.cap;
-            {
-                // ONE launch: shadow rays of bounce b + closest-hit rays of bounce b+1
-                TraceJob tj{};
-                tj.n_seg = windowed ? ctx->windows[0].n_seg : n_seg;
-                tj.seg.o = ws.so; tj.seg.v = ws.sv; tj.seg.stride = ws.sh_cap; tj.seg.lim = ws.slim; tj.seg.valid = nullptr;
-                tj.seg_light_origins = sd_pass.light_origins;      // (what shade_emit_node left out: ndt_kernels.hip)
-                tj.seg.out_obj = ws.sobj; tj.seg.out_prim = ws.sprim;
-                tj.seg_count = NDT_SEG_COUNTERS(ws, b);
-                tj.seg_stride = (upper + 63) & ~63LL;           // sizes the grid only
-                tj.dense.o = ws.ray_o; tj.dense.v = ws.ray_v; tj.dense.stride = ws.cap; tj.dense.lim = nullptr;
-                tj.dense.valid = ws.depth_left; tj.dense.out_obj = ws.hit_obj; tj.dense.out_prim = ws.hit_prim;
-                tj.begin = 0;
-                tj.count = next_upper;                          // sizes the grid only
-                tj.levels = ws.levels; tj.seg_level = b; tj.dense_level = (b + 1 == hand) ? -1 : b + 1;     // the frame kernel traces bounce `hand`
-                tj.publish_level = b;
-                tj.publish_tag = tag;
-                if ((rc = traced(tj, "shadow " + std::to_string(b) + (b + 1 == hand ? "" : " + closest " + std::to_string(b + 1)),
-                                 windowed ? &sd_win[0] : nullptr)))
-                    return rc;
-            }
-            for (int k = 1; windowed && k < n_win; ++k) {
-                // window k: fold the answers of window k-1 into the nodes' colours and emit their shadow rays of window k, then trace them
-                const ndt_hip_ctx::LightWindow &w = ctx->windows[k];
-                int *bank = ws.counters + NDT_CNT_WIN + 64 * (win_emits & 1);
-                int *next_bank = ws.counters + NDT_CNT_WIN + 64 * ((win_emits + 1) & 1);
-                ++win_emits;
-                kt->shade_window(s, ctx->d_blob, sd_win[k - 1], sd_win[k], shade_ws(upper), rg, b, upper, ctx->windows[k - 1].first, w.first,
-                                 bank, next_bank, w.n_seg, k > 1 ? 1 : 0);
-                if (w.n_seg == 0) continue;
-                TraceJob tj{};
-                tj.n_seg = w.n_seg;
-                tj.seg.o = ws.so; tj.seg.v = ws.sv; tj.seg.stride = ws.sh_cap; tj.seg.lim = ws.slim; tj.seg.valid = nullptr;
-                tj.seg_light_origins = sd_pass.light_origins;
-                tj.seg.out_obj = ws.sobj; tj.seg.out_prim = ws.sprim;
-                tj.seg_count = bank;
-                tj.seg_stride = (upper + 63) & ~63LL;           // sizes the grid only
-                tj.begin = 0;
-                tj.count = 0;                                   // shadow rays only
-                tj.levels = ws.levels; tj.seg_level = b; tj.dense_level = -1;
-                tj.publish_level = -1;
-                if ((rc = traced(tj, "shadow " + std::to_string(b) + " window " + std::to_string(k), &sd_win[k]))) return rc;
-            }
-            pending_finish = b;
-            pending_upper = upper;
-        }
-        // the lighting of the deepest bounce that has nodes: blended on the spot (its nodes have no child nodes), unless the frame
-        // kernel renders deeper bounces behind it (hybrid)
-        const bool resolve_with_finish = pending_finish >= 0 && !hybrid && pending_finish >= 1 && pending_finish == n_run - 1;
-        if (pending_finish >= 0 && windowed)
-            kt->shade_last(s, ctx->d_blob, sd_win[n_win - 1], shade_ws(pending_upper), rg, pending_finish, pending_upper, resolve_with_finish ? 1 : 0,
-                           ctx->windows[n_win - 1].first);
-        else if (pending_finish >= 0)
-            kt->shade_finish(s, ctx->d_blob, sd_pass, shade_ws(pending_upper), rg, pending_finish, pending_upper, resolve_with_finish ? 1 : 0);
-        StreamArgs sa = ctx->sa;
-        hipEvent_t ev_k0 = nullptr, ev_k1 = nullptr;
-        if (hybrid && n_run >= hand && hand < n_levels) {
-            // the nodes of bounce `hand`: posted by k_level_step(hand - 1)
-            const double t_wait = wall_s();
-            while (__atomic_load_n(&ctx->h_mail_tag[hand], __ATOMIC_ACQUIRE) != tag) {
-                if (wall_s() - t_wait > 30.0) {
-                    HIP_TRY(hipStreamSynchronize(s));
-                    if (__atomic_load_n(&ctx->h_mail_tag[hand], __ATOMIC_ACQUIRE) != tag) return fail(NDT_E_STATE, "bounce %d was never published", hand);
-                }
-            }
-            const LevelRange roots = ctx->h_mail[hand];
-            if (roots.count > 0) {
-                // the root range = the 64-aligned cover of the bounce's node range (the frame kernel works in batches of
-                // 64 slots); its queues are reset, and it runs
-                sa.root_begin = (int)(roots.begin & ~63LL);
-                sa.n_primary = (int)(((roots.begin + roots.count + 63) & ~63LL) - sa.root_begin);
-                sa.valid_begin = (int)roots.begin;
-                sa.valid_end = (int)(roots.begin + roots.count);
-                sa.roots_are_primaries = 0;
-                sa.fused = 0;
-                if (!prof) sa.wave_log = nullptr;
-                else if (sa.wave_log) HIP_TRY(hipMemsetAsync(sa.wave_log, 0, (size_t)24 * NDT_STREAM_LOG_WAVES * sizeof(unsigned int), s));
-                if ((long long)sa.root_begin + sa.n_primary > ws.cap) {
-                    cap *= 2;
-                    continue;
-                }
-                const long long sh_batches = (long long)sa.n_seg * (sa.seg_cap / 64) + NDT_STREAM_LOG_WAVES;
-                hipLaunchKernelGGL(k_stream_init, dim3(512), dim3(256), 0, s, ws, sa, (long long)sa.node_batches, sh_batches, 0);
-                if (prof) {
-                    ev_k0 = get_event(ctx, ev_n++);
-                    ev_k1 = get_event(ctx, ev_n++);
-                }
-                kt->frame_stream(s, ctx->d_blob, sd_pass, ws, rg, sa, ctx->tier, ctx->sd.mask_words, ev_k0, ev_k1);
-                if (prof) {
-                    trace_ev.push_back({ ev_k0, ev_k1 });
-                    trace_dbg.push_back("frame kernel, bounces " + std::to_string(hand) + " ..");
-                }
-                ++launches;
-                streamed = true;
-            }
-            n_run = hand;           // the bounces the per-bounce resolve below walks
-        }
-        // bottom-up colour resolve, deepest bounce first (the primaries last)
-        {
-            for (int b = n_run; b-- > 1;) {        // (bounce 0, the primaries: inside k_finish_pixels)
-                if (resolve_with_finish && b == n_run - 1) continue;
-                long long blocks = (level_nodes[b] + 255) / 256;
-                if (blocks > NDT_SHADE_MAX_BLOCKS) blocks = NDT_SHADE_MAX_BLOCKS;
-                hipLaunchKernelGGL(k_resolve, dim3((unsigned)blocks), dim3(256), 0, s, ctx->d_blob, sd_pass, ws, rg.specular, b);
-            }
-        }
-        hipLaunchKernelGGL(k_finish_pixels, dim3((unsigned)((rg.n_primary + NDT_FINISH_BLOCK - 1) / NDT_FINISH_BLOCK)), dim3(NDT_FINISH_BLOCK), 0, s, ctx->d_blob, sd_pass, ws,
-                           rg, ctx->dims, (double *)d_rgba, (double *)d_depth, n_run >= 1 ? 1 : 0);
-        const StreamCtl *sctl = streamed ? sa.ctl : nullptr;
-        if (prof)
-            hipExtLaunchKernelGGL(k_frame_done, dim3(1), dim3(64), 0, s, nullptr, ev_end, 0u, ws, n_run, ctx->d_done, tag, sctl);
-        else
-            hipLaunchKernelGGL(k_frame_done, dim3(1), dim3(64), 0, s, ws, n_run, ctx->d_done, tag, sctl);
-        HIP_TRY(hipGetLastError());
-        if (prof && ctx->debug_levels) {
-            // the bounce table only feeds the debug output
-            HIP_TRY(hipMemcpyAsync(hl, ws.levels, (size_t)(n_run + 1) * sizeof(LevelRange), hipMemcpyDeviceToHost, s));
-            HIP_TRY(hipStreamSynchronize(s));
-        }
-        {
-            // k_frame_done is the last kernel of the frame: once its tag is here, the image and the record are complete
-            const double t_wait = wall_s();
-            while (__atomic_load_n(&ctx->h_done[7], __ATOMIC_ACQUIRE) != tag) {
-                if (wall_s() - t_wait > 30.0) {
-                    HIP_TRY(hipStreamSynchronize(s));
-                    if (__atomic_load_n(&ctx->h_done[7], __ATOMIC_ACQUIRE) != tag) return fail(NDT_E_STATE, "the frame never completed");
-                }
-            }
-        }
-        if (prof) HIP_TRY(hipEventSynchronize(ev_end));     // the closing kernel has run: its completion is at most microseconds away
-        hc[0] = (int)(long long)ctx->h_done[0];
-        hc[2] = (int)(long long)ctx->h_done[1];
-        hc[3] = (int)(long long)ctx->h_done[2];
-        const unsigned long long ref_rays = ctx->h_done[5];
-        const int s_overflow = (int)(long long)ctx->h_done[8], s_abort = (int)(long long)ctx->h_done[9];
-        if (hc[2] != 0 || s_overflow != 0) {
-            if (ctx->debug_levels)
-                fprintf(stderr, "ndt_hip: overflow: per-bounce kernels %d (needs %d), frame kernel %d; pool %lld nodes, %lld shadow slots\n", hc[2],
-                        hc[3], s_overflow, cap, sh_cap);
-            // a pool overflowed somewhere in the frame: grow it and render again
-            if ((hc[2] & 1) || (s_overflow & 1)) cap *= 2;
-            if ((hc[2] & 2) || (s_overflow & 2)) {
-                sh_cap *= 2;
-                if (sh_cap < hc[3]) sh_cap = hc[3];
-            }
-            // (the frame kernel keeps the shadow rays of ALL its bounces: its segments grow with the node pool, together)
-            if (s_overflow != 0 && sh_cap < cap * (n_seg > 0 ? n_seg : 1)) sh_cap = cap * (n_seg > 0 ? n_seg : 1);
-            continue;
-        }
-        if (s_abort != 0)
-            return fail(NDT_E_STATE, "the frame kernel gave up (abort %d, where %d): a work item never arrived", s_abort & 0xff, s_abort >> 8);
-        const long long shadow_total = (long long)ctx->h_done[3];
-        const int levels_used = (int)ctx->h_done[4];
-        st = ndt_render_stats{};
-        st.rays_primary = n_pixels;
-        st.rays_secondary = (long long)hc[0] - rg.n_primary + (long long)ctx->h_done[10];
-        st.rays_shadow = shadow_total;
-        st.rays_ref_equiv = (long long)ref_rays;
-        st.levels = levels_used;
-        st.trace_launches = launches;
-        st.node_capacity = ws.cap;
-        if (prof) {
-            float ms = 0;
-            for (auto &pr : trace_ev) {
-                float m = 0;
-                HIP_TRY(hipEventElapsedTime(&m, pr.first, pr.second));
-                ms += m;
-            }
-            st.trace_ms = ms;
-            if (streamed && sa.wave_log && ev_k0) {
-                float km = 0;
-                HIP_TRY(hipEventElapsedTime(&km, ev_k0, ev_k1));
-                print_stream_probe(sa.wave_log, km);
-            }
-            if (ctx->debug_levels) {
-                for (int b = 0; b < levels_used; ++b)
-                    fprintf(stderr, "ndt_hip: bounce %d: %lld nodes, %lld shadow rays\n", b, hl[b].count, hl[b].n_shadow);
-                unsigned long long d[160];
-                if (hipMemcpy(d, ws.dbg, sizeof(d), hipMemcpyDeviceToHost) != hipSuccess) d[4] = 0;
-                if (shade_probe >= 0 && ws.shade_log) {
-                    std::vector<unsigned int> log((size_t)2 * NDT_SHADE_LOG_WAVES);
-                    if (hipMemcpy(log.data(), ws.shade_log, log.size() * sizeof(unsigned int), hipMemcpyDeviceToHost) == hipSuccess) {
-                        unsigned int t0 = 0;
-                        bool any = false;
-                        for (int w = 0; w < NDT_SHADE_LOG_WAVES; ++w)
-                            if (log[2 * w + 1] && (!any || (int)(log[2 * w] - t0) < 0)) {
-                                t0 = log[2 * w];
-                                any = true;
-                            }
-                        for (int part = 0; part < 2; ++part) {
-                            // part 0: lighting (shade_finish) wavefronts, part 1: shading (shade_emit) wavefronts
-                            int hist[48] = { 0 }, n_w = 0;
-                            double sum = 0, longest = 0, last_start = 0, last_end = 0;
-                            for (long long w = 0; w < NDT_SHADE_LOG_WAVES; ++w) {
-                                const bool lighting = w < shade_probe_finish_waves;
-                                if (!log[2 * w + 1] || lighting != (part == 0)) continue;
-                                const double st_us = (log[2 * w] - t0) / 100.0, dur = (log[2 * w + 1] - log[2 * w]) / 100.0;
-                                ++n_w;
-                                sum += dur;
-                                if (dur > longest) longest = dur;
-                                if (st_us > last_start) last_start = st_us;
-                                if (st_us + dur > last_end) last_end = st_us + dur;
-                                const int bin = (int)(dur / 4.0);
-                                ++hist[bin > 47 ? 47 : bin];
-                            }
-                            if (!n_w) continue;
-                            std::string line;
-                            for (int bin = 0; bin < 48; ++bin)
-                                if (hist[bin]) {
-                                    char buf[48];
-                                    snprintf(buf, sizeof buf, " %d-%d:%d", bin * 4, bin * 4 + 4, hist[bin]);
-                                    line += buf;
-                                }
-                            fprintf(stderr, "ndt_hip: shade launch %d, %s: %d wavefronts, mean life %.1f us, longest %.1f us, last start at %.1f us, last end at %.1f us; lives per 4 us:%s\n",
-                                    shade_probe, part == 0 ? "lighting" : "shading", n_w, sum / n_w, longest, last_start, last_end, line.c_str());
-                        }
-                    }
-                }
-                if (ctx->exit_probe) {
-                    // the life of every wavefront of every trace launch: when the queue runs dry (first exit), how long the
-                    // rest keeps going, and how much of that is the last wavefront's last batch
-                    std::vector<unsigned int> log((size_t)NDT_EXIT_LOG_LAUNCHES * NDT_EXIT_LOG_WORDS);
-                    if (hipMemcpy(log.data(), ws.exit_log, log.size() * sizeof(unsigned int), hipMemcpyDeviceToHost) == hipSuccess)
-                        for (int l = 0; l < NDT_EXIT_LOG_LAUNCHES && l < launches; ++l) {
-                            const unsigned int *q = log.data() + (size_t)l * NDT_EXIT_LOG_WORDS;
-                            unsigned int t0 = 0;
-                            int n_w = 0;
-                            for (int w = 0; w < NDT_EXIT_LOG_WORDS / 8; ++w)
-                                if (q[8 * w + 2]) {
-                                    if (!n_w || (int)(q[8 * w] - t0) < 0) t0 = q[8 * w];
-                                    ++n_w;
-                                }
-                            int hist[64] = { 0 };
-                            double first = 1e30, last = 0, last_batch = 0, start_spread = 0;
-                            int simd_of_wave[16][4] = { { 0 } };        // workgroup wavefront w -> SIMD it ran on
-                            int wpw = 12;                               // wavefronts per workgroup of this launch (logged by the kernel)
-                            for (int w = 0; w < NDT_EXIT_LOG_WORDS / 8; ++w)
-                                if (q[8 * w + 2]) {
-                                    // "out of work" = out of batches
-                                    const double st_us = (q[8 * w] - t0) / 100.0, ex_us = (q[8 * w + 4] - t0) / 100.0;
-                                    wpw = (int)(q[8 * w + 3] >> 24) > 0 && (q[8 * w + 3] >> 24) <= 16 ? (int)(q[8 * w + 3] >> 24) : wpw;
-                                    ++simd_of_wave[w % wpw][(q[8 * w + 3] >> 4) & 3];
-                                    if (st_us > start_spread) start_spread = st_us;
-                                    if (ex_us < first) first = ex_us;
-                                    if (ex_us > last) {
-                                        last = ex_us;
-                                        last_batch = (q[8 * w + 4] - q[8 * w + 1]) / 100.0;
-                                    }
-                                    const int bin = (int)(ex_us / 16.0);
-                                    ++hist[bin > 63 ? 63 : bin];
-                                }
-                            std::string line;
-                            for (int bin = 0; bin < 64; ++bin)
-                                if (hist[bin]) {
-                                    char buf[48];
-                                    snprintf(buf, sizeof buf, " %d-%d:%d", bin * 16, bin * 16 + 16, hist[bin]);
-                                    line += buf;
-                                }
-                            if (l == 0) {
-                                std::string m;
-                                for (int w = 0; w < wpw; ++w) {
-                                    char buf[64];
-                                    snprintf(buf, sizeof buf, " w%d:%d/%d/%d/%d", w, simd_of_wave[w][0], simd_of_wave[w][1], simd_of_wave[w][2], simd_of_wave[w][3]);
-                                    m += buf;
-                                }
-                                fprintf(stderr, "ndt_hip: SIMD 0/1/2/3 of the workgroup's wavefronts (%d per workgroup):%s\n", wpw, m.c_str());
-                            }
-                            fprintf(stderr, "ndt_hip: trace launch %d: %d wavefronts start within %.1f us; first out of work at %.1f us, last at %.1f us (its last batch: %.1f us); exits per 16 us:%s\n",
-                                    l, n_w, start_spread, first, last, last_batch, line.c_str());
-                        }
-                }
-                if (d[4]) {
-                    // NDT_PHASE_TIMING builds only (make -C ndt_amd/csrc timing)
-                    fprintf(stderr, "ndt_hip: wave cycles T %llu G %llu I %llu list-end %llu prologue %llu outside %llu over %llu waves\n", d[0], d[1], d[2], d[3], d[5], d[6], d[4]);
-                    if (d[7] || d[32])
-                        fprintf(stderr, "ndt_hip:    coherent leaf scan: fetching windows %llu, boxes / gates of the windows %llu (its intersections are in I)\n", d[32], d[7]);
-                    fprintf(stderr, "ndt_hip: per-ray counts over %llu rays: node visits %llu, face gates %llu (pass %llu), item gates %llu (pass %llu), isect hits %llu\n",
-                            d[14], d[8], d[9], d[10], d[11], d[12], d[13]);
-                    fprintf(stderr, "ndt_hip: batch time inside trace_kd (100 MHz wall clock): closest max %.1f us mean %.1f us, shadow max %.1f us mean %.1f us\n",
-                            d[40] / 100.0, d[44] ? d[42] / 100.0 / d[44] : 0.0, d[41] / 100.0, d[45] ? d[43] / 100.0 / d[45] : 0.0);
-                    fprintf(stderr, "ndt_hip: per-ray maxima: %llu node visits, %llu gates, %llu intersections; per-batch maxima: %llu T, %llu G, %llu I iterations\n",
-                            d[46], d[47], d[48], d[49], d[50], d[51]);
-                    if (d[58])
-                        fprintf(stderr, "ndt_hip: shade_emit per wavefront (wall-clock ticks, mean over %llu): load+isect %.0f, light tests %.0f, segment reserve %.0f, shadow stores %.0f, spawn %.0f; slowest wavefront %llu\n",
-                                d[58], (double)d[52] / d[58], (double)d[53] / d[58], (double)d[54] / d[58], (double)d[55] / d[58], (double)d[56] / d[58], d[59]);
-                    for (int kind = 0; kind < 2; ++kind) {
-                        const unsigned long long *q = d + 16 + 8 * kind;
-                        fprintf(stderr, "ndt_hip: loop occupancy (%s rays): T %.1f%% of %llu iters, G %.1f%% of %llu, I %.1f%% of %llu\n",
-                                kind ? "shadow" : "closest", q[0] ? 100.0 * q[1] / (64.0 * q[0]) : 0.0, q[0],
-                                q[2] ? 100.0 * q[3] / (64.0 * q[2]) : 0.0, q[2], q[4] ? 100.0 * q[5] / (64.0 * q[4]) : 0.0, q[4]);
-                        if (q[4])
-                            fprintf(stderr, "ndt_hip:    I iterations execute %.2f primitive types on average; the commonest type holds %.1f of %.1f active lanes\n",
-                                    (double)q[6] / q[4], (double)q[7] / q[4], (double)q[5] / q[4]);
-                    }
-                }
-                for (size_t i = 0; i < trace_ev.size(); ++i) {
-                    float m = 0;
-                    (void)hipEventElapsedTime(&m, trace_ev[i].first, trace_ev[i].second);
-                    fprintf(stderr, "ndt_hip: trace launch %zu: %.3f ms (%s)\n", i, m, trace_dbg[i].c_str());
-                }
-            }
-            float fm = 0;
-            HIP_TRY(hipEventElapsedTime(&fm, ev_begin, ev_end));
-            st.frame_ms = fm;
-        }
-        return NDT_OK;
-    }
-    return fail(NDT_E_NOMEM, "ray-tree workspace kept overflowing");
+    return render_pass_levels(ctx, rg, sd_pass, prof, hybrid, d_rgba, d_depth, cap, sh_cap, st);
 }
-

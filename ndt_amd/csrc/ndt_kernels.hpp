@@ -6,9 +6,9 @@
 #include "ndt_device.hpp"
 
 // One bounce of the ray tree.  The table lives in device memory (Workspace::levels): bounce b+1
-// is written by k_level_step after shade_emit(b) has spawned its nodes, and every kernel of a
-// bounce reads its range from there, so the host enqueues a whole frame without reading anything
-// back in between.
+// is written by the prologue of the trace launch behind shade_emit(b), which has spawned its nodes
+// (TraceJob::publish_level), and every kernel of a bounce reads its range from there, so the host
+// enqueues a whole frame without reading anything back in between.
 struct LevelRange {
     long long begin, count;     // nodes of the bounce
     long long seg_stride;       // capacity of one light's shadow segment for this bounce (>= count, multiple of 64)
@@ -49,8 +49,8 @@ struct Workspace {
     unsigned int *exit_log;         // [NDT_EXIT_LOG_LAUNCHES][NDT_EXIT_LOG_WORDS], NDT_HIP_EXIT_PROBE
     unsigned int *shade_log;        // NDT_HIP_SHADE_PROBE: {start, end} per wavefront of ONE shade launch (set for that launch only)
     LevelRange *levels;             // [NDT_MAX_LEVELS + 1] bounce table
-    // the same table in host-visible (mapped, coherent) memory + one tag per entry: k_level_step
-    // posts bounce b+1 here, the host polls the tag instead of synchronising the stream
+    // the same table in host-visible (mapped, coherent) memory + one tag per entry: the trace prologue
+    // posts bounce b+1 here (TraceJob::publish_level), the host polls the tag instead of synchronising the stream
     LevelRange *mail;
     unsigned long long *mail_tag;
 };
