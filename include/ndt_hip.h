@@ -314,6 +314,39 @@ int ndt_hip_render_rgba8(ndt_hip_ctx *ctx, const ndt_render_params *p, uint8_t *
 int ndt_hip_render_rgba8_async(ndt_hip_ctx *ctx, const ndt_render_params *p, uint8_t *rgba8, ndt_render_stats *stats);
 int ndt_hip_render_rgba8_wait(ndt_hip_ctx *ctx);
 
+/* The frame's image file made on the device: a complete, standard PNG (8-bit RGBA, one IDAT, no interlace) of the quantised
+ * image, delivered into host memory -- what crosses PCIe is the file, not the image.  Every scanline is filtered with
+ * filter 0 (None), 1 (Sub) or 2 (Up), whichever has the smallest sum of |filtered byte taken as int8| (ties to the lower
+ * number; the first row has zeros above it); the filtered stream is deflated in independent chunks of 32 KiB, each with
+ * distance-1 matches and a dynamic Huffman code of its own, each ending on a byte boundary; a chunk that would not shrink is
+ * stored, which bounds the file.  The same image gives the same bytes.
+ *   ndt_hip_png_bound          host arithmetic: the largest file the encoder can produce for width x rows; < 0 (NDT_E_INVALID)
+ *                              for a size it does not take
+ *   ndt_hip_encode_png_device  d_rgba8: width * rows * 4 bytes in the context's device memory
+ *   ndt_hip_encode_png         rgba8: the same in host memory (uploaded first)
+ *   ndt_hip_render_png         ndt_hip_render_rgba8 with the encoder in place of the download: every mode of it (-a, -n, stereo,
+ *                              row shards: the PNG's height is the shard's row count)
+ * `png` (host) receives the file, `cap` is its room.  NDT_E_INVALID: a NULL pointer, width < 1 or rows < 1, a size whose
+ * filtered stream rows * (1 + 4 * width) exceeds 2^31 - 1 bytes.  NDT_E_NOMEM: `cap` is smaller than the file -- the error text
+ * and stats->png_bytes carry the size needed and nothing is written to `png`.  The two encode calls need no scene.  Device
+ * buffers belong to the context, only grow and are reused.  The calls return when the file is complete.
+ * stats (may be NULL): idat_bytes = the zlib stream (header and Adler-32 included), chunks / chunks_stored = 32 KiB chunks in
+ * all / left uncompressed, launches = kernel launches, rows_filter[f] = scanlines filtered with f, encode_ms = host time of the
+ * encoder (launch to the file in host memory; the render of ndt_hip_render_png is not in it). */
+typedef struct ndt_png_stats {
+    int64_t png_bytes, idat_bytes;
+    int32_t chunks, chunks_stored, launches;
+    int32_t rows_filter[3];
+    double encode_ms;
+} ndt_png_stats;
+int64_t ndt_hip_png_bound(int32_t width, int32_t rows);
+int ndt_hip_encode_png_device(ndt_hip_ctx *ctx, const void *d_rgba8, int32_t width, int32_t rows, uint8_t *png, int64_t cap,
+                              ndt_png_stats *stats);
+int ndt_hip_encode_png(ndt_hip_ctx *ctx, const uint8_t *rgba8, int32_t width, int32_t rows, uint8_t *png, int64_t cap,
+                       ndt_png_stats *stats);
+int ndt_hip_render_png(ndt_hip_ctx *ctx, const ndt_render_params *p, uint8_t *png, int64_t cap, ndt_png_stats *stats,
+                       ndt_render_stats *render_stats);
+
 /* ONE frame over several contexts -- one per GPU of the node, or several on one GPU -- called from one host thread.
  * The rows `p` selects are dealt cyclically to the contexts exactly as the reference deals rows to MPI ranks in
  * MPI_MODE_ROW (ndt.c:812-820: row_start = rank, row_step = size): context k renders rows

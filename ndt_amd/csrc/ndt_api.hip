@@ -121,6 +121,7 @@ extern "C" int ndt_hip_destroy(ndt_hip_ctx *ctx)
     if (ctx->d_out) (void)hipFree(ctx->d_out);
     if (ctx->d_fit) (void)hipFree(ctx->d_fit);
     free_kd(ctx);
+    free_png(ctx);
     if (ctx->d_eyes) (void)hipFree(ctx->d_eyes);
     if (ctx->h_counters) (void)hipHostFree(ctx->h_counters);
     if (ctx->h_levels) (void)hipHostFree(ctx->h_levels);

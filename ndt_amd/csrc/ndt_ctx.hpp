@@ -11,6 +11,7 @@
 //   ndt_multi.hip    one frame over several contexts / devices
 //   ndt_fit.hip      ndt_hip_fit_spheres: the bounding-sphere fits of a frame (batched Nelder-Mead), kernel and launcher
 //   ndt_kd.hip       ndt_hip_build_kdtree: the kd-tree of a frame's item boxes, level by level; kernels, launcher and C ABI
+//   ndt_png.hip      ndt_hip_encode_png* / ndt_hip_render_png: a frame's PNG file made on the device; kernels, launcher and C ABI
 #pragma once
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
@@ -52,6 +53,15 @@ struct KdState {
     std::vector<double> bb_lower, bb_upper;
     int dims = 0, depth = 0, launches = 0, grows = 0;
     bool valid = false;
+};
+
+// ndt_hip_encode_png* (ndt_png.hip): grow-only device buffers, reused by the next frame
+struct PngState {
+    void *d_rgba8 = nullptr, *d_filtered = nullptr, *d_row_filter = nullptr, *d_slots = nullptr, *d_meta = nullptr, *d_offsets = nullptr,
+         *d_file = nullptr, *d_info = nullptr;
+    size_t rgba8_bytes = 0, filtered_bytes = 0, row_filter_bytes = 0, slots_bytes = 0, meta_bytes = 0, offsets_bytes = 0, file_bytes = 0,
+           info_bytes = 0;
+    void *h_info = nullptr;         // pinned: the info record of the last file
 };
 
 struct ndt_hip_ctx {
@@ -137,6 +147,7 @@ struct ndt_hip_ctx {
     size_t d_fit_bytes = 0;
     int fit_launches = 0;           // kernel launches of the last ndt_hip_fit_spheres call
     KdState kd;                     // ndt_hip_build_kdtree
+    PngState png;                   // ndt_hip_encode_png*, ndt_hip_render_png
     void *d_out = nullptr;          // staging for ndt_hip_render (host output)
     size_t d_out_bytes = 0;
     void *d_shard = nullptr;        // ndt_hip_render_multi: this context's rows before they are pushed into the frame
@@ -219,6 +230,9 @@ int fit_spheres_device(ndt_hip_ctx *ctx, int dims, long long n_lists, const int6
 // ndt_kd.hip: kd_tree_build for checked item boxes (no NaN), into ctx->kd; synchronous
 int build_kdtree_device(ndt_hip_ctx *ctx, int dims, int n_items, const double *lower, const double *upper, const unsigned char *finite);
 void free_kd(ndt_hip_ctx *ctx);
+
+// ndt_png.hip
+void free_png(ndt_hip_ctx *ctx);
 
 // ndt_aa.hip / ndt_sampled.hip
 int render_antialiased(ndt_hip_ctx *ctx, const ndt_render_params *p, void *d_rgba, ndt_render_stats &total, void *d_depth = nullptr);

@@ -1,0 +1,785 @@
+// ndt_png.hip -- a frame's PNG file made on the device: ndt_hip_png_bound / ndt_hip_encode_png_device / ndt_hip_encode_png /
+// ndt_hip_render_png.  The quantised image is in HBM already; what leaves the device is the finished file.
+//
+//   k_png_filter    one workgroup a scanline: filter 0 (None), 1 (Sub) or 2 (Up) by the smallest sum of |filtered byte as int8|
+//                   (ties to the lower number; row 0 has zeros above it), then the filtered stream, written as aligned words
+//   k_png_deflate   one workgroup an independent 32 KiB chunk of that stream: distance-1 matches, a dynamic Huffman code of
+//                   its own, the bits packed into an LDS image with ds_or; a chunk the code does not shrink is stored; every
+//                   chunk but the last ends on a byte boundary (an empty stored block: 00 00 FF FF)
+//   k_png_assemble  one workgroup: the chunks' places (a scan of their byte counts), the Adler-32 of the whole stream folded from
+//                   the chunks' pairs, signature / IHDR / IDAT header / Adler-32 / IEND
+//   k_png_place     one workgroup a chunk: its bytes to their place in the file
+//
+// No kernel waits for another workgroup, every loop's trip count comes from the chunk size (or the image size in the filter and
+// the assembler), and the only atomics are LDS atomics inside a workgroup.  The host reads the info record, then exactly the
+// file's bytes, and sets the IDAT chunk's CRC-32 over what arrived; it never sees the uncompressed image.
+#include "ndt_ctx.hpp"
+#include <chrono>
+
+namespace {
+
+constexpr int PNG_CHUNK = 32768;                // bytes of the filtered stream a workgroup compresses
+constexpr int PNG_SLOT = PNG_CHUNK + 64;        // a chunk's output slot: the stored form is 5 + 32768 bytes
+constexpr int PNG_SPAN = 32;                    // bytes of the chunk a lane holds in registers
+constexpr int PNG_DEFLATE_LANES = PNG_CHUNK / PNG_SPAN;
+constexpr int PNG_LITLEN = 286;                 // literal / length alphabet
+constexpr int PNG_FILE_HEAD = 8 + 25 + 8 + 2;   // signature, IHDR chunk, IDAT length + type, zlib header
+constexpr int PNG_FILE_EXTRA = PNG_FILE_HEAD + 4 + 4 + 12;      // ... Adler-32, IDAT CRC, IEND chunk
+constexpr unsigned ADLER_MOD = 65521u;
+
+struct ChunkMeta { unsigned bytes, stored, s1, s2; };   // s1, s2: the chunk's Adler pair from (0, 0), mod 65521
+
+struct PngInfo {
+    long long png_bytes, idat_bytes;
+    int chunks_stored, rows_filter[3];
+    int pad[8];
+};
+
+// the order the header lists the code-length code's own lengths in
+__constant__ int cl_order[19] = { 16, 17, 18, 0, 8, 7, 9, 6, 10, 5, 11, 4, 12, 3, 13, 2, 14, 1, 15 };
+__constant__ unsigned char png_signature[8] = { 0x89, 'P', 'N', 'G', 0x0d, 0x0a, 0x1a, 0x0a };
+__constant__ unsigned char png_iend[12] = { 0, 0, 0, 0, 'I', 'E', 'N', 'D', 0xae, 0x42, 0x60, 0x82 };
+
+// ------------------------------------------------------------------ workgroup scans
+
+// exclusive scan over the workgroup's lanes, from the lower lanes (DIR > 0) or the higher ones (DIR < 0); `op` commutes.
+// Every lane calls it; *total (may be null) gets the fold over all lanes.
+template <int DIR, typename Op>
+__device__ __forceinline__ long long block_scan_excl(long long v, long long identity, Op op, long long *wsum, long long *total)
+{
+    const int lane = (int)(threadIdx.x & 63), wave = (int)(threadIdx.x >> 6), n_waves = (int)(blockDim.x >> 6);
+    long long x = v;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const long long o = DIR > 0 ? __shfl_up(x, d, 64) : __shfl_down(x, d, 64);
+        if (DIR > 0 ? lane >= d : lane + d < 64) x = op(x, o);
+    }
+    if (lane == (DIR > 0 ? 63 : 0)) wsum[wave] = x;
+    long long prev = DIR > 0 ? __shfl_up(x, 1, 64) : __shfl_down(x, 1, 64);
+    if (DIR > 0 ? lane == 0 : lane == 63) prev = identity;
+    __syncthreads();
+    long long carry = identity, all = identity;
+    for (int w = 0; w < n_waves; ++w) {
+        const long long s = wsum[w];
+        all = op(all, s);
+        if (DIR > 0 ? w < wave : w > wave) carry = op(carry, s);
+    }
+    __syncthreads();
+    if (total) *total = all;
+    return op(carry, prev);
+}
+
+struct OpAdd { __device__ long long operator()(long long a, long long b) const { return a + b; } };
+struct OpMax { __device__ long long operator()(long long a, long long b) const { return a > b ? a : b; } };
+struct OpMin { __device__ long long operator()(long long a, long long b) const { return a < b ? a : b; } };
+
+// ------------------------------------------------------------------ the row filter
+
+// per byte a - b mod 256
+__device__ __forceinline__ unsigned bytes_sub(unsigned a, unsigned b)
+{
+    const unsigned h = 0x80808080u;
+    return ((a | h) - (b & ~h)) ^ ((a ^ ~b) & h);
+}
+// sum over the word's bytes of |byte as int8|
+__device__ __forceinline__ unsigned bytes_abs_sum(unsigned x)
+{
+    unsigned s = 0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const unsigned b = (x >> (8 * k)) & 255u;
+        s += b < 128u ? b : 256u - b;
+    }
+    return s;
+}
+
+// the filtered bytes of pixel x of a row as one word; pixel -1 ends in the row's filter byte, pixels from `width` on are zero
+__device__ __forceinline__ unsigned filtered_pixel(const unsigned *cur, const unsigned *up, int width, int filter, int x)
+{
+    if (x < 0) return (unsigned)filter << 24;
+    if (x >= width) return 0u;
+    const unsigned p = cur[x];
+    if (filter == 0) return p;
+    if (filter == 1) return bytes_sub(p, x > 0 ? cur[x - 1] : 0u);
+    return bytes_sub(p, up ? up[x] : 0u);
+}
+
+__global__ void __launch_bounds__(256) k_png_filter(const unsigned *__restrict__ image, unsigned char *out, unsigned char *row_filter,
+                                                    int width, int rows)
+{
+    __shared__ unsigned long long wave_sum[4][3];
+    __shared__ int chosen;
+    const int row = (int)blockIdx.x, tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const unsigned *cur = image + (long long)row * width, *up = row > 0 ? cur - width : nullptr;
+    unsigned long long s0 = 0, s1 = 0, s2 = 0;
+    for (int x = tid; x < width; x += 256) {
+        const unsigned p = cur[x], l = x > 0 ? cur[x - 1] : 0u, u = up ? up[x] : 0u;
+        s0 += bytes_abs_sum(p);
+        s1 += bytes_abs_sum(bytes_sub(p, l));
+        s2 += bytes_abs_sum(bytes_sub(p, u));
+    }
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) {
+        s0 += __shfl_down(s0, d, 64);
+        s1 += __shfl_down(s1, d, 64);
+        s2 += __shfl_down(s2, d, 64);
+    }
+    if (lane == 0) { wave_sum[wave][0] = s0; wave_sum[wave][1] = s1; wave_sum[wave][2] = s2; }
+    __syncthreads();
+    if (tid == 0) {
+        unsigned long long t[3];
+        for (int f = 0; f < 3; ++f) t[f] = wave_sum[0][f] + wave_sum[1][f] + wave_sum[2][f] + wave_sum[3][f];
+        int f = 0;
+        unsigned long long best = t[0];
+        if (t[1] < best) { best = t[1]; f = 1; }
+        if (t[2] < best) f = 2;
+        chosen = f;
+        row_filter[row] = (unsigned char)f;
+    }
+    __syncthreads();
+    const int filter = chosen;
+    // the row is bytes [g0, g0 + stride) of the stream: whole aligned words from a0 on, single bytes before and after them
+    const long long stride = 1 + 4LL * width, g0 = (long long)row * stride, a0 = (g0 + 3) & ~3LL;
+    const long long n_words = (g0 + stride - a0) >> 2;      // stride >= 5 > a0 - g0
+    unsigned *out32 = reinterpret_cast<unsigned *>(out);
+    for (long long j = tid; j < n_words; j += 256) {
+        const long long q = a0 + 4 * j - g0 - 1;            // the word's first byte is byte q & 3 of pixel q >> 2 (q = -1: the filter byte)
+        const int xa = (int)(q >> 2), b = (int)(q & 3);
+        const unsigned lo = filtered_pixel(cur, up, width, filter, xa);
+        unsigned val = lo;
+        if (b) val = (lo >> (8 * b)) | (filtered_pixel(cur, up, width, filter, xa + 1) << (32 - 8 * b));
+        out32[(a0 >> 2) + j] = val;
+    }
+    if (tid < 6) {
+        // up to 3 bytes before the first whole word and up to 3 after the last
+        const long long head = a0 - g0, tail0 = head + 4 * n_words;
+        const long long i = tid < 3 ? tid : tail0 + (tid - 3);
+        if (tid < 3 ? i < head : i < stride) {
+            const long long q = i - 1;
+            const unsigned f = filtered_pixel(cur, up, width, filter, (int)(q >> 2));
+            out[g0 + i] = (unsigned char)(f >> (8 * (int)(q & 3)));
+        }
+    }
+}
+
+// ------------------------------------------------------------------ Huffman codes of a chunk
+
+struct HuffScratch {
+    unsigned weight[2 * 288];       // leaves in ascending order [0, n), the nodes the merge makes [n, 2n - 1)
+    short parent[2 * 288];
+    short sorted_sym[288];
+    int num[16], next[16];          // codes per length, first code per length
+    int n_used;
+};
+
+// A length-limited Huffman code for freq[0 .. n_sym): code[s] = bit-reversed code | length << 16, 0 for an unused symbol.
+// Called by every lane of the workgroup (n_sym <= 288 <= lanes).  Lengths come from the two-queue merge over the symbols in
+// ascending order (one lane), overlong codes are pulled in the way every Kraft-sum repair does, and the lengths are dealt
+// shortest-to-most-frequent.  An alphabet with one used symbol gets a second code, so that the set is complete.
+__device__ void huff_build(const unsigned *freq, int n_sym, int max_bits, unsigned *code, HuffScratch &hs)
+{
+    const int t = (int)threadIdx.x;
+    if (t < 16) hs.num[t] = 0;
+    if (t == 0) hs.n_used = 0;
+    __syncthreads();
+    const unsigned f = t < n_sym ? freq[t] : 0u;
+    int rank = 0;
+    if (f) {
+        for (int j = 0; j < n_sym; ++j) {
+            const unsigned fj = freq[j];
+            rank += (fj && (fj < f || (fj == f && j < t))) ? 1 : 0;
+        }
+        atomicAdd(&hs.n_used, 1);
+    }
+    __syncthreads();
+    const int n = hs.n_used;
+    if (f) {
+        hs.sorted_sym[rank] = (short)t;
+        hs.weight[rank] = f;
+    }
+    if (t < n_sym) code[t] = 0u;
+    __syncthreads();
+    if (n < 2) {
+        if (t == 0 && n == 1) {
+            const int s = hs.sorted_sym[0], other = s == 0 ? 1 : 0;
+            code[s < other ? s : other] = 0u | (1u << 16);
+            code[s < other ? other : s] = 1u | (1u << 16);
+        }
+        __syncthreads();
+        return;
+    }
+    if (t == 0) {
+        int leaf = 0, node = n, made = n;
+        for (int step = 0; step < n - 1; ++step) {
+            int pick[2];
+            for (int k = 0; k < 2; ++k) {
+                if (leaf < n && (node >= made || hs.weight[leaf] <= hs.weight[node])) pick[k] = leaf++;
+                else pick[k] = node++;
+            }
+            hs.weight[made] = hs.weight[pick[0]] + hs.weight[pick[1]];
+            hs.parent[pick[0]] = (short)made;
+            hs.parent[pick[1]] = (short)made;
+            ++made;
+        }
+    }
+    __syncthreads();
+    if (t < n) {
+        int at = t, depth = 0;
+        for (int it = 0; it < n && at != 2 * n - 2; ++it) {
+            at = hs.parent[at];
+            ++depth;
+        }
+        atomicAdd(&hs.num[depth < max_bits ? depth : max_bits], 1);
+    }
+    __syncthreads();
+    if (t == 0) {
+        int total = 0;
+        for (int l = 1; l <= max_bits; ++l) total += hs.num[l] << (max_bits - l);
+        for (int it = 0; it < 288 && total > (1 << max_bits); ++it) {
+            hs.num[max_bits] -= 1;
+            for (int l = max_bits - 1; l >= 1; --l)
+                if (hs.num[l]) {
+                    hs.num[l] -= 1;
+                    hs.num[l + 1] += 2;
+                    break;
+                }
+            --total;
+        }
+        int c = 0;
+        hs.next[0] = 0;
+        for (int l = 1; l <= max_bits; ++l) {
+            c = (c + (l > 1 ? hs.num[l - 1] : 0)) << 1;
+            hs.next[l] = c;
+        }
+    }
+    __syncthreads();
+    int len = 0;
+    if (f) {
+        const int place = n - 1 - rank;         // 0: the most frequent symbol
+        int cum = 0;
+        for (int l = 1; l <= max_bits; ++l) {
+            cum += hs.num[l];
+            if (place < cum) { len = l; break; }
+        }
+        code[t] = (unsigned)len << 16;
+    }
+    __syncthreads();
+    unsigned mine = 0u;
+    if (len) {
+        int before = 0;
+        for (int j = 0; j < t; ++j) before += ((int)(code[j] >> 16) == len) ? 1 : 0;
+        const unsigned c = (unsigned)(hs.next[len] + before);
+        mine = (__brev(c) >> (32 - len)) | ((unsigned)len << 16);
+    }
+    __syncthreads();
+    if (t < n_sym) code[t] = mine;
+    __syncthreads();
+}
+
+// ------------------------------------------------------------------ a chunk's tokens
+
+// length 3 .. 258 -> symbol 257 .. 285, number of extra bits and their value
+__device__ __forceinline__ int length_symbol(int len, int &extra_bits, int &extra)
+{
+    if (len == 258) { extra_bits = 0; extra = 0; return 285; }
+    const int l = len - 3;
+    if (l < 8) { extra_bits = 0; extra = 0; return 257 + l; }
+    const int eb = (31 - __clz(l)) - 2;
+    extra_bits = eb;
+    extra = l & ((1 << eb) - 1);
+    return 257 + 4 * eb + 4 + ((l >> eb) & 3);
+}
+
+// What byte j of this lane's span becomes: 0 nothing (inside a match), 1 a literal, 2 a match of `len` bytes at distance 1.
+// A run of k equal bytes is one literal and matches over the other k - 1 bytes in pieces of 258; a last piece under 3 bytes is literals.
+// heads: bit j = byte j differs from the byte before it; run_start / run_end: where the runs open at the span's ends begin and end.
+__device__ __forceinline__ int token_at(int j, unsigned heads, int span0, int run_start, int run_end, int &len)
+{
+    const unsigned below = heads & ((2u << j) - 1u);
+    const unsigned above = j < 31 ? heads >> (j + 1) : 0u;
+    const int i = span0 + j;
+    const int s = below ? span0 + 31 - __clz(below) : run_start;
+    const int e = above ? i + 1 + (__ffs(above) - 1) : run_end;
+    const int o = i - s, m = e - s - 1;
+    if (o == 0 || m < 3) return 1;
+    const int q = o - 1, piece = q / 258, r = q - piece * 258;
+    const int left = m - piece * 258;
+    len = left < 258 ? left : 258;
+    if (len < 3) return 1;
+    return r == 0 ? 2 : 0;
+}
+
+__device__ __forceinline__ void put_bits(unsigned *image, unsigned pos, unsigned val, int n_bits)
+{
+    const unsigned w = pos >> 5, sh = pos & 31u;
+    atomicOr(&image[w], val << sh);
+    if ((int)sh + n_bits > 32) atomicOr(&image[w + 1], val >> (32u - sh));
+}
+
+// MODE 0: histogram of the span's tokens; 1: their bits; 2: the bits themselves at bit position `pos`.  Returns the bits.
+template <int MODE>
+__device__ __forceinline__ int walk_span(const unsigned (&w)[8], int valid, unsigned heads, int span0, int run_start, int run_end,
+                                         unsigned *ll_freq, const unsigned *ll_code, unsigned *image, unsigned pos, int *any_match)
+{
+    int bits = 0;
+    bool matched = false;
+#pragma unroll
+    for (int j = 0; j < PNG_SPAN; ++j) {
+        if (j < valid) {
+            const unsigned b = (w[j >> 2] >> (8 * (j & 3))) & 255u;
+            int len = 0;
+            const int kind = token_at(j, heads, span0, run_start, run_end, len);
+            if (kind == 1) {
+                if (MODE == 0) atomicAdd(&ll_freq[b], 1u);
+                else {
+                    const unsigned c = ll_code[b];
+                    if (MODE == 2) put_bits(image, pos + (unsigned)bits, c & 0xffffu, (int)(c >> 16));
+                    bits += (int)(c >> 16);
+                }
+            } else if (kind == 2) {
+                int eb, ev;
+                const int sym = length_symbol(len, eb, ev);
+                if (MODE == 0) {
+                    atomicAdd(&ll_freq[sym], 1u);
+                    matched = true;
+                } else {
+                    const unsigned c = ll_code[sym];
+                    const int cl = (int)(c >> 16), nb = cl + eb + 1;        // + the one distance code: '0'
+                    if (MODE == 2) put_bits(image, pos + (unsigned)bits, (c & 0xffffu) | ((unsigned)ev << cl), nb);
+                    bits += nb;
+                }
+            }
+        }
+    }
+    if (MODE == 0 && matched) atomicOr(any_match, 1);
+    return bits;
+}
+
+__global__ void __launch_bounds__(PNG_DEFLATE_LANES) k_png_deflate(const unsigned char *__restrict__ filtered, long long n_total,
+                                                                   int n_chunks, unsigned char *slots, ChunkMeta *meta)
+{
+    __shared__ unsigned image[PNG_SLOT / 4];
+    __shared__ unsigned ll_freq[288], ll_code[288];
+    __shared__ unsigned cl_freq[20], cl_code[20];
+    __shared__ unsigned short cl_tok[296];          // code-length symbol | extra << 5
+    __shared__ HuffScratch hs;
+    __shared__ long long wsum[16];
+    __shared__ int any_match, n_cl, n_hclen, n_hlit;
+    __shared__ unsigned long long adler_sum[2];
+
+    const int chunk = (int)blockIdx.x, t = (int)threadIdx.x;
+    const long long base = (long long)chunk * PNG_CHUNK;
+    const int n = (int)(n_total - base < PNG_CHUNK ? n_total - base : PNG_CHUNK);
+    const bool last = chunk == n_chunks - 1;
+    const int span0 = t * PNG_SPAN;
+    const int valid = n - span0 < 0 ? 0 : n - span0 > PNG_SPAN ? PNG_SPAN : n - span0;
+
+    // the lane's 32 bytes (the buffer is whole chunks long: the loads stay inside it; bytes from n on are never looked at)
+    unsigned w[8];
+    {
+        const uint4 *src = reinterpret_cast<const uint4 *>(filtered + base) + 2 * t;
+        const uint4 a = src[0], b = src[1];
+        w[0] = a.x; w[1] = a.y; w[2] = a.z; w[3] = a.w; w[4] = b.x; w[5] = b.y; w[6] = b.z; w[7] = b.w;
+    }
+    unsigned before = t > 0 ? (unsigned)filtered[base + span0 - 1] : 0x100u;      // the chunk's first byte heads a run
+
+    for (int k = t; k < PNG_SLOT / 4; k += PNG_DEFLATE_LANES) image[k] = 0u;
+    if (t < 288) ll_freq[t] = t == 256 ? 1u : 0u;                                  // one end-of-block
+    if (t < 20) cl_freq[t] = 0u;
+    if (t == 0) { any_match = 0; adler_sum[0] = 0ull; adler_sum[1] = 0ull; }
+
+    unsigned heads = 0u, sum = 0u, wsum_bytes = 0u;
+#pragma unroll
+    for (int j = 0; j < PNG_SPAN; ++j) {
+        const unsigned b = (w[j >> 2] >> (8 * (j & 3))) & 255u;
+        if (j < valid) {
+            if (b != before) heads |= 1u << j;
+            sum += b;
+            wsum_bytes += (unsigned)(valid - j) * b;
+        }
+        before = b;
+    }
+    __syncthreads();
+
+    // Adler-32 of the chunk from (0, 0): s1 = sum of bytes, s2 = sum of (n - i) * byte i
+    {
+        unsigned long long a = sum, b2 = (unsigned long long)wsum_bytes + (unsigned long long)(n - span0 - valid) * sum;
+        if (valid == 0) { a = 0ull; b2 = 0ull; }
+#pragma unroll
+        for (int d = 32; d >= 1; d >>= 1) {
+            a += __shfl_down(a, d, 64);
+            b2 += __shfl_down(b2, d, 64);
+        }
+        if ((t & 63) == 0) {
+            atomicAdd(&adler_sum[0], a);
+            atomicAdd(&adler_sum[1], b2);
+        }
+    }
+
+    // where the run open at the span's first byte began, and where the one open at its last byte ends
+    const long long my_last = heads ? (long long)(span0 + 31 - __clz(heads)) : -1ll;
+    const long long my_first = heads ? (long long)(span0 + __ffs(heads) - 1) : (long long)n;
+    const int run_start = (int)block_scan_excl<1>(my_last, -1ll, OpMax(), wsum, nullptr);
+    const int run_end = (int)block_scan_excl<-1>(my_first, (long long)n, OpMin(), wsum, nullptr);
+
+    walk_span<0>(w, valid, heads, span0, run_start, run_end, ll_freq, ll_code, image, 0u, &any_match);
+    __syncthreads();
+    huff_build(ll_freq, PNG_LITLEN, 15, ll_code, hs);
+
+    // the code lengths of the header, run-length coded with symbols 16 / 17 / 18 (one lane; at most 287 lengths)
+    if (t == 0) {
+        int hl = PNG_LITLEN;
+        for (int k = 0; k < 29 && (ll_code[hl - 1] >> 16) == 0u; ++k) --hl;       // symbol 256 is used: hl >= 257
+        n_hlit = hl;
+        const int total = hl + 1, dist_len = any_match ? 1 : 0;
+        int i = 0, count = 0;
+        for (int it = 0; it < 288 && i < total; ++it) {
+            const int v = i < hl ? (int)(ll_code[i] >> 16) : dist_len;
+            int run = 1;
+            for (int k = 1; k < 138 && i + k < total; ++k) {
+                const int u = i + k < hl ? (int)(ll_code[i + k] >> 16) : dist_len;
+                if (u != v) break;
+                ++run;
+            }
+            int sym, extra = 0, used = 1;
+            if (v == 0 && run >= 11) { sym = 18; extra = run - 11; used = run; }
+            else if (v == 0 && run >= 3) { sym = 17; extra = run - 3; used = run; }
+            else if (v != 0 && it > 0 && run >= 3 && i > 0 && (i - 1 < hl ? (int)(ll_code[i - 1] >> 16) : dist_len) == v) {
+                used = run < 6 ? run : 6;
+                sym = 16;
+                extra = used - 3;
+            } else sym = v;
+            cl_tok[count++] = (unsigned short)(sym | (extra << 5));
+            cl_freq[sym] += 1u;
+            i += used;
+        }
+        n_cl = count;
+    }
+    __syncthreads();
+    huff_build(cl_freq, 19, 7, cl_code, hs);
+    if (t == 0) {
+        int h = 19;
+        for (int k = 0; k < 15 && (cl_code[cl_order[h - 1]] >> 16) == 0u; ++k) --h;
+        n_hclen = h;
+    }
+    __syncthreads();
+    const int hclen = n_hclen, hlit = n_hlit, n_tok = n_cl;
+
+    // bit positions: header tokens, then the data tokens, then end-of-block
+    int cl_bits = 0;
+    unsigned cl_val = 0u;
+    if (t < n_tok) {
+        const int tok = cl_tok[t], sym = tok & 31, extra = tok >> 5;
+        const unsigned c = cl_code[sym];
+        const int eb = sym == 16 ? 2 : sym == 17 ? 3 : sym == 18 ? 7 : 0;
+        cl_bits = (int)(c >> 16) + eb;
+        cl_val = (c & 0xffffu) | ((unsigned)extra << (c >> 16));
+    }
+    long long cl_total = 0, tok_total = 0;
+    const int cl_pos = (int)block_scan_excl<1>((long long)cl_bits, 0ll, OpAdd(), wsum, &cl_total);
+    const int header_bits = 3 + 5 + 5 + 4 + 3 * hclen + (int)cl_total;
+    const int my_bits = walk_span<1>(w, valid, heads, span0, run_start, run_end, ll_freq, ll_code, image, 0u, &any_match);
+    const int my_pos = (int)block_scan_excl<1>((long long)my_bits, 0ll, OpAdd(), wsum, &tok_total);
+    const long long block_bits = (long long)header_bits + tok_total + (long long)(ll_code[256] >> 16);
+    // the block, then -- but for the last chunk -- an empty stored block: 3 bits, padding to a byte, 00 00 FF FF
+    const long long packed_bytes = last ? (block_bits + 7) >> 3 : ((block_bits + 3 + 7) >> 3) + 4;
+    const int stored_bytes = 5 + n;
+    const bool stored = packed_bytes >= (long long)stored_bytes;
+    int out_bytes;
+    if (!stored) {
+        out_bytes = (int)packed_bytes;
+        if (t == 0) put_bits(image, 0u, (last ? 1u : 0u) | (2u << 1) | ((unsigned)(hlit - 257) << 3) | (0u << 8) | ((unsigned)(hclen - 4) << 13), 17);
+        if (t < hclen) put_bits(image, 17u + 3u * (unsigned)t, cl_code[cl_order[t]] >> 16, 3);
+        if (t < n_tok) put_bits(image, 17u + 3u * (unsigned)hclen + (unsigned)cl_pos, cl_val, cl_bits);
+        walk_span<2>(w, valid, heads, span0, run_start, run_end, ll_freq, ll_code, image, (unsigned)header_bits + (unsigned)my_pos, &any_match);
+        if (t == 0) {
+            const unsigned eob = ll_code[256];
+            put_bits(image, (unsigned)(block_bits - (long long)(eob >> 16)), eob & 0xffffu, (int)(eob >> 16));
+            if (!last) put_bits(image, 8u * (unsigned)(out_bytes - 2), 0xffffu, 16);
+        }
+    } else {
+        // one stored block: BFINAL, LEN, NLEN, the bytes as they are
+        out_bytes = stored_bytes;
+        if (t == 0) {
+            const unsigned len = (unsigned)n & 0xffffu, nlen = ~len & 0xffffu;          // n = 32768 fits LEN
+            put_bits(image, 0u, (last ? 1u : 0u) | (len << 8) | ((nlen & 0xffu) << 24), 32);
+            put_bits(image, 32u, nlen >> 8, 8);
+        }
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+            const int have = valid - 4 * k;             // bytes of this word inside the chunk
+            if (have > 0) {
+                const unsigned x = have >= 4 ? w[k] : w[k] & ((1u << (8 * have)) - 1u);
+                put_bits(image, 8u * (unsigned)(5 + span0 + 4 * k), x, 32);
+            }
+        }
+    }
+    __syncthreads();
+    unsigned *slot = reinterpret_cast<unsigned *>(slots + (long long)chunk * PNG_SLOT);
+    const int words = (out_bytes + 3) >> 2;
+    for (int k = t; k < words; k += PNG_DEFLATE_LANES) slot[k] = image[k];
+    if (t == 0) {
+        ChunkMeta m;
+        m.bytes = (unsigned)out_bytes;
+        m.stored = stored ? 1u : 0u;
+        m.s1 = (unsigned)(adler_sum[0] % ADLER_MOD);
+        m.s2 = (unsigned)(adler_sum[1] % ADLER_MOD);
+        meta[chunk] = m;
+    }
+}
+
+// ------------------------------------------------------------------ the file around the chunks
+
+__device__ __forceinline__ void store_be32(unsigned char *p, unsigned v)
+{
+    p[0] = (unsigned char)(v >> 24); p[1] = (unsigned char)(v >> 16); p[2] = (unsigned char)(v >> 8); p[3] = (unsigned char)v;
+}
+
+__global__ void __launch_bounds__(1024) k_png_assemble(const ChunkMeta *__restrict__ meta, int n_chunks, long long n_total,
+                                                       const unsigned char *__restrict__ row_filter, int width, int rows,
+                                                       unsigned char *png, long long *offsets, PngInfo *info)
+{
+    __shared__ long long wsum[16];
+    __shared__ int filter_count[4];
+    const int t = (int)threadIdx.x;
+    if (t < 4) filter_count[t] = 0;
+    const int per = (n_chunks + 1023) / 1024, c0 = t * per, c1 = c0 + per < n_chunks ? c0 + per : n_chunks;
+    long long bytes = 0, s1 = 0, stored = 0;
+    for (int c = c0; c < c1; ++c) {
+        const ChunkMeta m = meta[c];
+        bytes += m.bytes;
+        s1 += m.s1;
+        stored += m.stored;
+    }
+    long long all_bytes = 0, all_s1 = 0, all_stored = 0, all_s2 = 0;
+    long long off = block_scan_excl<1>(bytes, 0ll, OpAdd(), wsum, &all_bytes);
+    long long before = block_scan_excl<1>(s1, 0ll, OpAdd(), wsum, &all_s1);
+    (void)block_scan_excl<1>(stored, 0ll, OpAdd(), wsum, &all_stored);
+    // Adler-32 of the stream: s1 = 1 + sum of the chunks' s1; a chunk of n bytes entered with s1 = a adds n * a + its own s2 to s2
+    long long s2 = 0;
+    for (int c = c0; c < c1; ++c) {
+        const ChunkMeta m = meta[c];
+        const long long nc = n_total - (long long)c * PNG_CHUNK < PNG_CHUNK ? n_total - (long long)c * PNG_CHUNK : PNG_CHUNK;
+        offsets[c] = off;
+        s2 += (long long)m.s2 + nc * ((1 + before) % (long long)ADLER_MOD);
+        off += m.bytes;
+        before += m.s1;
+    }
+    (void)block_scan_excl<1>(s2 % (long long)ADLER_MOD, 0ll, OpAdd(), wsum, &all_s2);
+    int mine[3] = { 0, 0, 0 };
+    for (int r = t; r < rows; r += 1024) {
+        const int f = row_filter[r];
+        mine[0] += f == 0; mine[1] += f == 1; mine[2] += f == 2;
+    }
+    for (int f = 0; f < 3; ++f)
+        if (mine[f]) atomicAdd(&filter_count[f], mine[f]);
+    __syncthreads();
+    if (t == 0) {
+        for (int k = 0; k < 8; ++k) png[k] = png_signature[k];
+        unsigned char *ihdr = png + 8;
+        store_be32(ihdr, 13u);
+        ihdr[4] = 'I'; ihdr[5] = 'H'; ihdr[6] = 'D'; ihdr[7] = 'R';
+        store_be32(ihdr + 8, (unsigned)width);
+        store_be32(ihdr + 12, (unsigned)rows);
+        ihdr[16] = 8; ihdr[17] = 6; ihdr[18] = 0; ihdr[19] = 0; ihdr[20] = 0;       // 8 bit, RGBA, no interlace
+        unsigned crc = 0xffffffffu;
+        for (int k = 4; k < 21; ++k) {
+            crc ^= ihdr[k];
+            for (int b = 0; b < 8; ++b) crc = (crc & 1u) ? 0xedb88320u ^ (crc >> 1) : crc >> 1;
+        }
+        store_be32(ihdr + 21, crc ^ 0xffffffffu);
+        const long long idat = 2 + all_bytes + 4;
+        unsigned char *q = png + 33;
+        store_be32(q, (unsigned)idat);
+        q[4] = 'I'; q[5] = 'D'; q[6] = 'A'; q[7] = 'T';
+        q[8] = 0x78; q[9] = 0x01;
+        unsigned char *z = png + PNG_FILE_HEAD + all_bytes;
+        const unsigned a = (unsigned)((1 + all_s1) % (long long)ADLER_MOD), b = (unsigned)(all_s2 % (long long)ADLER_MOD);
+        store_be32(z, (b << 16) | a);
+        store_be32(z + 4, 0u);          // the IDAT chunk's CRC-32: set by the host over the bytes that arrived
+        for (int k = 0; k < 12; ++k) z[8 + k] = png_iend[k];
+        info->png_bytes = PNG_FILE_EXTRA + all_bytes;
+        info->idat_bytes = idat;
+        info->chunks_stored = (int)all_stored;
+        for (int f = 0; f < 3; ++f) info->rows_filter[f] = filter_count[f];
+    }
+}
+
+__global__ void __launch_bounds__(256) k_png_place(const unsigned char *__restrict__ slots, const ChunkMeta *__restrict__ meta,
+                                                   const long long *__restrict__ offsets, unsigned char *png)
+{
+    const int chunk = (int)blockIdx.x;
+    const unsigned char *src = slots + (long long)chunk * PNG_SLOT;
+    unsigned char *dst = png + PNG_FILE_HEAD + offsets[chunk];
+    const int bytes = (int)meta[chunk].bytes;           // at most 5 + 32768
+    for (int k = (int)threadIdx.x; k < bytes; k += 256) dst[k] = src[k];
+}
+
+// ------------------------------------------------------------------ host
+
+// CRC-32 (the PNG polynomial), eight bytes a step
+struct CrcTables {
+    unsigned t[8][256];
+    CrcTables()
+    {
+        for (unsigned n = 0; n < 256; ++n) {
+            unsigned c = n;
+            for (int k = 0; k < 8; ++k) c = (c & 1u) ? 0xedb88320u ^ (c >> 1) : c >> 1;
+            t[0][n] = c;
+        }
+        for (unsigned n = 0; n < 256; ++n)
+            for (int k = 1; k < 8; ++k) t[k][n] = t[0][t[k - 1][n] & 255u] ^ (t[k - 1][n] >> 8);
+    }
+};
+
+unsigned crc32_of(const unsigned char *p, size_t len)
+{
+    static const CrcTables tab;
+    unsigned c = 0xffffffffu;
+    while (len >= 8) {
+        unsigned lo, hi;
+        memcpy(&lo, p, 4);
+        memcpy(&hi, p + 4, 4);
+        lo ^= c;
+        c = tab.t[7][lo & 255u] ^ tab.t[6][(lo >> 8) & 255u] ^ tab.t[5][(lo >> 16) & 255u] ^ tab.t[4][lo >> 24] ^
+            tab.t[3][hi & 255u] ^ tab.t[2][(hi >> 8) & 255u] ^ tab.t[1][(hi >> 16) & 255u] ^ tab.t[0][hi >> 24];
+        p += 8;
+        len -= 8;
+    }
+    while (len--) c = tab.t[0][(c ^ *p++) & 255u] ^ (c >> 8);
+    return c ^ 0xffffffffu;
+}
+
+int grow(ndt_hip_ctx *ctx, void **buf, size_t *have, size_t want)
+{
+    if (*have >= want) return NDT_OK;
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    if (*buf) HIP_TRY(hipFree(*buf));
+    *buf = nullptr;
+    *have = 0;
+    const hipError_t e = hipMalloc(buf, want);
+    if (e != hipSuccess) return fail(NDT_E_NOMEM, "ndt_hip_encode_png: hipMalloc of %zu bytes: %s", want, hipGetErrorString(e));
+    *have = want;
+    return NDT_OK;
+}
+
+// the filtered stream's length, or -1 for a size the encoder does not take
+long long stream_bytes(int32_t width, int32_t rows)
+{
+    if (width < 1 || rows < 1) return -1;
+    const long long n = (1 + 4LL * width) * (long long)rows;      // < 2^34 * 2^31
+    return n > 0x7fffffffLL ? -1 : n;
+}
+
+} // namespace
+
+extern "C" int64_t ndt_hip_png_bound(int32_t width, int32_t rows)
+{
+    const long long n = stream_bytes(width, rows);
+    if (n < 0) return NDT_E_INVALID;
+    // every chunk stored: 5 bytes a chunk on top of the stream
+    return PNG_FILE_EXTRA + n + 5 * ((n + PNG_CHUNK - 1) / PNG_CHUNK);
+}
+
+void ndt_impl::free_png(ndt_hip_ctx *ctx)
+{
+    PngState &ps = ctx->png;
+    void **bufs[] = { &ps.d_rgba8, &ps.d_filtered, &ps.d_row_filter, &ps.d_slots, &ps.d_meta, &ps.d_offsets, &ps.d_file, &ps.d_info };
+    for (void **b : bufs) {
+        if (*b) (void)hipFree(*b);
+        *b = nullptr;
+    }
+    if (ps.h_info) (void)hipHostFree(ps.h_info);
+    ps = PngState();
+}
+
+extern "C" int ndt_hip_encode_png_device(ndt_hip_ctx *ctx, const void *d_rgba8, int32_t width, int32_t rows, uint8_t *png, int64_t cap,
+                                         ndt_png_stats *stats)
+{
+    if (!ctx || !d_rgba8 || !png) return fail(NDT_E_INVALID, "ndt_hip_encode_png: NULL argument");
+    if (width < 1 || rows < 1) return fail(NDT_E_INVALID, "ndt_hip_encode_png: a %d x %d image", width, rows);
+    const long long n = stream_bytes(width, rows);
+    if (n < 0) return fail(NDT_E_INVALID, "ndt_hip_encode_png: the filtered stream of a %d x %d image exceeds 2^31 - 1 bytes", width, rows);
+    if (cap < 0) return fail(NDT_E_INVALID, "ndt_hip_encode_png: cap %lld", (long long)cap);
+    if (((uintptr_t)d_rgba8 & 3u) != 0) return fail(NDT_E_INVALID, "ndt_hip_encode_png: the image is not aligned to its 4-byte pixels");
+    const auto t0 = std::chrono::steady_clock::now();
+    HIP_TRY(hipSetDevice(ctx->device));
+    PngState &ps = ctx->png;
+    const int n_chunks = (int)((n + PNG_CHUNK - 1) / PNG_CHUNK);
+    const long long bound = ndt_hip_png_bound(width, rows);
+    int rc;
+    if ((rc = grow(ctx, &ps.d_filtered, &ps.filtered_bytes, (size_t)n_chunks * PNG_CHUNK))) return rc;
+    if ((rc = grow(ctx, &ps.d_row_filter, &ps.row_filter_bytes, (size_t)rows))) return rc;
+    if ((rc = grow(ctx, &ps.d_slots, &ps.slots_bytes, (size_t)n_chunks * PNG_SLOT))) return rc;
+    if ((rc = grow(ctx, &ps.d_meta, &ps.meta_bytes, (size_t)n_chunks * sizeof(ChunkMeta)))) return rc;
+    if ((rc = grow(ctx, &ps.d_offsets, &ps.offsets_bytes, (size_t)n_chunks * sizeof(long long)))) return rc;
+    if ((rc = grow(ctx, &ps.d_file, &ps.file_bytes, (size_t)bound))) return rc;
+    if ((rc = grow(ctx, &ps.d_info, &ps.info_bytes, sizeof(PngInfo)))) return rc;
+    if (!ps.h_info) HIP_TRY(hipHostMalloc(&ps.h_info, sizeof(PngInfo), hipHostMallocDefault));
+    hipStream_t s = ctx->stream;
+    hipLaunchKernelGGL(k_png_filter, dim3((unsigned)rows), dim3(256), 0, s, (const unsigned *)d_rgba8, (unsigned char *)ps.d_filtered,
+                       (unsigned char *)ps.d_row_filter, (int)width, (int)rows);
+    hipLaunchKernelGGL(k_png_deflate, dim3((unsigned)n_chunks), dim3(PNG_DEFLATE_LANES), 0, s, (const unsigned char *)ps.d_filtered, n, n_chunks,
+                       (unsigned char *)ps.d_slots, (ChunkMeta *)ps.d_meta);
+    hipLaunchKernelGGL(k_png_assemble, dim3(1), dim3(1024), 0, s, (const ChunkMeta *)ps.d_meta, n_chunks, n, (const unsigned char *)ps.d_row_filter,
+                       (int)width, (int)rows, (unsigned char *)ps.d_file, (long long *)ps.d_offsets, (PngInfo *)ps.d_info);
+    hipLaunchKernelGGL(k_png_place, dim3((unsigned)n_chunks), dim3(256), 0, s, (const unsigned char *)ps.d_slots, (const ChunkMeta *)ps.d_meta,
+                       (const long long *)ps.d_offsets, (unsigned char *)ps.d_file);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(ps.h_info, ps.d_info, sizeof(PngInfo), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    const PngInfo info = *(const PngInfo *)ps.h_info;
+    if (stats) {
+        *stats = ndt_png_stats{};
+        stats->png_bytes = info.png_bytes;
+        stats->idat_bytes = info.idat_bytes;
+        stats->chunks = n_chunks;
+        stats->chunks_stored = info.chunks_stored;
+        stats->launches = 4;
+        for (int f = 0; f < 3; ++f) stats->rows_filter[f] = info.rows_filter[f];
+    }
+    if (info.png_bytes < PNG_FILE_EXTRA || info.png_bytes > bound)
+        return fail(NDT_E_DEVICE, "ndt_hip_encode_png: the device reports a file of %lld bytes (bound %lld)", info.png_bytes, bound);
+    if (info.png_bytes > cap)
+        return fail(NDT_E_NOMEM, "ndt_hip_encode_png: the file is %lld bytes, the buffer %lld", info.png_bytes, (long long)cap);
+    HIP_TRY(hipMemcpyAsync(png, ps.d_file, (size_t)info.png_bytes, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    // the IDAT chunk's CRC-32 covers its type and data: bytes 37 .. 41 + idat_bytes of the file
+    const unsigned crc = crc32_of(png + 37, (size_t)(4 + info.idat_bytes));
+    uint8_t *q = png + 41 + info.idat_bytes;
+    q[0] = (uint8_t)(crc >> 24); q[1] = (uint8_t)(crc >> 16); q[2] = (uint8_t)(crc >> 8); q[3] = (uint8_t)crc;
+    if (stats) stats->encode_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return NDT_OK;
+}
+
+extern "C" int ndt_hip_encode_png(ndt_hip_ctx *ctx, const uint8_t *rgba8, int32_t width, int32_t rows, uint8_t *png, int64_t cap,
+                                  ndt_png_stats *stats)
+{
+    if (!ctx || !rgba8 || !png) return fail(NDT_E_INVALID, "ndt_hip_encode_png: NULL argument");
+    if (width < 1 || rows < 1) return fail(NDT_E_INVALID, "ndt_hip_encode_png: a %d x %d image", width, rows);
+    if (stream_bytes(width, rows) < 0)
+        return fail(NDT_E_INVALID, "ndt_hip_encode_png: the filtered stream of a %d x %d image exceeds 2^31 - 1 bytes", width, rows);
+    HIP_TRY(hipSetDevice(ctx->device));
+    const size_t bytes = (size_t)width * (size_t)rows * 4;
+    int rc = grow(ctx, &ctx->png.d_rgba8, &ctx->png.rgba8_bytes, bytes);
+    if (rc) return rc;
+    HIP_TRY(hipMemcpyAsync(ctx->png.d_rgba8, rgba8, bytes, hipMemcpyHostToDevice, ctx->stream));
+    return ndt_hip_encode_png_device(ctx, ctx->png.d_rgba8, width, rows, png, cap, stats);
+}
+
+extern "C" int ndt_hip_render_png(ndt_hip_ctx *ctx, const ndt_render_params *p, uint8_t *png, int64_t cap, ndt_png_stats *stats,
+                                  ndt_render_stats *render_stats)
+{
+    if (!ctx || !p || !png) return fail(NDT_E_INVALID, "ndt_hip_render_png: NULL argument");
+    if (p->width < 1 || p->height < 1 || p->row_step < 1 || p->row_begin < 0) return fail(NDT_E_INVALID, "bad geometry");
+    const int rows = ndt_hip_shard_rows(p->height, p->row_begin, p->row_step);
+    if (rows < 1) return fail(NDT_E_INVALID, "ndt_hip_render_png: the shard has no rows");
+    if (stream_bytes(p->width, rows) < 0)
+        return fail(NDT_E_INVALID, "ndt_hip_render_png: the filtered stream of a %d x %d image exceeds 2^31 - 1 bytes", p->width, rows);
+    HIP_TRY(hipSetDevice(ctx->device));
+    int rc = grow(ctx, &ctx->png.d_rgba8, &ctx->png.rgba8_bytes, (size_t)p->width * (size_t)rows * 4);
+    if (rc) return rc;
+    ndt_hip_ctx *one[1] = { ctx };
+    if ((rc = ndt_hip_render_multi_device(one, 1, p, NDT_IMAGE_RGBA8, ctx->png.d_rgba8, render_stats))) return rc;
+    return ndt_hip_encode_png_device(ctx, ctx->png.d_rgba8, p->width, rows, png, cap, stats);
+}

@@ -24,6 +24,7 @@ API_SYMBOLS = [
     "ndt_hip_item_boxes", "ndt_hip_render_rgba8_async", "ndt_hip_render_rgba8_wait",
     "ndt_hip_fit_spheres", "ndt_hip_fit_launches",
     "ndt_hip_build_kdtree", "ndt_hip_kdtree_fetch", "ndt_hip_kd_launches",
+    "ndt_hip_png_bound", "ndt_hip_encode_png_device", "ndt_hip_encode_png", "ndt_hip_render_png",
 ]
 
 IMAGE_F64, IMAGE_RGBA8 = 0, 1      # enum ndt_image_format
@@ -97,6 +98,12 @@ def load_library():
         lib.ndt_hip_build_kdtree.argtypes = [C.c_void_p, C.c_int32, C.c_int32] + [C.c_void_p] * 4
         lib.ndt_hip_kdtree_fetch.argtypes = [C.c_void_p] * 6
         lib.ndt_hip_kd_launches.argtypes = [C.c_void_p]
+    if hasattr(lib, "ndt_hip_png_bound"):
+        lib.ndt_hip_png_bound.argtypes = [C.c_int32, C.c_int32]
+        lib.ndt_hip_png_bound.restype = C.c_int64
+        lib.ndt_hip_encode_png_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p]
+        lib.ndt_hip_encode_png.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p]
+        lib.ndt_hip_render_png.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
     _lib = lib
     return lib
 
@@ -105,6 +112,20 @@ class KdCounts(C.Structure):
     """ndt_kd_counts: what ndt_hip_build_kdtree says about the tree it left in the context"""
     _fields_ = [("n_kd_nodes", C.c_int32), ("n_leaf_refs", C.c_int32), ("n_inf", C.c_int32), ("depth", C.c_int32),
                 ("launches", C.c_int32), ("grows", C.c_int32)]
+
+
+class PngStats(C.Structure):
+    """ndt_png_stats: what the device encoder says about the file it made"""
+    _fields_ = [("png_bytes", C.c_int64), ("idat_bytes", C.c_int64), ("chunks", C.c_int32), ("chunks_stored", C.c_int32),
+                ("launches", C.c_int32), ("rows_filter", C.c_int32 * 3), ("encode_ms", C.c_double)]
+
+
+def png_bound(width, rows):
+    """ndt_hip_png_bound: the largest file the device encoder can produce for a width x rows image (host arithmetic)."""
+    n = int(load_library().ndt_hip_png_bound(int(width), int(rows)))
+    if n < 0:
+        raise ValueError("no PNG of %d x %d: the size is empty or its filtered stream exceeds 2^31 - 1 bytes" % (width, rows))
+    return n
 
 
 def pack_boxes(dims, lower, upper, finite):
@@ -324,6 +345,40 @@ class NdtHip:
 
     def render_rgba8_wait(self):
         self._check(self.lib.ndt_hip_render_rgba8_wait(self.ctx))
+
+    def encode_png(self, rgba8, cap=None):
+        """ndt_hip_encode_png: the complete PNG file of a (rows, width, 4) uint8 host image, compressed on this context's GPU.
+        Returns the file's bytes; self.png_stats keeps the ndt_png_stats.  cap: room offered (default: ndt_hip_png_bound)."""
+        rgba8 = np.ascontiguousarray(rgba8, dtype=np.uint8)
+        if rgba8.ndim != 3 or rgba8.shape[2] != 4:
+            raise ValueError("rgba8 must be (rows, width, 4)")
+        rows, width = rgba8.shape[:2]
+        cap = png_bound(width, rows) if cap is None else int(cap)
+        out = np.zeros(max(cap, 1), dtype=np.uint8)
+        self.png_stats = PngStats()
+        self._check(self.lib.ndt_hip_encode_png(self.ctx, rgba8.ctypes.data, width, rows, out.ctypes.data, cap, C.byref(self.png_stats)))
+        return out[:self.png_stats.png_bytes].tobytes()
+
+    def encode_png_device(self, d_rgba8_ptr, width, rows, cap=None):
+        """ndt_hip_encode_png_device: the same for width * rows * 4 bytes at raw device pointer `d_rgba8_ptr`."""
+        cap = png_bound(width, rows) if cap is None else int(cap)
+        out = np.zeros(max(cap, 1), dtype=np.uint8)
+        self.png_stats = PngStats()
+        self._check(self.lib.ndt_hip_encode_png_device(self.ctx, C.c_void_p(d_rgba8_ptr), int(width), int(rows), out.ctypes.data, cap,
+                                                       C.byref(self.png_stats)))
+        return out[:self.png_stats.png_bytes].tobytes()
+
+    def render_png(self, width, height, depth, **kw):
+        """ndt_hip_render_png: render_rgba8 with the device's PNG encoder in place of the download.  Returns (the file's bytes,
+        RenderStats); self.png_stats keeps the ndt_png_stats.  The PNG's height is the row shard's."""
+        p = self.params(width, height, depth, **kw)
+        rows = shard_rows(height, p.row_begin, p.row_step)
+        cap = png_bound(width, rows)
+        out = np.zeros(cap, dtype=np.uint8)
+        st = RenderStats()
+        self.png_stats = PngStats()
+        self._check(self.lib.ndt_hip_render_png(self.ctx, C.byref(p), out.ctypes.data, cap, C.byref(self.png_stats), C.byref(st)))
+        return out[:self.png_stats.png_bytes].tobytes(), st
 
     def quantize_device(self, d_rgba_ptr, d_rgba8_ptr, n_pixels):
         self._check(self.lib.ndt_hip_quantize_device(self.ctx, C.c_void_p(d_rgba_ptr), C.c_void_p(d_rgba8_ptr),

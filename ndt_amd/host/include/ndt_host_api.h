@@ -409,6 +409,17 @@ int ndt_render_image_full(scene *scn, int width, int height, int samples, int th
 int ndt_render_image_rgba8(scene *scn, int width, int height, int samples, int threads, int aa_diff, int aa_depth, int stereo,
                            int specular, int max_optic_depth, unsigned char *rgba8);
 
+/* The same frame as a complete PNG file, compressed on the GPU (ndt_hip_render_png: the 8-bit image never leaves the device;
+ * `ndt_hip --png --deflate gpu`).  *png is malloc'ed -- the caller frees it -- and *png_bytes its length.  A frame spread over
+ * several contexts (ndt_render_use_devices) is gathered on the host and encoded from there on the first context.  Prints
+ * `compressed PNG of B bytes on GPU D in L launches`.  No fallback: without a device it fails like every render call. */
+int ndt_render_image_png(scene *scn, int width, int height, int samples, int threads, int aa_diff, int aa_depth, int stereo,
+                         int specular, int max_optic_depth, unsigned char **png, long long *png_bytes);
+/* ... of an 8-bit image that is in host memory already (ndt_hip_encode_png on the calling thread's first context) */
+int ndt_encode_image_png(const unsigned char *rgba8, int width, int height, unsigned char **png, long long *png_bytes);
+/* host milliseconds the device encoder took in the calling thread's last ndt_render_image_png / ndt_encode_image_png */
+double ndt_render_png_encode_ms(void);
+
 /* Which GPUs the calling thread's frames are rendered on (the settings are per thread, like the GPU contexts):
  *   ndt_render_use_device(d)     one context on device d -- `ndt_hip -j K` gives worker w device w mod device count,
  *                                the reference's MPI_MODE_FRAME (one frame per rank, ndt.c:1770-1830);

@@ -6,7 +6,8 @@
  * / JPEG encoding is outside this repository's scope).  `--dump-scene F` writes the flattened
  * scene of the last frame as an ndtscene file instead of rendering.  `--fit gpu` fits the frames'
  * bounding spheres on the GPU (ndt_hip_fit_spheres) instead of on the host's `-t` threads; `--kd gpu` builds their kd-trees
- * there (ndt_hip_build_kdtree) instead of on the host.  Neither falls back: what the device path cannot do ends the run. */
+ * there (ndt_hip_build_kdtree) instead of on the host; `--png --deflate gpu` has the GPU make the frame's PNG file, compressed
+ * (ndt_hip_render_png), instead of the host's stored-block writer.  None falls back: what the device path cannot do ends the run. */
 #include <dlfcn.h>
 #include <getopt.h>
 #include <pthread.h>
@@ -57,7 +58,7 @@ static unsigned char *quantise(const double *rgba, long n_values)
 
 /* ---- one frame: flatten, upload, render, save (what follows scene_setup in the reference's frame loop) */
 static struct {
-    int dims, width, height, depth, threads, aa_diff, aa_depth, stereo, specular, want_depth, samples, png, gpus;
+    int dims, width, height, depth, threads, aa_diff, aa_depth, stereo, specular, want_depth, samples, png, gpus, deflate_gpu;
     const char *raw_path;
 } job_opts;
 
@@ -69,10 +70,15 @@ static int render_frame(scene *scn, int i)
     const int want_f64 = job_opts.raw_path != NULL || job_opts.want_depth;
     double *rgba = want_f64 ? (double *)malloc((size_t)width * height * 4 * sizeof(double)) : NULL;
     double *depth_map = job_opts.want_depth ? (double *)malloc((size_t)width * height * sizeof(double)) : NULL;
-    unsigned char *rgba8 = NULL;
+    unsigned char *rgba8 = NULL, *png = NULL;      /* png: the finished file of --png --deflate gpu */
+    long long png_bytes = 0;
     double t0 = now_s();
     int ok;
-    if (want_f64) {
+    if (job_opts.deflate_gpu && !want_f64) {
+        /* the 8-bit image stays on the device: what comes back is the file */
+        ok = ndt_render_image_png(scn, width, height, job_opts.samples, job_opts.threads, job_opts.aa_diff, job_opts.aa_depth,
+                                  job_opts.stereo, job_opts.specular, job_opts.depth, &png, &png_bytes);
+    } else if (want_f64) {
         ok = ndt_render_image_full(scn, width, height, job_opts.samples, job_opts.threads, job_opts.aa_diff, job_opts.aa_depth,
                                    job_opts.stereo, job_opts.specular, job_opts.depth, rgba, depth_map);
         if (ok) rgba8 = quantise(rgba, (long)width * height * 4);
@@ -88,6 +94,18 @@ static int render_frame(scene *scn, int i)
         return 0;
     }
     printf("rendering took %.3fs\n", now_s() - t0);
+    const double t_file = now_s();
+    double encode_ms = png ? ndt_render_png_encode_ms() : 0.0;
+    if (job_opts.deflate_gpu && !png) {
+        /* the image was made on the host (--raw, -z): encoded from there */
+        if (!ndt_encode_image_png(rgba8, width, height, &png, &png_bytes)) {
+            free(rgba);
+            free(rgba8);
+            free(depth_map);
+            return 0;
+        }
+        encode_ms = ndt_render_png_encode_ms();
+    }
     char dir[512], path[1024];
     mkdir("images", 0700);
     snprintf(dir, sizeof(dir), "images/%s", scn->name); mkdir(dir, 0700);
@@ -95,12 +113,23 @@ static int render_frame(scene *scn, int i)
     snprintf(dir, sizeof(dir), "images/%s/%id/%ix%i", scn->name, job_opts.dims, width, height); mkdir(dir, 0700);
     if (job_opts.png) {
         snprintf(path, sizeof(path), "%s/%s_%ix%i_%04i.png", dir, scn->name, width, height, i);
-        write_png(path, rgba8, width, height);
+        if (png) {
+            FILE *f = fopen(path, "wb");
+            if (f) { fwrite(png, 1, (size_t)png_bytes, f); fclose(f); }
+        } else write_png(path, rgba8, width, height);
     } else {
         snprintf(path, sizeof(path), "%s/%s_%ix%i_%04i.ppm", dir, scn->name, width, height, i);
         write_ppm(path, rgba8, width, height);
     }
     printf("\tsaved %s\n", path);
+    if (getenv("NDT_HOST_TIMING")) {
+        /* with --deflate gpu and the image on the device, the encoder's share is inside "rendering took" */
+        const double ms = (now_s() - t_file) * 1e3;
+        if (png) fprintf(stderr, "ndt_hip: image file %.2f ms (compressed on the GPU %.2f, written %.2f)\n",
+                         job_opts.raw_path || job_opts.want_depth ? ms : ms + encode_ms, encode_ms,
+                         job_opts.raw_path || job_opts.want_depth ? ms - encode_ms : ms);
+        else fprintf(stderr, "ndt_hip: image file %.2f ms (%s, made and written by the host)\n", ms, job_opts.png ? "stored PNG" : "PPM");
+    }
     if (depth_map) {
         /* dbl_image_normalize (image.c:1025-1065) stretches the map to 0..1 before it is saved (ndt.c:1010-1016) */
         double lo = depth_map[0], hi = depth_map[0];
@@ -134,6 +163,7 @@ static int render_frame(scene *scn, int i)
     }
     free(rgba);
     free(rgba8);
+    free(png);
     free(depth_map);
     return 1;
 }
@@ -302,10 +332,12 @@ int main(int argc, char **argv)
     char *scene_path = NULL, *config = NULL, *dump_path = NULL, *raw_path = NULL;
     int fit_gpu = 0;        /* --fit host|gpu: where the frames' bounding spheres are fitted (default: host, on the -t threads) */
     int kd_gpu = 0;         /* --kd host|gpu: where the frames' kd-trees are built (default: host) */
+    int deflate_gpu = 0;    /* --deflate stored|gpu: who makes the --png file: the host, in stored blocks (default), or the GPU, compressed */
     char *objects_dir = "objects";      /* -o: where object plugins are looked for (object.c:119; ndt.c passes "objects") */
     static struct option longopts[] = { { "dump-scene", required_argument, NULL, 1000 },
                                         { "raw", required_argument, NULL, 1001 }, { "png", no_argument, NULL, 1002 },
                                         { "fit", required_argument, NULL, 1003 }, { "kd", required_argument, NULL, 1004 },
+                                        { "deflate", required_argument, NULL, 1005 },
                                         { NULL, 0, NULL, 0 } };
     int ch;
     while ((ch = getopt_long(argc, argv, "a:d:g:r:f:j:l:m:3:n:ps:t:u:o:zh", longopts, NULL)) != -1) {
@@ -365,14 +397,23 @@ int main(int argc, char **argv)
             else if (!strcmp(optarg, "host")) kd_gpu = 0;
             else { fprintf(stderr, "%s: --kd takes host or gpu, not '%s'\n", argv[0], optarg); return 1; }
             break;
+        case 1005:
+            if (!strcmp(optarg, "gpu")) deflate_gpu = 1;
+            else if (!strcmp(optarg, "stored")) deflate_gpu = 0;
+            else { fprintf(stderr, "%s: --deflate takes stored or gpu, not '%s'\n", argv[0], optarg); return 1; }
+            break;
         default:
             fprintf(stderr, "usage: %s -s scene.so|builtin:yaml [-d dims] [-r WxH|1080p|4k] [-f last|first:last[:total]] [-l depth]\n"
-                            "          [-a diff,depth] [-n samples] [-m s|o|a|m] [-p] [-z] [-j frames_in_flight] [-g gpus_per_frame] [-u config] [--dump-scene file.ndtscene] [--raw file.f64] [--png] [--fit host|gpu] [--kd host|gpu]\n", argv[0]);
+                            "          [-a diff,depth] [-n samples] [-m s|o|a|m] [-p] [-z] [-j frames_in_flight] [-g gpus_per_frame] [-u config] [--dump-scene file.ndtscene] [--raw file.f64] [--png [--deflate stored|gpu]] [--fit host|gpu] [--kd host|gpu]\n", argv[0]);
             return ch == 'h' ? 0 : 1;
         }
     }
     if (!scene_path || dims < 3 || width < 1 || height < 1) {
         fprintf(stderr, "%s: need -s scene.so, dims >= 3 and a resolution\n", argv[0]);
+        return 1;
+    }
+    if (deflate_gpu && !png) {
+        fprintf(stderr, "%s: --deflate gpu compresses the PNG file: it needs --png\n", argv[0]);
         return 1;
     }
     int (*setup)(scene *, int, int, int, char *) = NULL;
@@ -398,6 +439,7 @@ int main(int argc, char **argv)
     job_opts.aa_diff = aa_diff; job_opts.aa_depth = aa_depth; job_opts.stereo = stereo; job_opts.specular = specular;
     job_opts.want_depth = want_depth; job_opts.raw_path = raw_path; job_opts.samples = samples; job_opts.png = png;
     job_opts.gpus = gpus > 1 ? gpus : 1;
+    job_opts.deflate_gpu = deflate_gpu;
     ndt_render_fit_on_gpu(fit_gpu);
     ndt_render_kd_on_gpu(kd_gpu);
     if (job_opts.gpus > 1) {

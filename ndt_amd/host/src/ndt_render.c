@@ -136,6 +136,41 @@ int ndt_render_image_aa(scene *scn, int width, int height, int threads, int aa_d
     return ndt_render_image_full(scn, width, height, 1, threads, aa_diff, aa_depth, 0, 1, max_optic_depth, rgba, NULL);
 }
 
+/* ---- the frame's PNG file made on the GPU (ndt_hip_render_png / ndt_hip_encode_png) */
+#define NDT_HOST_IMAGE_PNG 100              /* render_any's `format` beside ndt_image_format; `out` is a png_out */
+typedef struct { unsigned char **png; long long *bytes; } png_out;
+static __thread double g_png_ms = 0.0;
+
+double ndt_render_png_encode_ms(void) { return g_png_ms; }
+
+static void say_png(const ndt_png_stats *ps)
+{
+    g_png_ms = ps->encode_ms;
+    printf("compressed PNG of %lld bytes on GPU %d in %d launches\n", (long long)ps->png_bytes, ndt_hip_device(g_ctx[0]), ps->launches);
+}
+
+int ndt_encode_image_png(const unsigned char *rgba8, int width, int height, unsigned char **png, long long *png_bytes)
+{
+    const int64_t cap = ndt_hip_png_bound(width, height);
+    ndt_png_stats ps;
+    *png = NULL;
+    *png_bytes = 0;
+    if (cap < 0) {
+        fprintf(stderr, "ndt_encode_image_png: no PNG of %d x %d: the size is empty or its filtered stream exceeds 2^31 - 1 bytes\n", width, height);
+        return 0;
+    }
+    unsigned char *buf = (unsigned char *)malloc((size_t)cap);
+    if (!buf || !have_contexts() || ndt_hip_encode_png(g_ctx[0], rgba8, width, height, buf, cap, &ps) != NDT_OK) {
+        fprintf(stderr, "ndt_encode_image_png: %s\n", buf ? ndt_hip_last_error() : "out of memory");
+        free(buf);
+        return 0;
+    }
+    say_png(&ps);
+    *png = buf;
+    *png_bytes = ps.png_bytes;
+    return 1;
+}
+
 static int render_any(scene *scn, int width, int height, int samples, int aa_diff, int aa_depth, int stereo, int specular,
                       int max_optic_depth, int format, void *out, double *depth, int threads)
 {
@@ -169,7 +204,29 @@ static int render_any(scene *scn, int width, int height, int samples, int aa_dif
             p.aa_diff = aa_diff;
             p.aa_depth = aa_depth;
         }
-        if (depth)      /* the depth map comes from the one-context call (a map is not split over devices) */
+        if (format == NDT_HOST_IMAGE_PNG) {
+            png_out *po = (png_out *)out;
+            const int64_t cap = ndt_hip_png_bound(width, height);
+            ndt_png_stats ps;
+            unsigned char *buf = cap > 0 ? (unsigned char *)malloc((size_t)cap) : NULL;
+            if (!buf) {
+                fprintf(stderr, "ndt_render_image_png: no PNG of %d x %d\n", width, height);
+                ok = 0;
+            } else if (g_n_ctx == 1) {
+                ok = ndt_hip_render_png(g_ctx[0], &p, buf, cap, &ps, NULL) == NDT_OK;
+            } else {
+                /* rows from several contexts: gathered into host memory, encoded from there on the first context */
+                unsigned char *rgba8 = (unsigned char *)malloc((size_t)width * height * 4);
+                ok = rgba8 && ndt_hip_render_multi(g_ctx, g_n_ctx, &p, NDT_IMAGE_RGBA8, rgba8, NULL) == NDT_OK &&
+                     ndt_hip_encode_png(g_ctx[0], rgba8, width, height, buf, cap, &ps) == NDT_OK;
+                free(rgba8);
+            }
+            if (ok) {
+                say_png(&ps);
+                *po->png = buf;
+                *po->bytes = ps.png_bytes;
+            } else free(buf);
+        } else if (depth)      /* the depth map comes from the one-context call (a map is not split over devices) */
             ok = format == NDT_IMAGE_F64 && ndt_hip_render_depth(g_ctx[0], &p, (double *)out, depth, NULL) == NDT_OK;
         else
             ok = ndt_hip_render_multi(g_ctx, g_n_ctx, &p, format, out, NULL) == NDT_OK;
@@ -198,8 +255,12 @@ static int render_any(scene *scn, int width, int height, int samples, int aa_dif
                      NDT_MS(ts0, ts1) - fit.gather_ms - fit.fit_ms - kds.build_ms);
         else
             snprintf(share, sizeof(share), "host fits %.2f, %s, rest %.2f", fit.fit_ms, tree, NDT_MS(ts0, ts1) - fit.fit_ms - kds.build_ms);
-        fprintf(stderr, "ndt_render_image: bounds + kd-tree + flatten %.2f ms (%s), upload %.2f ms, render + image to host %.2f ms\n",
-                NDT_MS(ts0, ts1), share, NDT_MS(ts1, ts2), NDT_MS(ts2, ts3));
+        if (format == NDT_HOST_IMAGE_PNG && ok)
+            fprintf(stderr, "ndt_render_image: bounds + kd-tree + flatten %.2f ms (%s), upload %.2f ms, render + image file to host %.2f ms (image file on the GPU %.2f)\n",
+                    NDT_MS(ts0, ts1), share, NDT_MS(ts1, ts2), NDT_MS(ts2, ts3), g_png_ms);
+        else
+            fprintf(stderr, "ndt_render_image: bounds + kd-tree + flatten %.2f ms (%s), upload %.2f ms, render + image to host %.2f ms\n",
+                    NDT_MS(ts0, ts1), share, NDT_MS(ts1, ts2), NDT_MS(ts2, ts3));
     }
     ndt_flat_builder_free(&fb);
     return ok;
@@ -218,4 +279,13 @@ int ndt_render_image_rgba8(scene *scn, int width, int height, int samples, int t
                            int specular, int max_optic_depth, unsigned char *rgba8)
 {
     return render_any(scn, width, height, samples, aa_diff, aa_depth, stereo, specular, max_optic_depth, NDT_IMAGE_RGBA8, rgba8, NULL, threads);
+}
+
+int ndt_render_image_png(scene *scn, int width, int height, int samples, int threads, int aa_diff, int aa_depth, int stereo,
+                         int specular, int max_optic_depth, unsigned char **png, long long *png_bytes)
+{
+    png_out po = { png, png_bytes };
+    *png = NULL;
+    *png_bytes = 0;
+    return render_any(scn, width, height, samples, aa_diff, aa_depth, stereo, specular, max_optic_depth, NDT_HOST_IMAGE_PNG, &po, NULL, threads);
 }
