@@ -347,6 +347,37 @@ int ndt_hip_encode_png(ndt_hip_ctx *ctx, const uint8_t *rgba8, int32_t width, in
 int ndt_hip_render_png(ndt_hip_ctx *ctx, const ndt_render_params *p, uint8_t *png, int64_t cap, ndt_png_stats *stats,
                        ndt_render_stats *render_stats);
 
+/* The depth map of `-z` finished on the device: what the reference does to the map before it saves it (ndt.c:1010-1016:
+ * dbl_image_normalize, image.c:1025-1065, stretches it to 0 .. 1; the grey image v, v, v, 1 is then quantised with pixel_d2c
+ * like every image).  With lo / hi the map's minimum / maximum, pixel i becomes the four bytes g, g, g, 255 with
+ * g = pixel_d2c(hi > lo ? (d[i] - lo) / (hi - lo) : 0.0) -- bit for bit the host's arithmetic.
+ *   ndt_hip_depth_rgba8_device   d_depth: n_pixels doubles in the context's device memory; d_rgba8: n_pixels * 4 bytes there.
+ *                                Two kernel launches: a reduction to one {lo, hi} record per workgroup, and a kernel whose
+ *                                workgroups each fold those records and then write their share of the pixels.
+ *                                range_out (host, may be NULL) receives lo, hi.  Synchronous.  No scene has to be uploaded.
+ *                                NDT_E_INVALID: a NULL pointer, n_pixels < 1, a misaligned pointer.  NDT_E_UNSUPPORTED: the map
+ *                                holds a NaN or an infinity -- the error text names the lowest such pixel, and d_rgba8 is
+ *                                not written (the reference's loop would give a range that depends on where the NaN sits).
+ *   ndt_hip_render_rgba8_depth   ndt_hip_render_depth_device into the context's buffers, the image quantised and the map finished
+ *                                there: rgba8 and depth8 (host) receive rows*width*4 bytes each -- 8 bytes a pixel cross PCIe
+ *                                where ndt_hip_render_depth moves 40.  Accepts and refuses what ndt_hip_render_depth does.
+ *   ndt_hip_render_png_depth     the same with ndt_hip_encode_png_device in place of the downloads.  The image always leaves as
+ *                                a file (png, cap); the map as a file (depth_png, depth_cap) or as its bytes (depth8): exactly
+ *                                one of depth_png / depth8 is not NULL.  stats (may be NULL): two records, [0] the image's
+ *                                file, [1] the map's.  A buffer that is too small: NDT_E_NOMEM with the size needed in the
+ *                                error text and in its stats record, and nothing written to that buffer (the image's file is
+ *                                made first: it has arrived when only depth_cap is short).
+ *   ndt_hip_depth_launches / ndt_hip_depth_ms   kernel launches of the context's last map (2), and the host time they took,
+ *                                launch to the range in host memory. */
+int ndt_hip_depth_rgba8_device(ndt_hip_ctx *ctx, const void *d_depth, int64_t n_pixels, void *d_rgba8, double *range_out);
+int ndt_hip_render_rgba8_depth(ndt_hip_ctx *ctx, const ndt_render_params *p, uint8_t *rgba8, uint8_t *depth8, double *range_out,
+                               ndt_render_stats *stats);
+int ndt_hip_render_png_depth(ndt_hip_ctx *ctx, const ndt_render_params *p, uint8_t *png, int64_t cap, uint8_t *depth_png,
+                             int64_t depth_cap, uint8_t *depth8, ndt_png_stats *stats, double *range_out,
+                             ndt_render_stats *render_stats);
+int ndt_hip_depth_launches(ndt_hip_ctx *ctx);
+double ndt_hip_depth_ms(ndt_hip_ctx *ctx);
+
 /* ONE frame over several contexts -- one per GPU of the node, or several on one GPU -- called from one host thread.
  * The rows `p` selects are dealt cyclically to the contexts exactly as the reference deals rows to MPI ranks in
  * MPI_MODE_ROW (ndt.c:812-820: row_start = rank, row_step = size): context k renders rows

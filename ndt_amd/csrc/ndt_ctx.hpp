@@ -12,6 +12,7 @@
 //   ndt_fit.hip      ndt_hip_fit_spheres: the bounding-sphere fits of a frame (batched Nelder-Mead), kernel and launcher
 //   ndt_kd.hip       ndt_hip_build_kdtree: the kd-tree of a frame's item boxes, level by level; kernels, launcher and C ABI
 //   ndt_png.hip      ndt_hip_encode_png* / ndt_hip_render_png: a frame's PNG file made on the device; kernels, launcher and C ABI
+//   ndt_depth.hip    ndt_hip_depth_rgba8_device / ndt_hip_render_*_depth: the depth map of `-z` normalised and quantised on the device
 #pragma once
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
@@ -62,6 +63,16 @@ struct PngState {
     size_t rgba8_bytes = 0, filtered_bytes = 0, row_filter_bytes = 0, slots_bytes = 0, meta_bytes = 0, offsets_bytes = 0, file_bytes = 0,
            info_bytes = 0;
     void *h_info = nullptr;         // pinned: the info record of the last file
+};
+
+// ndt_hip_depth_rgba8_device, ndt_hip_render_*_depth (ndt_depth.hip): grow-only device buffers, reused by the next frame
+struct DepthState {
+    void *d_records = nullptr;      // one {lo, hi, bad} record per workgroup of k_depth_range, and the folded one behind them
+    void *d_rgba8 = nullptr, *d_depth8 = nullptr;       // the two 8-bit images of ndt_hip_render_*_depth
+    size_t records_bytes = 0, rgba8_bytes = 0, depth8_bytes = 0;
+    void *h_result = nullptr;       // pinned: the folded record of the last map
+    int launches = 0;               // kernel launches of the last map
+    double finish_ms = 0.0;         // host time of the last map: launch to the folded record in host memory
 };
 
 struct ndt_hip_ctx {
@@ -148,6 +159,7 @@ struct ndt_hip_ctx {
     int fit_launches = 0;           // kernel launches of the last ndt_hip_fit_spheres call
     KdState kd;                     // ndt_hip_build_kdtree
     PngState png;                   // ndt_hip_encode_png*, ndt_hip_render_png
+    DepthState depth;               // ndt_hip_depth_rgba8_device, ndt_hip_render_*_depth
     void *d_out = nullptr;          // staging for ndt_hip_render (host output)
     size_t d_out_bytes = 0;
     void *d_shard = nullptr;        // ndt_hip_render_multi: this context's rows before they are pushed into the frame
@@ -233,6 +245,9 @@ void free_kd(ndt_hip_ctx *ctx);
 
 // ndt_png.hip
 void free_png(ndt_hip_ctx *ctx);
+
+// ndt_depth.hip
+void free_depth(ndt_hip_ctx *ctx);
 
 // ndt_aa.hip / ndt_sampled.hip
 int render_antialiased(ndt_hip_ctx *ctx, const ndt_render_params *p, void *d_rgba, ndt_render_stats &total, void *d_depth = nullptr);

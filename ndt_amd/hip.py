@@ -25,6 +25,7 @@ API_SYMBOLS = [
     "ndt_hip_fit_spheres", "ndt_hip_fit_launches",
     "ndt_hip_build_kdtree", "ndt_hip_kdtree_fetch", "ndt_hip_kd_launches",
     "ndt_hip_png_bound", "ndt_hip_encode_png_device", "ndt_hip_encode_png", "ndt_hip_render_png",
+    "ndt_hip_depth_rgba8_device", "ndt_hip_render_rgba8_depth", "ndt_hip_render_png_depth", "ndt_hip_depth_launches", "ndt_hip_depth_ms",
 ]
 
 IMAGE_F64, IMAGE_RGBA8 = 0, 1      # enum ndt_image_format
@@ -104,6 +105,14 @@ def load_library():
         lib.ndt_hip_encode_png_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p]
         lib.ndt_hip_encode_png.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p]
         lib.ndt_hip_render_png.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
+    if hasattr(lib, "ndt_hip_depth_rgba8_device"):
+        lib.ndt_hip_depth_rgba8_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
+        lib.ndt_hip_render_rgba8_depth.argtypes = [C.c_void_p] * 6
+        lib.ndt_hip_render_png_depth.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
+                                                 C.c_void_p, C.c_void_p]
+        lib.ndt_hip_depth_launches.argtypes = [C.c_void_p]
+        lib.ndt_hip_depth_ms.argtypes = [C.c_void_p]
+        lib.ndt_hip_depth_ms.restype = C.c_double
     _lib = lib
     return lib
 
@@ -379,6 +388,50 @@ class NdtHip:
         self.png_stats = PngStats()
         self._check(self.lib.ndt_hip_render_png(self.ctx, C.byref(p), out.ctypes.data, cap, C.byref(self.png_stats), C.byref(st)))
         return out[:self.png_stats.png_bytes].tobytes(), st
+
+    def depth_rgba8_device(self, d_depth_ptr, n_pixels, d_rgba8_ptr):
+        """ndt_hip_depth_rgba8_device: the map of n_pixels doubles at raw device pointer `d_depth_ptr` stretched to 0 .. 1 and
+        quantised into n_pixels * 4 bytes at `d_rgba8_ptr` (g, g, g, 255), in two launches.  Returns the map's (lo, hi)."""
+        rng = np.zeros(2, dtype=np.float64)
+        self._check(self.lib.ndt_hip_depth_rgba8_device(self.ctx, C.c_void_p(d_depth_ptr), int(n_pixels), C.c_void_p(d_rgba8_ptr),
+                                                        rng.ctypes.data))
+        return rng
+
+    def depth_launches(self):
+        """ndt_hip_depth_launches: kernel launches of the context's last depth map."""
+        return int(self.lib.ndt_hip_depth_launches(self.ctx))
+
+    def render_rgba8_depth(self, width, height, depth, **kw):
+        """ndt_hip_render_rgba8_depth: render_rgba8 with the `-z` map beside it, both finished on the device.  Returns
+        ((rows, width, 4) uint8 image, (rows, width, 4) uint8 map, float64 [lo, hi] of the map, RenderStats)."""
+        p = self.params(width, height, depth, **kw)
+        rows = shard_rows(height, p.row_begin, p.row_step)
+        out = np.zeros((rows, width, 4), dtype=np.uint8)
+        dm = np.zeros((rows, width, 4), dtype=np.uint8)
+        rng = np.zeros(2, dtype=np.float64)
+        st = RenderStats()
+        self._check(self.lib.ndt_hip_render_rgba8_depth(self.ctx, C.byref(p), out.ctypes.data, dm.ctypes.data, rng.ctypes.data, C.byref(st)))
+        return out, dm, rng, st
+
+    def render_png_depth(self, width, height, depth, depth_png=True, cap=None, depth_cap=None, **kw):
+        """ndt_hip_render_png_depth: the image as a PNG file made on the device, and the map as one too (depth_png=True) or
+        as its (rows, width, 4) bytes.  Returns (file, file or array, [lo, hi], RenderStats); self.png_stats keeps the two
+        ndt_png_stats (image, map).  cap / depth_cap: room offered (default: ndt_hip_png_bound)."""
+        p = self.params(width, height, depth, **kw)
+        rows = shard_rows(height, p.row_begin, p.row_step)
+        cap = png_bound(width, rows) if cap is None else int(cap)
+        depth_cap = png_bound(width, rows) if depth_cap is None else int(depth_cap)
+        out = np.zeros(max(cap, 1), dtype=np.uint8)
+        dpng = np.zeros(max(depth_cap, 1), dtype=np.uint8) if depth_png else None
+        dm = None if depth_png else np.zeros((rows, width, 4), dtype=np.uint8)
+        rng = np.zeros(2, dtype=np.float64)
+        st = RenderStats()
+        self.png_stats = (PngStats * 2)()
+        self._check(self.lib.ndt_hip_render_png_depth(self.ctx, C.byref(p), out.ctypes.data, cap, dpng.ctypes.data if depth_png else None,
+                                                      depth_cap, None if depth_png else dm.ctypes.data, C.byref(self.png_stats),
+                                                      rng.ctypes.data, C.byref(st)))
+        png = out[:self.png_stats[0].png_bytes].tobytes()
+        return png, (dpng[:self.png_stats[1].png_bytes].tobytes() if depth_png else dm), rng, st
 
     def quantize_device(self, d_rgba_ptr, d_rgba8_ptr, n_pixels):
         self._check(self.lib.ndt_hip_quantize_device(self.ctx, C.c_void_p(d_rgba_ptr), C.c_void_p(d_rgba8_ptr),

@@ -420,6 +420,27 @@ int ndt_encode_image_png(const unsigned char *rgba8, int width, int height, unsi
 /* host milliseconds the device encoder took in the calling thread's last ndt_render_image_png / ndt_encode_image_png */
 double ndt_render_png_encode_ms(void);
 
+/* The same frame with the depth map of `-z` beside it, both finished on the GPU (`ndt_hip -z --depth gpu`): the map is
+ * stretched to 0 .. 1 and quantised there (ndt_hip_render_rgba8_depth / ndt_hip_render_png_depth) instead of coming back in
+ * doubles with the image.  What arrives is what the driver writes its two files from:
+ *   want_png = 0                   rgba8 and depth8: width*height*4 bytes each (the map as g, g, g, 255)
+ *   want_png = 1, want_depth_png = 0   the image as a complete PNG file compressed on the GPU, the map as depth8
+ *   want_png = 1, want_depth_png = 1   both as PNG files
+ * The buffers that arrive are malloc'ed -- ndt_depth_frame_free frees them --, the others stay NULL.  range: the map's
+ * minimum and maximum.  Prints `finished depth map [lo, hi] on GPU D in L launches`.  One context renders the frame, whatever
+ * ndt_render_use_devices says (a map is not split over devices).  No fallback: without a device it fails like every render call. */
+typedef struct ndt_depth_frame {
+    unsigned char *rgba8, *depth8;
+    unsigned char *png, *depth_png;
+    long long png_bytes, depth_png_bytes;
+    double range[2];
+} ndt_depth_frame;
+int ndt_render_image_depth8(scene *scn, int width, int height, int samples, int threads, int aa_diff, int aa_depth, int stereo,
+                            int specular, int max_optic_depth, int want_png, int want_depth_png, ndt_depth_frame *out);
+void ndt_depth_frame_free(ndt_depth_frame *f);
+/* host milliseconds the GPU took to finish the map in the calling thread's last ndt_render_image_depth8 */
+double ndt_render_depth_finish_ms(void);
+
 /* Which GPUs the calling thread's frames are rendered on (the settings are per thread, like the GPU contexts):
  *   ndt_render_use_device(d)     one context on device d -- `ndt_hip -j K` gives worker w device w mod device count,
  *                                the reference's MPI_MODE_FRAME (one frame per rank, ndt.c:1770-1830);

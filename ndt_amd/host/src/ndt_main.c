@@ -2,12 +2,15 @@
  * BASELINE configs use (reference ndt.c:1450: -d -r -f -l -s -t -u -o).  It loads a scene
  * program exactly like the reference does (dlopen + dlsym scene_setup / scene_frames /
  * scene_cleanup, ndt.c:1654-1664), renders each frame with ndt_render_image and writes
- * images/<scene>/<N>d/<WxH>/<scene>_<WxH>_<frame>.ppm (binary PPM of the pixel_d2c bytes; PNG
- * / JPEG encoding is outside this repository's scope).  `--dump-scene F` writes the flattened
+ * images/<scene>/<N>d/<WxH>/<scene>_<WxH>_<frame>.ppm (binary PPM of the pixel_d2c bytes), or with `--png` the 8-bit RGBA
+ * PNG the reference writes by default (stored blocks from the host, or compressed by the GPU; JPEG is not written).  `-z` adds the
+ * normalised depth map, depth/<scene>_<WxH>_<frame>.ppm.  `--dump-scene F` writes the flattened
  * scene of the last frame as an ndtscene file instead of rendering.  `--fit gpu` fits the frames'
  * bounding spheres on the GPU (ndt_hip_fit_spheres) instead of on the host's `-t` threads; `--kd gpu` builds their kd-trees
  * there (ndt_hip_build_kdtree) instead of on the host; `--png --deflate gpu` has the GPU make the frame's PNG file, compressed
- * (ndt_hip_render_png), instead of the host's stored-block writer.  None falls back: what the device path cannot do ends the run. */
+ * (ndt_hip_render_png), instead of the host's stored-block writer; `-z --depth gpu` has the GPU normalise and quantise the depth
+ * map (ndt_hip_render_rgba8_depth) instead of sending it and the image back in doubles, and `--depth-png` then writes the map as a
+ * PNG compressed there as well.  None falls back: what the device path cannot do ends the run. */
 #include <dlfcn.h>
 #include <getopt.h>
 #include <pthread.h>
@@ -58,7 +61,7 @@ static unsigned char *quantise(const double *rgba, long n_values)
 
 /* ---- one frame: flatten, upload, render, save (what follows scene_setup in the reference's frame loop) */
 static struct {
-    int dims, width, height, depth, threads, aa_diff, aa_depth, stereo, specular, want_depth, samples, png, gpus, deflate_gpu;
+    int dims, width, height, depth, threads, aa_diff, aa_depth, stereo, specular, want_depth, samples, png, gpus, deflate_gpu, depth_gpu, depth_png;
     const char *raw_path;
 } job_opts;
 
@@ -67,14 +70,24 @@ static int render_frame(scene *scn, int i)
     const int width = job_opts.width, height = job_opts.height;
     /* the image in doubles only when something asks for it (--raw, the depth map of -z); otherwise the GPU quantises
      * and 4 bytes per pixel come back instead of 32 */
-    const int want_f64 = job_opts.raw_path != NULL || job_opts.want_depth;
+    /* (--depth gpu: the map is finished on the device as well, and -z asks for no doubles) */
+    const int want_f64 = job_opts.raw_path != NULL || (job_opts.want_depth && !job_opts.depth_gpu);
     double *rgba = want_f64 ? (double *)malloc((size_t)width * height * 4 * sizeof(double)) : NULL;
-    double *depth_map = job_opts.want_depth ? (double *)malloc((size_t)width * height * sizeof(double)) : NULL;
+    double *depth_map = job_opts.want_depth && !job_opts.depth_gpu ? (double *)malloc((size_t)width * height * sizeof(double)) : NULL;
+    ndt_depth_frame df;                             /* --depth gpu: the 8-bit images or files that arrive */
+    memset(&df, 0, sizeof(df));
     unsigned char *rgba8 = NULL, *png = NULL;      /* png: the finished file of --png --deflate gpu */
     long long png_bytes = 0;
     double t0 = now_s();
     int ok;
-    if (job_opts.deflate_gpu && !want_f64) {
+    if (job_opts.depth_gpu) {
+        ok = ndt_render_image_depth8(scn, width, height, job_opts.samples, job_opts.threads, job_opts.aa_diff, job_opts.aa_depth,
+                                     job_opts.stereo, job_opts.specular, job_opts.depth, job_opts.deflate_gpu, job_opts.depth_png, &df);
+        /* from here on the image is where the other paths leave it; the map stays in df */
+        rgba8 = df.rgba8; df.rgba8 = NULL;
+        png = df.png; df.png = NULL;
+        png_bytes = df.png_bytes;
+    } else if (job_opts.deflate_gpu && !want_f64) {
         /* the 8-bit image stays on the device: what comes back is the file */
         ok = ndt_render_image_png(scn, width, height, job_opts.samples, job_opts.threads, job_opts.aa_diff, job_opts.aa_depth,
                                   job_opts.stereo, job_opts.specular, job_opts.depth, &png, &png_bytes);
@@ -126,9 +139,23 @@ static int render_frame(scene *scn, int i)
         /* with --deflate gpu and the image on the device, the encoder's share is inside "rendering took" */
         const double ms = (now_s() - t_file) * 1e3;
         if (png) fprintf(stderr, "ndt_hip: image file %.2f ms (compressed on the GPU %.2f, written %.2f)\n",
-                         job_opts.raw_path || job_opts.want_depth ? ms : ms + encode_ms, encode_ms,
-                         job_opts.raw_path || job_opts.want_depth ? ms - encode_ms : ms);
+                         want_f64 ? ms : ms + encode_ms, encode_ms, want_f64 ? ms - encode_ms : ms);
         else fprintf(stderr, "ndt_hip: image file %.2f ms (%s, made and written by the host)\n", ms, job_opts.png ? "stored PNG" : "PPM");
+    }
+    if (job_opts.depth_gpu) {
+        /* the map arrived normalised and quantised (or as its file): only the writing is left */
+        const double t_depth = now_s();
+        mkdir("depth", 0700);
+        snprintf(path, sizeof(path), "depth/%s_%ix%i_%04i.%s", scn->name, width, height, i, df.depth_png ? "png" : "ppm");
+        if (df.depth_png) {
+            FILE *f = fopen(path, "wb");
+            if (f) { fwrite(df.depth_png, 1, (size_t)df.depth_png_bytes, f); fclose(f); }
+        } else write_ppm(path, df.depth8, width, height);
+        printf("\tsaved %s\n", path);
+        if (getenv("NDT_HOST_TIMING"))
+            fprintf(stderr, "ndt_hip: depth file %.2f ms (map finished on the GPU %.2f, inside \"rendering took\"; %s written by the host)\n",
+                    (now_s() - t_depth) * 1e3, ndt_render_depth_finish_ms(), df.depth_png ? "PNG made there," : "PPM made and");
+        ndt_depth_frame_free(&df);
     }
     if (depth_map) {
         /* dbl_image_normalize (image.c:1025-1065) stretches the map to 0..1 before it is saved (ndt.c:1010-1016) */
@@ -332,12 +359,15 @@ int main(int argc, char **argv)
     char *scene_path = NULL, *config = NULL, *dump_path = NULL, *raw_path = NULL;
     int fit_gpu = 0;        /* --fit host|gpu: where the frames' bounding spheres are fitted (default: host, on the -t threads) */
     int kd_gpu = 0;         /* --kd host|gpu: where the frames' kd-trees are built (default: host) */
+    int depth_gpu = 0;      /* --depth host|gpu: who normalises and quantises the depth map of -z: the host, from doubles (default), or the GPU */
+    int depth_png = 0;      /* --depth-png: the map as a PNG compressed on the GPU instead of a PPM (needs --depth gpu --png --deflate gpu) */
     int deflate_gpu = 0;    /* --deflate stored|gpu: who makes the --png file: the host, in stored blocks (default), or the GPU, compressed */
     char *objects_dir = "objects";      /* -o: where object plugins are looked for (object.c:119; ndt.c passes "objects") */
     static struct option longopts[] = { { "dump-scene", required_argument, NULL, 1000 },
                                         { "raw", required_argument, NULL, 1001 }, { "png", no_argument, NULL, 1002 },
                                         { "fit", required_argument, NULL, 1003 }, { "kd", required_argument, NULL, 1004 },
                                         { "deflate", required_argument, NULL, 1005 },
+                                        { "depth", required_argument, NULL, 1006 }, { "depth-png", no_argument, NULL, 1007 },
                                         { NULL, 0, NULL, 0 } };
     int ch;
     while ((ch = getopt_long(argc, argv, "a:d:g:r:f:j:l:m:3:n:ps:t:u:o:zh", longopts, NULL)) != -1) {
@@ -402,9 +432,15 @@ int main(int argc, char **argv)
             else if (!strcmp(optarg, "stored")) deflate_gpu = 0;
             else { fprintf(stderr, "%s: --deflate takes stored or gpu, not '%s'\n", argv[0], optarg); return 1; }
             break;
+        case 1006:
+            if (!strcmp(optarg, "gpu")) depth_gpu = 1;
+            else if (!strcmp(optarg, "host")) depth_gpu = 0;
+            else { fprintf(stderr, "%s: --depth takes host or gpu, not '%s'\n", argv[0], optarg); return 1; }
+            break;
+        case 1007: depth_png = 1; break;
         default:
             fprintf(stderr, "usage: %s -s scene.so|builtin:yaml [-d dims] [-r WxH|1080p|4k] [-f last|first:last[:total]] [-l depth]\n"
-                            "          [-a diff,depth] [-n samples] [-m s|o|a|m] [-p] [-z] [-j frames_in_flight] [-g gpus_per_frame] [-u config] [--dump-scene file.ndtscene] [--raw file.f64] [--png [--deflate stored|gpu]] [--fit host|gpu] [--kd host|gpu]\n", argv[0]);
+                            "          [-a diff,depth] [-n samples] [-m s|o|a|m] [-p] [-z] [-j frames_in_flight] [-g gpus_per_frame] [-u config] [--dump-scene file.ndtscene] [--raw file.f64] [--png [--deflate stored|gpu]] [--fit host|gpu] [--kd host|gpu] [--depth host|gpu [--depth-png]]\n", argv[0]);
             return ch == 'h' ? 0 : 1;
         }
     }
@@ -414,6 +450,18 @@ int main(int argc, char **argv)
     }
     if (deflate_gpu && !png) {
         fprintf(stderr, "%s: --deflate gpu compresses the PNG file: it needs --png\n", argv[0]);
+        return 1;
+    }
+    if (depth_gpu && !want_depth) {
+        fprintf(stderr, "%s: --depth gpu finishes the depth map of -z: it needs -z\n", argv[0]);
+        return 1;
+    }
+    if (depth_gpu && raw_path) {
+        fprintf(stderr, "%s: --depth gpu brings no doubles back and --raw dumps them: take --depth host with --raw\n", argv[0]);
+        return 1;
+    }
+    if (depth_png && !(depth_gpu && png && deflate_gpu)) {
+        fprintf(stderr, "%s: --depth-png has the GPU compress the map's PNG: it needs --depth gpu --png --deflate gpu\n", argv[0]);
         return 1;
     }
     int (*setup)(scene *, int, int, int, char *) = NULL;
@@ -440,6 +488,8 @@ int main(int argc, char **argv)
     job_opts.want_depth = want_depth; job_opts.raw_path = raw_path; job_opts.samples = samples; job_opts.png = png;
     job_opts.gpus = gpus > 1 ? gpus : 1;
     job_opts.deflate_gpu = deflate_gpu;
+    job_opts.depth_gpu = depth_gpu;
+    job_opts.depth_png = depth_png;
     ndt_render_fit_on_gpu(fit_gpu);
     ndt_render_kd_on_gpu(kd_gpu);
     if (job_opts.gpus > 1) {

@@ -171,6 +171,59 @@ int ndt_encode_image_png(const unsigned char *rgba8, int width, int height, unsi
     return 1;
 }
 
+/* ---- the depth map of -z finished on the GPU (ndt_hip_render_rgba8_depth / ndt_hip_render_png_depth) */
+#define NDT_HOST_IMAGE_DEPTH8 101           /* render_any's `format`; `out` is a depth_out */
+typedef struct { ndt_depth_frame *frame; int want_png, want_depth_png; } depth_out;
+static __thread double g_depth_ms = 0.0;
+
+double ndt_render_depth_finish_ms(void) { return g_depth_ms; }
+
+void ndt_depth_frame_free(ndt_depth_frame *f)
+{
+    free(f->rgba8);
+    free(f->depth8);
+    free(f->png);
+    free(f->depth_png);
+    memset(f, 0, sizeof(*f));
+}
+
+static int render_depth8(const ndt_render_params *p, depth_out *d)
+{
+    ndt_depth_frame *f = d->frame;
+    const size_t bytes = (size_t)p->width * (size_t)p->height * 4;
+    int rc;
+    if (d->want_png) {
+        const int64_t cap = ndt_hip_png_bound(p->width, p->height);
+        ndt_png_stats ps[2];
+        if (cap < 0) {
+            fprintf(stderr, "ndt_render_image_depth8: no PNG of %d x %d\n", p->width, p->height);
+            return 0;
+        }
+        f->png = (unsigned char *)malloc((size_t)cap);
+        if (d->want_depth_png) f->depth_png = (unsigned char *)malloc((size_t)cap);
+        else f->depth8 = (unsigned char *)malloc(bytes);
+        if (!f->png || !(d->want_depth_png ? f->depth_png : f->depth8)) return 0;
+        rc = ndt_hip_render_png_depth(g_ctx[0], p, f->png, cap, f->depth_png, cap, f->depth8, ps, f->range, NULL);
+        if (rc != NDT_OK) return 0;
+        f->png_bytes = ps[0].png_bytes;
+        f->depth_png_bytes = ps[1].png_bytes;
+        g_png_ms = ps[0].encode_ms + ps[1].encode_ms;
+        printf("compressed PNG of %lld bytes on GPU %d in %d launches\n", (long long)ps[0].png_bytes, ndt_hip_device(g_ctx[0]), ps[0].launches);
+        if (d->want_depth_png)
+            printf("compressed depth PNG of %lld bytes on GPU %d in %d launches\n", (long long)ps[1].png_bytes, ndt_hip_device(g_ctx[0]), ps[1].launches);
+    } else {
+        f->rgba8 = (unsigned char *)malloc(bytes);
+        f->depth8 = (unsigned char *)malloc(bytes);
+        if (!f->rgba8 || !f->depth8) return 0;
+        rc = ndt_hip_render_rgba8_depth(g_ctx[0], p, f->rgba8, f->depth8, f->range, NULL);
+        if (rc != NDT_OK) return 0;
+    }
+    g_depth_ms = ndt_hip_depth_ms(g_ctx[0]);
+    printf("finished depth map [%.17g, %.17g] on GPU %d in %d launches\n", f->range[0], f->range[1], ndt_hip_device(g_ctx[0]),
+           ndt_hip_depth_launches(g_ctx[0]));
+    return 1;
+}
+
 static int render_any(scene *scn, int width, int height, int samples, int aa_diff, int aa_depth, int stereo, int specular,
                       int max_optic_depth, int format, void *out, double *depth, int threads)
 {
@@ -226,6 +279,8 @@ static int render_any(scene *scn, int width, int height, int samples, int aa_dif
                 *po->png = buf;
                 *po->bytes = ps.png_bytes;
             } else free(buf);
+        } else if (format == NDT_HOST_IMAGE_DEPTH8) {
+            ok = render_depth8(&p, (depth_out *)out);
         } else if (depth)      /* the depth map comes from the one-context call (a map is not split over devices) */
             ok = format == NDT_IMAGE_F64 && ndt_hip_render_depth(g_ctx[0], &p, (double *)out, depth, NULL) == NDT_OK;
         else
@@ -255,7 +310,11 @@ static int render_any(scene *scn, int width, int height, int samples, int aa_dif
                      NDT_MS(ts0, ts1) - fit.gather_ms - fit.fit_ms - kds.build_ms);
         else
             snprintf(share, sizeof(share), "host fits %.2f, %s, rest %.2f", fit.fit_ms, tree, NDT_MS(ts0, ts1) - fit.fit_ms - kds.build_ms);
-        if (format == NDT_HOST_IMAGE_PNG && ok)
+        if (format == NDT_HOST_IMAGE_DEPTH8 && ok)
+            fprintf(stderr, "ndt_render_image: bounds + kd-tree + flatten %.2f ms (%s), upload %.2f ms, render + 8-bit image and depth map to host %.2f ms (depth map finished on the GPU %.2f%s)\n",
+                    NDT_MS(ts0, ts1), share, NDT_MS(ts1, ts2), NDT_MS(ts2, ts3), g_depth_ms,
+                    ((depth_out *)out)->want_png ? ", image files made there" : "");
+        else if (format == NDT_HOST_IMAGE_PNG && ok)
             fprintf(stderr, "ndt_render_image: bounds + kd-tree + flatten %.2f ms (%s), upload %.2f ms, render + image file to host %.2f ms (image file on the GPU %.2f)\n",
                     NDT_MS(ts0, ts1), share, NDT_MS(ts1, ts2), NDT_MS(ts2, ts3), g_png_ms);
         else
@@ -279,6 +338,19 @@ int ndt_render_image_rgba8(scene *scn, int width, int height, int samples, int t
                            int specular, int max_optic_depth, unsigned char *rgba8)
 {
     return render_any(scn, width, height, samples, aa_diff, aa_depth, stereo, specular, max_optic_depth, NDT_IMAGE_RGBA8, rgba8, NULL, threads);
+}
+
+int ndt_render_image_depth8(scene *scn, int width, int height, int samples, int threads, int aa_diff, int aa_depth, int stereo,
+                            int specular, int max_optic_depth, int want_png, int want_depth_png, ndt_depth_frame *out)
+{
+    depth_out d = { out, want_png != 0, want_png && want_depth_png };
+    memset(out, 0, sizeof(*out));
+    g_depth_ms = 0.0;
+    if (!render_any(scn, width, height, samples, aa_diff, aa_depth, stereo, specular, max_optic_depth, NDT_HOST_IMAGE_DEPTH8, &d, NULL, threads)) {
+        ndt_depth_frame_free(out);
+        return 0;
+    }
+    return 1;
 }
 
 int ndt_render_image_png(scene *scn, int width, int height, int samples, int threads, int aa_diff, int aa_depth, int stereo,
