@@ -347,6 +347,46 @@ int ndt_hip_encode_png(ndt_hip_ctx *ctx, const uint8_t *rgba8, int32_t width, in
 int ndt_hip_render_png(ndt_hip_ctx *ctx, const ndt_render_params *p, uint8_t *png, int64_t cap, ndt_png_stats *stats,
                        ndt_render_stats *render_stats);
 
+/* The frame's image file as a JPEG made on the device: a complete baseline JFIF file (SOF0, 8 bit, Y Cb Cr) of the quantised
+ * image, alpha ignored -- what the reference's libjpeg writer saves (image.c:346-412), in libjpeg's integer arithmetic: its
+ * colour transform, its 4:2:0 averaging, its slow integer DCT, its quantiser, the Annex K tables scaled by `quality` the way
+ * jpeg_set_quality does, the Annex K.3 Huffman tables.  Segments: SOI, APP0 (JFIF 1.01), DQT 0, DQT 1, SOF0, DHT x 4, DRI, SOS,
+ * the scan, EOI.  One restart interval per MCU row (16 x 16 pixels under 4:2:0, 8 x 8 under 4:4:4): every interval is coded on
+ * its own, RSTm between them.  Edges as libjpeg pads them.  The same image and parameters give the same
+ * bytes -- the bytes libjpeg writes for them with restart_in_rows = 1.
+ *   ndt_hip_jpeg_bound          host arithmetic: the largest file the encoder can produce; < 0 (NDT_E_INVALID) for a size or
+ *                               parameters it does not take
+ *   ndt_hip_encode_jpeg_device  d_rgba8: width * rows * 4 bytes in the context's device memory
+ *   ndt_hip_encode_jpeg         rgba8: the same in host memory (uploaded first)
+ *   ndt_hip_render_jpeg         ndt_hip_render_rgba8 with the encoder in place of the download: every mode of it (-a, -n, stereo,
+ *                               row shards: the file's height is the shard's row count)
+ * jp == NULL: the defaults (quality 95, 4:2:0).  `jpg` (host) receives the file, `cap` is its room.  NDT_E_INVALID, before
+ * any device call: a NULL pointer, width < 1 or rows < 1, a dimension above 65535 (SOF0's limit), a quality outside 0 .. 100,
+ * a sampling outside 0 .. 1, a reserved word that is not 0.  NDT_E_NOMEM: `cap` is smaller than the file -- the error text and
+ * stats->jpeg_bytes carry the size needed and nothing is written to `jpg`.  The two encode calls need no scene.  Device buffers
+ * belong to the context, only grow and are reused.  The calls return when the file is complete; none falls back.
+ * stats (may be NULL): scan_bytes = what lies between SOS and EOI (stuffing and RSTm included), stuffed_bytes = the 0x00 bytes
+ * put behind 0xFF, mcus / intervals = MCUs and restart intervals, launches = kernel launches, passes_max = the most passes an
+ * interval took through the entropy coder's LDS bit buffer, encode_ms = host time of the encoder (launch to the file in host
+ * memory; the render of ndt_hip_render_jpeg is not in it). */
+typedef struct ndt_jpeg_params {
+    int32_t quality;        /* 1 .. 100; 0 = 95 */
+    int32_t sampling;       /* 0 = 4:2:0, 1 = 4:4:4 */
+    int32_t reserved[2];    /* must be 0 */
+} ndt_jpeg_params;
+typedef struct ndt_jpeg_stats {
+    int64_t jpeg_bytes, scan_bytes, stuffed_bytes;
+    int32_t mcus, intervals, launches, passes_max;
+    double encode_ms;
+} ndt_jpeg_stats;
+int64_t ndt_hip_jpeg_bound(int32_t width, int32_t rows, const ndt_jpeg_params *jp);
+int ndt_hip_encode_jpeg_device(ndt_hip_ctx *ctx, const void *d_rgba8, int32_t width, int32_t rows, const ndt_jpeg_params *jp,
+                               uint8_t *jpg, int64_t cap, ndt_jpeg_stats *stats);
+int ndt_hip_encode_jpeg(ndt_hip_ctx *ctx, const uint8_t *rgba8, int32_t width, int32_t rows, const ndt_jpeg_params *jp, uint8_t *jpg,
+                        int64_t cap, ndt_jpeg_stats *stats);
+int ndt_hip_render_jpeg(ndt_hip_ctx *ctx, const ndt_render_params *p, const ndt_jpeg_params *jp, uint8_t *jpg, int64_t cap,
+                        ndt_jpeg_stats *stats, ndt_render_stats *render_stats);
+
 /* The depth map of `-z` finished on the device: what the reference does to the map before it saves it (ndt.c:1010-1016:
  * dbl_image_normalize, image.c:1025-1065, stretches it to 0 .. 1; the grey image v, v, v, 1 is then quantised with pixel_d2c
  * like every image).  With lo / hi the map's minimum / maximum, pixel i becomes the four bytes g, g, g, 255 with

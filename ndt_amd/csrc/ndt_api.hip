@@ -122,6 +122,7 @@ extern "C" int ndt_hip_destroy(ndt_hip_ctx *ctx)
     if (ctx->d_fit) (void)hipFree(ctx->d_fit);
     free_kd(ctx);
     free_png(ctx);
+    free_jpeg(ctx);
     free_depth(ctx);
     if (ctx->d_eyes) (void)hipFree(ctx->d_eyes);
     if (ctx->h_counters) (void)hipHostFree(ctx->h_counters);

@@ -12,6 +12,7 @@
 //   ndt_fit.hip      ndt_hip_fit_spheres: the bounding-sphere fits of a frame (batched Nelder-Mead), kernel and launcher
 //   ndt_kd.hip       ndt_hip_build_kdtree: the kd-tree of a frame's item boxes, level by level; kernels, launcher and C ABI
 //   ndt_png.hip      ndt_hip_encode_png* / ndt_hip_render_png: a frame's PNG file made on the device; kernels, launcher and C ABI
+//   ndt_jpeg.hip     ndt_hip_encode_jpeg* / ndt_hip_render_jpeg: a frame's JPEG file made on the device; kernels, launcher and C ABI
 //   ndt_depth.hip    ndt_hip_depth_rgba8_device / ndt_hip_render_*_depth: the depth map of `-z` normalised and quantised on the device
 #pragma once
 #include <hip/hip_runtime.h>
@@ -62,6 +63,13 @@ struct PngState {
          *d_file = nullptr, *d_info = nullptr;
     size_t rgba8_bytes = 0, filtered_bytes = 0, row_filter_bytes = 0, slots_bytes = 0, meta_bytes = 0, offsets_bytes = 0, file_bytes = 0,
            info_bytes = 0;
+    void *h_info = nullptr;         // pinned: the info record of the last file
+};
+
+// ndt_hip_encode_jpeg* (ndt_jpeg.hip): grow-only device buffers, reused by the next frame
+struct JpegState {
+    void *d_rgba8 = nullptr, *d_coef = nullptr, *d_slots = nullptr, *d_meta = nullptr, *d_offsets = nullptr, *d_file = nullptr, *d_info = nullptr;
+    size_t rgba8_bytes = 0, coef_bytes = 0, slots_bytes = 0, meta_bytes = 0, offsets_bytes = 0, file_bytes = 0, info_bytes = 0;
     void *h_info = nullptr;         // pinned: the info record of the last file
 };
 
@@ -159,6 +167,7 @@ struct ndt_hip_ctx {
     int fit_launches = 0;           // kernel launches of the last ndt_hip_fit_spheres call
     KdState kd;                     // ndt_hip_build_kdtree
     PngState png;                   // ndt_hip_encode_png*, ndt_hip_render_png
+    JpegState jpeg;                 // ndt_hip_encode_jpeg*, ndt_hip_render_jpeg
     DepthState depth;               // ndt_hip_depth_rgba8_device, ndt_hip_render_*_depth
     void *d_out = nullptr;          // staging for ndt_hip_render (host output)
     size_t d_out_bytes = 0;
@@ -245,6 +254,9 @@ void free_kd(ndt_hip_ctx *ctx);
 
 // ndt_png.hip
 void free_png(ndt_hip_ctx *ctx);
+
+// ndt_jpeg.hip
+void free_jpeg(ndt_hip_ctx *ctx);
 
 // ndt_depth.hip
 void free_depth(ndt_hip_ctx *ctx);

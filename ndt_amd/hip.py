@@ -25,6 +25,7 @@ API_SYMBOLS = [
     "ndt_hip_fit_spheres", "ndt_hip_fit_launches",
     "ndt_hip_build_kdtree", "ndt_hip_kdtree_fetch", "ndt_hip_kd_launches",
     "ndt_hip_png_bound", "ndt_hip_encode_png_device", "ndt_hip_encode_png", "ndt_hip_render_png",
+    "ndt_hip_jpeg_bound", "ndt_hip_encode_jpeg_device", "ndt_hip_encode_jpeg", "ndt_hip_render_jpeg",
     "ndt_hip_depth_rgba8_device", "ndt_hip_render_rgba8_depth", "ndt_hip_render_png_depth", "ndt_hip_depth_launches", "ndt_hip_depth_ms",
 ]
 
@@ -105,6 +106,12 @@ def load_library():
         lib.ndt_hip_encode_png_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p]
         lib.ndt_hip_encode_png.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p]
         lib.ndt_hip_render_png.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
+    if hasattr(lib, "ndt_hip_jpeg_bound"):
+        lib.ndt_hip_jpeg_bound.argtypes = [C.c_int32, C.c_int32, C.c_void_p]
+        lib.ndt_hip_jpeg_bound.restype = C.c_int64
+        lib.ndt_hip_encode_jpeg_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
+        lib.ndt_hip_encode_jpeg.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
+        lib.ndt_hip_render_jpeg.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
     if hasattr(lib, "ndt_hip_depth_rgba8_device"):
         lib.ndt_hip_depth_rgba8_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
         lib.ndt_hip_render_rgba8_depth.argtypes = [C.c_void_p] * 6
@@ -127,6 +134,38 @@ class PngStats(C.Structure):
     """ndt_png_stats: what the device encoder says about the file it made"""
     _fields_ = [("png_bytes", C.c_int64), ("idat_bytes", C.c_int64), ("chunks", C.c_int32), ("chunks_stored", C.c_int32),
                 ("launches", C.c_int32), ("rows_filter", C.c_int32 * 3), ("encode_ms", C.c_double)]
+
+
+class JpegParams(C.Structure):
+    """ndt_jpeg_params: quality 1 .. 100 (0 = 95), sampling 0 = 4:2:0 / 1 = 4:4:4"""
+    _fields_ = [("quality", C.c_int32), ("sampling", C.c_int32), ("reserved", C.c_int32 * 2)]
+
+
+class JpegStats(C.Structure):
+    """ndt_jpeg_stats: what the device encoder says about the file it made"""
+    _fields_ = [("jpeg_bytes", C.c_int64), ("scan_bytes", C.c_int64), ("stuffed_bytes", C.c_int64), ("mcus", C.c_int32),
+                ("intervals", C.c_int32), ("launches", C.c_int32), ("passes_max", C.c_int32), ("encode_ms", C.c_double)]
+
+
+JPEG_SAMPLING = {"420": 0, "444": 1}
+
+
+def jpeg_params(quality=95, sampling="420"):
+    """The ndt_jpeg_params of a quality 1 .. 100 and a sampling "420" or "444"; ValueError for anything else."""
+    if int(quality) != quality or not 1 <= quality <= 100:
+        raise ValueError("JPEG quality %r is outside 1 .. 100" % (quality,))
+    if str(sampling) not in JPEG_SAMPLING:
+        raise ValueError("JPEG sampling %r is neither '420' nor '444'" % (sampling,))
+    return JpegParams(int(quality), JPEG_SAMPLING[str(sampling)])
+
+
+def jpeg_bound(width, rows, quality=95, sampling="420"):
+    """ndt_hip_jpeg_bound: the largest file the device encoder can produce for a width x rows image (host arithmetic)."""
+    jp = jpeg_params(quality, sampling)
+    n = int(load_library().ndt_hip_jpeg_bound(int(width), int(rows), C.byref(jp)))
+    if n < 0:
+        raise ValueError("no JPEG of %d x %d: a side is empty or above 65535" % (width, rows))
+    return n
 
 
 def png_bound(width, rows):
@@ -388,6 +427,45 @@ class NdtHip:
         self.png_stats = PngStats()
         self._check(self.lib.ndt_hip_render_png(self.ctx, C.byref(p), out.ctypes.data, cap, C.byref(self.png_stats), C.byref(st)))
         return out[:self.png_stats.png_bytes].tobytes(), st
+
+    def encode_jpeg(self, rgba8, quality=95, sampling="420", cap=None):
+        """ndt_hip_encode_jpeg: the complete baseline JFIF file of a (rows, width, 4) uint8 host image (alpha ignored), made on
+        this context's GPU.  Returns the file's bytes; self.jpeg_stats keeps the ndt_jpeg_stats.  cap: room offered (default:
+        ndt_hip_jpeg_bound)."""
+        rgba8 = np.ascontiguousarray(rgba8, dtype=np.uint8)
+        if rgba8.ndim != 3 or rgba8.shape[2] != 4:
+            raise ValueError("rgba8 must be (rows, width, 4)")
+        rows, width = rgba8.shape[:2]
+        jp = jpeg_params(quality, sampling)
+        cap = jpeg_bound(width, rows, quality, sampling) if cap is None else int(cap)
+        out = np.zeros(max(cap, 1), dtype=np.uint8)
+        self.jpeg_stats = JpegStats()
+        self._check(self.lib.ndt_hip_encode_jpeg(self.ctx, rgba8.ctypes.data, width, rows, C.byref(jp), out.ctypes.data, cap,
+                                                 C.byref(self.jpeg_stats)))
+        return out[:self.jpeg_stats.jpeg_bytes].tobytes()
+
+    def encode_jpeg_device(self, d_rgba8_ptr, width, rows, quality=95, sampling="420", cap=None):
+        """ndt_hip_encode_jpeg_device: the same for width * rows * 4 bytes at raw device pointer `d_rgba8_ptr`."""
+        jp = jpeg_params(quality, sampling)
+        cap = jpeg_bound(width, rows, quality, sampling) if cap is None else int(cap)
+        out = np.zeros(max(cap, 1), dtype=np.uint8)
+        self.jpeg_stats = JpegStats()
+        self._check(self.lib.ndt_hip_encode_jpeg_device(self.ctx, C.c_void_p(d_rgba8_ptr), int(width), int(rows), C.byref(jp),
+                                                        out.ctypes.data, cap, C.byref(self.jpeg_stats)))
+        return out[:self.jpeg_stats.jpeg_bytes].tobytes()
+
+    def render_jpeg(self, width, height, depth, quality=95, sampling="420", **kw):
+        """ndt_hip_render_jpeg: render_rgba8 with the device's JPEG encoder in place of the download.  Returns (the file's bytes,
+        RenderStats); self.jpeg_stats keeps the ndt_jpeg_stats.  The file's height is the row shard's."""
+        p = self.params(width, height, depth, **kw)
+        rows = shard_rows(height, p.row_begin, p.row_step)
+        jp = jpeg_params(quality, sampling)
+        cap = jpeg_bound(width, rows, quality, sampling)
+        out = np.zeros(cap, dtype=np.uint8)
+        st = RenderStats()
+        self.jpeg_stats = JpegStats()
+        self._check(self.lib.ndt_hip_render_jpeg(self.ctx, C.byref(p), C.byref(jp), out.ctypes.data, cap, C.byref(self.jpeg_stats), C.byref(st)))
+        return out[:self.jpeg_stats.jpeg_bytes].tobytes(), st
 
     def depth_rgba8_device(self, d_depth_ptr, n_pixels, d_rgba8_ptr):
         """ndt_hip_depth_rgba8_device: the map of n_pixels doubles at raw device pointer `d_depth_ptr` stretched to 0 .. 1 and

@@ -420,6 +420,18 @@ int ndt_encode_image_png(const unsigned char *rgba8, int width, int height, unsi
 /* host milliseconds the device encoder took in the calling thread's last ndt_render_image_png / ndt_encode_image_png */
 double ndt_render_png_encode_ms(void);
 
+/* The same frame as a complete baseline JPEG file made on the GPU (ndt_hip_render_jpeg: the 8-bit image never leaves the device;
+ * `ndt_hip --jpeg`): what the reference's libjpeg writer saves, at `quality` 1 .. 100 (0 = its 95) and `sampling` 0 = 4:2:0 (its
+ * default) or 1 = 4:4:4.  *jpg is malloc'ed -- the caller frees it -- and *jpg_bytes its length.  A frame spread over several
+ * contexts (ndt_render_use_devices) is gathered on the host and encoded from there on the first context.  Prints
+ * `encoded JPEG of B bytes on GPU D in L launches`.  No fallback: without a device it fails like every render call. */
+int ndt_render_image_jpeg(scene *scn, int width, int height, int samples, int threads, int aa_diff, int aa_depth, int stereo,
+                          int specular, int max_optic_depth, int quality, int sampling, unsigned char **jpg, long long *jpg_bytes);
+/* ... of an 8-bit image that is in host memory already (ndt_hip_encode_jpeg on the calling thread's first context) */
+int ndt_encode_image_jpeg(const unsigned char *rgba8, int width, int height, int quality, int sampling, unsigned char **jpg, long long *jpg_bytes);
+/* host milliseconds the device encoder took in the calling thread's last ndt_render_image_jpeg / ndt_encode_image_jpeg */
+double ndt_render_jpeg_encode_ms(void);
+
 /* The same frame with the depth map of `-z` beside it, both finished on the GPU (`ndt_hip -z --depth gpu`): the map is
  * stretched to 0 .. 1 and quantised there (ndt_hip_render_rgba8_depth / ndt_hip_render_png_depth) instead of coming back in
  * doubles with the image.  What arrives is what the driver writes its two files from:

@@ -3,7 +3,9 @@
  * program exactly like the reference does (dlopen + dlsym scene_setup / scene_frames /
  * scene_cleanup, ndt.c:1654-1664), renders each frame with ndt_render_image and writes
  * images/<scene>/<N>d/<WxH>/<scene>_<WxH>_<frame>.ppm (binary PPM of the pixel_d2c bytes), or with `--png` the 8-bit RGBA
- * PNG the reference writes by default (stored blocks from the host, or compressed by the GPU; JPEG is not written).  `-z` adds the
+ * PNG the reference writes by default (stored blocks from the host, or compressed by the GPU), or with `--jpeg` the baseline JPEG
+ * its libjpeg build writes (made by the GPU: ndt_hip_render_jpeg; quality 95 and 4:2:0 like the reference's, or
+ * `--jpeg-quality Q`, `--jpeg-sampling 420|444`).  `-z` adds the
  * normalised depth map, depth/<scene>_<WxH>_<frame>.ppm.  `--dump-scene F` writes the flattened
  * scene of the last frame as an ndtscene file instead of rendering.  `--fit gpu` fits the frames'
  * bounding spheres on the GPU (ndt_hip_fit_spheres) instead of on the host's `-t` threads; `--kd gpu` builds their kd-trees
@@ -62,6 +64,7 @@ static unsigned char *quantise(const double *rgba, long n_values)
 /* ---- one frame: flatten, upload, render, save (what follows scene_setup in the reference's frame loop) */
 static struct {
     int dims, width, height, depth, threads, aa_diff, aa_depth, stereo, specular, want_depth, samples, png, gpus, deflate_gpu, depth_gpu, depth_png;
+    int jpeg, jpeg_quality, jpeg_sampling;      /* --jpeg: the frame's file is a JPEG made on the GPU; quality 1 .. 100, sampling 0 = 4:2:0 / 1 = 4:4:4 */
     const char *raw_path;
 } job_opts;
 
@@ -76,7 +79,7 @@ static int render_frame(scene *scn, int i)
     double *depth_map = job_opts.want_depth && !job_opts.depth_gpu ? (double *)malloc((size_t)width * height * sizeof(double)) : NULL;
     ndt_depth_frame df;                             /* --depth gpu: the 8-bit images or files that arrive */
     memset(&df, 0, sizeof(df));
-    unsigned char *rgba8 = NULL, *png = NULL;      /* png: the finished file of --png --deflate gpu */
+    unsigned char *rgba8 = NULL, *png = NULL;      /* png: the finished file of --png --deflate gpu, or of --jpeg */
     long long png_bytes = 0;
     double t0 = now_s();
     int ok;
@@ -87,6 +90,11 @@ static int render_frame(scene *scn, int i)
         rgba8 = df.rgba8; df.rgba8 = NULL;
         png = df.png; df.png = NULL;
         png_bytes = df.png_bytes;
+    } else if (job_opts.jpeg && !want_f64) {
+        /* the 8-bit image stays on the device: what comes back is the file */
+        ok = ndt_render_image_jpeg(scn, width, height, job_opts.samples, job_opts.threads, job_opts.aa_diff, job_opts.aa_depth,
+                                   job_opts.stereo, job_opts.specular, job_opts.depth, job_opts.jpeg_quality, job_opts.jpeg_sampling,
+                                   &png, &png_bytes);
     } else if (job_opts.deflate_gpu && !want_f64) {
         /* the 8-bit image stays on the device: what comes back is the file */
         ok = ndt_render_image_png(scn, width, height, job_opts.samples, job_opts.threads, job_opts.aa_diff, job_opts.aa_depth,
@@ -108,23 +116,28 @@ static int render_frame(scene *scn, int i)
     }
     printf("rendering took %.3fs\n", now_s() - t0);
     const double t_file = now_s();
-    double encode_ms = png ? ndt_render_png_encode_ms() : 0.0;
-    if (job_opts.deflate_gpu && !png) {
+    double encode_ms = png ? (job_opts.jpeg ? ndt_render_jpeg_encode_ms() : ndt_render_png_encode_ms()) : 0.0;
+    if ((job_opts.deflate_gpu || job_opts.jpeg) && !png) {
         /* the image was made on the host (--raw, -z): encoded from there */
-        if (!ndt_encode_image_png(rgba8, width, height, &png, &png_bytes)) {
+        if (!(job_opts.jpeg ? ndt_encode_image_jpeg(rgba8, width, height, job_opts.jpeg_quality, job_opts.jpeg_sampling, &png, &png_bytes)
+                            : ndt_encode_image_png(rgba8, width, height, &png, &png_bytes))) {
             free(rgba);
             free(rgba8);
             free(depth_map);
             return 0;
         }
-        encode_ms = ndt_render_png_encode_ms();
+        encode_ms = job_opts.jpeg ? ndt_render_jpeg_encode_ms() : ndt_render_png_encode_ms();
     }
     char dir[512], path[1024];
     mkdir("images", 0700);
     snprintf(dir, sizeof(dir), "images/%s", scn->name); mkdir(dir, 0700);
     snprintf(dir, sizeof(dir), "images/%s/%id", scn->name, job_opts.dims); mkdir(dir, 0700);
     snprintf(dir, sizeof(dir), "images/%s/%id/%ix%i", scn->name, job_opts.dims, width, height); mkdir(dir, 0700);
-    if (job_opts.png) {
+    if (job_opts.jpeg) {
+        snprintf(path, sizeof(path), "%s/%s_%ix%i_%04i.jpg", dir, scn->name, width, height, i);
+        FILE *f = fopen(path, "wb");
+        if (f) { fwrite(png, 1, (size_t)png_bytes, f); fclose(f); }
+    } else if (job_opts.png) {
         snprintf(path, sizeof(path), "%s/%s_%ix%i_%04i.png", dir, scn->name, width, height, i);
         if (png) {
             FILE *f = fopen(path, "wb");
@@ -138,8 +151,8 @@ static int render_frame(scene *scn, int i)
     if (getenv("NDT_HOST_TIMING")) {
         /* with --deflate gpu and the image on the device, the encoder's share is inside "rendering took" */
         const double ms = (now_s() - t_file) * 1e3;
-        if (png) fprintf(stderr, "ndt_hip: image file %.2f ms (compressed on the GPU %.2f, written %.2f)\n",
-                         want_f64 ? ms : ms + encode_ms, encode_ms, want_f64 ? ms - encode_ms : ms);
+        if (png) fprintf(stderr, "ndt_hip: image file %.2f ms (%s on the GPU %.2f, written %.2f)\n",
+                         want_f64 ? ms : ms + encode_ms, job_opts.jpeg ? "JPEG made" : "compressed", encode_ms, want_f64 ? ms - encode_ms : ms);
         else fprintf(stderr, "ndt_hip: image file %.2f ms (%s, made and written by the host)\n", ms, job_opts.png ? "stored PNG" : "PPM");
     }
     if (job_opts.depth_gpu) {
@@ -362,12 +375,17 @@ int main(int argc, char **argv)
     int depth_gpu = 0;      /* --depth host|gpu: who normalises and quantises the depth map of -z: the host, from doubles (default), or the GPU */
     int depth_png = 0;      /* --depth-png: the map as a PNG compressed on the GPU instead of a PPM (needs --depth gpu --png --deflate gpu) */
     int deflate_gpu = 0;    /* --deflate stored|gpu: who makes the --png file: the host, in stored blocks (default), or the GPU, compressed */
+    int jpeg = 0;           /* --jpeg: the frame's file is the baseline JPEG the reference's libjpeg build writes (image.c:346-412), made on the GPU */
+    int jpeg_quality = 0;   /* --jpeg-quality 1 .. 100 (default: the reference's 95) */
+    int jpeg_sampling = -1; /* --jpeg-sampling 420|444 (default: 4:2:0, libjpeg's) */
     char *objects_dir = "objects";      /* -o: where object plugins are looked for (object.c:119; ndt.c passes "objects") */
     static struct option longopts[] = { { "dump-scene", required_argument, NULL, 1000 },
                                         { "raw", required_argument, NULL, 1001 }, { "png", no_argument, NULL, 1002 },
                                         { "fit", required_argument, NULL, 1003 }, { "kd", required_argument, NULL, 1004 },
                                         { "deflate", required_argument, NULL, 1005 },
                                         { "depth", required_argument, NULL, 1006 }, { "depth-png", no_argument, NULL, 1007 },
+                                        { "jpeg", no_argument, NULL, 1008 }, { "jpeg-quality", required_argument, NULL, 1009 },
+                                        { "jpeg-sampling", required_argument, NULL, 1010 },
                                         { NULL, 0, NULL, 0 } };
     int ch;
     while ((ch = getopt_long(argc, argv, "a:d:g:r:f:j:l:m:3:n:ps:t:u:o:zh", longopts, NULL)) != -1) {
@@ -438,9 +456,25 @@ int main(int argc, char **argv)
             else { fprintf(stderr, "%s: --depth takes host or gpu, not '%s'\n", argv[0], optarg); return 1; }
             break;
         case 1007: depth_png = 1; break;
+        case 1008: jpeg = 1; break;
+        case 1009: {
+            char *end = NULL;
+            const long q = strtol(optarg, &end, 10);
+            if (end == optarg || *end || q < 1 || q > 100) {
+                fprintf(stderr, "%s: --jpeg-quality takes 1 .. 100, not '%s'\n", argv[0], optarg);
+                return 1;
+            }
+            jpeg_quality = (int)q;
+            break;
+        }
+        case 1010:
+            if (!strcmp(optarg, "420")) jpeg_sampling = 0;
+            else if (!strcmp(optarg, "444")) jpeg_sampling = 1;
+            else { fprintf(stderr, "%s: --jpeg-sampling takes 420 or 444, not '%s'\n", argv[0], optarg); return 1; }
+            break;
         default:
             fprintf(stderr, "usage: %s -s scene.so|builtin:yaml [-d dims] [-r WxH|1080p|4k] [-f last|first:last[:total]] [-l depth]\n"
-                            "          [-a diff,depth] [-n samples] [-m s|o|a|m] [-p] [-z] [-j frames_in_flight] [-g gpus_per_frame] [-u config] [--dump-scene file.ndtscene] [--raw file.f64] [--png [--deflate stored|gpu]] [--fit host|gpu] [--kd host|gpu] [--depth host|gpu [--depth-png]]\n", argv[0]);
+                            "          [-a diff,depth] [-n samples] [-m s|o|a|m] [-p] [-z] [-j frames_in_flight] [-g gpus_per_frame] [-u config] [--dump-scene file.ndtscene] [--raw file.f64] [--png [--deflate stored|gpu]] [--jpeg [--jpeg-quality 1..100] [--jpeg-sampling 420|444]] [--fit host|gpu] [--kd host|gpu] [--depth host|gpu [--depth-png]]\n", argv[0]);
             return ch == 'h' ? 0 : 1;
         }
     }
@@ -450,6 +484,26 @@ int main(int argc, char **argv)
     }
     if (deflate_gpu && !png) {
         fprintf(stderr, "%s: --deflate gpu compresses the PNG file: it needs --png\n", argv[0]);
+        return 1;
+    }
+    if (jpeg && png) {
+        fprintf(stderr, "%s: --jpeg and --png each name the frame's one image file: take one\n", argv[0]);
+        return 1;
+    }
+    if (jpeg && raw_path) {
+        fprintf(stderr, "%s: --jpeg has the GPU make the file from its 8-bit image and --raw brings doubles back: take one\n", argv[0]);
+        return 1;
+    }
+    if (jpeg_quality && !jpeg) {
+        fprintf(stderr, "%s: --jpeg-quality sets the JPEG file's quality: it needs --jpeg\n", argv[0]);
+        return 1;
+    }
+    if (jpeg_sampling >= 0 && !jpeg) {
+        fprintf(stderr, "%s: --jpeg-sampling sets the JPEG file's chroma sampling: it needs --jpeg\n", argv[0]);
+        return 1;
+    }
+    if (jpeg && depth_gpu) {
+        fprintf(stderr, "%s: --jpeg with --depth gpu: the device finishes the map beside a PNG or a PPM only; take --depth host with --jpeg\n", argv[0]);
         return 1;
     }
     if (depth_gpu && !want_depth) {
@@ -490,6 +544,7 @@ int main(int argc, char **argv)
     job_opts.deflate_gpu = deflate_gpu;
     job_opts.depth_gpu = depth_gpu;
     job_opts.depth_png = depth_png;
+    job_opts.jpeg = jpeg; job_opts.jpeg_quality = jpeg_quality; job_opts.jpeg_sampling = jpeg_sampling < 0 ? 0 : jpeg_sampling;
     ndt_render_fit_on_gpu(fit_gpu);
     ndt_render_kd_on_gpu(kd_gpu);
     if (job_opts.gpus > 1) {

@@ -171,6 +171,51 @@ int ndt_encode_image_png(const unsigned char *rgba8, int width, int height, unsi
     return 1;
 }
 
+/* ---- the frame's JPEG file made on the GPU (ndt_hip_render_jpeg / ndt_hip_encode_jpeg) */
+#define NDT_HOST_IMAGE_JPEG 102             /* render_any's `format`; `out` is a jpeg_out */
+typedef struct { unsigned char **jpg; long long *bytes; ndt_jpeg_params jp; } jpeg_out;
+static __thread double g_jpeg_ms = 0.0;
+
+double ndt_render_jpeg_encode_ms(void) { return g_jpeg_ms; }
+
+static void say_jpeg(const ndt_jpeg_stats *js)
+{
+    g_jpeg_ms = js->encode_ms;
+    printf("encoded JPEG of %lld bytes on GPU %d in %d launches\n", (long long)js->jpeg_bytes, ndt_hip_device(g_ctx[0]), js->launches);
+}
+
+static ndt_jpeg_params jpeg_params_of(int quality, int sampling)
+{
+    ndt_jpeg_params jp;
+    memset(&jp, 0, sizeof(jp));
+    jp.quality = quality;
+    jp.sampling = sampling;
+    return jp;
+}
+
+int ndt_encode_image_jpeg(const unsigned char *rgba8, int width, int height, int quality, int sampling, unsigned char **jpg, long long *jpg_bytes)
+{
+    const ndt_jpeg_params jp = jpeg_params_of(quality, sampling);
+    const int64_t cap = ndt_hip_jpeg_bound(width, height, &jp);
+    ndt_jpeg_stats js;
+    *jpg = NULL;
+    *jpg_bytes = 0;
+    if (cap < 0) {
+        fprintf(stderr, "ndt_encode_image_jpeg: no JPEG of %d x %d at quality %d, sampling %d\n", width, height, quality, sampling);
+        return 0;
+    }
+    unsigned char *buf = (unsigned char *)malloc((size_t)cap);
+    if (!buf || !have_contexts() || ndt_hip_encode_jpeg(g_ctx[0], rgba8, width, height, &jp, buf, cap, &js) != NDT_OK) {
+        fprintf(stderr, "ndt_encode_image_jpeg: %s\n", buf ? ndt_hip_last_error() : "out of memory");
+        free(buf);
+        return 0;
+    }
+    say_jpeg(&js);
+    *jpg = buf;
+    *jpg_bytes = js.jpeg_bytes;
+    return 1;
+}
+
 /* ---- the depth map of -z finished on the GPU (ndt_hip_render_rgba8_depth / ndt_hip_render_png_depth) */
 #define NDT_HOST_IMAGE_DEPTH8 101           /* render_any's `format`; `out` is a depth_out */
 typedef struct { ndt_depth_frame *frame; int want_png, want_depth_png; } depth_out;
@@ -279,6 +324,28 @@ static int render_any(scene *scn, int width, int height, int samples, int aa_dif
                 *po->png = buf;
                 *po->bytes = ps.png_bytes;
             } else free(buf);
+        } else if (format == NDT_HOST_IMAGE_JPEG) {
+            jpeg_out *jo = (jpeg_out *)out;
+            const int64_t cap = ndt_hip_jpeg_bound(width, height, &jo->jp);
+            ndt_jpeg_stats js;
+            unsigned char *buf = cap > 0 ? (unsigned char *)malloc((size_t)cap) : NULL;
+            if (!buf) {
+                fprintf(stderr, "ndt_render_image_jpeg: no JPEG of %d x %d at quality %d, sampling %d\n", width, height, jo->jp.quality, jo->jp.sampling);
+                ok = 0;
+            } else if (g_n_ctx == 1) {
+                ok = ndt_hip_render_jpeg(g_ctx[0], &p, &jo->jp, buf, cap, &js, NULL) == NDT_OK;
+            } else {
+                /* rows from several contexts: gathered into host memory, encoded from there on the first context */
+                unsigned char *rgba8 = (unsigned char *)malloc((size_t)width * height * 4);
+                ok = rgba8 && ndt_hip_render_multi(g_ctx, g_n_ctx, &p, NDT_IMAGE_RGBA8, rgba8, NULL) == NDT_OK &&
+                     ndt_hip_encode_jpeg(g_ctx[0], rgba8, width, height, &jo->jp, buf, cap, &js) == NDT_OK;
+                free(rgba8);
+            }
+            if (ok) {
+                say_jpeg(&js);
+                *jo->jpg = buf;
+                *jo->bytes = js.jpeg_bytes;
+            } else free(buf);
         } else if (format == NDT_HOST_IMAGE_DEPTH8) {
             ok = render_depth8(&p, (depth_out *)out);
         } else if (depth)      /* the depth map comes from the one-context call (a map is not split over devices) */
@@ -314,9 +381,9 @@ static int render_any(scene *scn, int width, int height, int samples, int aa_dif
             fprintf(stderr, "ndt_render_image: bounds + kd-tree + flatten %.2f ms (%s), upload %.2f ms, render + 8-bit image and depth map to host %.2f ms (depth map finished on the GPU %.2f%s)\n",
                     NDT_MS(ts0, ts1), share, NDT_MS(ts1, ts2), NDT_MS(ts2, ts3), g_depth_ms,
                     ((depth_out *)out)->want_png ? ", image files made there" : "");
-        else if (format == NDT_HOST_IMAGE_PNG && ok)
+        else if ((format == NDT_HOST_IMAGE_PNG || format == NDT_HOST_IMAGE_JPEG) && ok)
             fprintf(stderr, "ndt_render_image: bounds + kd-tree + flatten %.2f ms (%s), upload %.2f ms, render + image file to host %.2f ms (image file on the GPU %.2f)\n",
-                    NDT_MS(ts0, ts1), share, NDT_MS(ts1, ts2), NDT_MS(ts2, ts3), g_png_ms);
+                    NDT_MS(ts0, ts1), share, NDT_MS(ts1, ts2), NDT_MS(ts2, ts3), format == NDT_HOST_IMAGE_PNG ? g_png_ms : g_jpeg_ms);
         else
             fprintf(stderr, "ndt_render_image: bounds + kd-tree + flatten %.2f ms (%s), upload %.2f ms, render + image to host %.2f ms\n",
                     NDT_MS(ts0, ts1), share, NDT_MS(ts1, ts2), NDT_MS(ts2, ts3));
@@ -360,4 +427,13 @@ int ndt_render_image_png(scene *scn, int width, int height, int samples, int thr
     *png = NULL;
     *png_bytes = 0;
     return render_any(scn, width, height, samples, aa_diff, aa_depth, stereo, specular, max_optic_depth, NDT_HOST_IMAGE_PNG, &po, NULL, threads);
+}
+
+int ndt_render_image_jpeg(scene *scn, int width, int height, int samples, int threads, int aa_diff, int aa_depth, int stereo,
+                          int specular, int max_optic_depth, int quality, int sampling, unsigned char **jpg, long long *jpg_bytes)
+{
+    jpeg_out jo = { jpg, jpg_bytes, jpeg_params_of(quality, sampling) };
+    *jpg = NULL;
+    *jpg_bytes = 0;
+    return render_any(scn, width, height, samples, aa_diff, aa_depth, stereo, specular, max_optic_depth, NDT_HOST_IMAGE_JPEG, &jo, NULL, threads);
 }
