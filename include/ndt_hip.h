@@ -418,6 +418,49 @@ int ndt_hip_render_png_depth(ndt_hip_ctx *ctx, const ndt_render_params *p, uint8
 int ndt_hip_depth_launches(ndt_hip_ctx *ctx);
 double ndt_hip_depth_ms(ndt_hip_ctx *ctx);
 
+/* Regular K x K supersampling with a box filter in linear light, on the device (`ndt_hip --ssaa K`).  The ssaa frame of size
+ * W x H is the frame of size K W x K H of the same scene and camera averaged over K x K blocks in doubles: sub-sample (a, b) of
+ * output pixel (i, j) is pixel (K i + b, K j + a) of the large frame -- sub-sample (0, 0) is the plain frame's own sample -- and,
+ * per channel, alpha included,
+ *     out = (((s[0][0] + s[0][1]) + ... + s[0][K-1]) + s[1][0] + ... + s[K-1][K-1]) / (double)(K * K)
+ * summed strictly left to right, sub-row a outer, sub-column b inner.  The 8-bit image is pixel_d2c of that.  The depth map of
+ * an ssaa frame is the depth of sub-sample (0, 0): the plain W x H frame's map, not an average.  K = 1 is the plain frame.
+ * Sub-row a of the output rows of a shard (row_begin b, row_step S) is the cyclic shard row_begin K b + a, row_step K S of the
+ * large frame: a frame is K renders of ndt_hip_render_depth_device -- either pipeline; samples > 1 included, whose streams are
+ * functions of the pixel id -- each folded into the accumulator by one kernel launch.  Memory: a frame K times as wide, not
+ * K * K times as large; the buffers belong to the context, only grow and are reused.
+ *   ndt_hip_ssaa_fold_device     one fold step on device buffers: d_pass = rows x K width_out x 4 doubles (sub-row a of the
+ *                                rows), d_acc = rows x width_out x 4 doubles.  a = 0 writes d_acc, a > 0 adds to it, a = K - 1
+ *                                then divides by K * K and, with d_rgba8 not NULL, writes rows x width_out x 4 bytes there
+ *                                (earlier steps leave d_rgba8 alone).  d_pass and d_acc aligned to 16 bytes.  Synchronous.
+ *                                No scene has to be uploaded.
+ *   ndt_hip_render_ssaa_device   the whole frame into d_rgba (device, rows x width x 4 doubles, aligned to 16 bytes) and, when
+ *                                d_depth is not NULL, the map into d_depth (rows x width doubles).  stats sums the K passes;
+ *                                rays_ref_equiv is that of the K W x K H frame.
+ *   ndt_hip_render_ssaa          the same into host memory (depth may be NULL)
+ *   ndt_hip_render_ssaa_rgba8 / _png / _jpeg   the same frame as its bytes (written by the last fold), or through
+ *                                ndt_hip_encode_png_device / ndt_hip_encode_jpeg_device as a file
+ *   ndt_hip_render_ssaa_rgba8_depth   the bytes and the map finished by ndt_hip_depth_rgba8_device
+ *   ndt_hip_ssaa_launches / ndt_hip_ssaa_ms   fold launches of the context's last ssaa frame (K; 0 for K = 1), and their summed
+ *                                device time
+ * NDT_E_INVALID with the cause in the error text, before any device work and with nothing written: K outside 1 .. 8,
+ * recursive_aa set, NDT_STEREO_HIDEF (its 1080-line packing is not scalable), K * width or K * height beyond INT32_MAX, a NULL
+ * pointer, an odd width side by side or an odd height over/under (the halves would not line up with the large frame's).
+ * Everything else is accepted and refused as ndt_hip_render_depth_device does for the large frame.  There is no fallback. */
+int ndt_hip_ssaa_fold_device(ndt_hip_ctx *ctx, const void *d_pass, void *d_acc, int32_t width_out, int32_t rows, int32_t K, int32_t a,
+                             void *d_rgba8);
+int ndt_hip_render_ssaa_device(ndt_hip_ctx *ctx, const ndt_render_params *p, int32_t K, void *d_rgba, void *d_depth, ndt_render_stats *stats);
+int ndt_hip_render_ssaa(ndt_hip_ctx *ctx, const ndt_render_params *p, int32_t K, double *rgba, double *depth, ndt_render_stats *stats);
+int ndt_hip_render_ssaa_rgba8(ndt_hip_ctx *ctx, const ndt_render_params *p, int32_t K, uint8_t *rgba8, ndt_render_stats *stats);
+int ndt_hip_render_ssaa_png(ndt_hip_ctx *ctx, const ndt_render_params *p, int32_t K, uint8_t *png, int64_t cap, ndt_png_stats *stats,
+                            ndt_render_stats *render_stats);
+int ndt_hip_render_ssaa_jpeg(ndt_hip_ctx *ctx, const ndt_render_params *p, int32_t K, const ndt_jpeg_params *jp, uint8_t *jpg, int64_t cap,
+                             ndt_jpeg_stats *stats, ndt_render_stats *render_stats);
+int ndt_hip_render_ssaa_rgba8_depth(ndt_hip_ctx *ctx, const ndt_render_params *p, int32_t K, uint8_t *rgba8, uint8_t *depth8, double *range_out,
+                                    ndt_render_stats *stats);
+int ndt_hip_ssaa_launches(ndt_hip_ctx *ctx);
+double ndt_hip_ssaa_ms(ndt_hip_ctx *ctx);
+
 /* ONE frame over several contexts -- one per GPU of the node, or several on one GPU -- called from one host thread.
  * The rows `p` selects are dealt cyclically to the contexts exactly as the reference deals rows to MPI ranks in
  * MPI_MODE_ROW (ndt.c:812-820: row_start = rank, row_step = size): context k renders rows

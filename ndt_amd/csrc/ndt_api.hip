@@ -124,6 +124,7 @@ extern "C" int ndt_hip_destroy(ndt_hip_ctx *ctx)
     free_png(ctx);
     free_jpeg(ctx);
     free_depth(ctx);
+    free_ssaa(ctx);
     if (ctx->d_eyes) (void)hipFree(ctx->d_eyes);
     if (ctx->h_counters) (void)hipHostFree(ctx->h_counters);
     if (ctx->h_levels) (void)hipHostFree(ctx->h_levels);

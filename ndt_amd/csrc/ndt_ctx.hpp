@@ -14,6 +14,7 @@
 //   ndt_png.hip      ndt_hip_encode_png* / ndt_hip_render_png: a frame's PNG file made on the device; kernels, launcher and C ABI
 //   ndt_jpeg.hip     ndt_hip_encode_jpeg* / ndt_hip_render_jpeg: a frame's JPEG file made on the device; kernels, launcher and C ABI
 //   ndt_depth.hip    ndt_hip_depth_rgba8_device / ndt_hip_render_*_depth: the depth map of `-z` normalised and quantised on the device
+//   ndt_ssaa.hip     ndt_hip_ssaa_fold_device / ndt_hip_render_ssaa*: K x K supersampling, K ordinary renders folded on the device
 #pragma once
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
@@ -81,6 +82,18 @@ struct DepthState {
     void *h_result = nullptr;       // pinned: the folded record of the last map
     int launches = 0;               // kernel launches of the last map
     double finish_ms = 0.0;         // host time of the last map: launch to the folded record in host memory
+};
+
+// ndt_hip_render_ssaa* (ndt_ssaa.hip): grow-only device buffers, reused by the next frame
+struct SsaaState {
+    void *d_pass = nullptr;         // one pass of the large frame: rows x K width x 4 doubles, and its depth map behind them when wanted
+    void *d_acc = nullptr;          // the frame of the calls that deliver to host memory or as a file: rows x width x 4 doubles (+ the map)
+    void *d_rgba8 = nullptr, *d_depth8 = nullptr;       // its 8-bit image (written by the last fold) and finished map
+    size_t pass_bytes = 0, acc_bytes = 0, rgba8_bytes = 0, depth8_bytes = 0;
+    hipEvent_t ev[16] = {};         // around every fold launch of a frame
+    int launches = 0;               // fold launches of the last frame
+    int factor = 0;                 // its K
+    double fold_ms = 0.0;           // their summed device time
 };
 
 struct ndt_hip_ctx {
@@ -169,6 +182,7 @@ struct ndt_hip_ctx {
     PngState png;                   // ndt_hip_encode_png*, ndt_hip_render_png
     JpegState jpeg;                 // ndt_hip_encode_jpeg*, ndt_hip_render_jpeg
     DepthState depth;               // ndt_hip_depth_rgba8_device, ndt_hip_render_*_depth
+    SsaaState ssaa;                 // ndt_hip_render_ssaa*
     void *d_out = nullptr;          // staging for ndt_hip_render (host output)
     size_t d_out_bytes = 0;
     void *d_shard = nullptr;        // ndt_hip_render_multi: this context's rows before they are pushed into the frame
@@ -260,6 +274,9 @@ void free_jpeg(ndt_hip_ctx *ctx);
 
 // ndt_depth.hip
 void free_depth(ndt_hip_ctx *ctx);
+
+// ndt_ssaa.hip
+void free_ssaa(ndt_hip_ctx *ctx);
 
 // ndt_aa.hip / ndt_sampled.hip
 int render_antialiased(ndt_hip_ctx *ctx, const ndt_render_params *p, void *d_rgba, ndt_render_stats &total, void *d_depth = nullptr);

@@ -27,6 +27,8 @@ API_SYMBOLS = [
     "ndt_hip_png_bound", "ndt_hip_encode_png_device", "ndt_hip_encode_png", "ndt_hip_render_png",
     "ndt_hip_jpeg_bound", "ndt_hip_encode_jpeg_device", "ndt_hip_encode_jpeg", "ndt_hip_render_jpeg",
     "ndt_hip_depth_rgba8_device", "ndt_hip_render_rgba8_depth", "ndt_hip_render_png_depth", "ndt_hip_depth_launches", "ndt_hip_depth_ms",
+    "ndt_hip_ssaa_fold_device", "ndt_hip_render_ssaa_device", "ndt_hip_render_ssaa", "ndt_hip_render_ssaa_rgba8", "ndt_hip_render_ssaa_png",
+    "ndt_hip_render_ssaa_jpeg", "ndt_hip_render_ssaa_rgba8_depth", "ndt_hip_ssaa_launches", "ndt_hip_ssaa_ms",
 ]
 
 IMAGE_F64, IMAGE_RGBA8 = 0, 1      # enum ndt_image_format
@@ -120,6 +122,17 @@ def load_library():
         lib.ndt_hip_depth_launches.argtypes = [C.c_void_p]
         lib.ndt_hip_depth_ms.argtypes = [C.c_void_p]
         lib.ndt_hip_depth_ms.restype = C.c_double
+    if hasattr(lib, "ndt_hip_ssaa_fold_device"):    # (absent from earlier builds, which profiles/ab_libs.sh loads to compare)
+        lib.ndt_hip_ssaa_fold_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]
+        lib.ndt_hip_render_ssaa_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.ndt_hip_render_ssaa.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.ndt_hip_render_ssaa_rgba8.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
+        lib.ndt_hip_render_ssaa_png.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
+        lib.ndt_hip_render_ssaa_jpeg.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
+        lib.ndt_hip_render_ssaa_rgba8_depth.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.ndt_hip_ssaa_launches.argtypes = [C.c_void_p]
+        lib.ndt_hip_ssaa_ms.argtypes = [C.c_void_p]
+        lib.ndt_hip_ssaa_ms.restype = C.c_double
     _lib = lib
     return lib
 
@@ -347,10 +360,20 @@ class NdtHip:
         return p
 
     def render(self, width, height, depth, row_begin=0, row_step=1, specular=1, profile=0, aa=None, stereo=0,
-               depth_map=False, samples=1):
+               depth_map=False, samples=1, ssaa=None):
         """render_image for a row shard; returns ((rows, width, 4) float64 host array, RenderStats).
         aa = (aa_diff, aa_depth) switches recursive anti-aliasing on; stereo = ndt_stereo_mode;
-        depth_map=True returns (rgba, (rows, width) depth map, stats)."""
+        depth_map=True returns (rgba, (rows, width) depth map, stats); ssaa = K supersamples K x K on the device (render_ssaa:
+        the library refuses it beside aa)."""
+        if ssaa is not None:
+            p = self.params(width, height, depth, row_begin, row_step, specular, profile, aa, stereo, samples)
+            rows = shard_rows(height, row_begin, row_step)
+            out = np.zeros((rows, width, 4), dtype=np.float64)
+            dm = np.zeros((rows, width), dtype=np.float64) if depth_map else None
+            st = RenderStats()
+            self._check(self.lib.ndt_hip_render_ssaa(self.ctx, C.byref(p), int(ssaa), out.ctypes.data, dm.ctypes.data if depth_map else None,
+                                                     C.byref(st)))
+            return (out, dm, st) if depth_map else (out, st)
         p = self.params(width, height, depth, row_begin, row_step, specular, profile, aa, stereo, samples)
         if depth_map:
             rows = shard_rows(height, row_begin, row_step)
@@ -510,6 +533,91 @@ class NdtHip:
                                                       rng.ctypes.data, C.byref(st)))
         png = out[:self.png_stats[0].png_bytes].tobytes()
         return png, (dpng[:self.png_stats[1].png_bytes].tobytes() if depth_png else dm), rng, st
+
+    def ssaa_fold_device(self, d_pass_ptr, d_acc_ptr, width_out, rows, k, a, d_rgba8_ptr=None):
+        """ndt_hip_ssaa_fold_device: sub-row `a` of a k x k supersampled frame (rows x k * width_out x 4 doubles at raw device
+        pointer `d_pass_ptr`) folded into the rows x width_out x 4 doubles at `d_acc_ptr`; the last step (a = k - 1) divides by
+        k * k and, with `d_rgba8_ptr`, writes the 8-bit image there."""
+        self._check(self.lib.ndt_hip_ssaa_fold_device(self.ctx, C.c_void_p(d_pass_ptr), C.c_void_p(d_acc_ptr), int(width_out), int(rows),
+                                                      int(k), int(a), C.c_void_p(d_rgba8_ptr) if d_rgba8_ptr else None))
+
+    def ssaa_launches(self):
+        """ndt_hip_ssaa_launches: fold launches of the context's last supersampled frame."""
+        return int(self.lib.ndt_hip_ssaa_launches(self.ctx))
+
+    def ssaa_ms(self):
+        """ndt_hip_ssaa_ms: summed device time of those launches."""
+        return float(self.lib.ndt_hip_ssaa_ms(self.ctx))
+
+    def _ssaa_params(self, width, height, depth, kw):
+        for name in ("aa", "depth_map"):
+            if kw.get(name):
+                raise ValueError("ssaa is not combined with %s here" % name)
+        kw = {k: v for k, v in kw.items() if k not in ("aa", "depth_map")}
+        p = self.params(width, height, depth, **kw)
+        return p, shard_rows(height, p.row_begin, p.row_step)
+
+    def render_ssaa(self, width, height, depth, ssaa, depth_map=False, **kw):
+        """ndt_hip_render_ssaa: the width x height frame supersampled ssaa x ssaa on the device (a box filter in linear light over
+        the ssaa * width x ssaa * height frame).  Returns ((rows, width, 4) float64, RenderStats), with depth_map=True
+        (rgba, (rows, width) map of sub-sample (0, 0), stats)."""
+        p, rows = self._ssaa_params(width, height, depth, kw)
+        out = np.zeros((rows, width, 4), dtype=np.float64)
+        dm = np.zeros((rows, width), dtype=np.float64) if depth_map else None
+        st = RenderStats()
+        self._check(self.lib.ndt_hip_render_ssaa(self.ctx, C.byref(p), int(ssaa), out.ctypes.data, dm.ctypes.data if depth_map else None,
+                                                 C.byref(st)))
+        return (out, dm, st) if depth_map else (out, st)
+
+    def render_ssaa_device(self, d_rgba_ptr, width, height, depth, ssaa, d_depth_ptr=None, **kw):
+        """ndt_hip_render_ssaa_device: the same, left in HBM at raw device pointers (the image aligned to 16 bytes)."""
+        p, _ = self._ssaa_params(width, height, depth, kw)
+        st = RenderStats()
+        self._check(self.lib.ndt_hip_render_ssaa_device(self.ctx, C.byref(p), int(ssaa), C.c_void_p(d_rgba_ptr),
+                                                        C.c_void_p(d_depth_ptr) if d_depth_ptr else None, C.byref(st)))
+        return st
+
+    def render_ssaa_rgba8(self, width, height, depth, ssaa, **kw):
+        """ndt_hip_render_ssaa_rgba8: the supersampled frame as the bytes the reference stores: ((rows, width, 4) uint8, stats)."""
+        p, rows = self._ssaa_params(width, height, depth, kw)
+        out = np.zeros((rows, width, 4), dtype=np.uint8)
+        st = RenderStats()
+        self._check(self.lib.ndt_hip_render_ssaa_rgba8(self.ctx, C.byref(p), int(ssaa), out.ctypes.data, C.byref(st)))
+        return out, st
+
+    def render_ssaa_png(self, width, height, depth, ssaa, **kw):
+        """ndt_hip_render_ssaa_png: ... as a PNG file made on the device: (the file's bytes, stats); self.png_stats keeps the record."""
+        p, rows = self._ssaa_params(width, height, depth, kw)
+        cap = png_bound(width, rows)
+        out = np.zeros(cap, dtype=np.uint8)
+        st = RenderStats()
+        self.png_stats = PngStats()
+        self._check(self.lib.ndt_hip_render_ssaa_png(self.ctx, C.byref(p), int(ssaa), out.ctypes.data, cap, C.byref(self.png_stats), C.byref(st)))
+        return out[:self.png_stats.png_bytes].tobytes(), st
+
+    def render_ssaa_jpeg(self, width, height, depth, ssaa, quality=95, sampling="420", **kw):
+        """ndt_hip_render_ssaa_jpeg: ... as a JPEG file made on the device: (the file's bytes, stats); self.jpeg_stats keeps the record."""
+        p, rows = self._ssaa_params(width, height, depth, kw)
+        jp = jpeg_params(quality, sampling)
+        cap = jpeg_bound(width, rows, quality, sampling)
+        out = np.zeros(cap, dtype=np.uint8)
+        st = RenderStats()
+        self.jpeg_stats = JpegStats()
+        self._check(self.lib.ndt_hip_render_ssaa_jpeg(self.ctx, C.byref(p), int(ssaa), C.byref(jp), out.ctypes.data, cap,
+                                                      C.byref(self.jpeg_stats), C.byref(st)))
+        return out[:self.jpeg_stats.jpeg_bytes].tobytes(), st
+
+    def render_ssaa_rgba8_depth(self, width, height, depth, ssaa, **kw):
+        """ndt_hip_render_ssaa_rgba8_depth: the supersampled frame's bytes and its map (sub-sample (0, 0)'s) finished on the device:
+        ((rows, width, 4) uint8 image, (rows, width, 4) uint8 map, float64 [lo, hi], stats)."""
+        p, rows = self._ssaa_params(width, height, depth, kw)
+        out = np.zeros((rows, width, 4), dtype=np.uint8)
+        dm = np.zeros((rows, width, 4), dtype=np.uint8)
+        rng = np.zeros(2, dtype=np.float64)
+        st = RenderStats()
+        self._check(self.lib.ndt_hip_render_ssaa_rgba8_depth(self.ctx, C.byref(p), int(ssaa), out.ctypes.data, dm.ctypes.data, rng.ctypes.data,
+                                                            C.byref(st)))
+        return out, dm, rng, st
 
     def quantize_device(self, d_rgba_ptr, d_rgba8_ptr, n_pixels):
         self._check(self.lib.ndt_hip_quantize_device(self.ctx, C.c_void_p(d_rgba_ptr), C.c_void_p(d_rgba8_ptr),

@@ -453,6 +453,26 @@ void ndt_depth_frame_free(ndt_depth_frame *f);
 /* host milliseconds the GPU took to finish the map in the calling thread's last ndt_render_image_depth8 */
 double ndt_render_depth_finish_ms(void);
 
+/* The same frames supersampled ssaa x ssaa on the GPU (`ndt_hip --ssaa K`, K = 1 .. 8; ndt_hip_render_ssaa*): the frame of ssaa
+ * times the size, averaged over ssaa x ssaa blocks in doubles, in linear light, before anything is quantised; the map of
+ * _full and _depth8 is the plain frame's.  One variant per call above, without the -a arguments (supersampling is not combined
+ * with recursive anti-aliasing) and with `ssaa` before the outputs; ssaa = 1 is the plain call.  With ndt_render_use_devices
+ * every context renders and folds its own cyclic row shard, one context after the other; the rows meet on the host.  _depth8
+ * with files: the two 8-bit images come back and are encoded from host memory.  Each prints `supersampled KxK on GPU D in L
+ * launches`.  No fallback: the library's refusals (HIDEF frame packing, an odd width side by side, ...) end the call. */
+int ndt_render_image_ssaa_full(scene *scn, int width, int height, int samples, int threads, int stereo, int specular, int max_optic_depth,
+                               int ssaa, double *rgba, double *depth);
+int ndt_render_image_ssaa_rgba8(scene *scn, int width, int height, int samples, int threads, int stereo, int specular, int max_optic_depth,
+                                int ssaa, unsigned char *rgba8);
+int ndt_render_image_ssaa_png(scene *scn, int width, int height, int samples, int threads, int stereo, int specular, int max_optic_depth,
+                              int ssaa, unsigned char **png, long long *png_bytes);
+int ndt_render_image_ssaa_jpeg(scene *scn, int width, int height, int samples, int threads, int stereo, int specular, int max_optic_depth,
+                               int ssaa, int quality, int sampling, unsigned char **jpg, long long *jpg_bytes);
+int ndt_render_image_ssaa_depth8(scene *scn, int width, int height, int samples, int threads, int stereo, int specular, int max_optic_depth,
+                                 int ssaa, int want_png, int want_depth_png, ndt_depth_frame *out);
+/* summed device milliseconds of the fold launches of the calling thread's last supersampled frame */
+double ndt_render_ssaa_fold_ms(void);
+
 /* Which GPUs the calling thread's frames are rendered on (the settings are per thread, like the GPU contexts):
  *   ndt_render_use_device(d)     one context on device d -- `ndt_hip -j K` gives worker w device w mod device count,
  *                                the reference's MPI_MODE_FRAME (one frame per rank, ndt.c:1770-1830);

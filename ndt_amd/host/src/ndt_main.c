@@ -12,7 +12,10 @@
  * there (ndt_hip_build_kdtree) instead of on the host; `--png --deflate gpu` has the GPU make the frame's PNG file, compressed
  * (ndt_hip_render_png), instead of the host's stored-block writer; `-z --depth gpu` has the GPU normalise and quantise the depth
  * map (ndt_hip_render_rgba8_depth) instead of sending it and the image back in doubles, and `--depth-png` then writes the map as a
- * PNG compressed there as well.  None falls back: what the device path cannot do ends the run. */
+ * PNG compressed there as well.  `--ssaa K` (1 .. 8, default 1) supersamples every frame K x K on the GPU: K renders of the frame
+ * K times the size, folded there into a box-filtered average in linear light before anything is quantised (ndt_hip_render_ssaa*);
+ * with every output flag, -m s|o|a, -n, -g and -j, not with -a or -m h.  None falls back: what the device path cannot do ends
+ * the run. */
 #include <dlfcn.h>
 #include <getopt.h>
 #include <pthread.h>
@@ -65,6 +68,7 @@ static unsigned char *quantise(const double *rgba, long n_values)
 static struct {
     int dims, width, height, depth, threads, aa_diff, aa_depth, stereo, specular, want_depth, samples, png, gpus, deflate_gpu, depth_gpu, depth_png;
     int jpeg, jpeg_quality, jpeg_sampling;      /* --jpeg: the frame's file is a JPEG made on the GPU; quality 1 .. 100, sampling 0 = 4:2:0 / 1 = 4:4:4 */
+    int ssaa;                                   /* --ssaa K: every frame supersampled K x K on the GPU (1: the plain frame) */
     const char *raw_path;
 } job_opts;
 
@@ -83,7 +87,31 @@ static int render_frame(scene *scn, int i)
     long long png_bytes = 0;
     double t0 = now_s();
     int ok;
-    if (job_opts.depth_gpu) {
+    if (job_opts.ssaa > 1) {
+        /* the same five ways out, through the supersampled calls */
+        const int K = job_opts.ssaa;
+        if (job_opts.depth_gpu) {
+            ok = ndt_render_image_ssaa_depth8(scn, width, height, job_opts.samples, job_opts.threads, job_opts.stereo, job_opts.specular,
+                                              job_opts.depth, K, job_opts.deflate_gpu, job_opts.depth_png, &df);
+            rgba8 = df.rgba8; df.rgba8 = NULL;
+            png = df.png; df.png = NULL;
+            png_bytes = df.png_bytes;
+        } else if (job_opts.jpeg && !want_f64)
+            ok = ndt_render_image_ssaa_jpeg(scn, width, height, job_opts.samples, job_opts.threads, job_opts.stereo, job_opts.specular,
+                                            job_opts.depth, K, job_opts.jpeg_quality, job_opts.jpeg_sampling, &png, &png_bytes);
+        else if (job_opts.deflate_gpu && !want_f64)
+            ok = ndt_render_image_ssaa_png(scn, width, height, job_opts.samples, job_opts.threads, job_opts.stereo, job_opts.specular,
+                                           job_opts.depth, K, &png, &png_bytes);
+        else if (want_f64) {
+            ok = ndt_render_image_ssaa_full(scn, width, height, job_opts.samples, job_opts.threads, job_opts.stereo, job_opts.specular,
+                                            job_opts.depth, K, rgba, depth_map);
+            if (ok) rgba8 = quantise(rgba, (long)width * height * 4);
+        } else {
+            rgba8 = (unsigned char *)malloc((size_t)width * height * 4);
+            ok = ndt_render_image_ssaa_rgba8(scn, width, height, job_opts.samples, job_opts.threads, job_opts.stereo, job_opts.specular,
+                                             job_opts.depth, K, rgba8);
+        }
+    } else if (job_opts.depth_gpu) {
         ok = ndt_render_image_depth8(scn, width, height, job_opts.samples, job_opts.threads, job_opts.aa_diff, job_opts.aa_depth,
                                      job_opts.stereo, job_opts.specular, job_opts.depth, job_opts.deflate_gpu, job_opts.depth_png, &df);
         /* from here on the image is where the other paths leave it; the map stays in df */
@@ -378,6 +406,7 @@ int main(int argc, char **argv)
     int jpeg = 0;           /* --jpeg: the frame's file is the baseline JPEG the reference's libjpeg build writes (image.c:346-412), made on the GPU */
     int jpeg_quality = 0;   /* --jpeg-quality 1 .. 100 (default: the reference's 95) */
     int jpeg_sampling = -1; /* --jpeg-sampling 420|444 (default: 4:2:0, libjpeg's) */
+    int ssaa = 1;           /* --ssaa K: every frame supersampled K x K on the GPU, 1 .. 8 (default 1: the plain frame) */
     char *objects_dir = "objects";      /* -o: where object plugins are looked for (object.c:119; ndt.c passes "objects") */
     static struct option longopts[] = { { "dump-scene", required_argument, NULL, 1000 },
                                         { "raw", required_argument, NULL, 1001 }, { "png", no_argument, NULL, 1002 },
@@ -385,7 +414,7 @@ int main(int argc, char **argv)
                                         { "deflate", required_argument, NULL, 1005 },
                                         { "depth", required_argument, NULL, 1006 }, { "depth-png", no_argument, NULL, 1007 },
                                         { "jpeg", no_argument, NULL, 1008 }, { "jpeg-quality", required_argument, NULL, 1009 },
-                                        { "jpeg-sampling", required_argument, NULL, 1010 },
+                                        { "jpeg-sampling", required_argument, NULL, 1010 }, { "ssaa", required_argument, NULL, 1011 },
                                         { NULL, 0, NULL, 0 } };
     int ch;
     while ((ch = getopt_long(argc, argv, "a:d:g:r:f:j:l:m:3:n:ps:t:u:o:zh", longopts, NULL)) != -1) {
@@ -472,14 +501,32 @@ int main(int argc, char **argv)
             else if (!strcmp(optarg, "444")) jpeg_sampling = 1;
             else { fprintf(stderr, "%s: --jpeg-sampling takes 420 or 444, not '%s'\n", argv[0], optarg); return 1; }
             break;
+        case 1011: {
+            char *end = NULL;
+            const long k = strtol(optarg, &end, 10);
+            if (end == optarg || *end || k < 1 || k > 8) {
+                fprintf(stderr, "%s: --ssaa takes 1 .. 8, not '%s'\n", argv[0], optarg);
+                return 1;
+            }
+            ssaa = (int)k;
+            break;
+        }
         default:
             fprintf(stderr, "usage: %s -s scene.so|builtin:yaml [-d dims] [-r WxH|1080p|4k] [-f last|first:last[:total]] [-l depth]\n"
-                            "          [-a diff,depth] [-n samples] [-m s|o|a|m] [-p] [-z] [-j frames_in_flight] [-g gpus_per_frame] [-u config] [--dump-scene file.ndtscene] [--raw file.f64] [--png [--deflate stored|gpu]] [--jpeg [--jpeg-quality 1..100] [--jpeg-sampling 420|444]] [--fit host|gpu] [--kd host|gpu] [--depth host|gpu [--depth-png]]\n", argv[0]);
+                            "          [-a diff,depth] [-n samples] [-m s|o|a|m] [-p] [-z] [-j frames_in_flight] [-g gpus_per_frame] [-u config] [--dump-scene file.ndtscene] [--raw file.f64] [--png [--deflate stored|gpu]] [--jpeg [--jpeg-quality 1..100] [--jpeg-sampling 420|444]] [--fit host|gpu] [--kd host|gpu] [--depth host|gpu [--depth-png]] [--ssaa 1..8]\n", argv[0]);
             return ch == 'h' ? 0 : 1;
         }
     }
     if (!scene_path || dims < 3 || width < 1 || height < 1) {
         fprintf(stderr, "%s: need -s scene.so, dims >= 3 and a resolution\n", argv[0]);
+        return 1;
+    }
+    if (ssaa > 1 && aa_depth >= 0) {
+        fprintf(stderr, "%s: --ssaa with -a: a frame is supersampled or anti-aliased recursively, not both: take one\n", argv[0]);
+        return 1;
+    }
+    if (ssaa > 1 && stereo == 4) {
+        fprintf(stderr, "%s: --ssaa with -m h: the 1080-line frame packing is not scalable: take -m s, o or a\n", argv[0]);
         return 1;
     }
     if (deflate_gpu && !png) {
@@ -544,6 +591,7 @@ int main(int argc, char **argv)
     job_opts.deflate_gpu = deflate_gpu;
     job_opts.depth_gpu = depth_gpu;
     job_opts.depth_png = depth_png;
+    job_opts.ssaa = ssaa;
     job_opts.jpeg = jpeg; job_opts.jpeg_quality = jpeg_quality; job_opts.jpeg_sampling = jpeg_sampling < 0 ? 0 : jpeg_sampling;
     ndt_render_fit_on_gpu(fit_gpu);
     ndt_render_kd_on_gpu(kd_gpu);

@@ -269,8 +269,124 @@ static int render_depth8(const ndt_render_params *p, depth_out *d)
     return 1;
 }
 
+/* ---- the frame supersampled K x K on the GPU (ndt_hip_render_ssaa*; `ndt_hip --ssaa K`) */
+static __thread double g_ssaa_ms = 0.0;
+
+double ndt_render_ssaa_fold_ms(void) { return g_ssaa_ms; }
+
+/* the doubles (format NDT_IMAGE_F64) or the bytes (NDT_IMAGE_RGBA8) of the ssaa frame in host memory: from the one context, or
+ * from several, each of which renders and folds its own cyclic row shard, context after context */
+static int ssaa_image(const ndt_render_params *p, int K, int format, void *out, int *launches)
+{
+    const size_t px = format == NDT_IMAGE_F64 ? 4 * sizeof(double) : 4;
+    *launches = 0;
+    g_ssaa_ms = 0.0;
+    if (g_n_ctx == 1) {
+        const int rc = format == NDT_IMAGE_F64 ? ndt_hip_render_ssaa(g_ctx[0], p, K, (double *)out, NULL, NULL)
+                                               : ndt_hip_render_ssaa_rgba8(g_ctx[0], p, K, (unsigned char *)out, NULL);
+        *launches = ndt_hip_ssaa_launches(g_ctx[0]);
+        g_ssaa_ms = ndt_hip_ssaa_ms(g_ctx[0]);
+        return rc == NDT_OK;
+    }
+    const size_t row_bytes = (size_t)p->width * px;
+    unsigned char *part = (unsigned char *)malloc(row_bytes * (size_t)((p->height + g_n_ctx - 1) / g_n_ctx));
+    int ok = part != NULL;
+    for (int k = 0; ok && k < g_n_ctx; ++k) {
+        ndt_render_params q = *p;
+        q.row_begin = k;
+        q.row_step = g_n_ctx;
+        const int rows = ndt_hip_shard_rows(p->height, k, g_n_ctx);
+        if (rows < 1) continue;
+        ok = (format == NDT_IMAGE_F64 ? ndt_hip_render_ssaa(g_ctx[k], &q, K, (double *)part, NULL, NULL)
+                                      : ndt_hip_render_ssaa_rgba8(g_ctx[k], &q, K, part, NULL)) == NDT_OK;
+        for (int r = 0; ok && r < rows; ++r)
+            memcpy((unsigned char *)out + (size_t)(k + r * g_n_ctx) * row_bytes, part + (size_t)r * row_bytes, row_bytes);
+        *launches += ndt_hip_ssaa_launches(g_ctx[k]);
+        g_ssaa_ms += ndt_hip_ssaa_ms(g_ctx[k]);
+    }
+    free(part);
+    return ok;
+}
+
+/* every format of render_any for an ssaa frame */
+static int render_ssaa_any(const ndt_render_params *p, int K, int format, void *out, double *depth)
+{
+    const int width = p->width, height = p->height;
+    int ok = 0, launches = 0;
+    if (format == NDT_HOST_IMAGE_PNG || format == NDT_HOST_IMAGE_JPEG) {
+        const int png = format == NDT_HOST_IMAGE_PNG;
+        png_out *po = (png_out *)out;
+        jpeg_out *jo = (jpeg_out *)out;
+        const int64_t cap = png ? ndt_hip_png_bound(width, height) : ndt_hip_jpeg_bound(width, height, &jo->jp);
+        ndt_png_stats ps;
+        ndt_jpeg_stats js;
+        unsigned char *buf = cap > 0 ? (unsigned char *)malloc((size_t)cap) : NULL;
+        if (!buf) {
+            fprintf(stderr, "ndt_render_image_ssaa: no %s of %d x %d\n", png ? "PNG" : "JPEG", width, height);
+            return 0;
+        }
+        if (g_n_ctx == 1) {
+            ok = (png ? ndt_hip_render_ssaa_png(g_ctx[0], p, K, buf, cap, &ps, NULL)
+                      : ndt_hip_render_ssaa_jpeg(g_ctx[0], p, K, &jo->jp, buf, cap, &js, NULL)) == NDT_OK;
+            launches = ndt_hip_ssaa_launches(g_ctx[0]);
+            g_ssaa_ms = ndt_hip_ssaa_ms(g_ctx[0]);
+        } else {
+            /* rows from several contexts: gathered into host memory, encoded from there on the first context */
+            unsigned char *rgba8 = (unsigned char *)malloc((size_t)width * height * 4);
+            ok = rgba8 && ssaa_image(p, K, NDT_IMAGE_RGBA8, rgba8, &launches) &&
+                 (png ? ndt_hip_encode_png(g_ctx[0], rgba8, width, height, buf, cap, &ps)
+                      : ndt_hip_encode_jpeg(g_ctx[0], rgba8, width, height, &jo->jp, buf, cap, &js)) == NDT_OK;
+            free(rgba8);
+        }
+        if (!ok) free(buf);
+        else if (png) {
+            say_png(&ps);
+            *po->png = buf;
+            *po->bytes = ps.png_bytes;
+        } else {
+            say_jpeg(&js);
+            *jo->jpg = buf;
+            *jo->bytes = js.jpeg_bytes;
+        }
+    } else if (format == NDT_HOST_IMAGE_DEPTH8) {
+        /* (one context, like every frame with a map) the two 8-bit images come back; files are encoded from them */
+        depth_out *d = (depth_out *)out;
+        ndt_depth_frame *f = d->frame;
+        const size_t bytes = (size_t)width * (size_t)height * 4;
+        f->rgba8 = (unsigned char *)malloc(bytes);
+        f->depth8 = (unsigned char *)malloc(bytes);
+        ok = f->rgba8 && f->depth8 && ndt_hip_render_ssaa_rgba8_depth(g_ctx[0], p, K, f->rgba8, f->depth8, f->range, NULL) == NDT_OK;
+        launches = ndt_hip_ssaa_launches(g_ctx[0]);
+        g_ssaa_ms = ndt_hip_ssaa_ms(g_ctx[0]);
+        if (ok) {
+            g_depth_ms = ndt_hip_depth_ms(g_ctx[0]);
+            printf("finished depth map [%.17g, %.17g] on GPU %d in %d launches\n", f->range[0], f->range[1], ndt_hip_device(g_ctx[0]),
+                   ndt_hip_depth_launches(g_ctx[0]));
+        }
+        if (ok && d->want_png) {
+            ok = ndt_encode_image_png(f->rgba8, width, height, &f->png, &f->png_bytes);
+            free(f->rgba8);
+            f->rgba8 = NULL;
+            if (ok && d->want_depth_png) {
+                const double image_ms = g_png_ms;
+                ok = ndt_encode_image_png(f->depth8, width, height, &f->depth_png, &f->depth_png_bytes);
+                g_png_ms += image_ms;
+                free(f->depth8);
+                f->depth8 = NULL;
+            }
+        }
+    } else if (depth) {     /* the depth map comes from the one-context call (a map is not split over devices) */
+        ok = format == NDT_IMAGE_F64 && ndt_hip_render_ssaa(g_ctx[0], p, K, (double *)out, depth, NULL) == NDT_OK;
+        launches = ndt_hip_ssaa_launches(g_ctx[0]);
+        g_ssaa_ms = ndt_hip_ssaa_ms(g_ctx[0]);
+    } else
+        ok = ssaa_image(p, K, format, out, &launches);
+    if (ok) printf("supersampled %dx%d on GPU %d in %d launches\n", K, K, ndt_hip_device(g_ctx[0]), launches);
+    return ok;
+}
+
 static int render_any(scene *scn, int width, int height, int samples, int aa_diff, int aa_depth, int stereo, int specular,
-                      int max_optic_depth, int format, void *out, double *depth, int threads)
+                      int max_optic_depth, int format, void *out, double *depth, int threads, int ssaa)
 {
     char err[256];
     ndt_flat_builder fb;
@@ -302,7 +418,9 @@ static int render_any(scene *scn, int width, int height, int samples, int aa_dif
             p.aa_diff = aa_diff;
             p.aa_depth = aa_depth;
         }
-        if (format == NDT_HOST_IMAGE_PNG) {
+        if (ssaa != 1) {        /* (0, 9, ... reach the library, which says what is wrong with them) */
+            ok = render_ssaa_any(&p, ssaa, format, out, depth);
+        } else if (format == NDT_HOST_IMAGE_PNG) {
             png_out *po = (png_out *)out;
             const int64_t cap = ndt_hip_png_bound(width, height);
             ndt_png_stats ps;
@@ -387,6 +505,8 @@ static int render_any(scene *scn, int width, int height, int samples, int aa_dif
         else
             fprintf(stderr, "ndt_render_image: bounds + kd-tree + flatten %.2f ms (%s), upload %.2f ms, render + image to host %.2f ms\n",
                     NDT_MS(ts0, ts1), share, NDT_MS(ts1, ts2), NDT_MS(ts2, ts3));
+        if (ssaa != 1 && ok)
+            fprintf(stderr, "ndt_render_image: of the render, supersampling %dx%d: the folds on the GPU %.2f ms\n", ssaa, ssaa, g_ssaa_ms);
     }
     ndt_flat_builder_free(&fb);
     return ok;
@@ -398,13 +518,13 @@ int ndt_render_image_full(scene *scn, int width, int height, int samples, int th
                           int specular, int max_optic_depth, double *rgba, double *depth)
 {
     /* (the pthread fan-out of ndt.c:949-975 is the GPU's job now; `threads` fits the scene's bounding spheres in parallel) */
-    return render_any(scn, width, height, samples, aa_diff, aa_depth, stereo, specular, max_optic_depth, NDT_IMAGE_F64, rgba, depth, threads);
+    return render_any(scn, width, height, samples, aa_diff, aa_depth, stereo, specular, max_optic_depth, NDT_IMAGE_F64, rgba, depth, threads, 1);
 }
 
 int ndt_render_image_rgba8(scene *scn, int width, int height, int samples, int threads, int aa_diff, int aa_depth, int stereo,
                            int specular, int max_optic_depth, unsigned char *rgba8)
 {
-    return render_any(scn, width, height, samples, aa_diff, aa_depth, stereo, specular, max_optic_depth, NDT_IMAGE_RGBA8, rgba8, NULL, threads);
+    return render_any(scn, width, height, samples, aa_diff, aa_depth, stereo, specular, max_optic_depth, NDT_IMAGE_RGBA8, rgba8, NULL, threads, 1);
 }
 
 int ndt_render_image_depth8(scene *scn, int width, int height, int samples, int threads, int aa_diff, int aa_depth, int stereo,
@@ -413,7 +533,7 @@ int ndt_render_image_depth8(scene *scn, int width, int height, int samples, int 
     depth_out d = { out, want_png != 0, want_png && want_depth_png };
     memset(out, 0, sizeof(*out));
     g_depth_ms = 0.0;
-    if (!render_any(scn, width, height, samples, aa_diff, aa_depth, stereo, specular, max_optic_depth, NDT_HOST_IMAGE_DEPTH8, &d, NULL, threads)) {
+    if (!render_any(scn, width, height, samples, aa_diff, aa_depth, stereo, specular, max_optic_depth, NDT_HOST_IMAGE_DEPTH8, &d, NULL, threads, 1)) {
         ndt_depth_frame_free(out);
         return 0;
     }
@@ -426,7 +546,7 @@ int ndt_render_image_png(scene *scn, int width, int height, int samples, int thr
     png_out po = { png, png_bytes };
     *png = NULL;
     *png_bytes = 0;
-    return render_any(scn, width, height, samples, aa_diff, aa_depth, stereo, specular, max_optic_depth, NDT_HOST_IMAGE_PNG, &po, NULL, threads);
+    return render_any(scn, width, height, samples, aa_diff, aa_depth, stereo, specular, max_optic_depth, NDT_HOST_IMAGE_PNG, &po, NULL, threads, 1);
 }
 
 int ndt_render_image_jpeg(scene *scn, int width, int height, int samples, int threads, int aa_diff, int aa_depth, int stereo,
@@ -435,5 +555,49 @@ int ndt_render_image_jpeg(scene *scn, int width, int height, int samples, int th
     jpeg_out jo = { jpg, jpg_bytes, jpeg_params_of(quality, sampling) };
     *jpg = NULL;
     *jpg_bytes = 0;
-    return render_any(scn, width, height, samples, aa_diff, aa_depth, stereo, specular, max_optic_depth, NDT_HOST_IMAGE_JPEG, &jo, NULL, threads);
+    return render_any(scn, width, height, samples, aa_diff, aa_depth, stereo, specular, max_optic_depth, NDT_HOST_IMAGE_JPEG, &jo, NULL, threads, 1);
+}
+
+/* ---- the same calls for a frame supersampled ssaa x ssaa on the GPU (no -a beside it: the library refuses the pair) */
+int ndt_render_image_ssaa_full(scene *scn, int width, int height, int samples, int threads, int stereo, int specular, int max_optic_depth,
+                               int ssaa, double *rgba, double *depth)
+{
+    return render_any(scn, width, height, samples, -1, -1, stereo, specular, max_optic_depth, NDT_IMAGE_F64, rgba, depth, threads, ssaa);
+}
+
+int ndt_render_image_ssaa_rgba8(scene *scn, int width, int height, int samples, int threads, int stereo, int specular, int max_optic_depth,
+                                int ssaa, unsigned char *rgba8)
+{
+    return render_any(scn, width, height, samples, -1, -1, stereo, specular, max_optic_depth, NDT_IMAGE_RGBA8, rgba8, NULL, threads, ssaa);
+}
+
+int ndt_render_image_ssaa_png(scene *scn, int width, int height, int samples, int threads, int stereo, int specular, int max_optic_depth,
+                              int ssaa, unsigned char **png, long long *png_bytes)
+{
+    png_out po = { png, png_bytes };
+    *png = NULL;
+    *png_bytes = 0;
+    return render_any(scn, width, height, samples, -1, -1, stereo, specular, max_optic_depth, NDT_HOST_IMAGE_PNG, &po, NULL, threads, ssaa);
+}
+
+int ndt_render_image_ssaa_jpeg(scene *scn, int width, int height, int samples, int threads, int stereo, int specular, int max_optic_depth,
+                               int ssaa, int quality, int sampling, unsigned char **jpg, long long *jpg_bytes)
+{
+    jpeg_out jo = { jpg, jpg_bytes, jpeg_params_of(quality, sampling) };
+    *jpg = NULL;
+    *jpg_bytes = 0;
+    return render_any(scn, width, height, samples, -1, -1, stereo, specular, max_optic_depth, NDT_HOST_IMAGE_JPEG, &jo, NULL, threads, ssaa);
+}
+
+int ndt_render_image_ssaa_depth8(scene *scn, int width, int height, int samples, int threads, int stereo, int specular, int max_optic_depth,
+                                 int ssaa, int want_png, int want_depth_png, ndt_depth_frame *out)
+{
+    depth_out d = { out, want_png != 0, want_png && want_depth_png };
+    memset(out, 0, sizeof(*out));
+    g_depth_ms = 0.0;
+    if (!render_any(scn, width, height, samples, -1, -1, stereo, specular, max_optic_depth, NDT_HOST_IMAGE_DEPTH8, &d, NULL, threads, ssaa)) {
+        ndt_depth_frame_free(out);
+        return 0;
+    }
+    return 1;
 }
