@@ -513,6 +513,9 @@ int ndt_hip_multi_path_taken(ndt_hip_ctx *ctx);
  *   "multi_path"      ndt_hip_render_multi: 0 auto (stores on the same device, peer stores over xGMI, a staged copy where
  *                     there is no peer access), 1 never staged, 2 always staged -- also between contexts of one device
  *   "shade_pair"      0: lighting of a bounce and shading of the next as two launches
+ *   "light_overlap"   per-bounce pipeline, one light window, not hybrid: 1 (default) the lighting of every bounce but the
+ *                     deepest runs on the context's second stream beside the next bounce's trace launch (and "shade_pair" has
+ *                     nothing to pair); 0 every launch on the one stream.  Same image, same counts
  *   "light_window"    lights the lighting kernels take per window: 0 (default) auto, windows of 64; k in 1..64 at most k
  *                     list entries a window (ambient ones included).  A scene of more than one window renders every pass
  *                     with the per-bounce kernels, whatever "pipeline" says, and pays a shading and a trace launch per

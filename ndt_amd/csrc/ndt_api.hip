@@ -61,7 +61,7 @@ extern "C" int ndt_hip_create(int device, ndt_hip_ctx **out)
     ctx->device = device;
     {
         // the environment is read here, once: nothing on the render or upload path looks at it
-        static const char *const names[] = { "hybrid_level", "stream_below", "stream_below_list", "hull_box", "face_box", "face_tree", "face_groups", "item_sets", "gate_prepass", "gate_prepass_below", "item_boxes", "leaf_history", "leaf_scan", "leaf_scan_group", "multi_path", "sample_seed", "stream_fused", "fuse_primaries", "shade_pair", "light_window", "debug_levels",
+        static const char *const names[] = { "hybrid_level", "stream_below", "stream_below_list", "hull_box", "face_box", "face_tree", "face_groups", "item_sets", "gate_prepass", "gate_prepass_below", "item_boxes", "leaf_history", "leaf_scan", "leaf_scan_group", "multi_path", "sample_seed", "stream_fused", "fuse_primaries", "shade_pair", "light_overlap", "light_window", "debug_levels",
                                              "exit_probe", "shade_probe", "stream_probe", "test_small_pool" };
         const char *pl = getenv("NDT_HIP_PIPELINE");
         if (pl) (void)ndt_hip_set_option(ctx, "pipeline", !strcmp(pl, "levels") ? 1 : !strcmp(pl, "stream") ? 2 : !strcmp(pl, "hybrid") ? 3 : 0);
@@ -79,6 +79,13 @@ extern "C" int ndt_hip_create(int device, ndt_hip_ctx **out)
         if (getenv("NDT_HIP_NO_SHADE_PAIR") && atoi(getenv("NDT_HIP_NO_SHADE_PAIR"))) ctx->shade_pair = false;
     }
     e = hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking);
+    if (e == hipSuccess) {
+        // the light stream at the lowest priority: its kernels take what the main stream's leave idle
+        int least = 0, greatest = 0;
+        e = hipDeviceGetStreamPriorityRange(&least, &greatest);
+        if (e == hipSuccess) e = hipStreamCreateWithPriority(&ctx->light_stream, hipStreamNonBlocking, least);
+        if (e != hipSuccess) (void)hipStreamDestroy(ctx->stream);
+    }
     if (e != hipSuccess) {
         delete ctx;
         return fail(NDT_E_DEVICE, "hipStreamCreate: %s", hipGetErrorString(e));
@@ -94,6 +101,7 @@ extern "C" int ndt_hip_create(int device, ndt_hip_ctx **out)
     if (e == hipSuccess) e = hipHostGetDevicePointer((void **)&ctx->d_done, ctx->h_done, 0);
     if (e == hipSuccess) memset(ctx->h_done, 0, 16 * sizeof(unsigned long long));
     if (e != hipSuccess) {
+        (void)hipStreamDestroy(ctx->light_stream);
         (void)hipStreamDestroy(ctx->stream);
         delete ctx;
         return fail(NDT_E_DEVICE, "hipHostMalloc: %s", hipGetErrorString(e));
@@ -107,7 +115,7 @@ extern "C" int ndt_hip_destroy(ndt_hip_ctx *ctx)
     if (!ctx) return NDT_OK;
     worker_stop(ctx);
     (void)hipSetDevice(ctx->device);
-    (void)hipStreamSynchronize(ctx->stream);
+    (void)sync_streams(ctx);
     free_workspace(ctx);
     free_stage(ctx);
     free_async(ctx);
@@ -132,6 +140,7 @@ extern "C" int ndt_hip_destroy(ndt_hip_ctx *ctx)
     if (ctx->h_mail_tag) (void)hipHostFree(ctx->h_mail_tag);
     if (ctx->h_done) (void)hipHostFree(ctx->h_done);
     for (hipEvent_t ev : ctx->ev_pool) (void)hipEventDestroy(ev);
+    (void)hipStreamDestroy(ctx->light_stream);
     (void)hipStreamDestroy(ctx->stream);
     delete ctx;
     return NDT_OK;
@@ -165,6 +174,7 @@ extern "C" int ndt_hip_set_option(ndt_hip_ctx *ctx, const char *name, int64_t va
     } else if (!strcmp(name, "stream_fused")) ctx->stream_fused = on;
     else if (!strcmp(name, "fuse_primaries")) ctx->fuse_primaries = value < 0 ? -1 : on ? 1 : 0;
     else if (!strcmp(name, "shade_pair")) ctx->shade_pair = on;
+    else if (!strcmp(name, "light_overlap")) ctx->light_overlap = on;
     else if (!strcmp(name, "light_window")) {
         if (value < 0 || value > 64) return fail(NDT_E_INVALID, "light_window %lld (0 auto, 1 .. 64)", (long long)value);
         ctx->light_window = (int)value;
@@ -210,7 +220,7 @@ extern "C" int ndt_hip_upload_scene(ndt_hip_ctx *ctx, const ndt_flat_scene *fs)
     ctx->dims = fs->dims;
     ctx->kt = table_for(fs->dims);
     if (!ctx->kt) return fail(NDT_E_UNSUPPORTED, "no kernels for %d dimensions", fs->dims);
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    HIP_TRY(sync_streams(ctx));          // (the lighting kernels read the blob too)
     if (ctx->d_blob_words < ctx->blob.size()) {
         if (ctx->d_blob) HIP_TRY(hipFree(ctx->d_blob));
         ctx->d_blob = nullptr;

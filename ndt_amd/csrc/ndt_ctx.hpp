@@ -99,6 +99,10 @@ struct SsaaState {
 struct ndt_hip_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
+    // the light stream (lowest priority): where the per-bounce pipeline lights bounce b beside the trace launch of bounce b + 1
+    // (option "light_overlap", ndt_frame.hip:FrameInFlight::light_beside).  The main stream waits for it through events of
+    // ev_pool; a frame leaves nothing running on it (FrameInFlight::render joins it on every way out)
+    hipStream_t light_stream = nullptr;
     const NdtKernelTable *kt = nullptr;
     int dims = 0;
     bool have_scene = false;
@@ -151,6 +155,9 @@ struct ndt_hip_ctx {
     // ndt_hip_set_option / NDT_HIP_* at context creation (include/ndt_hip.h)
     bool stream_probe = false, exit_probe = false, debug_levels = false, test_small_pool = false;
     bool hull_box = true, face_box = true, shade_pair = true;
+    // per-bounce pipeline, one light window, not hybrid: shade_finish(b) on the light stream beside the trace launch of bounce b + 1,
+    // plain shade_emit(b) on the main stream instead of the pair (measured: profiles/r09_light_overlap.md)
+    bool light_overlap = true;
     bool face_tree = true;          // hcubes of more than 63 faces: a hierarchy over the face boxes (ndt_device.hpp:hull_faces)
     bool face_groups = true;        // ... and an index of the faces by the set of hull axes their boxes are thin on (hull_faces)
     // per-bounce kernels: the first trace launch makes the primaries it traces (no k_primary; k_trace's PRIM variant, planar camera).
@@ -242,6 +249,8 @@ SceneDesc window_desc(const ndt_hip_ctx *ctx, const SceneDesc &sd, int k);
 
 // ndt_frame.hip
 void free_workspace(ndt_hip_ctx *ctx);
+// both streams of the context idle: before memory that kernels of either may still use is freed
+hipError_t sync_streams(ndt_hip_ctx *ctx);
 int ensure_workspace(ndt_hip_ctx *ctx, long long cap, long long sh_cap);
 int render_pass(ndt_hip_ctx *ctx, RenderGeom rg, bool prof, void *d_rgba, ndt_render_stats &st, void *d_depth = nullptr);
 void launch_fill_black(hipStream_t s, double *rgba, long long n_pixels);

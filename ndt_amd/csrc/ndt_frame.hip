@@ -14,6 +14,13 @@ static void free_stream_args(ndt_hip_ctx *ctx)
     ctx->sa_nseg = 0;
 }
 
+hipError_t ndt_impl::sync_streams(ndt_hip_ctx *ctx)
+{
+    const hipError_t e = hipStreamSynchronize(ctx->stream);
+    if (e != hipSuccess || !ctx->light_stream) return e;
+    return hipStreamSynchronize(ctx->light_stream);
+}
+
 void ndt_impl::free_workspace(ndt_hip_ctx *ctx)
 {
     for (void *p : ctx->ws_allocs) (void)hipFree(p);
@@ -53,7 +60,7 @@ int ndt_impl::ensure_workspace(ndt_hip_ctx *ctx, long long cap, long long sh_cap
     if (sh_cap < ws.sh_cap) sh_cap = ws.sh_cap;
     cap = (cap + 63) & ~63LL;           // vectors are stored in tiles of 64 slots (load_soa / store_soa)
     sh_cap = (sh_cap + 63) & ~63LL;
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    HIP_TRY(sync_streams(ctx));
     free_workspace(ctx);
     const int n = ctx->dims;
     int rc;
@@ -83,8 +90,9 @@ int ndt_impl::ensure_workspace(ndt_hip_ctx *ctx, long long cap, long long sh_cap
     if ((rc = ws_alloc(ctx, &ws.so, (size_t)n * sh_cap))) return give_up(rc);
     if ((rc = ws_alloc(ctx, &ws.sv, (size_t)n * sh_cap))) return give_up(rc);
     if ((rc = ws_alloc(ctx, &ws.slim, (size_t)sh_cap))) return give_up(rc);
-    if ((rc = ws_alloc(ctx, &ws.sobj, (size_t)sh_cap))) return give_up(rc);
-    if ((rc = ws_alloc(ctx, &ws.sprim, (size_t)sh_cap))) return give_up(rc);
+    // (three banks of the answers, taken in turn by the bounces: Workspace::sobj)
+    if ((rc = ws_alloc(ctx, &ws.sobj, (size_t)3 * sh_cap))) return give_up(rc);
+    if ((rc = ws_alloc(ctx, &ws.sprim, (size_t)3 * sh_cap))) return give_up(rc);
     if ((rc = ws_alloc(ctx, &ws.counters, NDT_CNT_ALLOC))) return give_up(rc);
     if ((rc = ws_alloc(ctx, &ws.ref_rays, 64 * 8))) return give_up(rc);
     if ((rc = ws_alloc(ctx, &ws.dbg, 160))) return give_up(rc);
@@ -111,7 +119,7 @@ static int ensure_stream_args(ndt_hip_ctx *ctx)
     const int n_seg = ctx->n_shadow_lights > 0 ? ctx->n_shadow_lights : 1;
     if (ctx->sa.ctl && ctx->sa_cap == ws.cap && ctx->sa_sh_cap == ws.sh_cap && ctx->sa_nseg == n_seg) return NDT_OK;
     if (!ctx->sa_allocs.empty()) {
-        HIP_TRY(hipStreamSynchronize(ctx->stream));
+        HIP_TRY(sync_streams(ctx));
         free_stream_args(ctx);
     }
     StreamArgs &sa = ctx->sa;
@@ -516,6 +524,16 @@ struct FrameInFlight {
     // window counters in turn)
     const int n_win;
     const bool windowed;
+    // Option light_overlap (one light window, not hybrid): the lighting of every bounce but the deepest runs on the light stream,
+    // beside the trace launch of the NEXT bounce, which does not need it.  Nothing is put on the main stream
+    // for it: shade_finish(b) is launched when the mailbox says that the stream has passed the trace launch of bounce b
+    // (light_beside).  ev_lit[b % 3], on the light stream behind shade_finish(b), marks the last reader of bank b % 3 of the
+    // shadow answers.
+    const bool overlap;
+    hipStream_t ls;
+    hipEvent_t ev_lit[3] = { nullptr, nullptr, nullptr };
+    int light_next = 0;                         // the first bounce whose lighting has not gone to the light stream
+    hipEvent_t light_tail = nullptr;            // the light stream's last event, while the main stream has not waited for it
     std::vector<SceneDesc> sd_win;
     int win_emits = 0;
     unsigned long long tag = 0;
@@ -539,7 +557,7 @@ struct FrameInFlight {
     FrameInFlight(ndt_hip_ctx *c, const RenderGeom &g, const SceneDesc &sd, bool p, bool hyb, void *rgba, void *depth)
         : ctx(c), rg(g), sd_pass(sd), prof(p), hybrid(hyb), d_rgba(rgba), d_depth(depth), s(c->stream), kt(c->kt), ws(c->ws),
           n_levels(g.max_depth > 1 ? g.max_depth : 1), hand(hyb ? c->hybrid_level : n_levels + 1), n_win((int)c->windows.size()),
-          windowed(n_win > 1), n_run(n_levels)
+          windowed(n_win > 1), overlap(c->light_overlap && !windowed && !hyb), ls(c->light_stream), n_run(n_levels)
     {
         ws.mail = ctx->d_mail;
         ws.mail_tag = ctx->d_mail_tag;
@@ -547,11 +565,15 @@ struct FrameInFlight {
     }
 
     int render(long long &cap, long long &sh_cap, ndt_render_stats &st);
+    int render_frame(long long &cap, long long &sh_cap, ndt_render_stats &st);
     int frame_init(long long &sh_cap);
     int traced(TraceJob &tj, const std::string &what, const SceneDesc *sd_job = nullptr);
-    Workspace shade_ws(long long finish_nodes);
+    int answer_bank(int b) const { return overlap ? b % 3 : 0; }   // of sobj / sprim, for the shadow rays of bounce b
+    Workspace shade_ws(long long finish_nodes, int b, hipStream_t on);
     int trace_primaries();
     void light_and_shade(int b, long long upper);
+    int light_beside(int b);
+    hipError_t join_light();
     int trace_bounce(int b, long long upper);
     int trace_windows(int b, long long upper);
     void light_last();
@@ -562,7 +584,39 @@ struct FrameInFlight {
     hipError_t print_debug(int levels_used);
 };
 
+// Every way out of a frame -- its image, PASS_AGAIN, an error -- leaves the main stream behind whatever the frame put on the light
+// stream: the attempt that follows, or whoever synchronises the main stream before freeing the pools, is behind it too
 int FrameInFlight::render(long long &cap, long long &sh_cap, ndt_render_stats &st)
+{
+    const int rc = render_frame(cap, sh_cap, st);
+    const hipError_t e = join_light();          // (a frame that closed has joined already: light_tail is null)
+    if (rc == NDT_OK && e != hipSuccess) return fail(NDT_E_DEVICE, "joining the light stream: %s", hipGetErrorString(e));
+    return rc;
+}
+
+// the main stream waits (on the device) for the light stream's last launch
+hipError_t FrameInFlight::join_light()
+{
+    if (!light_tail) return hipSuccess;
+    const hipError_t e = hipStreamWaitEvent(s, light_tail, 0);
+    light_tail = nullptr;
+    return e;
+}
+
+// light_overlap: the lighting of bounce b on the light stream.  The caller has seen the mailbox tag of bounce b + 2: the prologue
+// of trace launch b + 1 posted it, so the main stream has passed trace launch b -- the shadow answers of bounce b are complete, as
+// is everything else shade_finish_node reads -- and the kernel needs no event to wait for: it starts at once,
+// beside trace launch b + 1, and the main stream carries no marker for it.
+int FrameInFlight::light_beside(int b)
+{
+    kt->shade_finish(ls, ctx->d_blob, sd_pass, shade_ws(level_nodes[b], b, ls), rg, b, level_nodes[b], 0);
+    HIP_TRY(hipEventRecord(ev_lit[b % 3], ls));
+    light_tail = ev_lit[b % 3];
+    light_next = b + 1;
+    return NDT_OK;
+}
+
+int FrameInFlight::render_frame(long long &cap, long long &sh_cap, ndt_render_stats &st)
 {
     int rc;
     if ((rc = frame_init(sh_cap))) return rc;
@@ -574,9 +628,11 @@ int FrameInFlight::render(long long &cap, long long &sh_cap, ndt_render_stats &s
         if ((windowed ? b + 2 : queue_slot + 1) > NDT_QUEUE_SLOTS || b + 1 > NDT_MAX_LEVELS)
             return fail(NDT_E_UNSUPPORTED, "more than %d bounces", NDT_QUEUE_SLOTS - 1);
         if (b > 0) {
-            // published by the trace launch of bounce b - 1, which ran right after shade_emit(b - 1)
+            // published by the trace launch of bounce b - 1, which ran right after shade_emit(b - 1) -- and behind trace launch
+            // b - 2: the lighting of bounce b - 2 can go (light_overlap)
             if ((rc = wait_for_tag(ctx, &ctx->h_mail_tag[b], tag, "bounce %d was never published", b))) return rc;
             upper = ctx->h_mail[b].count;
+            if (overlap && b >= 2 && (rc = light_beside(b - 2))) return rc;
             if (upper <= 0) {
                 n_run = b;
                 break;
@@ -590,7 +646,13 @@ int FrameInFlight::render(long long &cap, long long &sh_cap, ndt_render_stats &s
         pending_upper = upper;
     }
     light_last();
+    if (overlap && n_run >= 2 && light_next == n_run - 2) {
+        // the bounce limit ended the loop: the last trace launch posts a bounce of its own, and with it where the stream is
+        if ((rc = wait_for_tag(ctx, &ctx->h_mail_tag[n_run], tag, "bounce %d was never published", n_run))) return rc;
+        if ((rc = light_beside(n_run - 2))) return rc;
+    }
     if (hybrid && n_run >= hand && hand < n_levels && (rc = hand_off(cap))) return rc;
+    HIP_TRY(join_light());                  // the resolve reads the colours every bounce's lighting left
     resolve();
     launch_finish_pixels(ctx, sd_pass, ws, rg, d_rgba, d_depth, n_run >= 1 ? 1 : 0);
     if ((rc = close())) return rc;
@@ -606,6 +668,8 @@ int FrameInFlight::frame_init(long long &sh_cap)
         ev_begin = get_event(ctx, ev_n++);
         ev_end = get_event(ctx, ev_n++);
     }
+    for (int p = 0; overlap && p < 3; ++p)
+        if (!(ev_lit[p] = get_event(ctx, ev_n++))) return fail(NDT_E_DEVICE, "hipEventCreate failed");
     if (prof && ctx->exit_probe)
         HIP_TRY(hipMemsetAsync(ws.exit_log, 0, (size_t)NDT_EXIT_LOG_LAUNCHES * NDT_EXIT_LOG_WORDS * sizeof(unsigned int), s));
     tag = ++ctx->frame_tag;
@@ -647,15 +711,18 @@ int FrameInFlight::traced(TraceJob &tj, const std::string &what, const SceneDesc
     return NDT_OK;
 }
 
-// the workspace a shade launch gets: with the shade probe's log if it is the probed launch (`finish_nodes` of it are lit)
-Workspace FrameInFlight::shade_ws(long long finish_nodes)
+// the workspace a shade launch on stream `on` gets: the bank of the shadow answers of bounce b (the bounce it lights, if it lights
+// one), and the shade probe's log if it is the probed launch (`finish_nodes` of it are lit; the log is cleared on the launch's stream)
+Workspace FrameInFlight::shade_ws(long long finish_nodes, int b, hipStream_t on)
 {
     Workspace w = ws;
+    w.sobj += answer_bank(b) * ws.sh_cap;
+    w.sprim += answer_bank(b) * ws.sh_cap;
     if (shade_launch++ != ctx->shade_probe || !prof) {
         w.shade_log = nullptr;
     } else {
         shade_probe_finish_waves = (finish_nodes + 255) / 256 * 4;
-        (void)hipMemsetAsync(w.shade_log, 0, (size_t)2 * NDT_SHADE_LOG_WAVES * sizeof(unsigned int), s);
+        (void)hipMemsetAsync(w.shade_log, 0, (size_t)2 * NDT_SHADE_LOG_WAVES * sizeof(unsigned int), on);
     }
     return w;
 }
@@ -668,13 +735,15 @@ static void job_closest(TraceJob &tj, const Workspace &ws)
     tj.begin = 0;
 }
 
-// the segmented half: shadow rays of bounce b (at most `upper` nodes) in n_seg segments of the shadow queue, counted in seg_count
-static void job_shadow(TraceJob &tj, const Workspace &ws, const SceneDesc &sd_pass, int b, long long upper, int n_seg, const int *seg_count)
+// the segmented half: shadow rays of bounce b (at most `upper` nodes) in n_seg segments of the shadow queue, counted in seg_count;
+// the answers go to bank `bank` of sobj / sprim
+static void job_shadow(TraceJob &tj, const Workspace &ws, const SceneDesc &sd_pass, int b, long long upper, int n_seg, const int *seg_count,
+                       int bank = 0)
 {
     tj.n_seg = n_seg;
     tj.seg.o = ws.so; tj.seg.v = ws.sv; tj.seg.stride = ws.sh_cap; tj.seg.lim = ws.slim; tj.seg.valid = nullptr;
     tj.seg_light_origins = sd_pass.light_origins;      // (what shade_emit_node left out: ndt_kernels.hip)
-    tj.seg.out_obj = ws.sobj; tj.seg.out_prim = ws.sprim;
+    tj.seg.out_obj = ws.sobj + bank * ws.sh_cap; tj.seg.out_prim = ws.sprim + bank * ws.sh_cap;
     tj.seg_count = seg_count;
     tj.seg_stride = (upper + 63) & ~63LL;           // sizes the grid only
     tj.levels = ws.levels;
@@ -700,19 +769,25 @@ int FrameInFlight::trace_primaries()
 }
 
 // Hit points, shadow rays of bounce b, and the rays of the next bounce -- in the same launch as the lighting of the previous
-// bounce, which is waiting for the shadow answers the last trace launch produced
+// bounce, which is waiting for the shadow answers the last trace launch produced; or (light_overlap) alone: the next trace launch
+// needs what shade_emit(b) makes, nothing before the resolve needs what shade_finish(b - 1) does, and that goes to the light
+// stream once the stream has passed the trace launch it depends on (render_frame, light_beside)
 void FrameInFlight::light_and_shade(int b, long long upper)
 {
     if (windowed) {
         // (the lighting of the last window of bounce b-1 and the shading of bounce b see different lights: two launches)
         if (pending_finish >= 0)
-            kt->shade_last(s, ctx->d_blob, sd_win[n_win - 1], shade_ws(pending_upper), rg, pending_finish, pending_upper, 0, ctx->windows[n_win - 1].first);
-        kt->shade_emit(s, ctx->d_blob, sd_win[0], shade_ws(0), rg, b, upper);
+            kt->shade_last(s, ctx->d_blob, sd_win[n_win - 1], shade_ws(pending_upper, pending_finish, s), rg, pending_finish, pending_upper, 0,
+                           ctx->windows[n_win - 1].first);
+        kt->shade_emit(s, ctx->d_blob, sd_win[0], shade_ws(0, b, s), rg, b, upper);
+    } else if (overlap) {
+        kt->shade_emit(s, ctx->d_blob, sd_pass, shade_ws(0, b, s), rg, b, upper);
     } else if (pending_finish >= 0 && ctx->shade_pair) {
-        kt->shade_pair(s, ctx->d_blob, sd_pass, shade_ws(pending_upper), rg, pending_finish, pending_upper, upper);
+        kt->shade_pair(s, ctx->d_blob, sd_pass, shade_ws(pending_upper, pending_finish, s), rg, pending_finish, pending_upper, upper);
     } else {
-        if (pending_finish >= 0) kt->shade_finish(s, ctx->d_blob, sd_pass, shade_ws(pending_upper), rg, pending_finish, pending_upper, 0);
-        kt->shade_emit(s, ctx->d_blob, sd_pass, shade_ws(0), rg, b, upper);
+        if (pending_finish >= 0)
+            kt->shade_finish(s, ctx->d_blob, sd_pass, shade_ws(pending_upper, pending_finish, s), rg, pending_finish, pending_upper, 0);
+        kt->shade_emit(s, ctx->d_blob, sd_pass, shade_ws(0, b, s), rg, b, upper);
     }
     pending_finish = -1;
 }
@@ -724,12 +799,16 @@ int FrameInFlight::trace_bounce(int b, long long upper)
     if (next_upper > ws.cap) next_upper = ws.cap;
     const bool last = b + 1 == hand;            // the frame kernel traces bounce `hand`
     TraceJob tj{};
-    job_shadow(tj, ws, sd_pass, b, upper, windowed ? ctx->windows[0].n_seg : ctx->n_shadow_lights, NDT_SEG_COUNTERS(ws, b));
+    job_shadow(tj, ws, sd_pass, b, upper, windowed ? ctx->windows[0].n_seg : ctx->n_shadow_lights, NDT_SEG_COUNTERS(ws, b), answer_bank(b));
     job_closest(tj, ws);
     tj.count = next_upper;                      // sizes the grid only
     tj.dense_level = last ? -1 : b + 1;
     tj.publish_level = b;
     tj.publish_tag = tag;
+    // (light_overlap) the launch writes the bank of answers that shade_finish(b - 3) read: behind it.  That lighting went to the
+    // light stream a whole bounce ago (with the tag of bounce b - 1), so in a healthy frame the event is long past, and a wait
+    // for a past event puts nothing on the stream
+    if (overlap && b >= 3) HIP_TRY(hipStreamWaitEvent(s, ev_lit[b % 3], 0));
     return traced(tj, "shadow " + std::to_string(b) + (last ? "" : " + closest " + std::to_string(b + 1)), windowed ? &sd_win[0] : nullptr);
 }
 
@@ -742,7 +821,7 @@ int FrameInFlight::trace_windows(int b, long long upper)
         int *bank = ws.counters + NDT_CNT_WIN + 64 * (win_emits & 1);
         int *next_bank = ws.counters + NDT_CNT_WIN + 64 * ((win_emits + 1) & 1);
         ++win_emits;
-        kt->shade_window(s, ctx->d_blob, sd_win[k - 1], sd_win[k], shade_ws(upper), rg, b, upper, ctx->windows[k - 1].first, w.first, bank, next_bank,
+        kt->shade_window(s, ctx->d_blob, sd_win[k - 1], sd_win[k], shade_ws(upper, b, s), rg, b, upper, ctx->windows[k - 1].first, w.first, bank, next_bank,
                          w.n_seg, k > 1 ? 1 : 0);
         if (w.n_seg == 0) continue;
         TraceJob tj{};
@@ -758,15 +837,17 @@ int FrameInFlight::trace_windows(int b, long long upper)
 
 // The lighting of the deepest bounce that has nodes: blended on the spot (its nodes have no child nodes), unless the frame
 // kernel renders deeper bounces behind it (hybrid)
+// (light_overlap: on the main stream, like the resolve that follows it)
 void FrameInFlight::light_last()
 {
     if (pending_finish < 0) return;
     resolve_with_finish = !hybrid && pending_finish >= 1 && pending_finish == n_run - 1;
     if (windowed)
-        kt->shade_last(s, ctx->d_blob, sd_win[n_win - 1], shade_ws(pending_upper), rg, pending_finish, pending_upper, resolve_with_finish ? 1 : 0,
-                       ctx->windows[n_win - 1].first);
+        kt->shade_last(s, ctx->d_blob, sd_win[n_win - 1], shade_ws(pending_upper, pending_finish, s), rg, pending_finish, pending_upper,
+                       resolve_with_finish ? 1 : 0, ctx->windows[n_win - 1].first);
     else
-        kt->shade_finish(s, ctx->d_blob, sd_pass, shade_ws(pending_upper), rg, pending_finish, pending_upper, resolve_with_finish ? 1 : 0);
+        kt->shade_finish(s, ctx->d_blob, sd_pass, shade_ws(pending_upper, pending_finish, s), rg, pending_finish, pending_upper,
+                         resolve_with_finish ? 1 : 0);
 }
 
 // Hybrid: the frame kernel renders the forest rooted at the nodes of bounce `hand` (its queues are reset, and it runs).

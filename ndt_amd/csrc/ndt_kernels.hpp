@@ -38,7 +38,11 @@ struct Workspace {
     long long sh_cap;
     double *so, *sv;            // [N][sh_cap]
     double *slim;               // [sh_cap]   dist_limit
-    int *sobj, *sprim;          // [sh_cap]
+    // [3][sh_cap] the answers, in three banks taken in turn by the bounces (what a kernel is handed points at the bank of ITS
+    // bounce): with option light_overlap the lighting of bounce b - 1 reads its answers while the trace launch of bounce b writes
+    // its own, and may still do so when that of bounce b + 1 is enqueued (ndt_frame.hip:FrameInFlight::answer_bank; bank 0 only
+    // without the option, and in the frame kernel)
+    int *sobj, *sprim;
     // counters: [0] node tail, [2] overflow flags (1 nodes, 2 shadows),
     // [NDT_CNT_QUEUE ..) work-queue heads, [NDT_CNT_SEG ..) shadow rays per light segment
     int *counters;
