@@ -516,6 +516,10 @@ int ndt_hip_multi_path_taken(ndt_hip_ctx *ctx);
  *   "light_overlap"   per-bounce pipeline, one light window, not hybrid: 1 (default) the lighting of every bounce but the
  *                     deepest runs on the context's second stream beside the next bounce's trace launch (and "shade_pair" has
  *                     nothing to pair); 0 every launch on the one stream.  Same image, same counts
+ *   "early_pixels"    where "light_overlap" applies (a no-op elsewhere): the pixels of primaries that are final long before the
+ *                     end of the frame are finished on the second stream, and the frame's last launch takes the rest.  0 off;
+ *                     1 (default) the primaries that hit nothing, beside the second trace launch; 2 also the hit ones without
+ *                     a reflection or refraction ray, behind the lighting of the primaries.  Same image, same counts
  *   "light_window"    lights the lighting kernels take per window: 0 (default) auto, windows of 64; k in 1..64 at most k
  *                     list entries a window (ambient ones included).  A scene of more than one window renders every pass
  *                     with the per-bounce kernels, whatever "pipeline" says, and pays a shading and a trace launch per

@@ -61,7 +61,7 @@ extern "C" int ndt_hip_create(int device, ndt_hip_ctx **out)
     ctx->device = device;
     {
         // the environment is read here, once: nothing on the render or upload path looks at it
-        static const char *const names[] = { "hybrid_level", "stream_below", "stream_below_list", "hull_box", "face_box", "face_tree", "face_groups", "item_sets", "gate_prepass", "gate_prepass_below", "item_boxes", "leaf_history", "leaf_scan", "leaf_scan_group", "multi_path", "sample_seed", "stream_fused", "fuse_primaries", "shade_pair", "light_overlap", "light_window", "debug_levels",
+        static const char *const names[] = { "hybrid_level", "stream_below", "stream_below_list", "hull_box", "face_box", "face_tree", "face_groups", "item_sets", "gate_prepass", "gate_prepass_below", "item_boxes", "leaf_history", "leaf_scan", "leaf_scan_group", "multi_path", "sample_seed", "stream_fused", "fuse_primaries", "shade_pair", "light_overlap", "early_pixels", "light_window", "debug_levels",
                                              "exit_probe", "shade_probe", "stream_probe", "test_small_pool" };
         const char *pl = getenv("NDT_HIP_PIPELINE");
         if (pl) (void)ndt_hip_set_option(ctx, "pipeline", !strcmp(pl, "levels") ? 1 : !strcmp(pl, "stream") ? 2 : !strcmp(pl, "hybrid") ? 3 : 0);
@@ -175,6 +175,10 @@ extern "C" int ndt_hip_set_option(ndt_hip_ctx *ctx, const char *name, int64_t va
     else if (!strcmp(name, "fuse_primaries")) ctx->fuse_primaries = value < 0 ? -1 : on ? 1 : 0;
     else if (!strcmp(name, "shade_pair")) ctx->shade_pair = on;
     else if (!strcmp(name, "light_overlap")) ctx->light_overlap = on;
+    else if (!strcmp(name, "early_pixels")) {
+        if (value < 0 || value > 2) return fail(NDT_E_INVALID, "early_pixels %lld (0 off, 1 missed primaries, 2 and childless ones)", (long long)value);
+        ctx->early_pixels = (int)value;
+    }
     else if (!strcmp(name, "light_window")) {
         if (value < 0 || value > 64) return fail(NDT_E_INVALID, "light_window %lld (0 auto, 1 .. 64)", (long long)value);
         ctx->light_window = (int)value;

@@ -158,6 +158,11 @@ struct ndt_hip_ctx {
     // per-bounce pipeline, one light window, not hybrid: shade_finish(b) on the light stream beside the trace launch of bounce b + 1,
     // plain shade_emit(b) on the main stream instead of the pair (measured: profiles/r09_light_overlap.md)
     bool light_overlap = true;
+    // ... and, where that applies, the pixels of primaries that are final early finished on the light stream instead of at the end of
+    // the frame: 0 off, 1 the primaries that missed (beside trace launch 1), 2 also the hit ones without a child (behind
+    // shade_finish(0): measured no better than 1, the lighting behind it on the light stream starts later).
+    // FrameInFlight::early_pixels_beside; measured: profiles/r10_early_pixels.md
+    int early_pixels = 1;
     bool face_tree = true;          // hcubes of more than 63 faces: a hierarchy over the face boxes (ndt_device.hpp:hull_faces)
     bool face_groups = true;        // ... and an index of the faces by the set of hull axes their boxes are thin on (hull_faces)
     // per-bounce kernels: the first trace launch makes the primaries it traces (no k_primary; k_trace's PRIM variant, planar camera).

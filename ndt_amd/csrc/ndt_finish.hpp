@@ -19,6 +19,24 @@ template <bool COH> __device__ __forceinline__ int fin_ldi(const int *p)
     return *p;
 }
 
+// Which part of a frame's primaries node g belongs to (option early_pixels).  Decided from words that are
+// final once shade_emit(0) has run, so every launch that asks gets the same answer, and the parts are disjoint and complete:
+//   1  the primary missed (or hit closer than EPSILON: shade_emit cleared hit_obj): its colour and count are shade_emit(0)'s,
+//      resolve_node does nothing for it;
+//   2  it hit and has no child at all (-1 and -1 exactly): final once shade_finish(0) has lit it, resolve_node rewrites its
+//      colour and count unchanged;
+//   0  everything else: a child node, a child that was cut off (-2 blends black), a padding slot (depth_left <= 0).
+// A missed primary costs two words, a hit one four.
+#define NDT_PART_REST 0
+#define NDT_PART_MISSED 1
+#define NDT_PART_CHILDLESS 2
+__device__ __forceinline__ int pixel_part(const Workspace &ws, long long g)
+{
+    if (ws.depth_left[g] <= 0) return NDT_PART_REST;
+    if (ws.hit_obj[g] < 0) return NDT_PART_MISSED;
+    return (ws.child_refl[g] == -1 && ws.child_refr[g] == -1) ? NDT_PART_CHILDLESS : NDT_PART_REST;
+}
+
 // get_pixel_color's adaptive loop (ndt.c:488-568) replayed on the one deterministic sample:
 // with samples == 1 the reference re-traces the identical ray k times, k decided by the
 // running-mean test below; the result is (c+...+c)/k and the k-fold ray count.

@@ -311,6 +311,15 @@ __global__ void __launch_bounds__(256) k_resolve(const double *blob, SceneDesc s
 #ifndef NDT_FINISH_BLOCK
 #define NDT_FINISH_BLOCK 256
 #endif
+// What a finish launch adds to the frame's reference-equivalent ray count (every thread of the workgroup calls this): wavefront
+// sum, then one atomic per wavefront spread over 64 cache lines (a single word saturates near 90 atomics/us, and there are 32k
+// wavefronts at 1080p)
+__device__ __forceinline__ void add_ref_rays(const Workspace &ws, unsigned long long weighted)
+{
+    for (int d = 32; d > 0; d >>= 1) weighted += __shfl_down(weighted, d, 64);
+    if ((threadIdx.x & 63) == 0 && weighted) atomicAdd(ws.ref_rays + 8 * ((blockIdx.x * (NDT_FINISH_BLOCK / 64) + (threadIdx.x >> 6)) & 63), weighted);
+}
+
 __global__ void __launch_bounds__(NDT_FINISH_BLOCK) k_finish_pixels(const double *blob, SceneDesc sd, Workspace ws, RenderGeom rg, int N_,
                                                        double *rgba, double *depth_out, int resolve0)
 {
@@ -318,10 +327,23 @@ __global__ void __launch_bounds__(NDT_FINISH_BLOCK) k_finish_pixels(const double
     unsigned long long weighted = 0ull;
     if (resolve0 && g < rg.n_primary) resolve_node(blob, sd, ws, rg.specular, g);
     if (g < rg.n_primary && ws.depth_left[g] > 0) weighted = finish_pixel<false>(blob, sd, ws, rg, N_, g, rgba, depth_out);
-    // wavefront sum, then one atomic per wavefront spread over 64 cache lines (a single word
-    // saturates near 90 atomics/us, and there are 32k wavefronts at 1080p)
-    for (int d = 32; d > 0; d >>= 1) weighted += __shfl_down(weighted, d, 64);
-    if ((threadIdx.x & 63) == 0 && weighted) atomicAdd(ws.ref_rays + 8 * ((blockIdx.x * (NDT_FINISH_BLOCK / 64) + (threadIdx.x >> 6)) & 63), weighted);
+    add_ref_rays(ws, weighted);
+}
+
+// early_pixels: the pixels of the parts in `take` (bit p: part p of pixel_part) and no others.  Launched early for part 1 or 2
+// on the light stream, and as the frame's final launch for the parts no early launch took; a frame without early launches keeps
+// k_finish_pixels above.  A pixel that is not taken is left alone -- resolve_node is not idempotent -- after the two to four
+// words pixel_part reads.  The sums of ref_rays are integers: whichever launch adds a pixel's share, the total is the same.
+__global__ void __launch_bounds__(NDT_FINISH_BLOCK) k_finish_part(const double *blob, SceneDesc sd, Workspace ws, RenderGeom rg, int N_,
+                                                     double *rgba, double *depth_out, int resolve0, int take)
+{
+    const long long g = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    unsigned long long weighted = 0ull;
+    if (g < rg.n_primary && ((take >> pixel_part(ws, g)) & 1)) {
+        if (resolve0) resolve_node(blob, sd, ws, rg.specular, g);
+        if (ws.depth_left[g] > 0) weighted = finish_pixel<false>(blob, sd, ws, rg, N_, g, rgba, depth_out);
+    }
+    add_ref_rays(ws, weighted);
 }
 
 // max_optic_depth <= 0: get_ray_color returns black without tracing (ndt.c:340)
@@ -402,6 +424,14 @@ static void launch_finish_pixels(ndt_hip_ctx *ctx, const SceneDesc &sd_pass, con
 {
     hipLaunchKernelGGL(k_finish_pixels, dim3((unsigned)((rg.n_primary + NDT_FINISH_BLOCK - 1) / NDT_FINISH_BLOCK)), dim3(NDT_FINISH_BLOCK), 0, ctx->stream,
                        ctx->d_blob, sd_pass, ws, rg, ctx->dims, (double *)d_rgba, (double *)d_depth, resolve0);
+}
+
+// early_pixels: the parts in `take` only, on stream `on`
+static void launch_finish_part(ndt_hip_ctx *ctx, hipStream_t on, const SceneDesc &sd_pass, const Workspace &ws, const RenderGeom &rg, void *d_rgba,
+                               void *d_depth, int resolve0, int take)
+{
+    hipLaunchKernelGGL(k_finish_part, dim3((unsigned)((rg.n_primary + NDT_FINISH_BLOCK - 1) / NDT_FINISH_BLOCK)), dim3(NDT_FINISH_BLOCK), 0, on,
+                       ctx->d_blob, sd_pass, ws, rg, ctx->dims, (double *)d_rgba, (double *)d_depth, resolve0, take);
 }
 
 // The frame kernel's arguments for a forest rooted at node slots [begin, begin + count): the primaries of a whole frame, or the
@@ -534,6 +564,12 @@ struct FrameInFlight {
     hipEvent_t ev_lit[3] = { nullptr, nullptr, nullptr };
     int light_next = 0;                         // the first bounce whose lighting has not gone to the light stream
     hipEvent_t light_tail = nullptr;            // the light stream's last event, while the main stream has not waited for it
+    // Option early_pixels (where `overlap` holds): the pixels of primaries that are final long before the end of the frame are
+    // finished on the light stream -- part 1 (missed) beside trace launch 1, part 2 (hit, no child) behind shade_finish(0) --
+    // and the frame's final launch takes the parts that were not launched in this attempt (early_pixels_beside)
+    const int early;                            // 0 none, 1 part 1, 2 parts 1 and 2
+    int early_done = 0;                         // bit p: part p was launched early in this attempt
+    hipEvent_t ev_early = nullptr;              // on the light stream behind the launch of part 1
     std::vector<SceneDesc> sd_win;
     int win_emits = 0;
     unsigned long long tag = 0;
@@ -557,7 +593,8 @@ struct FrameInFlight {
     FrameInFlight(ndt_hip_ctx *c, const RenderGeom &g, const SceneDesc &sd, bool p, bool hyb, void *rgba, void *depth)
         : ctx(c), rg(g), sd_pass(sd), prof(p), hybrid(hyb), d_rgba(rgba), d_depth(depth), s(c->stream), kt(c->kt), ws(c->ws),
           n_levels(g.max_depth > 1 ? g.max_depth : 1), hand(hyb ? c->hybrid_level : n_levels + 1), n_win((int)c->windows.size()),
-          windowed(n_win > 1), overlap(c->light_overlap && !windowed && !hyb), ls(c->light_stream), n_run(n_levels)
+          windowed(n_win > 1), overlap(c->light_overlap && !windowed && !hyb), ls(c->light_stream), early(overlap ? c->early_pixels : 0),
+          n_run(n_levels)
     {
         ws.mail = ctx->d_mail;
         ws.mail_tag = ctx->d_mail_tag;
@@ -573,6 +610,8 @@ struct FrameInFlight {
     int trace_primaries();
     void light_and_shade(int b, long long upper);
     int light_beside(int b);
+    int early_pixels_beside(int part);
+    int mark_light_tail(hipEvent_t ev);
     hipError_t join_light();
     int trace_bounce(int b, long long upper);
     int trace_windows(int b, long long upper);
@@ -610,9 +649,36 @@ hipError_t FrameInFlight::join_light()
 int FrameInFlight::light_beside(int b)
 {
     kt->shade_finish(ls, ctx->d_blob, sd_pass, shade_ws(level_nodes[b], b, ls), rg, b, level_nodes[b], 0);
-    HIP_TRY(hipEventRecord(ev_lit[b % 3], ls));
-    light_tail = ev_lit[b % 3];
+    // (early_pixels 2: the primaries without a child are final now; their pixels go directly behind, ahead of the event)
+    int rc;
+    if (b == 0 && early >= 2 && (rc = early_pixels_beside(NDT_PART_CHILDLESS))) return rc;
+    if ((rc = mark_light_tail(ev_lit[b % 3]))) return rc;
     light_next = b + 1;
+    return NDT_OK;
+}
+
+// early_pixels: the pixels of one part of the primaries on the light stream, with nothing to wait for and no marker on the main
+// stream.  Part 1: the caller has seen the mailbox tag of bounce 1, which the prologue of trace launch 1 posted -- the main stream
+// has passed shade_emit(0), which wrote everything pixel_part and a missed primary's pixel read; the launch runs as trace launch 1
+// drains, and its own event becomes the light stream's tail.  Part 2: the caller has just put shade_finish(0) on this stream and
+// records the event behind both.  Either way the joins that order the main stream behind the lighting order it behind this.
+int FrameInFlight::early_pixels_beside(int part)
+{
+    launch_finish_part(ctx, ls, sd_pass, ws, rg, d_rgba, d_depth, 0, 1 << part);
+    early_done |= 1 << part;
+    return part == NDT_PART_MISSED ? mark_light_tail(ev_early) : NDT_OK;
+}
+
+// `ev` behind whatever has just been put on the light stream: from now on the joins wait for it.  If the event cannot be
+// recorded no join could cover those launches, so the host waits for the light stream here, before the error goes out
+int FrameInFlight::mark_light_tail(hipEvent_t ev)
+{
+    const hipError_t e = hipEventRecord(ev, ls);
+    if (e != hipSuccess) {
+        (void)hipStreamSynchronize(ls);
+        return fail(NDT_E_DEVICE, "hipEventRecord on the light stream: %s", hipGetErrorString(e));
+    }
+    light_tail = ev;
     return NDT_OK;
 }
 
@@ -632,6 +698,7 @@ int FrameInFlight::render_frame(long long &cap, long long &sh_cap, ndt_render_st
             // b - 2: the lighting of bounce b - 2 can go (light_overlap)
             if ((rc = wait_for_tag(ctx, &ctx->h_mail_tag[b], tag, "bounce %d was never published", b))) return rc;
             upper = ctx->h_mail[b].count;
+            if (early >= 1 && b == 1 && (rc = early_pixels_beside(NDT_PART_MISSED))) return rc;
             if (overlap && b >= 2 && (rc = light_beside(b - 2))) return rc;
             if (upper <= 0) {
                 n_run = b;
@@ -654,7 +721,9 @@ int FrameInFlight::render_frame(long long &cap, long long &sh_cap, ndt_render_st
     if (hybrid && n_run >= hand && hand < n_levels && (rc = hand_off(cap))) return rc;
     HIP_TRY(join_light());                  // the resolve reads the colours every bounce's lighting left
     resolve();
-    launch_finish_pixels(ctx, sd_pass, ws, rg, d_rgba, d_depth, n_run >= 1 ? 1 : 0);
+    // (early_pixels: the parts that went to the light stream in this attempt are finished; the final launch takes the others)
+    if (early_done) launch_finish_part(ctx, s, sd_pass, ws, rg, d_rgba, d_depth, n_run >= 1 ? 1 : 0, 7 & ~early_done);
+    else launch_finish_pixels(ctx, sd_pass, ws, rg, d_rgba, d_depth, n_run >= 1 ? 1 : 0);
     if ((rc = close())) return rc;
     return report(cap, sh_cap, st);
 }
@@ -670,6 +739,7 @@ int FrameInFlight::frame_init(long long &sh_cap)
     }
     for (int p = 0; overlap && p < 3; ++p)
         if (!(ev_lit[p] = get_event(ctx, ev_n++))) return fail(NDT_E_DEVICE, "hipEventCreate failed");
+    if (early && !(ev_early = get_event(ctx, ev_n++))) return fail(NDT_E_DEVICE, "hipEventCreate failed");
     if (prof && ctx->exit_probe)
         HIP_TRY(hipMemsetAsync(ws.exit_log, 0, (size_t)NDT_EXIT_LOG_LAUNCHES * NDT_EXIT_LOG_WORDS * sizeof(unsigned int), s));
     tag = ++ctx->frame_tag;
