@@ -461,6 +461,48 @@ int ndt_hip_render_ssaa_rgba8_depth(ndt_hip_ctx *ctx, const ndt_render_params *p
 int ndt_hip_ssaa_launches(ndt_hip_ctx *ctx);
 double ndt_hip_ssaa_ms(ndt_hip_ctx *ctx);
 
+/* 16 bits a sample (`ndt_hip --png16`): the frame and its depth map as PNG files of bit depth 16, made on the device from the
+ * double framebuffer -- every other file passes through pixel_d2c's 256 levels.  A sample is
+ *     q16(x) = (uint16_t)(sqrt(m) * 65535),   m = x clamped to 0 .. 1 by pixel_d2c's two comparisons in their order,
+ * stored most significant byte first, as the file has it.  The colour file is colour type 6 (RGBA, 8 bytes a pixel), the
+ * map's colour type 0 (grey, 2 bytes a pixel) with the value q16(hi > lo ? (d - lo) / (hi - lo) : 0.0) of
+ * ndt_hip_depth_rgba8_device's lo / hi.  One IDAT, no interlace.  The row heuristic is the 8-bit file's with the pixel's width as
+ * a parameter (Sub looks 8 or 2 bytes to the left; row stride 1 + 8 * width or 1 + 2 * width), and the deflate, assemble and
+ * place kernels are the 8-bit file's own: the same image gives the same bytes.
+ *   ndt_hip_quantize16_device    d_rgba: n_pixels * 4 doubles (device, aligned to 16 bytes); d_rgba16: n_pixels * 8 bytes (device,
+ *                                aligned to 8): q16 of every channel in file byte order.  One launch, on the context's stream;
+ *                                not synchronised, like ndt_hip_quantize_device.
+ *   ndt_hip_depth_grey16_device  ndt_hip_depth_rgba8_device with one grey sample a pixel: d_grey16 = n_pixels * 2 bytes (device,
+ *                                aligned to 4).  The same two launches, range and refusal of a NaN or an infinity.
+ *   ndt_hip_png16_bound          the largest file for width x rows with channels = 4 (RGBA) or 1 (grey); < 0 (NDT_E_INVALID) for
+ *                                other channel counts and for a size the encoder does not take: the 8-bit limit (a filtered
+ *                                stream of at most 2^31 - 1 bytes) with this stride
+ *   ndt_hip_encode_png16_device / ndt_hip_encode_png16   the file of width * rows * channels samples in file byte order, in the
+ *                                context's device memory (aligned to the pixel: 8 or 2 bytes) or in host memory.  Errors and
+ *                                stats are those of ndt_hip_encode_png_device / ndt_hip_encode_png.  No scene is needed.
+ *   ndt_hip_render_png16         ndt_hip_render_device, ndt_hip_quantize16_device and the encoder: every mode of ndt_hip_render_png
+ *   ndt_hip_render_png16_depth   ndt_hip_render_png_depth with both files at 16 bits; stats: two records.  Accepts and refuses
+ *                                what ndt_hip_render_depth does
+ *   ndt_hip_render_ssaa_png16 / _png16_depth   the same for the ssaa frame: q16 of the finished accumulator (one launch behind
+ *                                the last fold) and, for the map, of sub-sample (0, 0)'s
+ * Device buffers belong to the context, only grow and are reused.  The calls return when the file is in host memory.  None falls
+ * back. */
+int ndt_hip_quantize16_device(ndt_hip_ctx *ctx, const void *d_rgba, void *d_rgba16, int64_t n_pixels);
+int ndt_hip_depth_grey16_device(ndt_hip_ctx *ctx, const void *d_depth, int64_t n_pixels, void *d_grey16, double *range_out);
+int64_t ndt_hip_png16_bound(int32_t width, int32_t rows, int32_t channels);
+int ndt_hip_encode_png16_device(ndt_hip_ctx *ctx, const void *d_samples, int32_t width, int32_t rows, int32_t channels, uint8_t *png,
+                                int64_t cap, ndt_png_stats *stats);
+int ndt_hip_encode_png16(ndt_hip_ctx *ctx, const uint8_t *samples, int32_t width, int32_t rows, int32_t channels, uint8_t *png,
+                         int64_t cap, ndt_png_stats *stats);
+int ndt_hip_render_png16(ndt_hip_ctx *ctx, const ndt_render_params *p, uint8_t *png, int64_t cap, ndt_png_stats *stats,
+                         ndt_render_stats *render_stats);
+int ndt_hip_render_png16_depth(ndt_hip_ctx *ctx, const ndt_render_params *p, uint8_t *png, int64_t cap, uint8_t *depth_png,
+                               int64_t depth_cap, ndt_png_stats *stats, double *range_out, ndt_render_stats *render_stats);
+int ndt_hip_render_ssaa_png16(ndt_hip_ctx *ctx, const ndt_render_params *p, int32_t K, uint8_t *png, int64_t cap, ndt_png_stats *stats,
+                              ndt_render_stats *render_stats);
+int ndt_hip_render_ssaa_png16_depth(ndt_hip_ctx *ctx, const ndt_render_params *p, int32_t K, uint8_t *png, int64_t cap, uint8_t *depth_png,
+                                    int64_t depth_cap, ndt_png_stats *stats, double *range_out, ndt_render_stats *render_stats);
+
 /* ONE frame over several contexts -- one per GPU of the node, or several on one GPU -- called from one host thread.
  * The rows `p` selects are dealt cyclically to the contexts exactly as the reference deals rows to MPI ranks in
  * MPI_MODE_ROW (ndt.c:812-820: row_start = rank, row_step = size): context k renders rows

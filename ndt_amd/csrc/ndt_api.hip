@@ -265,6 +265,44 @@ extern "C" int ndt_hip_quantize_device(ndt_hip_ctx *ctx, const void *d_rgba, voi
     return NDT_OK;
 }
 
+int ndt_impl::ensure_out(ndt_hip_ctx *ctx, size_t bytes)
+{
+    if (ctx->d_out_bytes >= bytes) return NDT_OK;
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    if (ctx->d_out) HIP_TRY(hipFree(ctx->d_out));
+    ctx->d_out = nullptr;
+    ctx->d_out_bytes = 0;
+    HIP_TRY(hipMalloc(&ctx->d_out, bytes));
+    ctx->d_out_bytes = bytes;
+    return NDT_OK;
+}
+
+// one lane a pixel: four doubles in (two 16-byte loads), four samples out as one 8-byte store
+__global__ void __launch_bounds__(256) k_quantize16(const double2 *__restrict__ rgba, uint2 *out, long long n_pixels)
+{
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n_pixels) return;
+    const double2 rg = rgba[2 * i], ba = rgba[2 * i + 1];
+    uint2 px;
+    px.x = q16_file_order(rg.x) | (q16_file_order(rg.y) << 16);
+    px.y = q16_file_order(ba.x) | (q16_file_order(ba.y) << 16);
+    out[i] = px;
+}
+
+extern "C" int ndt_hip_quantize16_device(ndt_hip_ctx *ctx, const void *d_rgba, void *d_rgba16, int64_t n_pixels)
+{
+    if (!ctx || !d_rgba || !d_rgba16 || n_pixels < 0) return fail(NDT_E_INVALID, "ndt_hip_quantize16_device: bad argument");
+    if (((uintptr_t)d_rgba & 15u) != 0 || ((uintptr_t)d_rgba16 & 7u) != 0)
+        return fail(NDT_E_INVALID, "ndt_hip_quantize16_device: the doubles must be aligned to 16 bytes, the samples to their 8-byte pixels");
+    if (n_pixels > 0x7fffffffLL * 256) return fail(NDT_E_INVALID, "ndt_hip_quantize16_device: %lld pixels", (long long)n_pixels);
+    HIP_TRY(hipSetDevice(ctx->device));
+    if (n_pixels == 0) return NDT_OK;
+    hipLaunchKernelGGL(k_quantize16, dim3((unsigned)((n_pixels + 255) / 256)), dim3(256), 0, ctx->stream, (const double2 *)d_rgba,
+                       (uint2 *)d_rgba16, (long long)n_pixels);
+    HIP_TRY(hipGetLastError());
+    return NDT_OK;
+}
+
 // ------------------------------------------------------------------ trace_kd batches
 
 extern "C" int ndt_hip_trace_rays(ndt_hip_ctx *ctx, int64_t n_rays, const double *o, const double *v, const double *dist_limit,

@@ -47,6 +47,17 @@ using namespace ndt_impl;
         if (e_ != hipSuccess) return fail(NDT_E_DEVICE, "%s: %s", #expr, hipGetErrorString(e_));   \
     } while (0)
 
+// q16, the 16-bit sample of every 16-bit file: pixel_d2c's clamp (the same two comparisons in the same order) and square root,
+// scaled to 65535; the sample's two bytes come back in the order a PNG file has them (most significant first) in the low half.
+// The one definition: k_quantize16 (ndt_api.hip) and k_depth_finish<true> (ndt_depth.hip) both call it.
+__device__ __forceinline__ unsigned int q16_file_order(double d)
+{
+    double m = (1.0 < d) ? 1.0 : d;
+    m = (0.0 > m) ? 0.0 : m;
+    const unsigned int v = (unsigned int)(unsigned short)(sqrt(m) * 65535);
+    return (v >> 8) | ((v & 255u) << 8);
+}
+
 // ndt_hip_build_kdtree (ndt_kd.hip): grow-only device buffers, reused by the next build, and the last tree in its final layout
 struct KdState {
     void *d_bounds = nullptr, *d_refs = nullptr, *d_nodes = nullptr, *d_slices = nullptr, *d_slice_off[2] = { nullptr, nullptr }, *d_totals = nullptr;
@@ -65,6 +76,8 @@ struct PngState {
     size_t rgba8_bytes = 0, filtered_bytes = 0, row_filter_bytes = 0, slots_bytes = 0, meta_bytes = 0, offsets_bytes = 0, file_bytes = 0,
            info_bytes = 0;
     void *h_info = nullptr;         // pinned: the info record of the last file
+    void *d_rgba16 = nullptr;       // ndt_hip_render_png16: the frame's 16-bit samples in file byte order
+    size_t rgba16_bytes = 0;
 };
 
 // ndt_hip_encode_jpeg* (ndt_jpeg.hip): grow-only device buffers, reused by the next frame
@@ -78,7 +91,8 @@ struct JpegState {
 struct DepthState {
     void *d_records = nullptr;      // one {lo, hi, bad} record per workgroup of k_depth_range, and the folded one behind them
     void *d_rgba8 = nullptr, *d_depth8 = nullptr;       // the two 8-bit images of ndt_hip_render_*_depth
-    size_t records_bytes = 0, rgba8_bytes = 0, depth8_bytes = 0;
+    void *d_rgba16 = nullptr, *d_grey16 = nullptr;      // the two 16-bit images of ndt_hip_render_png16_depth (file byte order)
+    size_t records_bytes = 0, rgba8_bytes = 0, depth8_bytes = 0, rgba16_bytes = 0, grey16_bytes = 0;
     void *h_result = nullptr;       // pinned: the folded record of the last map
     int launches = 0;               // kernel launches of the last map
     double finish_ms = 0.0;         // host time of the last map: launch to the folded record in host memory
@@ -89,7 +103,8 @@ struct SsaaState {
     void *d_pass = nullptr;         // one pass of the large frame: rows x K width x 4 doubles, and its depth map behind them when wanted
     void *d_acc = nullptr;          // the frame of the calls that deliver to host memory or as a file: rows x width x 4 doubles (+ the map)
     void *d_rgba8 = nullptr, *d_depth8 = nullptr;       // its 8-bit image (written by the last fold) and finished map
-    size_t pass_bytes = 0, acc_bytes = 0, rgba8_bytes = 0, depth8_bytes = 0;
+    void *d_rgba16 = nullptr, *d_grey16 = nullptr;      // ndt_hip_render_ssaa_png16*: the 16-bit samples of the accumulator and of the map
+    size_t pass_bytes = 0, acc_bytes = 0, rgba8_bytes = 0, depth8_bytes = 0, rgba16_bytes = 0, grey16_bytes = 0;
     hipEvent_t ev[16] = {};         // around every fold launch of a frame
     int launches = 0;               // fold launches of the last frame
     int factor = 0;                 // its K
@@ -282,6 +297,9 @@ void free_kd(ndt_hip_ctx *ctx);
 
 // ndt_png.hip
 void free_png(ndt_hip_ctx *ctx);
+
+// ndt_api.hip: ctx->d_out, the staging of a frame in doubles (and its map behind it), grown to `bytes`
+int ensure_out(ndt_hip_ctx *ctx, size_t bytes);
 
 // ndt_jpeg.hip
 void free_jpeg(ndt_hip_ctx *ctx);

@@ -3,7 +3,8 @@
 //
 //   k_depth_range    every workgroup reduces its share of the map to one {lo, hi, bad} record
 //   k_depth_finish   every workgroup folds the records itself (no third launch, nobody waits for anybody), then normalises and
-//                    quantises its share of the map: one 32-bit store a pixel
+//                    quantises its share of the map: one 32-bit store a pixel (g, g, g, 255), or -- SIXTEEN -- one 16-bit grey
+//                    sample a lane in a PNG file's byte order, two lanes' samples in one 32-bit store
 //
 // The host loop compares `x < lo` and `x > hi` starting from element 0.  For a map without NaN that is the minimum and the
 // maximum, whatever the order (signed zeros compare equal: which zero's sign the range carries is the fold order's, and no byte
@@ -84,9 +85,11 @@ __device__ __forceinline__ unsigned int depth_d2c(double d)
     return (unsigned int)(unsigned char)(sqrt(m) * 255);
 }
 
+// `out`: n 4-byte pixels, or -- SIXTEEN -- n 2-byte samples from a 4-byte aligned address
+template <bool SIXTEEN>
 __global__ void __launch_bounds__(DEPTH_FINISH_LANES) k_depth_finish(const double *__restrict__ depth, long long n,
                                                                      const DepthRecord *__restrict__ records, int n_records,
-                                                                     unsigned int *rgba8, DepthRecord *result)
+                                                                     void *out, DepthRecord *result)
 {
     double lo = INFINITY, hi = -INFINITY;
     long long bad = -1;
@@ -111,10 +114,19 @@ __global__ void __launch_bounds__(DEPTH_FINISH_LANES) k_depth_finish(const doubl
 #pragma unroll
         for (int u = 0; u < DEPTH_UNROLL; ++u) {
             const long long i = at + u * stride;
-            if (i < n) {
+            if (SIXTEEN) {
+                // every lane of the wavefront is here (the trip count is the map size's alone) and pixel i is even where the
+                // lane is (the stride is even): lane 2k takes lane 2k + 1's sample and stores the two as one word
+                const unsigned int v16 = q16_file_order(spread ? (x[u] - lo) / width : 0.0);
+                const unsigned int next = __shfl_down(v16, 1, 64);
+                if ((i & 1) == 0) {
+                    if (i + 1 < n) reinterpret_cast<unsigned int *>(out)[i >> 1] = v16 | (next << 16);
+                    else if (i < n) reinterpret_cast<unsigned short *>(out)[i] = (unsigned short)v16;       // the last of an odd n
+                }
+            } else if (i < n) {
                 const double v = spread ? (x[u] - lo) / width : 0.0;
                 const unsigned int v8 = depth_d2c(v);
-                rgba8[i] = v8 | (v8 << 8) | (v8 << 16) | (255u << 24);      // depth_d2c(1.0) = 255: the alpha
+                reinterpret_cast<unsigned int *>(out)[i] = v8 | (v8 << 8) | (v8 << 16) | (255u << 24);      // depth_d2c(1.0) = 255: the alpha
             }
         }
     }
@@ -133,10 +145,10 @@ int grow(ndt_hip_ctx *ctx, void **buf, size_t *have, size_t want)
     return NDT_OK;
 }
 
-// ndt_hip_render_depth_device into the context's buffers, then both 8-bit images in HBM: ds.d_rgba8 (the quantised image) and
-// ds.d_depth8 (the finished map).  *pixels = 0: the shard has no rows (nothing was made).
-int render_both_8bit(ndt_hip_ctx *ctx, const ndt_render_params *p, double *range_out, ndt_render_stats *stats, int *rows_out,
-                     size_t *pixels_out)
+// ndt_hip_render_depth_device into the context's buffers, then both images in HBM: at 8 bits ds.d_rgba8 (the quantised image)
+// and ds.d_depth8 (the finished map), at 16 ds.d_rgba16 and ds.d_grey16.  *pixels = 0: the shard has no rows (nothing was made).
+int render_both(ndt_hip_ctx *ctx, const ndt_render_params *p, bool sixteen, double *range_out, ndt_render_stats *stats, int *rows_out,
+                size_t *pixels_out)
 {
     HIP_TRY(hipSetDevice(ctx->device));
     const int rows = ndt_hip_shard_rows(p->height, p->row_begin, p->row_step);
@@ -147,44 +159,29 @@ int render_both_8bit(ndt_hip_ctx *ctx, const ndt_render_params *p, double *range
     // (a frame without pixels: the render call says what is wrong with it, or that nothing is)
     if (pixels == 0) return ndt_hip_render_depth_device(ctx, p, (void *)ctx, nullptr, stats);
     const size_t img_bytes = pixels * 4 * sizeof(double), bytes = img_bytes + img_bytes / 4;       // the map sits behind the image
-    if (ctx->d_out_bytes < bytes) {
-        HIP_TRY(hipStreamSynchronize(ctx->stream));
-        if (ctx->d_out) HIP_TRY(hipFree(ctx->d_out));
-        ctx->d_out = nullptr;
-        ctx->d_out_bytes = 0;
-        HIP_TRY(hipMalloc(&ctx->d_out, bytes));
-        ctx->d_out_bytes = bytes;
-    }
     DepthState &ds = ctx->depth;
     int rc;
-    if ((rc = grow(ctx, &ds.d_rgba8, &ds.rgba8_bytes, pixels * 4))) return rc;
-    if ((rc = grow(ctx, &ds.d_depth8, &ds.depth8_bytes, pixels * 4))) return rc;
+    if ((rc = ensure_out(ctx, bytes))) return rc;
+    if (sixteen) {
+        if ((rc = grow(ctx, &ds.d_rgba16, &ds.rgba16_bytes, pixels * 8))) return rc;
+        if ((rc = grow(ctx, &ds.d_grey16, &ds.grey16_bytes, (pixels * 2 + 3) & ~(size_t)3))) return rc;
+    } else {
+        if ((rc = grow(ctx, &ds.d_rgba8, &ds.rgba8_bytes, pixels * 4))) return rc;
+        if ((rc = grow(ctx, &ds.d_depth8, &ds.depth8_bytes, pixels * 4))) return rc;
+    }
     void *d_depth = (char *)ctx->d_out + img_bytes;
     if ((rc = ndt_hip_render_depth_device(ctx, p, ctx->d_out, d_depth, stats))) return rc;
+    if (sixteen) {
+        if ((rc = ndt_hip_depth_grey16_device(ctx, d_depth, (int64_t)pixels, ds.d_grey16, range_out))) return rc;
+        return ndt_hip_quantize16_device(ctx, ctx->d_out, ds.d_rgba16, (int64_t)pixels);
+    }
     if ((rc = ndt_hip_depth_rgba8_device(ctx, d_depth, (int64_t)pixels, ds.d_depth8, range_out))) return rc;
     return ndt_hip_quantize_device(ctx, ctx->d_out, ds.d_rgba8, (int64_t)pixels);
 }
 
-} // namespace
-
-void ndt_impl::free_depth(ndt_hip_ctx *ctx)
+// the two launches over a map of n_pixels doubles; `who` names the entry point in errors
+int finish_map(ndt_hip_ctx *ctx, const char *who, bool sixteen, const void *d_depth, int64_t n_pixels, void *d_out, double *range_out)
 {
-    DepthState &ds = ctx->depth;
-    void **bufs[] = { &ds.d_records, &ds.d_rgba8, &ds.d_depth8 };
-    for (void **b : bufs) {
-        if (*b) (void)hipFree(*b);
-        *b = nullptr;
-    }
-    if (ds.h_result) (void)hipHostFree(ds.h_result);
-    ds = DepthState();
-}
-
-extern "C" int ndt_hip_depth_rgba8_device(ndt_hip_ctx *ctx, const void *d_depth, int64_t n_pixels, void *d_rgba8, double *range_out)
-{
-    if (!ctx || !d_depth || !d_rgba8) return fail(NDT_E_INVALID, "ndt_hip_depth_rgba8_device: NULL argument");
-    if (n_pixels < 1) return fail(NDT_E_INVALID, "ndt_hip_depth_rgba8_device: a map of %lld pixels", (long long)n_pixels);
-    if (((uintptr_t)d_depth & 7u) != 0 || ((uintptr_t)d_rgba8 & 3u) != 0)
-        return fail(NDT_E_INVALID, "ndt_hip_depth_rgba8_device: the map is not aligned to its doubles, or the image not to its 4-byte pixels");
     const auto t0 = std::chrono::steady_clock::now();
     HIP_TRY(hipSetDevice(ctx->device));
     DepthState &ds = ctx->depth;
@@ -202,8 +199,12 @@ extern "C" int ndt_hip_depth_rgba8_device(ndt_hip_ctx *ctx, const void *d_depth,
     const int n_groups = (int)(want_groups < DEPTH_FINISH_GROUPS ? want_groups : DEPTH_FINISH_GROUPS);
     hipStream_t s = ctx->stream;
     hipLaunchKernelGGL(k_depth_range, dim3((unsigned)n_records), dim3(DEPTH_RANGE_LANES), 0, s, (const double *)d_depth, n, records);
-    hipLaunchKernelGGL(k_depth_finish, dim3((unsigned)n_groups), dim3(DEPTH_FINISH_LANES), 0, s, (const double *)d_depth, n,
-                       (const DepthRecord *)records, n_records, (unsigned int *)d_rgba8, result);
+    if (sixteen)
+        hipLaunchKernelGGL(k_depth_finish<true>, dim3((unsigned)n_groups), dim3(DEPTH_FINISH_LANES), 0, s, (const double *)d_depth, n,
+                           (const DepthRecord *)records, n_records, d_out, result);
+    else
+        hipLaunchKernelGGL(k_depth_finish<false>, dim3((unsigned)n_groups), dim3(DEPTH_FINISH_LANES), 0, s, (const double *)d_depth, n,
+                           (const DepthRecord *)records, n_records, d_out, result);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(ds.h_result, result, sizeof(DepthRecord), hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
@@ -211,12 +212,44 @@ extern "C" int ndt_hip_depth_rgba8_device(ndt_hip_ctx *ctx, const void *d_depth,
     ds.finish_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     const DepthRecord r = *(const DepthRecord *)ds.h_result;
     if (r.bad >= 0)
-        return fail(NDT_E_UNSUPPORTED, "ndt_hip_depth_rgba8_device: the depth map holds a NaN or an infinity (pixel %lld): there is no range to stretch", r.bad);
+        return fail(NDT_E_UNSUPPORTED, "%s: the depth map holds a NaN or an infinity (pixel %lld): there is no range to stretch", who, r.bad);
     if (range_out) {
         range_out[0] = r.lo;
         range_out[1] = r.hi;
     }
     return NDT_OK;
+}
+
+} // namespace
+
+void ndt_impl::free_depth(ndt_hip_ctx *ctx)
+{
+    DepthState &ds = ctx->depth;
+    void **bufs[] = { &ds.d_records, &ds.d_rgba8, &ds.d_depth8, &ds.d_rgba16, &ds.d_grey16 };
+    for (void **b : bufs) {
+        if (*b) (void)hipFree(*b);
+        *b = nullptr;
+    }
+    if (ds.h_result) (void)hipHostFree(ds.h_result);
+    ds = DepthState();
+}
+
+extern "C" int ndt_hip_depth_rgba8_device(ndt_hip_ctx *ctx, const void *d_depth, int64_t n_pixels, void *d_rgba8, double *range_out)
+{
+    if (!ctx || !d_depth || !d_rgba8) return fail(NDT_E_INVALID, "ndt_hip_depth_rgba8_device: NULL argument");
+    if (n_pixels < 1) return fail(NDT_E_INVALID, "ndt_hip_depth_rgba8_device: a map of %lld pixels", (long long)n_pixels);
+    if (((uintptr_t)d_depth & 7u) != 0 || ((uintptr_t)d_rgba8 & 3u) != 0)
+        return fail(NDT_E_INVALID, "ndt_hip_depth_rgba8_device: the map is not aligned to its doubles, or the image not to its 4-byte pixels");
+    return finish_map(ctx, "ndt_hip_depth_rgba8_device", false, d_depth, n_pixels, d_rgba8, range_out);
+}
+
+extern "C" int ndt_hip_depth_grey16_device(ndt_hip_ctx *ctx, const void *d_depth, int64_t n_pixels, void *d_grey16, double *range_out)
+{
+    if (!ctx || !d_depth || !d_grey16) return fail(NDT_E_INVALID, "ndt_hip_depth_grey16_device: NULL argument");
+    if (n_pixels < 1) return fail(NDT_E_INVALID, "ndt_hip_depth_grey16_device: a map of %lld pixels", (long long)n_pixels);
+    if (((uintptr_t)d_depth & 7u) != 0 || ((uintptr_t)d_grey16 & 3u) != 0)
+        return fail(NDT_E_INVALID, "ndt_hip_depth_grey16_device: the map is not aligned to its doubles, or the samples not to 4 bytes");
+    return finish_map(ctx, "ndt_hip_depth_grey16_device", true, d_depth, n_pixels, d_grey16, range_out);
 }
 
 extern "C" int ndt_hip_depth_launches(ndt_hip_ctx *ctx) { return ctx ? ctx->depth.launches : 0; }
@@ -228,7 +261,7 @@ extern "C" int ndt_hip_render_rgba8_depth(ndt_hip_ctx *ctx, const ndt_render_par
     if (!ctx || !p || !rgba8 || !depth8) return fail(NDT_E_INVALID, "ndt_hip_render_rgba8_depth: NULL argument");
     int rows = 0;
     size_t pixels = 0;
-    int rc = render_both_8bit(ctx, p, range_out, stats, &rows, &pixels);
+    int rc = render_both(ctx, p, false, range_out, stats, &rows, &pixels);
     if (rc || pixels == 0) return rc;
     HIP_TRY(hipMemcpyAsync(rgba8, ctx->depth.d_rgba8, pixels * 4, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipMemcpyAsync(depth8, ctx->depth.d_depth8, pixels * 4, hipMemcpyDeviceToHost, ctx->stream));
@@ -251,11 +284,30 @@ extern "C" int ndt_hip_render_png_depth(ndt_hip_ctx *ctx, const ndt_render_param
     if (stats) stats[0] = stats[1] = ndt_png_stats{};
     int rows = 0;
     size_t pixels = 0;
-    int rc = render_both_8bit(ctx, p, range_out, render_stats, &rows, &pixels);
+    int rc = render_both(ctx, p, false, range_out, render_stats, &rows, &pixels);
     if (rc) return rc;
     if ((rc = ndt_hip_encode_png_device(ctx, ctx->depth.d_rgba8, p->width, rows, png, cap, stats ? &stats[0] : nullptr))) return rc;
     if (depth_png) return ndt_hip_encode_png_device(ctx, ctx->depth.d_depth8, p->width, rows, depth_png, depth_cap, stats ? &stats[1] : nullptr);
     HIP_TRY(hipMemcpyAsync(depth8, ctx->depth.d_depth8, pixels * 4, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     return NDT_OK;
+}
+
+extern "C" int ndt_hip_render_png16_depth(ndt_hip_ctx *ctx, const ndt_render_params *p, uint8_t *png, int64_t cap, uint8_t *depth_png,
+                                          int64_t depth_cap, ndt_png_stats *stats, double *range_out, ndt_render_stats *render_stats)
+{
+    if (!ctx || !p || !png || !depth_png) return fail(NDT_E_INVALID, "ndt_hip_render_png16_depth: NULL argument");
+    if (p->width < 1 || p->height < 1 || p->row_step < 1 || p->row_begin < 0)
+        return fail(NDT_E_INVALID, "ndt_hip_render_png16_depth: bad geometry: %d x %d, rows %d by %d", p->width, p->height, p->row_begin, p->row_step);
+    const int shard = ndt_hip_shard_rows(p->height, p->row_begin, p->row_step);
+    if (shard < 1) return fail(NDT_E_INVALID, "ndt_hip_render_png16_depth: the shard has no rows");
+    if (ndt_hip_png16_bound(p->width, shard, 4) < 0)
+        return fail(NDT_E_INVALID, "ndt_hip_render_png16_depth: the filtered stream of a %d x %d image exceeds 2^31 - 1 bytes", p->width, shard);
+    if (stats) stats[0] = stats[1] = ndt_png_stats{};
+    int rows = 0;
+    size_t pixels = 0;
+    int rc = render_both(ctx, p, true, range_out, render_stats, &rows, &pixels);
+    if (rc) return rc;
+    if ((rc = ndt_hip_encode_png16_device(ctx, ctx->depth.d_rgba16, p->width, rows, 4, png, cap, stats ? &stats[0] : nullptr))) return rc;
+    return ndt_hip_encode_png16_device(ctx, ctx->depth.d_grey16, p->width, rows, 1, depth_png, depth_cap, stats ? &stats[1] : nullptr);
 }

@@ -1,8 +1,11 @@
 // ndt_png.hip -- a frame's PNG file made on the device: ndt_hip_png_bound / ndt_hip_encode_png_device / ndt_hip_encode_png /
-// ndt_hip_render_png.  The quantised image is in HBM already; what leaves the device is the finished file.
+// ndt_hip_render_png, and their 16-bit twins ndt_hip_png16_bound / ndt_hip_encode_png16* / ndt_hip_render_png16.  The quantised
+// image is in HBM already; what leaves the device is the finished file.
 //
 //   k_png_filter    one workgroup a scanline: filter 0 (None), 1 (Sub) or 2 (Up) by the smallest sum of |filtered byte as int8|
 //                   (ties to the lower number; row 0 has zeros above it), then the filtered stream, written as aligned words
+//   k_png_filter_wide<BPP>   the same for pixels of 8 bytes (16-bit RGBA) and 2 bytes (16-bit grey): the row as words, Sub
+//                   against the bytes BPP to the left
 //   k_png_deflate   one workgroup an independent 32 KiB chunk of that stream: distance-1 matches, a dynamic Huffman code of
 //                   its own, the bits packed into an LDS image with ds_or; a chunk the code does not shrink is stored; every
 //                   chunk but the last ends on a byte boundary (an empty stored block: 00 00 FF FF)
@@ -157,6 +160,110 @@ __global__ void __launch_bounds__(256) k_png_filter(const unsigned *__restrict__
         if (tid < 3 ? i < head : i < stride) {
             const long long q = i - 1;
             const unsigned f = filtered_pixel(cur, up, width, filter, (int)(q >> 2));
+            out[g0 + i] = (unsigned char)(f >> (8 * (int)(q & 3)));
+        }
+    }
+}
+
+// ------------------------------------------------------------------ the row filter for pixels of 2 and 8 bytes
+
+// Word k of a row of n_bytes bytes; every word before the row is zero, and so is every byte from n_bytes on.  A row of 8-byte
+// pixels is aligned to them; a row of 2-byte pixels to two bytes only, so its word is two 16-bit loads.
+template <int BPP>
+__device__ __forceinline__ unsigned row_word(const unsigned char *row, int n_bytes, int k)
+{
+    if (k < 0 || 4LL * k >= (long long)n_bytes) return 0u;
+    if (BPP == 8) return reinterpret_cast<const unsigned *>(row)[k];
+    const unsigned short *h = reinterpret_cast<const unsigned short *>(row);
+    const unsigned lo = h[2 * k], hi = 4LL * k + 2 < (long long)n_bytes ? (unsigned)h[2 * k + 1] : 0u;
+    return lo | (hi << 16);
+}
+
+// the row's bytes BPP to the left of word k's: two words back, or the other half of this word and of the one before
+template <int BPP>
+__device__ __forceinline__ unsigned left_word(const unsigned char *row, int n_bytes, int k, unsigned p)
+{
+    if (BPP == 8) return row_word<8>(row, n_bytes, k - 2);
+    return (p << 16) | (row_word<2>(row, n_bytes, k - 1) >> 16);
+}
+
+// the mask of word k's bytes that are inside the row
+__device__ __forceinline__ unsigned inside_mask(int n_bytes, int k)
+{
+    const long long left = (long long)n_bytes - 4LL * k;
+    return left >= 4 ? 0xffffffffu : left <= 0 ? 0u : (1u << (8 * (int)left)) - 1u;
+}
+
+// the filtered bytes of word k of a row; word -1 ends in the row's filter byte, bytes from n_bytes on are zero
+template <int BPP>
+__device__ __forceinline__ unsigned filtered_word(const unsigned char *cur, const unsigned char *up, int n_bytes, int filter, int k)
+{
+    if (k < 0) return (unsigned)filter << 24;
+    const unsigned p = row_word<BPP>(cur, n_bytes, k);
+    if (filter == 0) return p;
+    const unsigned other = filter == 1 ? left_word<BPP>(cur, n_bytes, k, p) : up ? row_word<BPP>(up, n_bytes, k) : 0u;
+    return bytes_sub(p, other) & inside_mask(n_bytes, k);
+}
+
+// k_png_filter for BPP = 8 or 2 bytes a pixel: the same workgroup a row, the same three sums reduced the same way, the same
+// aligned words with up to 3 head and tail bytes.  `image` is aligned to BPP.
+template <int BPP>
+__global__ void __launch_bounds__(256) k_png_filter_wide(const unsigned char *__restrict__ image, unsigned char *out, unsigned char *row_filter,
+                                                         int width, int rows)
+{
+    static_assert(BPP == 2 || BPP == 8, "16-bit grey or 16-bit RGBA");
+    __shared__ unsigned long long wave_sum[4][3];
+    __shared__ int chosen;
+    const int row = (int)blockIdx.x, tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int n_bytes = BPP * width, n_row_words = (int)(((long long)n_bytes + 3) >> 2);      // the stream is under 2^31 bytes
+    const unsigned char *cur = image + (long long)row * n_bytes, *up = row > 0 ? cur - n_bytes : nullptr;
+    unsigned long long s0 = 0, s1 = 0, s2 = 0;
+    for (int k = tid; k < n_row_words; k += 256) {
+        const unsigned p = row_word<BPP>(cur, n_bytes, k), l = left_word<BPP>(cur, n_bytes, k, p);
+        const unsigned u = up ? row_word<BPP>(up, n_bytes, k) : 0u, inside = inside_mask(n_bytes, k);
+        s0 += bytes_abs_sum(p);
+        s1 += bytes_abs_sum(bytes_sub(p, l) & inside);
+        s2 += bytes_abs_sum(bytes_sub(p, u) & inside);
+    }
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) {
+        s0 += __shfl_down(s0, d, 64);
+        s1 += __shfl_down(s1, d, 64);
+        s2 += __shfl_down(s2, d, 64);
+    }
+    if (lane == 0) { wave_sum[wave][0] = s0; wave_sum[wave][1] = s1; wave_sum[wave][2] = s2; }
+    __syncthreads();
+    if (tid == 0) {
+        unsigned long long t[3];
+        for (int f = 0; f < 3; ++f) t[f] = wave_sum[0][f] + wave_sum[1][f] + wave_sum[2][f] + wave_sum[3][f];
+        int f = 0;
+        unsigned long long best = t[0];
+        if (t[1] < best) { best = t[1]; f = 1; }
+        if (t[2] < best) f = 2;
+        chosen = f;
+        row_filter[row] = (unsigned char)f;
+    }
+    __syncthreads();
+    const int filter = chosen;
+    // the row is bytes [g0, g0 + stride) of the stream: whole aligned words from a0 on, single bytes before and after them
+    const long long stride = 1 + (long long)n_bytes, g0 = (long long)row * stride, a0 = (g0 + 3) & ~3LL;
+    const long long n_words = (g0 + stride - a0) >> 2;      // stride >= 3 >= a0 - g0
+    unsigned *out32 = reinterpret_cast<unsigned *>(out);
+    for (long long j = tid; j < n_words; j += 256) {
+        const long long q = a0 + 4 * j - g0 - 1;            // the word's first byte is byte q & 3 of row word q >> 2 (q = -1: the filter byte)
+        const int ka = (int)(q >> 2), b = (int)(q & 3);
+        const unsigned lo = filtered_word<BPP>(cur, up, n_bytes, filter, ka);
+        unsigned val = lo;
+        if (b) val = (lo >> (8 * b)) | (filtered_word<BPP>(cur, up, n_bytes, filter, ka + 1) << (32 - 8 * b));
+        out32[(a0 >> 2) + j] = val;
+    }
+    if (tid < 6) {
+        // up to 3 bytes before the first whole word and up to 3 after the last
+        const long long head = a0 - g0, tail0 = head + 4 * n_words;
+        const long long i = tid < 3 ? tid : tail0 + (tid - 3);
+        if ((tid < 3 ? i < head : true) && i < stride) {
+            const long long q = i - 1;
+            const unsigned f = filtered_word<BPP>(cur, up, n_bytes, filter, (int)(q >> 2));
             out[g0 + i] = (unsigned char)(f >> (8 * (int)(q & 3)));
         }
     }
@@ -537,7 +644,8 @@ __device__ __forceinline__ void store_be32(unsigned char *p, unsigned v)
 
 __global__ void __launch_bounds__(1024) k_png_assemble(const ChunkMeta *__restrict__ meta, int n_chunks, long long n_total,
                                                        const unsigned char *__restrict__ row_filter, int width, int rows,
-                                                       unsigned char *png, long long *offsets, PngInfo *info)
+                                                       int bit_depth, int colour_type, unsigned char *png, long long *offsets,
+                                                       PngInfo *info)
 {
     __shared__ long long wsum[16];
     __shared__ int filter_count[4];
@@ -581,7 +689,8 @@ __global__ void __launch_bounds__(1024) k_png_assemble(const ChunkMeta *__restri
         ihdr[4] = 'I'; ihdr[5] = 'H'; ihdr[6] = 'D'; ihdr[7] = 'R';
         store_be32(ihdr + 8, (unsigned)width);
         store_be32(ihdr + 12, (unsigned)rows);
-        ihdr[16] = 8; ihdr[17] = 6; ihdr[18] = 0; ihdr[19] = 0; ihdr[20] = 0;       // 8 bit, RGBA, no interlace
+        ihdr[16] = (unsigned char)bit_depth; ihdr[17] = (unsigned char)colour_type;     // 8 / 6 (RGBA), 16 / 6 or 16 / 0 (grey)
+        ihdr[18] = 0; ihdr[19] = 0; ihdr[20] = 0;                                       // no interlace
         unsigned crc = 0xffffffffu;
         for (int k = 4; k < 21; ++k) {
             crc ^= ihdr[k];
@@ -663,50 +772,39 @@ int grow(ndt_hip_ctx *ctx, void **buf, size_t *have, size_t want)
     return NDT_OK;
 }
 
-// the filtered stream's length, or -1 for a size the encoder does not take
-long long stream_bytes(int32_t width, int32_t rows)
+// the filtered stream's length for pixels of bpp bytes, or -1 for a size the encoder does not take
+long long stream_bytes(int32_t width, int32_t rows, int bpp = 4)
 {
     if (width < 1 || rows < 1) return -1;
-    const long long n = (1 + 4LL * width) * (long long)rows;      // < 2^34 * 2^31
+    const long long n = (1 + (long long)bpp * width) * (long long)rows;      // < 2^35 * 2^31
     return n > 0x7fffffffLL ? -1 : n;
 }
 
-} // namespace
+// every chunk stored: 5 bytes a chunk on top of the stream
+long long file_bound(long long n) { return PNG_FILE_EXTRA + n + 5 * ((n + PNG_CHUNK - 1) / PNG_CHUNK); }
 
-extern "C" int64_t ndt_hip_png_bound(int32_t width, int32_t rows)
-{
-    const long long n = stream_bytes(width, rows);
-    if (n < 0) return NDT_E_INVALID;
-    // every chunk stored: 5 bytes a chunk on top of the stream
-    return PNG_FILE_EXTRA + n + 5 * ((n + PNG_CHUNK - 1) / PNG_CHUNK);
-}
+// what the encoder is told about the image: bytes a pixel, and the IHDR's bit depth and colour type
+struct PngFormat { int bpp, bit_depth, colour_type; };
+constexpr PngFormat PNG_RGBA8 = { 4, 8, 6 }, PNG_RGBA16 = { 8, 16, 6 }, PNG_GREY16 = { 2, 16, 0 };
 
-void ndt_impl::free_png(ndt_hip_ctx *ctx)
-{
-    PngState &ps = ctx->png;
-    void **bufs[] = { &ps.d_rgba8, &ps.d_filtered, &ps.d_row_filter, &ps.d_slots, &ps.d_meta, &ps.d_offsets, &ps.d_file, &ps.d_info };
-    for (void **b : bufs) {
-        if (*b) (void)hipFree(*b);
-        *b = nullptr;
-    }
-    if (ps.h_info) (void)hipHostFree(ps.h_info);
-    ps = PngState();
-}
+// channels 4 -> RGBA16, 1 -> GREY16, anything else -> nullptr
+const PngFormat *format16(int32_t channels) { return channels == 4 ? &PNG_RGBA16 : channels == 1 ? &PNG_GREY16 : nullptr; }
 
-extern "C" int ndt_hip_encode_png_device(ndt_hip_ctx *ctx, const void *d_rgba8, int32_t width, int32_t rows, uint8_t *png, int64_t cap,
-                                         ndt_png_stats *stats)
+// The file of width x rows pixels of format `f` at d_image (the context's device memory); `who` names the entry point in errors.
+int encode_device(ndt_hip_ctx *ctx, const char *who, const void *d_image, int32_t width, int32_t rows, const PngFormat &f, uint8_t *png,
+                  int64_t cap, ndt_png_stats *stats)
 {
-    if (!ctx || !d_rgba8 || !png) return fail(NDT_E_INVALID, "ndt_hip_encode_png: NULL argument");
-    if (width < 1 || rows < 1) return fail(NDT_E_INVALID, "ndt_hip_encode_png: a %d x %d image", width, rows);
-    const long long n = stream_bytes(width, rows);
-    if (n < 0) return fail(NDT_E_INVALID, "ndt_hip_encode_png: the filtered stream of a %d x %d image exceeds 2^31 - 1 bytes", width, rows);
-    if (cap < 0) return fail(NDT_E_INVALID, "ndt_hip_encode_png: cap %lld", (long long)cap);
-    if (((uintptr_t)d_rgba8 & 3u) != 0) return fail(NDT_E_INVALID, "ndt_hip_encode_png: the image is not aligned to its 4-byte pixels");
+    if (!ctx || !d_image || !png) return fail(NDT_E_INVALID, "%s: NULL argument", who);
+    if (width < 1 || rows < 1) return fail(NDT_E_INVALID, "%s: a %d x %d image", who, width, rows);
+    const long long n = stream_bytes(width, rows, f.bpp);
+    if (n < 0) return fail(NDT_E_INVALID, "%s: the filtered stream of a %d x %d image exceeds 2^31 - 1 bytes", who, width, rows);
+    if (cap < 0) return fail(NDT_E_INVALID, "%s: cap %lld", who, (long long)cap);
+    if (((uintptr_t)d_image & (uintptr_t)(f.bpp - 1)) != 0) return fail(NDT_E_INVALID, "%s: the image is not aligned to its %d-byte pixels", who, f.bpp);
     const auto t0 = std::chrono::steady_clock::now();
     HIP_TRY(hipSetDevice(ctx->device));
     PngState &ps = ctx->png;
     const int n_chunks = (int)((n + PNG_CHUNK - 1) / PNG_CHUNK);
-    const long long bound = ndt_hip_png_bound(width, rows);
+    const long long bound = file_bound(n);
     int rc;
     if ((rc = grow(ctx, &ps.d_filtered, &ps.filtered_bytes, (size_t)n_chunks * PNG_CHUNK))) return rc;
     if ((rc = grow(ctx, &ps.d_row_filter, &ps.row_filter_bytes, (size_t)rows))) return rc;
@@ -717,12 +815,20 @@ extern "C" int ndt_hip_encode_png_device(ndt_hip_ctx *ctx, const void *d_rgba8, 
     if ((rc = grow(ctx, &ps.d_info, &ps.info_bytes, sizeof(PngInfo)))) return rc;
     if (!ps.h_info) HIP_TRY(hipHostMalloc(&ps.h_info, sizeof(PngInfo), hipHostMallocDefault));
     hipStream_t s = ctx->stream;
-    hipLaunchKernelGGL(k_png_filter, dim3((unsigned)rows), dim3(256), 0, s, (const unsigned *)d_rgba8, (unsigned char *)ps.d_filtered,
-                       (unsigned char *)ps.d_row_filter, (int)width, (int)rows);
+    if (f.bpp == 4)
+        hipLaunchKernelGGL(k_png_filter, dim3((unsigned)rows), dim3(256), 0, s, (const unsigned *)d_image, (unsigned char *)ps.d_filtered,
+                           (unsigned char *)ps.d_row_filter, (int)width, (int)rows);
+    else if (f.bpp == 8)
+        hipLaunchKernelGGL(k_png_filter_wide<8>, dim3((unsigned)rows), dim3(256), 0, s, (const unsigned char *)d_image,
+                           (unsigned char *)ps.d_filtered, (unsigned char *)ps.d_row_filter, (int)width, (int)rows);
+    else
+        hipLaunchKernelGGL(k_png_filter_wide<2>, dim3((unsigned)rows), dim3(256), 0, s, (const unsigned char *)d_image,
+                           (unsigned char *)ps.d_filtered, (unsigned char *)ps.d_row_filter, (int)width, (int)rows);
     hipLaunchKernelGGL(k_png_deflate, dim3((unsigned)n_chunks), dim3(PNG_DEFLATE_LANES), 0, s, (const unsigned char *)ps.d_filtered, n, n_chunks,
                        (unsigned char *)ps.d_slots, (ChunkMeta *)ps.d_meta);
     hipLaunchKernelGGL(k_png_assemble, dim3(1), dim3(1024), 0, s, (const ChunkMeta *)ps.d_meta, n_chunks, n, (const unsigned char *)ps.d_row_filter,
-                       (int)width, (int)rows, (unsigned char *)ps.d_file, (long long *)ps.d_offsets, (PngInfo *)ps.d_info);
+                       (int)width, (int)rows, f.bit_depth, f.colour_type, (unsigned char *)ps.d_file, (long long *)ps.d_offsets,
+                       (PngInfo *)ps.d_info);
     hipLaunchKernelGGL(k_png_place, dim3((unsigned)n_chunks), dim3(256), 0, s, (const unsigned char *)ps.d_slots, (const ChunkMeta *)ps.d_meta,
                        (const long long *)ps.d_offsets, (unsigned char *)ps.d_file);
     HIP_TRY(hipGetLastError());
@@ -736,12 +842,12 @@ extern "C" int ndt_hip_encode_png_device(ndt_hip_ctx *ctx, const void *d_rgba8, 
         stats->chunks = n_chunks;
         stats->chunks_stored = info.chunks_stored;
         stats->launches = 4;
-        for (int f = 0; f < 3; ++f) stats->rows_filter[f] = info.rows_filter[f];
+        for (int k = 0; k < 3; ++k) stats->rows_filter[k] = info.rows_filter[k];
     }
     if (info.png_bytes < PNG_FILE_EXTRA || info.png_bytes > bound)
-        return fail(NDT_E_DEVICE, "ndt_hip_encode_png: the device reports a file of %lld bytes (bound %lld)", info.png_bytes, bound);
+        return fail(NDT_E_DEVICE, "%s: the device reports a file of %lld bytes (bound %lld)", who, info.png_bytes, bound);
     if (info.png_bytes > cap)
-        return fail(NDT_E_NOMEM, "ndt_hip_encode_png: the file is %lld bytes, the buffer %lld", info.png_bytes, (long long)cap);
+        return fail(NDT_E_NOMEM, "%s: the file is %lld bytes, the buffer %lld", who, info.png_bytes, (long long)cap);
     HIP_TRY(hipMemcpyAsync(png, ps.d_file, (size_t)info.png_bytes, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
     // the IDAT chunk's CRC-32 covers its type and data: bytes 37 .. 41 + idat_bytes of the file
@@ -752,19 +858,82 @@ extern "C" int ndt_hip_encode_png_device(ndt_hip_ctx *ctx, const void *d_rgba8, 
     return NDT_OK;
 }
 
+// the image of width x rows pixels of format `f` from host memory into the context's upload buffer
+int upload_image(ndt_hip_ctx *ctx, const char *who, const void *image, int32_t width, int32_t rows, const PngFormat &f)
+{
+    if (!ctx || !image) return fail(NDT_E_INVALID, "%s: NULL argument", who);
+    if (width < 1 || rows < 1) return fail(NDT_E_INVALID, "%s: a %d x %d image", who, width, rows);
+    if (stream_bytes(width, rows, f.bpp) < 0)
+        return fail(NDT_E_INVALID, "%s: the filtered stream of a %d x %d image exceeds 2^31 - 1 bytes", who, width, rows);
+    HIP_TRY(hipSetDevice(ctx->device));
+    const size_t bytes = (size_t)width * (size_t)rows * (size_t)f.bpp;
+    int rc = grow(ctx, &ctx->png.d_rgba8, &ctx->png.rgba8_bytes, bytes);
+    if (rc) return rc;
+    HIP_TRY(hipMemcpyAsync(ctx->png.d_rgba8, image, bytes, hipMemcpyHostToDevice, ctx->stream));
+    return NDT_OK;
+}
+
+} // namespace
+
+extern "C" int64_t ndt_hip_png_bound(int32_t width, int32_t rows)
+{
+    const long long n = stream_bytes(width, rows);
+    if (n < 0) return NDT_E_INVALID;
+    return file_bound(n);
+}
+
+extern "C" int64_t ndt_hip_png16_bound(int32_t width, int32_t rows, int32_t channels)
+{
+    const PngFormat *f = format16(channels);
+    const long long n = f ? stream_bytes(width, rows, f->bpp) : -1;
+    if (n < 0) return NDT_E_INVALID;
+    return file_bound(n);
+}
+
+void ndt_impl::free_png(ndt_hip_ctx *ctx)
+{
+    PngState &ps = ctx->png;
+    void **bufs[] = { &ps.d_rgba8, &ps.d_rgba16, &ps.d_filtered, &ps.d_row_filter, &ps.d_slots, &ps.d_meta, &ps.d_offsets, &ps.d_file, &ps.d_info };
+    for (void **b : bufs) {
+        if (*b) (void)hipFree(*b);
+        *b = nullptr;
+    }
+    if (ps.h_info) (void)hipHostFree(ps.h_info);
+    ps = PngState();
+}
+
+extern "C" int ndt_hip_encode_png_device(ndt_hip_ctx *ctx, const void *d_rgba8, int32_t width, int32_t rows, uint8_t *png, int64_t cap,
+                                         ndt_png_stats *stats)
+{
+    return encode_device(ctx, "ndt_hip_encode_png", d_rgba8, width, rows, PNG_RGBA8, png, cap, stats);
+}
+
 extern "C" int ndt_hip_encode_png(ndt_hip_ctx *ctx, const uint8_t *rgba8, int32_t width, int32_t rows, uint8_t *png, int64_t cap,
                                   ndt_png_stats *stats)
 {
-    if (!ctx || !rgba8 || !png) return fail(NDT_E_INVALID, "ndt_hip_encode_png: NULL argument");
-    if (width < 1 || rows < 1) return fail(NDT_E_INVALID, "ndt_hip_encode_png: a %d x %d image", width, rows);
-    if (stream_bytes(width, rows) < 0)
-        return fail(NDT_E_INVALID, "ndt_hip_encode_png: the filtered stream of a %d x %d image exceeds 2^31 - 1 bytes", width, rows);
-    HIP_TRY(hipSetDevice(ctx->device));
-    const size_t bytes = (size_t)width * (size_t)rows * 4;
-    int rc = grow(ctx, &ctx->png.d_rgba8, &ctx->png.rgba8_bytes, bytes);
+    if (!png) return fail(NDT_E_INVALID, "ndt_hip_encode_png: NULL argument");
+    int rc = upload_image(ctx, "ndt_hip_encode_png", rgba8, width, rows, PNG_RGBA8);
     if (rc) return rc;
-    HIP_TRY(hipMemcpyAsync(ctx->png.d_rgba8, rgba8, bytes, hipMemcpyHostToDevice, ctx->stream));
     return ndt_hip_encode_png_device(ctx, ctx->png.d_rgba8, width, rows, png, cap, stats);
+}
+
+extern "C" int ndt_hip_encode_png16_device(ndt_hip_ctx *ctx, const void *d_samples, int32_t width, int32_t rows, int32_t channels, uint8_t *png,
+                                           int64_t cap, ndt_png_stats *stats)
+{
+    const PngFormat *f = format16(channels);
+    if (!f) return fail(NDT_E_INVALID, "ndt_hip_encode_png16: %d channels: a 16-bit file is grey (1) or RGBA (4)", channels);
+    return encode_device(ctx, "ndt_hip_encode_png16", d_samples, width, rows, *f, png, cap, stats);
+}
+
+extern "C" int ndt_hip_encode_png16(ndt_hip_ctx *ctx, const uint8_t *samples, int32_t width, int32_t rows, int32_t channels, uint8_t *png,
+                                    int64_t cap, ndt_png_stats *stats)
+{
+    const PngFormat *f = format16(channels);
+    if (!f) return fail(NDT_E_INVALID, "ndt_hip_encode_png16: %d channels: a 16-bit file is grey (1) or RGBA (4)", channels);
+    if (!png) return fail(NDT_E_INVALID, "ndt_hip_encode_png16: NULL argument");
+    int rc = upload_image(ctx, "ndt_hip_encode_png16", samples, width, rows, *f);
+    if (rc) return rc;
+    return encode_device(ctx, "ndt_hip_encode_png16", ctx->png.d_rgba8, width, rows, *f, png, cap, stats);
 }
 
 extern "C" int ndt_hip_render_png(ndt_hip_ctx *ctx, const ndt_render_params *p, uint8_t *png, int64_t cap, ndt_png_stats *stats,
@@ -782,4 +951,25 @@ extern "C" int ndt_hip_render_png(ndt_hip_ctx *ctx, const ndt_render_params *p, 
     ndt_hip_ctx *one[1] = { ctx };
     if ((rc = ndt_hip_render_multi_device(one, 1, p, NDT_IMAGE_RGBA8, ctx->png.d_rgba8, render_stats))) return rc;
     return ndt_hip_encode_png_device(ctx, ctx->png.d_rgba8, p->width, rows, png, cap, stats);
+}
+
+extern "C" int ndt_hip_render_png16(ndt_hip_ctx *ctx, const ndt_render_params *p, uint8_t *png, int64_t cap, ndt_png_stats *stats,
+                                    ndt_render_stats *render_stats)
+{
+    if (!ctx || !p || !png) return fail(NDT_E_INVALID, "ndt_hip_render_png16: NULL argument");
+    if (p->width < 1 || p->height < 1 || p->row_step < 1 || p->row_begin < 0)
+        return fail(NDT_E_INVALID, "ndt_hip_render_png16: bad geometry: %d x %d, rows %d by %d", p->width, p->height, p->row_begin, p->row_step);
+    const int rows = ndt_hip_shard_rows(p->height, p->row_begin, p->row_step);
+    if (rows < 1) return fail(NDT_E_INVALID, "ndt_hip_render_png16: the shard has no rows");
+    if (stream_bytes(p->width, rows, 8) < 0)
+        return fail(NDT_E_INVALID, "ndt_hip_render_png16: the filtered stream of a %d x %d image exceeds 2^31 - 1 bytes", p->width, rows);
+    HIP_TRY(hipSetDevice(ctx->device));
+    // the frame in doubles where ndt_hip_render leaves it, its 16-bit samples beside the encoder's buffers
+    const size_t pixels = (size_t)p->width * (size_t)rows;
+    int rc = ensure_out(ctx, pixels * 4 * sizeof(double));
+    if (rc) return rc;
+    if ((rc = grow(ctx, &ctx->png.d_rgba16, &ctx->png.rgba16_bytes, pixels * 8))) return rc;
+    if ((rc = ndt_hip_render_device(ctx, p, ctx->d_out, render_stats))) return rc;
+    if ((rc = ndt_hip_quantize16_device(ctx, ctx->d_out, ctx->png.d_rgba16, (int64_t)pixels))) return rc;
+    return encode_device(ctx, "ndt_hip_render_png16", ctx->png.d_rgba16, p->width, rows, PNG_RGBA16, png, cap, stats);
 }

@@ -234,7 +234,7 @@ int render_ssaa_own(ndt_hip_ctx *ctx, const ndt_render_params *p, int K, bool wa
 void ndt_impl::free_ssaa(ndt_hip_ctx *ctx)
 {
     SsaaState &ss = ctx->ssaa;
-    void **bufs[] = { &ss.d_pass, &ss.d_acc, &ss.d_rgba8, &ss.d_depth8 };
+    void **bufs[] = { &ss.d_pass, &ss.d_acc, &ss.d_rgba8, &ss.d_depth8, &ss.d_rgba16, &ss.d_grey16 };
     for (void **b : bufs) {
         if (*b) (void)hipFree(*b);
         *b = nullptr;
@@ -349,4 +349,46 @@ extern "C" int ndt_hip_render_ssaa_rgba8_depth(ndt_hip_ctx *ctx, const ndt_rende
     HIP_TRY(hipMemcpyAsync(depth8, ss.d_depth8, pixels * 4, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     return NDT_OK;
+}
+
+// the 16-bit files: the finished accumulator through ndt_hip_quantize16_device (one launch behind the last fold, which is left as
+// it is), the map of sub-sample (0, 0) through ndt_hip_depth_grey16_device
+static int ssaa_png16(const char *who, ndt_hip_ctx *ctx, const ndt_render_params *p, int32_t K, uint8_t *png, int64_t cap, uint8_t *depth_png,
+                      int64_t depth_cap, ndt_png_stats *stats, double *range_out, ndt_render_stats *render_stats)
+{
+    int rc = refuse(who, ctx, p, K, png);
+    if (rc) return rc;
+    const int shard = ndt_hip_shard_rows(p->height, p->row_begin, p->row_step);
+    if (shard < 1) return fail(NDT_E_INVALID, "%s: the shard has no rows", who);
+    if (ndt_hip_png16_bound(p->width, shard, 4) < 0)
+        return fail(NDT_E_INVALID, "%s: the filtered stream of a %d x %d image exceeds 2^31 - 1 bytes", who, p->width, shard);
+    if (range_out) range_out[0] = range_out[1] = 0.0;
+    int rows = 0;
+    size_t pixels = 0;
+    if ((rc = render_ssaa_own(ctx, p, K, depth_png != nullptr, false, render_stats, &rows, &pixels))) return rc;
+    SsaaState &ss = ctx->ssaa;
+    if ((rc = grow(ctx, &ss.d_rgba16, &ss.rgba16_bytes, pixels * 8))) return rc;
+    if ((rc = ndt_hip_quantize16_device(ctx, ss.d_acc, ss.d_rgba16, (int64_t)pixels))) return rc;
+    if (depth_png) {
+        if ((rc = grow(ctx, &ss.d_grey16, &ss.grey16_bytes, (pixels * 2 + 3) & ~(size_t)3))) return rc;
+        if ((rc = ndt_hip_depth_grey16_device(ctx, (char *)ss.d_acc + pixels * 4 * sizeof(double), (int64_t)pixels, ss.d_grey16, range_out))) return rc;
+    }
+    if ((rc = ndt_hip_encode_png16_device(ctx, ss.d_rgba16, p->width, rows, 4, png, cap, stats))) return rc;
+    if (!depth_png) return NDT_OK;
+    return ndt_hip_encode_png16_device(ctx, ss.d_grey16, p->width, rows, 1, depth_png, depth_cap, stats ? &stats[1] : nullptr);
+}
+
+extern "C" int ndt_hip_render_ssaa_png16(ndt_hip_ctx *ctx, const ndt_render_params *p, int32_t K, uint8_t *png, int64_t cap, ndt_png_stats *stats,
+                                         ndt_render_stats *render_stats)
+{
+    return ssaa_png16("ndt_hip_render_ssaa_png16", ctx, p, K, png, cap, nullptr, 0, stats, nullptr, render_stats);
+}
+
+extern "C" int ndt_hip_render_ssaa_png16_depth(ndt_hip_ctx *ctx, const ndt_render_params *p, int32_t K, uint8_t *png, int64_t cap,
+                                               uint8_t *depth_png, int64_t depth_cap, ndt_png_stats *stats, double *range_out,
+                                               ndt_render_stats *render_stats)
+{
+    if (!depth_png) return fail(NDT_E_INVALID, "ndt_hip_render_ssaa_png16_depth: NULL argument");
+    if (stats) stats[0] = stats[1] = ndt_png_stats{};
+    return ssaa_png16("ndt_hip_render_ssaa_png16_depth", ctx, p, K, png, cap, depth_png, depth_cap, stats, range_out, render_stats);
 }

@@ -29,6 +29,8 @@ API_SYMBOLS = [
     "ndt_hip_depth_rgba8_device", "ndt_hip_render_rgba8_depth", "ndt_hip_render_png_depth", "ndt_hip_depth_launches", "ndt_hip_depth_ms",
     "ndt_hip_ssaa_fold_device", "ndt_hip_render_ssaa_device", "ndt_hip_render_ssaa", "ndt_hip_render_ssaa_rgba8", "ndt_hip_render_ssaa_png",
     "ndt_hip_render_ssaa_jpeg", "ndt_hip_render_ssaa_rgba8_depth", "ndt_hip_ssaa_launches", "ndt_hip_ssaa_ms",
+    "ndt_hip_quantize16_device", "ndt_hip_depth_grey16_device", "ndt_hip_png16_bound", "ndt_hip_encode_png16_device", "ndt_hip_encode_png16",
+    "ndt_hip_render_png16", "ndt_hip_render_png16_depth", "ndt_hip_render_ssaa_png16", "ndt_hip_render_ssaa_png16_depth",
 ]
 
 IMAGE_F64, IMAGE_RGBA8 = 0, 1      # enum ndt_image_format
@@ -133,6 +135,19 @@ def load_library():
         lib.ndt_hip_ssaa_launches.argtypes = [C.c_void_p]
         lib.ndt_hip_ssaa_ms.argtypes = [C.c_void_p]
         lib.ndt_hip_ssaa_ms.restype = C.c_double
+    if hasattr(lib, "ndt_hip_png16_bound"):         # (absent from earlier builds, which profiles/ab_libs.sh loads to compare)
+        lib.ndt_hip_quantize16_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]
+        lib.ndt_hip_depth_grey16_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
+        lib.ndt_hip_png16_bound.argtypes = [C.c_int32, C.c_int32, C.c_int32]
+        lib.ndt_hip_png16_bound.restype = C.c_int64
+        lib.ndt_hip_encode_png16_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p]
+        lib.ndt_hip_encode_png16.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p]
+        lib.ndt_hip_render_png16.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
+        lib.ndt_hip_render_png16_depth.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
+                                                   C.c_void_p]
+        lib.ndt_hip_render_ssaa_png16.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
+        lib.ndt_hip_render_ssaa_png16_depth.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
+                                                        C.c_void_p, C.c_void_p, C.c_void_p]
     _lib = lib
     return lib
 
@@ -186,6 +201,16 @@ def png_bound(width, rows):
     n = int(load_library().ndt_hip_png_bound(int(width), int(rows)))
     if n < 0:
         raise ValueError("no PNG of %d x %d: the size is empty or its filtered stream exceeds 2^31 - 1 bytes" % (width, rows))
+    return n
+
+
+def png16_bound(width, rows, channels=4):
+    """ndt_hip_png16_bound: the largest 16-bit file the device encoder can produce for a width x rows image of 4 (RGBA) or 1 (grey)
+    channels (host arithmetic)."""
+    n = int(load_library().ndt_hip_png16_bound(int(width), int(rows), int(channels)))
+    if n < 0:
+        raise ValueError("no 16-bit PNG of %d x %d x %d: the channels are neither 1 nor 4, the size is empty or its filtered stream "
+                         "exceeds 2^31 - 1 bytes" % (width, rows, channels))
     return n
 
 
@@ -450,6 +475,91 @@ class NdtHip:
         self.png_stats = PngStats()
         self._check(self.lib.ndt_hip_render_png(self.ctx, C.byref(p), out.ctypes.data, cap, C.byref(self.png_stats), C.byref(st)))
         return out[:self.png_stats.png_bytes].tobytes(), st
+
+    def encode_png16(self, samples, cap=None):
+        """ndt_hip_encode_png16: the complete 16-bit PNG file of a (rows, width, 4) RGBA or (rows, width) grey host image of uint16
+        values, compressed on this context's GPU.  Returns the file's bytes; self.png_stats keeps the ndt_png_stats."""
+        samples = np.asarray(samples)
+        if samples.dtype != np.uint16 or not (samples.ndim == 2 or (samples.ndim == 3 and samples.shape[2] == 4)):
+            raise ValueError("samples must be uint16, (rows, width, 4) or (rows, width)")
+        rows, width = samples.shape[:2]
+        channels = 4 if samples.ndim == 3 else 1
+        wire = np.ascontiguousarray(samples.astype(">u2"))          # file byte order
+        cap = png16_bound(width, rows, channels) if cap is None else int(cap)
+        out = np.zeros(max(cap, 1), dtype=np.uint8)
+        self.png_stats = PngStats()
+        self._check(self.lib.ndt_hip_encode_png16(self.ctx, wire.ctypes.data, width, rows, channels, out.ctypes.data, cap,
+                                                  C.byref(self.png_stats)))
+        return out[:self.png_stats.png_bytes].tobytes()
+
+    def encode_png16_device(self, d_samples_ptr, width, rows, channels, cap=None):
+        """ndt_hip_encode_png16_device: the same for width * rows * channels samples in file byte order at raw device pointer
+        `d_samples_ptr`."""
+        cap = png16_bound(width, rows, channels) if cap is None else int(cap)
+        out = np.zeros(max(cap, 1), dtype=np.uint8)
+        self.png_stats = PngStats()
+        self._check(self.lib.ndt_hip_encode_png16_device(self.ctx, C.c_void_p(d_samples_ptr), int(width), int(rows), int(channels),
+                                                         out.ctypes.data, cap, C.byref(self.png_stats)))
+        return out[:self.png_stats.png_bytes].tobytes()
+
+    def quantize16_device(self, d_rgba_ptr, d_rgba16_ptr, n_pixels):
+        """ndt_hip_quantize16_device: n_pixels * 4 doubles at `d_rgba_ptr` to n_pixels * 8 bytes of 16-bit samples in file byte
+        order at `d_rgba16_ptr` (on the context's stream: synchronize() before reading them)."""
+        self._check(self.lib.ndt_hip_quantize16_device(self.ctx, C.c_void_p(d_rgba_ptr), C.c_void_p(d_rgba16_ptr), int(n_pixels)))
+
+    def depth_grey16_device(self, d_depth_ptr, n_pixels, d_grey16_ptr):
+        """ndt_hip_depth_grey16_device: depth_rgba8_device with one 16-bit grey sample a pixel, in file byte order.  Returns (lo, hi)."""
+        rng = np.zeros(2, dtype=np.float64)
+        self._check(self.lib.ndt_hip_depth_grey16_device(self.ctx, C.c_void_p(d_depth_ptr), int(n_pixels), C.c_void_p(d_grey16_ptr),
+                                                         rng.ctypes.data))
+        return rng
+
+    def render_png16(self, width, height, depth, **kw):
+        """ndt_hip_render_png16: render_png at 16 bits a sample.  Returns (the file's bytes, RenderStats); self.png_stats keeps the
+        ndt_png_stats."""
+        p = self.params(width, height, depth, **kw)
+        rows = shard_rows(height, p.row_begin, p.row_step)
+        cap = png16_bound(width, rows, 4)
+        out = np.zeros(cap, dtype=np.uint8)
+        st = RenderStats()
+        self.png_stats = PngStats()
+        self._check(self.lib.ndt_hip_render_png16(self.ctx, C.byref(p), out.ctypes.data, cap, C.byref(self.png_stats), C.byref(st)))
+        return out[:self.png_stats.png_bytes].tobytes(), st
+
+    def render_png16_depth(self, width, height, depth, cap=None, depth_cap=None, **kw):
+        """ndt_hip_render_png16_depth: the image as a 16-bit RGBA file and the map as a 16-bit grey one.  Returns (file, file,
+        [lo, hi], RenderStats); self.png_stats keeps the two ndt_png_stats (image, map)."""
+        p = self.params(width, height, depth, **kw)
+        rows = shard_rows(height, p.row_begin, p.row_step)
+        cap = png16_bound(width, rows, 4) if cap is None else int(cap)
+        depth_cap = png16_bound(width, rows, 1) if depth_cap is None else int(depth_cap)
+        out, dpng = np.zeros(max(cap, 1), dtype=np.uint8), np.zeros(max(depth_cap, 1), dtype=np.uint8)
+        rng = np.zeros(2, dtype=np.float64)
+        st = RenderStats()
+        self.png_stats = (PngStats * 2)()
+        self._check(self.lib.ndt_hip_render_png16_depth(self.ctx, C.byref(p), out.ctypes.data, cap, dpng.ctypes.data, depth_cap,
+                                                        C.byref(self.png_stats), rng.ctypes.data, C.byref(st)))
+        return out[:self.png_stats[0].png_bytes].tobytes(), dpng[:self.png_stats[1].png_bytes].tobytes(), rng, st
+
+    def render_ssaa_png16(self, width, height, depth, ssaa, depth_map=False, **kw):
+        """ndt_hip_render_ssaa_png16 (depth_map=True: ndt_hip_render_ssaa_png16_depth): the supersampled frame as a 16-bit file:
+        (the file's bytes, stats), or (file, the map's file, [lo, hi], stats); self.png_stats keeps the record(s)."""
+        p, rows = self._ssaa_params(width, height, depth, kw)
+        cap = png16_bound(width, rows, 4)
+        out = np.zeros(cap, dtype=np.uint8)
+        st = RenderStats()
+        if not depth_map:
+            self.png_stats = PngStats()
+            self._check(self.lib.ndt_hip_render_ssaa_png16(self.ctx, C.byref(p), int(ssaa), out.ctypes.data, cap, C.byref(self.png_stats),
+                                                           C.byref(st)))
+            return out[:self.png_stats.png_bytes].tobytes(), st
+        depth_cap = png16_bound(width, rows, 1)
+        dpng = np.zeros(depth_cap, dtype=np.uint8)
+        rng = np.zeros(2, dtype=np.float64)
+        self.png_stats = (PngStats * 2)()
+        self._check(self.lib.ndt_hip_render_ssaa_png16_depth(self.ctx, C.byref(p), int(ssaa), out.ctypes.data, cap, dpng.ctypes.data,
+                                                             depth_cap, C.byref(self.png_stats), rng.ctypes.data, C.byref(st)))
+        return out[:self.png_stats[0].png_bytes].tobytes(), dpng[:self.png_stats[1].png_bytes].tobytes(), rng, st
 
     def encode_jpeg(self, rgba8, quality=95, sampling="420", cap=None):
         """ndt_hip_encode_jpeg: the complete baseline JFIF file of a (rows, width, 4) uint8 host image (alpha ignored), made on

@@ -470,6 +470,16 @@ int ndt_render_image_ssaa_jpeg(scene *scn, int width, int height, int samples, i
                                int ssaa, int quality, int sampling, unsigned char **jpg, long long *jpg_bytes);
 int ndt_render_image_ssaa_depth8(scene *scn, int width, int height, int samples, int threads, int stereo, int specular, int max_optic_depth,
                                  int ssaa, int want_png, int want_depth_png, ndt_depth_frame *out);
+/* The same frames as files of 16 bits a sample, made on the GPU from the double framebuffer (`ndt_hip --png --deflate gpu --png16`;
+ * ndt_hip_render_png16*, ndt_hip_render_ssaa_png16*): the image as a 16-bit RGBA PNG and, for _depth, the map beside it as a
+ * 16-bit grey PNG -- out->png and out->depth_png arrive, with out->range; ndt_depth_frame_free frees them.  ssaa = 1 is the plain
+ * frame (with -a when aa_depth >= 0), ssaa = 2 .. 8 the supersampled one (aa_depth < 0 then).  One context makes the files: after
+ * ndt_render_use_devices(n > 1) the calls fail and say so.  Each prints `compressed 16-bit PNG of B bytes on GPU D in L launches`
+ * (_depth: and `compressed 16-bit depth PNG of ...`, `finished depth map ...`).  No fallback. */
+int ndt_render_image_png16(scene *scn, int width, int height, int samples, int threads, int aa_diff, int aa_depth, int stereo,
+                           int specular, int max_optic_depth, int ssaa, unsigned char **png, long long *png_bytes);
+int ndt_render_image_png16_depth(scene *scn, int width, int height, int samples, int threads, int aa_diff, int aa_depth, int stereo,
+                                 int specular, int max_optic_depth, int ssaa, ndt_depth_frame *out);
 /* summed device milliseconds of the fold launches of the calling thread's last supersampled frame */
 double ndt_render_ssaa_fold_ms(void);
 

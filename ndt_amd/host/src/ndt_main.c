@@ -14,8 +14,10 @@
  * map (ndt_hip_render_rgba8_depth) instead of sending it and the image back in doubles, and `--depth-png` then writes the map as a
  * PNG compressed there as well.  `--ssaa K` (1 .. 8, default 1) supersamples every frame K x K on the GPU: K renders of the frame
  * K times the size, folded there into a box-filtered average in linear light before anything is quantised (ndt_hip_render_ssaa*);
- * with every output flag, -m s|o|a, -n, -g and -j, not with -a or -m h.  None falls back: what the device path cannot do ends
- * the run. */
+ * with every output flag, -m s|o|a, -n, -g and -j, not with -a or -m h.  `--png16` (with `--png --deflate gpu`) has the GPU make
+ * the PNG at 16 bits a sample from the double framebuffer (ndt_hip_render_png16), and with `-z --depth gpu --depth-png` the map's
+ * file as 16-bit grey; on one GPU context a frame (not with -g N > 1).  None falls back: what the device path cannot do ends the
+ * run. */
 #include <dlfcn.h>
 #include <getopt.h>
 #include <pthread.h>
@@ -69,6 +71,7 @@ static struct {
     int dims, width, height, depth, threads, aa_diff, aa_depth, stereo, specular, want_depth, samples, png, gpus, deflate_gpu, depth_gpu, depth_png;
     int jpeg, jpeg_quality, jpeg_sampling;      /* --jpeg: the frame's file is a JPEG made on the GPU; quality 1 .. 100, sampling 0 = 4:2:0 / 1 = 4:4:4 */
     int ssaa;                                   /* --ssaa K: every frame supersampled K x K on the GPU (1: the plain frame) */
+    int png16;                                  /* --png16: the PNG files carry 16 bits a sample */
     const char *raw_path;
 } job_opts;
 
@@ -87,7 +90,18 @@ static int render_frame(scene *scn, int i)
     long long png_bytes = 0;
     double t0 = now_s();
     int ok;
-    if (job_opts.ssaa > 1) {
+    if (job_opts.png16) {
+        /* the doubles stay on the device: what comes back is the 16-bit file, or two */
+        const int aa_depth = job_opts.ssaa > 1 ? -1 : job_opts.aa_depth;
+        if (job_opts.depth_gpu) {
+            ok = ndt_render_image_png16_depth(scn, width, height, job_opts.samples, job_opts.threads, job_opts.aa_diff, aa_depth,
+                                              job_opts.stereo, job_opts.specular, job_opts.depth, job_opts.ssaa, &df);
+            png = df.png; df.png = NULL;
+            png_bytes = df.png_bytes;
+        } else
+            ok = ndt_render_image_png16(scn, width, height, job_opts.samples, job_opts.threads, job_opts.aa_diff, aa_depth, job_opts.stereo,
+                                        job_opts.specular, job_opts.depth, job_opts.ssaa, &png, &png_bytes);
+    } else if (job_opts.ssaa > 1) {
         /* the same five ways out, through the supersampled calls */
         const int K = job_opts.ssaa;
         if (job_opts.depth_gpu) {
@@ -407,6 +421,7 @@ int main(int argc, char **argv)
     int jpeg_quality = 0;   /* --jpeg-quality 1 .. 100 (default: the reference's 95) */
     int jpeg_sampling = -1; /* --jpeg-sampling 420|444 (default: 4:2:0, libjpeg's) */
     int ssaa = 1;           /* --ssaa K: every frame supersampled K x K on the GPU, 1 .. 8 (default 1: the plain frame) */
+    int png16 = 0;          /* --png16: the PNG files at 16 bits a sample, made on the GPU from the doubles (needs --png --deflate gpu) */
     char *objects_dir = "objects";      /* -o: where object plugins are looked for (object.c:119; ndt.c passes "objects") */
     static struct option longopts[] = { { "dump-scene", required_argument, NULL, 1000 },
                                         { "raw", required_argument, NULL, 1001 }, { "png", no_argument, NULL, 1002 },
@@ -415,6 +430,7 @@ int main(int argc, char **argv)
                                         { "depth", required_argument, NULL, 1006 }, { "depth-png", no_argument, NULL, 1007 },
                                         { "jpeg", no_argument, NULL, 1008 }, { "jpeg-quality", required_argument, NULL, 1009 },
                                         { "jpeg-sampling", required_argument, NULL, 1010 }, { "ssaa", required_argument, NULL, 1011 },
+                                        { "png16", no_argument, NULL, 1012 },
                                         { NULL, 0, NULL, 0 } };
     int ch;
     while ((ch = getopt_long(argc, argv, "a:d:g:r:f:j:l:m:3:n:ps:t:u:o:zh", longopts, NULL)) != -1) {
@@ -511,9 +527,10 @@ int main(int argc, char **argv)
             ssaa = (int)k;
             break;
         }
+        case 1012: png16 = 1; break;
         default:
             fprintf(stderr, "usage: %s -s scene.so|builtin:yaml [-d dims] [-r WxH|1080p|4k] [-f last|first:last[:total]] [-l depth]\n"
-                            "          [-a diff,depth] [-n samples] [-m s|o|a|m] [-p] [-z] [-j frames_in_flight] [-g gpus_per_frame] [-u config] [--dump-scene file.ndtscene] [--raw file.f64] [--png [--deflate stored|gpu]] [--jpeg [--jpeg-quality 1..100] [--jpeg-sampling 420|444]] [--fit host|gpu] [--kd host|gpu] [--depth host|gpu [--depth-png]] [--ssaa 1..8]\n", argv[0]);
+                            "          [-a diff,depth] [-n samples] [-m s|o|a|m] [-p] [-z] [-j frames_in_flight] [-g gpus_per_frame] [-u config] [--dump-scene file.ndtscene] [--raw file.f64] [--png [--deflate stored|gpu]] [--jpeg [--jpeg-quality 1..100] [--jpeg-sampling 420|444]] [--fit host|gpu] [--kd host|gpu] [--depth host|gpu [--depth-png]] [--ssaa 1..8] [--png16]\n", argv[0]);
             return ch == 'h' ? 0 : 1;
         }
     }
@@ -527,6 +544,26 @@ int main(int argc, char **argv)
     }
     if (ssaa > 1 && stereo == 4) {
         fprintf(stderr, "%s: --ssaa with -m h: the 1080-line frame packing is not scalable: take -m s, o or a\n", argv[0]);
+        return 1;
+    }
+    if (png16 && jpeg) {
+        fprintf(stderr, "%s: --png16 with --jpeg: a JPEG has 8 bits a sample; --png16 needs --png --deflate gpu\n", argv[0]);
+        return 1;
+    }
+    if (png16 && raw_path) {
+        fprintf(stderr, "%s: --png16 keeps the doubles on the GPU and --raw brings them back: take one\n", argv[0]);
+        return 1;
+    }
+    if (png16 && !(png && deflate_gpu)) {
+        fprintf(stderr, "%s: --png16 has the GPU make the PNG file at 16 bits a sample: it needs --png --deflate gpu\n", argv[0]);
+        return 1;
+    }
+    if (png16 && want_depth && !(depth_gpu && depth_png)) {
+        fprintf(stderr, "%s: --png16 with -z: the map's 16-bit file is made on the GPU: it needs --depth gpu --depth-png\n", argv[0]);
+        return 1;
+    }
+    if (png16 && gpus > 1) {
+        fprintf(stderr, "%s: --png16 with -g %d: the rows of several contexts are gathered as 8-bit pixels; a 16-bit file is made by one context: take -g 1 (or -j)\n", argv[0], gpus);
         return 1;
     }
     if (deflate_gpu && !png) {
@@ -592,6 +629,7 @@ int main(int argc, char **argv)
     job_opts.depth_gpu = depth_gpu;
     job_opts.depth_png = depth_png;
     job_opts.ssaa = ssaa;
+    job_opts.png16 = png16;
     job_opts.jpeg = jpeg; job_opts.jpeg_quality = jpeg_quality; job_opts.jpeg_sampling = jpeg_sampling < 0 ? 0 : jpeg_sampling;
     ndt_render_fit_on_gpu(fit_gpu);
     ndt_render_kd_on_gpu(kd_gpu);

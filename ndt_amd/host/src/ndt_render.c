@@ -385,6 +385,63 @@ static int render_ssaa_any(const ndt_render_params *p, int K, int format, void *
     return ok;
 }
 
+/* ---- the frame's files at 16 bits a sample (ndt_hip_render_png16*, ndt_hip_render_ssaa_png16*; `ndt_hip --png16`) */
+#define NDT_HOST_IMAGE_PNG16 103            /* render_any's `format`; `out` is a png_out */
+#define NDT_HOST_IMAGE_PNG16_DEPTH 104      /* ... `out` is an ndt_depth_frame: png and depth_png arrive */
+
+static int render_png16(const ndt_render_params *p, int K, int format, void *out)
+{
+    const int width = p->width, height = p->height, with_map = format == NDT_HOST_IMAGE_PNG16_DEPTH;
+    const int64_t cap = ndt_hip_png16_bound(width, height, 4), depth_cap = ndt_hip_png16_bound(width, height, 1);
+    ndt_png_stats ps[2];
+    double range[2] = { 0.0, 0.0 };
+    if (g_n_ctx > 1) {
+        /* (the rows of several contexts meet as 8-bit pixels or as doubles on the host: there is no 16-bit gather) */
+        fprintf(stderr, "ndt_render_image_png16: a 16-bit PNG is made by one GPU context, not by %d\n", g_n_ctx);
+        return 0;
+    }
+    if (cap < 0 || depth_cap < 0) {
+        fprintf(stderr, "ndt_render_image_png16: no 16-bit PNG of %d x %d\n", width, height);
+        return 0;
+    }
+    unsigned char *buf = (unsigned char *)malloc((size_t)cap), *dbuf = with_map ? (unsigned char *)malloc((size_t)depth_cap) : NULL;
+    int ok = buf && (dbuf || !with_map);
+    if (ok && with_map)
+        ok = (K != 1 ? ndt_hip_render_ssaa_png16_depth(g_ctx[0], p, K, buf, cap, dbuf, depth_cap, ps, range, NULL)
+                     : ndt_hip_render_png16_depth(g_ctx[0], p, buf, cap, dbuf, depth_cap, ps, range, NULL)) == NDT_OK;
+    else if (ok)
+        ok = (K != 1 ? ndt_hip_render_ssaa_png16(g_ctx[0], p, K, buf, cap, ps, NULL) : ndt_hip_render_png16(g_ctx[0], p, buf, cap, ps, NULL)) == NDT_OK;
+    if (!ok) {
+        free(buf);
+        free(dbuf);
+        return 0;
+    }
+    if (K != 1) {
+        g_ssaa_ms = ndt_hip_ssaa_ms(g_ctx[0]);
+        printf("supersampled %dx%d on GPU %d in %d launches\n", K, K, ndt_hip_device(g_ctx[0]), ndt_hip_ssaa_launches(g_ctx[0]));
+    }
+    g_png_ms = ps[0].encode_ms + (with_map ? ps[1].encode_ms : 0.0);
+    printf("compressed 16-bit PNG of %lld bytes on GPU %d in %d launches\n", (long long)ps[0].png_bytes, ndt_hip_device(g_ctx[0]), ps[0].launches);
+    if (!with_map) {
+        png_out *po = (png_out *)out;
+        *po->png = buf;
+        *po->bytes = ps[0].png_bytes;
+        return 1;
+    }
+    ndt_depth_frame *f = (ndt_depth_frame *)out;
+    f->png = buf;
+    f->png_bytes = ps[0].png_bytes;
+    f->depth_png = dbuf;
+    f->depth_png_bytes = ps[1].png_bytes;
+    f->range[0] = range[0];
+    f->range[1] = range[1];
+    g_depth_ms = ndt_hip_depth_ms(g_ctx[0]);
+    printf("compressed 16-bit depth PNG of %lld bytes on GPU %d in %d launches\n", (long long)ps[1].png_bytes, ndt_hip_device(g_ctx[0]), ps[1].launches);
+    printf("finished depth map [%.17g, %.17g] on GPU %d in %d launches\n", f->range[0], f->range[1], ndt_hip_device(g_ctx[0]),
+           ndt_hip_depth_launches(g_ctx[0]));
+    return 1;
+}
+
 static int render_any(scene *scn, int width, int height, int samples, int aa_diff, int aa_depth, int stereo, int specular,
                       int max_optic_depth, int format, void *out, double *depth, int threads, int ssaa)
 {
@@ -418,7 +475,9 @@ static int render_any(scene *scn, int width, int height, int samples, int aa_dif
             p.aa_diff = aa_diff;
             p.aa_depth = aa_depth;
         }
-        if (ssaa != 1) {        /* (0, 9, ... reach the library, which says what is wrong with them) */
+        if (format == NDT_HOST_IMAGE_PNG16 || format == NDT_HOST_IMAGE_PNG16_DEPTH) {
+            ok = render_png16(&p, ssaa, format, out);
+        } else if (ssaa != 1) {        /* (0, 9, ... reach the library, which says what is wrong with them) */
             ok = render_ssaa_any(&p, ssaa, format, out, depth);
         } else if (format == NDT_HOST_IMAGE_PNG) {
             png_out *po = (png_out *)out;
@@ -499,9 +558,10 @@ static int render_any(scene *scn, int width, int height, int samples, int aa_dif
             fprintf(stderr, "ndt_render_image: bounds + kd-tree + flatten %.2f ms (%s), upload %.2f ms, render + 8-bit image and depth map to host %.2f ms (depth map finished on the GPU %.2f%s)\n",
                     NDT_MS(ts0, ts1), share, NDT_MS(ts1, ts2), NDT_MS(ts2, ts3), g_depth_ms,
                     ((depth_out *)out)->want_png ? ", image files made there" : "");
-        else if ((format == NDT_HOST_IMAGE_PNG || format == NDT_HOST_IMAGE_JPEG) && ok)
+        else if ((format == NDT_HOST_IMAGE_PNG || format == NDT_HOST_IMAGE_JPEG || format == NDT_HOST_IMAGE_PNG16 ||
+                  format == NDT_HOST_IMAGE_PNG16_DEPTH) && ok)
             fprintf(stderr, "ndt_render_image: bounds + kd-tree + flatten %.2f ms (%s), upload %.2f ms, render + image file to host %.2f ms (image file on the GPU %.2f)\n",
-                    NDT_MS(ts0, ts1), share, NDT_MS(ts1, ts2), NDT_MS(ts2, ts3), format == NDT_HOST_IMAGE_PNG ? g_png_ms : g_jpeg_ms);
+                    NDT_MS(ts0, ts1), share, NDT_MS(ts1, ts2), NDT_MS(ts2, ts3), format == NDT_HOST_IMAGE_JPEG ? g_jpeg_ms : g_png_ms);
         else
             fprintf(stderr, "ndt_render_image: bounds + kd-tree + flatten %.2f ms (%s), upload %.2f ms, render + image to host %.2f ms\n",
                     NDT_MS(ts0, ts1), share, NDT_MS(ts1, ts2), NDT_MS(ts2, ts3));
@@ -596,6 +656,28 @@ int ndt_render_image_ssaa_depth8(scene *scn, int width, int height, int samples,
     memset(out, 0, sizeof(*out));
     g_depth_ms = 0.0;
     if (!render_any(scn, width, height, samples, -1, -1, stereo, specular, max_optic_depth, NDT_HOST_IMAGE_DEPTH8, &d, NULL, threads, ssaa)) {
+        ndt_depth_frame_free(out);
+        return 0;
+    }
+    return 1;
+}
+
+/* ---- the frame's files at 16 bits a sample (`ndt_hip --png16`); ssaa = 1: the plain frame, with -a when aa_depth >= 0 */
+int ndt_render_image_png16(scene *scn, int width, int height, int samples, int threads, int aa_diff, int aa_depth, int stereo,
+                           int specular, int max_optic_depth, int ssaa, unsigned char **png, long long *png_bytes)
+{
+    png_out po = { png, png_bytes };
+    *png = NULL;
+    *png_bytes = 0;
+    return render_any(scn, width, height, samples, aa_diff, aa_depth, stereo, specular, max_optic_depth, NDT_HOST_IMAGE_PNG16, &po, NULL, threads, ssaa);
+}
+
+int ndt_render_image_png16_depth(scene *scn, int width, int height, int samples, int threads, int aa_diff, int aa_depth, int stereo,
+                                 int specular, int max_optic_depth, int ssaa, ndt_depth_frame *out)
+{
+    memset(out, 0, sizeof(*out));
+    g_depth_ms = 0.0;
+    if (!render_any(scn, width, height, samples, aa_diff, aa_depth, stereo, specular, max_optic_depth, NDT_HOST_IMAGE_PNG16_DEPTH, out, NULL, threads, ssaa)) {
         ndt_depth_frame_free(out);
         return 0;
     }
