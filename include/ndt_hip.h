@@ -528,8 +528,7 @@ int ndt_hip_multi_path_taken(ndt_hip_ctx *ctx);
  * on.  The same names, upper-cased behind NDT_HIP_ (NDT_HIP_PIPELINE, NDT_HIP_DEBUG_LEVELS ...), are read from the
  * environment ONCE, when the context is created; nothing on the render or upload path looks at the environment.
  *   "pipeline"        0 auto, 1 levels (one trace launch + shade launches per bounce), 2 stream (the whole ray tree in
- *                     one persistent launch), 3 hybrid -- DESIGN.md section 3; the environment takes the words
- *   "hybrid_level"    hybrid: the bounce from which on the frame kernel renders (default 2)
+ *                     one persistent launch) -- DESIGN.md section 3; the environment takes the words
  *   "stream_below"    auto: passes of up to this many primaries go to the streaming frame kernel
  *   "stream_below_list"  ... and passes over a list of samples (recursive anti-aliasing) of up to this many (default 30 000)
  *   "hull_box" / "face_box"   0: upload hcubes without the hull box / without the per-face boxes (tests prove them neutral)
@@ -554,10 +553,9 @@ int ndt_hip_multi_path_taken(ndt_hip_ctx *ctx);
  *                     from (0, the default, and any other value give images that are independent draws of one distribution)
  *   "multi_path"      ndt_hip_render_multi: 0 auto (stores on the same device, peer stores over xGMI, a staged copy where
  *                     there is no peer access), 1 never staged, 2 always staged -- also between contexts of one device
- *   "shade_pair"      0: lighting of a bounce and shading of the next as two launches
- *   "light_overlap"   per-bounce pipeline, one light window, not hybrid: 1 (default) the lighting of every bounce but the
- *                     deepest runs on the context's second stream beside the next bounce's trace launch (and "shade_pair" has
- *                     nothing to pair); 0 every launch on the one stream.  Same image, same counts
+ *   "light_overlap"   per-bounce pipeline, one light window: 1 (default) the lighting of every bounce but the deepest runs
+ *                     on the context's second stream beside the next bounce's trace launch; 0 every launch on the one stream,
+ *                     the lighting of a bounce in front of the shading of the next.  Same image, same counts
  *   "early_pixels"    where "light_overlap" applies (a no-op elsewhere): the pixels of primaries that are final long before the
  *                     end of the frame are finished on the second stream, and the frame's last launch takes the rest.  0 off;
  *                     1 (default) the primaries that hit nothing, beside the second trace launch; 2 also the hit ones without

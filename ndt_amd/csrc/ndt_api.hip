@@ -61,22 +61,21 @@ extern "C" int ndt_hip_create(int device, ndt_hip_ctx **out)
     ctx->device = device;
     {
         // the environment is read here, once: nothing on the render or upload path looks at it
-        static const char *const names[] = { "hybrid_level", "stream_below", "stream_below_list", "hull_box", "face_box", "face_tree", "face_groups", "item_sets", "gate_prepass", "gate_prepass_below", "item_boxes", "leaf_history", "leaf_scan", "leaf_scan_group", "multi_path", "sample_seed", "stream_fused", "fuse_primaries", "shade_pair", "light_overlap", "early_pixels", "light_window", "debug_levels",
+        static const char *const names[] = { "stream_below", "stream_below_list", "hull_box", "face_box", "face_tree", "face_groups", "item_sets", "gate_prepass", "gate_prepass_below", "item_boxes", "leaf_history", "leaf_scan", "leaf_scan_group", "multi_path", "sample_seed", "stream_fused", "fuse_primaries", "light_overlap", "early_pixels", "light_window", "debug_levels",
                                              "exit_probe", "shade_probe", "stream_probe", "test_small_pool" };
         const char *pl = getenv("NDT_HIP_PIPELINE");
-        if (pl) (void)ndt_hip_set_option(ctx, "pipeline", !strcmp(pl, "levels") ? 1 : !strcmp(pl, "stream") ? 2 : !strcmp(pl, "hybrid") ? 3 : 0);
+        if (pl) (void)ndt_hip_set_option(ctx, "pipeline", !strcmp(pl, "levels") ? 1 : !strcmp(pl, "stream") ? 2 : 0);
         for (const char *nm : names) {
             char env[64] = "NDT_HIP_";
             size_t k = strlen(env);
             for (const char *q = nm; *q && k + 1 < sizeof(env); ++q) env[k++] = (char)toupper((unsigned char)*q);
             env[k] = 0;
             const char *v = getenv(env);
-            // (historical spellings: NDT_HIP_NO_HULL_BOX=1, NDT_HIP_NO_FACE_BOX=1, NDT_HIP_NO_SHADE_PAIR=1)
+            // (historical spellings: NDT_HIP_NO_HULL_BOX=1, NDT_HIP_NO_FACE_BOX=1)
             if (v && *v) (void)ndt_hip_set_option(ctx, nm, !strcmp(nm, "shade_probe") ? atoll(v) + 1 : atoll(v));
         }
         if (getenv("NDT_HIP_NO_HULL_BOX")) ctx->hull_box = false;
         if (getenv("NDT_HIP_NO_FACE_BOX")) ctx->face_box = false;
-        if (getenv("NDT_HIP_NO_SHADE_PAIR") && atoi(getenv("NDT_HIP_NO_SHADE_PAIR"))) ctx->shade_pair = false;
     }
     e = hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking);
     if (e == hipSuccess) {
@@ -151,10 +150,9 @@ extern "C" int ndt_hip_set_option(ndt_hip_ctx *ctx, const char *name, int64_t va
     if (!ctx || !name) return fail(NDT_E_INVALID, "NULL argument");
     const bool on = value != 0;
     if (!strcmp(name, "pipeline")) {
-        if (value < 0 || value > 3) return fail(NDT_E_INVALID, "pipeline %lld", (long long)value);
+        if (value < 0 || value > 2) return fail(NDT_E_INVALID, "pipeline %lld", (long long)value);
         ctx->pipeline = (int)value;
-    } else if (!strcmp(name, "hybrid_level")) ctx->hybrid_level = (int)value;
-    else if (!strcmp(name, "stream_below")) ctx->stream_below = value;
+    } else if (!strcmp(name, "stream_below")) ctx->stream_below = value;
     else if (!strcmp(name, "stream_below_list")) ctx->stream_below_list = value;
     else if (!strcmp(name, "hull_box")) ctx->hull_box = on;
     else if (!strcmp(name, "face_box")) ctx->face_box = on;
@@ -173,7 +171,6 @@ extern "C" int ndt_hip_set_option(ndt_hip_ctx *ctx, const char *name, int64_t va
         ctx->multi_path = (int)value;
     } else if (!strcmp(name, "stream_fused")) ctx->stream_fused = on;
     else if (!strcmp(name, "fuse_primaries")) ctx->fuse_primaries = value < 0 ? -1 : on ? 1 : 0;
-    else if (!strcmp(name, "shade_pair")) ctx->shade_pair = on;
     else if (!strcmp(name, "light_overlap")) ctx->light_overlap = on;
     else if (!strcmp(name, "early_pixels")) {
         if (value < 0 || value > 2) return fail(NDT_E_INVALID, "early_pixels %lld (0 off, 1 missed primaries, 2 and childless ones)", (long long)value);

@@ -153,25 +153,22 @@ struct ndt_hip_ctx {
     long long ws_slab_words = 0;
     int ws_nseg = 0;
     // the streaming frame kernel (ndt_stream.hpp): its queues and counters live beside the workspace
-    // Which pipeline renders a pass (fixed at context creation: NDT_HIP_PIPELINE=auto | levels | stream | hybrid).
+    // Which pipeline renders a pass (fixed at context creation: NDT_HIP_PIPELINE=auto | levels | stream).
     //   levels  one trace launch + shade launches per bounce: three wavefronts per SIMD in the trace kernel, shade kernels
     //           with the whole chip's wavefront slots -- the better one where the rays are many (1080p: 1.46 ms against 1.77);
     //   stream  the streaming frame kernel (ndt_stream.hpp): no per-bounce latency floor -- the better one for passes of up
     //           to about a million primaries (64x36: 0.64 against 0.77 ms, 480x270: 0.61 against 0.72, 960x540: 0.68 against
     //           0.85), which is also what one GPU of eight renders of a 3840x2160 frame;
-    //   hybrid  the first hybrid_level bounces per bounce, the deeper ones by the frame kernel: measured, not chosen by
-    //           auto (the benchmark frame has a quarter of its rays in bounces 2 and 3: 2.28 ms; hypercube 3-D 0.65 = levels);
     //   auto    stream up to stream_below primaries, levels above.
-    int pipeline = 0;               // 0 auto, 1 levels, 2 stream, 3 hybrid
-    int hybrid_level = 2;           // hybrid: the bounce from which on the frame kernel renders (NDT_HIP_HYBRID_LEVEL)
+    int pipeline = 0;               // 0 auto, 1 levels, 2 stream
     long long stream_below = 1000000;       // where the two cross on the benchmark scene (profiles/r03_frame_time_vs_size_*.txt: 1280x720 stream 0.918 / levels 0.965 ms, 1408x792 1.054 / 1.045; the r::8 shard of a 3840x2160 frame, 1.04 M primaries: 0.977 per bounce, 1.00 streamed)
     long long stream_below_list = 30000;    // ... for passes over a list of samples (-a): 1080p -a 20,4 of the benchmark scene 27.6 -> 24.0 ms, balls 14.0 -> 12.7
     StreamArgs sa{};
     // ndt_hip_set_option / NDT_HIP_* at context creation (include/ndt_hip.h)
     bool stream_probe = false, exit_probe = false, debug_levels = false, test_small_pool = false;
-    bool hull_box = true, face_box = true, shade_pair = true;
-    // per-bounce pipeline, one light window, not hybrid: shade_finish(b) on the light stream beside the trace launch of bounce b + 1,
-    // plain shade_emit(b) on the main stream instead of the pair (measured: profiles/r09_light_overlap.md)
+    bool hull_box = true, face_box = true;
+    // per-bounce pipeline, one light window: shade_finish(b) on the light stream beside the trace launch of bounce b + 1, not on the
+    // main stream in front of shade_emit(b + 1) (measured: profiles/r09_light_overlap.md)
     bool light_overlap = true;
     // ... and, where that applies, the pixels of primaries that are final early finished on the light stream instead of at the end of
     // the frame: 0 off, 1 the primaries that missed (beside trace launch 1), 2 also the hit ones without a child (behind

@@ -169,9 +169,7 @@ __global__ void k_frame_init(Workspace ws, int n_primary, LevelRange level0, int
 // tag instead of queueing three small read-backs and synchronising the stream.  One wavefront.
 //   [0] node tail  [1] overflow flags  [2] shadow slots wanted  [3] shadow rays of the frame  [4] bounces with nodes
 //   [5] rays the reference would have traced  [7] tag
-// Hybrid pipeline (`c` set): the frame kernel rendered the deeper bounces; its counts are added and its flags reported:
-//   [8] its overflow flags  [9] its abort word  [10] nodes it spawned
-__global__ void k_frame_done(Workspace ws, int n_run, unsigned long long *done, unsigned long long tag, const StreamCtl *c)
+__global__ void k_frame_done(Workspace ws, int n_run, unsigned long long *done, unsigned long long tag)
 {
     const int lane = threadIdx.x;
     unsigned long long ref = ws.ref_rays[8 * lane];         // 64 partial sums, one 64-byte line each
@@ -187,14 +185,6 @@ __global__ void k_frame_done(Workspace ws, int n_run, unsigned long long *done, 
     done[0] = (unsigned long long)(long long)ws.counters[0];
     done[1] = (unsigned long long)(long long)ws.counters[2];
     done[2] = (unsigned long long)(long long)ws.counters[3];
-    done[8] = done[9] = done[10] = 0ull;
-    if (c) {
-        shadow += c->n_shadow.v;
-        if (c->max_level.v + 1 > used) used = c->max_level.v + 1;
-        done[8] = (unsigned long long)(long long)c->overflow.v;
-        done[9] = (unsigned long long)(long long)(c->abort.v | (c->timeout_where.v << 8));
-        done[10] = (unsigned long long)(long long)c->n_children.v;
-    }
     done[3] = (unsigned long long)shadow;
     done[4] = (unsigned long long)used;
     done[5] = ref;
@@ -203,9 +193,8 @@ __global__ void k_frame_done(Workspace ws, int n_run, unsigned long long *done, 
 }
 
 // The streaming pipeline's frame reset: control block, fill / lighting counters and rings of the batches the frame can
-// have, the reference-ray partial sums.  (Sized by the pool, not by the frame: a few MB of zeros.)
-// (frame_too: also the frame's own accumulators -- not in the hybrid pipeline, where the per-bounce kernels own them)
-__global__ void __launch_bounds__(256) k_stream_init(Workspace ws, StreamArgs sa, long long node_batches, long long sh_batches, int frame_too)
+// have, the frame's own accumulators.  (Sized by the pool, not by the frame: a few MB of zeros.)
+__global__ void __launch_bounds__(256) k_stream_init(Workspace ws, StreamArgs sa, long long node_batches, long long sh_batches)
 {
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x, stride = (long long)gridDim.x * blockDim.x;
     // the control block: zeros, except the node tail (the pool behind the primaries is free) and the primaries' share of
@@ -233,10 +222,8 @@ __global__ void __launch_bounds__(256) k_stream_init(Workspace ws, StreamArgs sa
         sa.sh_fill[k] = 0;
         sa.sh_ring[k] = 0;
     }
-    if (frame_too) {
-        for (long long k = i; k < 64 * 8; k += stride) ws.ref_rays[k] = 0ull;
-        for (long long k = i; k < 4; k += stride) ws.counters[k] = 0;
-    }
+    for (long long k = i; k < 64 * 8; k += stride) ws.ref_rays[k] = 0ull;
+    for (long long k = i; k < 4; k += stride) ws.counters[k] = 0;
 }
 
 // The streaming pipeline's closing record, in host-visible memory (the host polls the tag):
@@ -434,27 +421,26 @@ static void launch_finish_part(ndt_hip_ctx *ctx, hipStream_t on, const SceneDesc
                        ctx->d_blob, sd_pass, ws, rg, ctx->dims, (double *)d_rgba, (double *)d_depth, resolve0, take);
 }
 
-// The frame kernel's arguments for a forest rooted at node slots [begin, begin + count): the primaries of a whole frame, or the
-// nodes of the bounce at which the hybrid pipeline hands over.  The root range is the 64-aligned cover of the slots (the frame
-// kernel works in batches of 64).
-static int stream_roots(ndt_hip_ctx *ctx, bool prof, long long begin, long long count, int primaries, StreamArgs &sa)
+// The frame kernel's arguments for a frame of `count` primaries: the roots of its forest, from slot 0, in batches of 64 (the last
+// one padded)
+static int stream_roots(ndt_hip_ctx *ctx, bool prof, long long count, StreamArgs &sa)
 {
     sa = ctx->sa;
-    sa.root_begin = (int)(begin & ~63LL);
-    sa.n_primary = (int)(((begin + count + 63) & ~63LL) - sa.root_begin);
-    sa.valid_begin = (int)begin;
-    sa.valid_end = (int)(begin + count);
-    sa.roots_are_primaries = primaries;
+    sa.root_begin = 0;
+    sa.n_primary = (int)((count + 63) & ~63LL);
+    sa.valid_begin = 0;
+    sa.valid_end = (int)count;
+    sa.roots_are_primaries = 1;
     sa.fused = 0;
     if (!prof) sa.wave_log = nullptr;
     else if (sa.wave_log) HIP_TRY(hipMemsetAsync(sa.wave_log, 0, (size_t)24 * NDT_STREAM_LOG_WAVES * sizeof(unsigned int), ctx->stream));
     return NDT_OK;
 }
 
-static void launch_stream_init(ndt_hip_ctx *ctx, const Workspace &ws, const StreamArgs &sa, int frame_too, hipEvent_t ev_start)
+static void launch_stream_init(ndt_hip_ctx *ctx, const Workspace &ws, const StreamArgs &sa, hipEvent_t ev_start)
 {
     const long long sh_batches = (long long)sa.n_seg * (sa.seg_cap / 64) + NDT_STREAM_LOG_WAVES;
-    launch_stamped(k_stream_init, dim3(512), dim3(256), ctx->stream, ev_start, nullptr, ws, sa, (long long)sa.node_batches, sh_batches, frame_too);
+    launch_stamped(k_stream_init, dim3(512), dim3(256), ctx->stream, ev_start, nullptr, ws, sa, (long long)sa.node_batches, sh_batches);
 }
 
 // render_pass_levels and one attempt of it: the pools overflowed and have been grown, render the pass again (not an NDT_E_* code)
@@ -479,7 +465,7 @@ static int render_pass_stream(ndt_hip_ctx *ctx, const RenderGeom &rg, const Scen
         if (rc) return rc;
         const Workspace ws = ctx->ws;
         StreamArgs sa;
-        if ((rc = stream_roots(ctx, prof, 0, rg.n_primary, 1, sa))) return rc;
+        if ((rc = stream_roots(ctx, prof, rg.n_primary, sa))) return rc;
         // the kernel makes its own primaries and writes its own pixels (option stream_fused, on by default)
         sa.fused = ctx->stream_fused ? 1 : 0;
         sa.rgba = (double *)d_rgba;
@@ -492,7 +478,7 @@ static int render_pass_stream(ndt_hip_ctx *ctx, const RenderGeom &rg, const Scen
             ev_k1 = get_event(ctx, 3);
         }
         const unsigned long long tag = ++ctx->frame_tag;
-        launch_stream_init(ctx, ws, sa, 1, ev_begin);
+        launch_stream_init(ctx, ws, sa, ev_begin);
         if (!sa.fused) kt->primary(s, ctx->d_blob, sd_pass, ws, rg);
         kt->frame_stream(s, ctx->d_blob, sd_pass, ws, rg, sa, ctx->tier, ctx->sd.mask_words, ev_k0, ev_k1);
         if (!sa.fused) launch_finish_pixels(ctx, sd_pass, ws, rg, d_rgba, d_depth, 0);
@@ -538,23 +524,16 @@ struct FrameInFlight {
     const RenderGeom &rg;
     const SceneDesc &sd_pass;
     const bool prof;
-    // Hybrid pipeline: the first `hand` bounces -- where the rays are -- go through the per-bounce kernels (three
-    // wavefronts per SIMD in the trace kernel, shade kernels with the whole chip's wavefront slots); the deeper
-    // bounces, a few per cent of the rays but a launch latency each (one slow batch: 0.15-0.2 ms per trace launch
-    // and 75 us per shade launch, three times over on the benchmark frame), are ONE launch of the frame kernel
-    // rooted at the nodes of bounce `hand`.
-    const bool hybrid;
     void *d_rgba, *d_depth;
     hipStream_t s;
     const NdtKernelTable *kt;
     Workspace ws;
     const int n_levels;             // a node spawns children only while depth_left > 1
-    const int hand;                 // hybrid: the bounce the frame kernel takes over; else none
     // light windows: window k's scene description, and how many window emits the frame has had (they take the two banks of
     // window counters in turn)
     const int n_win;
     const bool windowed;
-    // Option light_overlap (one light window, not hybrid): the lighting of every bounce but the deepest runs on the light stream,
+    // Option light_overlap (one light window): the lighting of every bounce but the deepest runs on the light stream,
     // beside the trace launch of the NEXT bounce, which does not need it.  Nothing is put on the main stream
     // for it: shade_finish(b) is launched when the mailbox says that the stream has passed the trace launch of bounce b
     // (light_beside).  ev_lit[b % 3], on the light stream behind shade_finish(b), marks the last reader of bank b % 3 of the
@@ -574,9 +553,9 @@ struct FrameInFlight {
     int win_emits = 0;
     unsigned long long tag = 0;
     int slots = 0, queue_slot = 0;  // work queues zeroed by frame init / handed out so far
-    int launches = 0;               // trace launches + the frame kernel's
+    int launches = 0;               // trace launches
     size_t ev_n = 0;
-    hipEvent_t ev_begin = nullptr, ev_end = nullptr, ev_k0 = nullptr, ev_k1 = nullptr;
+    hipEvent_t ev_begin = nullptr, ev_end = nullptr;
     std::vector<std::pair<hipEvent_t, hipEvent_t>> trace_ev;
     std::vector<std::string> trace_dbg;
     // NDT_HIP_SHADE_PROBE=<k>: the k-th shade launch of the frame logs the life of each of its wavefronts
@@ -587,14 +566,11 @@ struct FrameInFlight {
     int pending_finish = -1;                    // bounce whose lighting has not been launched yet
     long long pending_upper = 0;
     bool resolve_with_finish = false;           // the deepest bounce was blended by its lighting launch
-    StreamArgs sa{};                            // hybrid: the frame kernel's launch, if there was one
-    bool streamed = false;
 
-    FrameInFlight(ndt_hip_ctx *c, const RenderGeom &g, const SceneDesc &sd, bool p, bool hyb, void *rgba, void *depth)
-        : ctx(c), rg(g), sd_pass(sd), prof(p), hybrid(hyb), d_rgba(rgba), d_depth(depth), s(c->stream), kt(c->kt), ws(c->ws),
-          n_levels(g.max_depth > 1 ? g.max_depth : 1), hand(hyb ? c->hybrid_level : n_levels + 1), n_win((int)c->windows.size()),
-          windowed(n_win > 1), overlap(c->light_overlap && !windowed && !hyb), ls(c->light_stream), early(overlap ? c->early_pixels : 0),
-          n_run(n_levels)
+    FrameInFlight(ndt_hip_ctx *c, const RenderGeom &g, const SceneDesc &sd, bool p, void *rgba, void *depth)
+        : ctx(c), rg(g), sd_pass(sd), prof(p), d_rgba(rgba), d_depth(depth), s(c->stream), kt(c->kt), ws(c->ws),
+          n_levels(g.max_depth > 1 ? g.max_depth : 1), n_win((int)c->windows.size()), windowed(n_win > 1),
+          overlap(c->light_overlap && !windowed), ls(c->light_stream), early(overlap ? c->early_pixels : 0), n_run(n_levels)
     {
         ws.mail = ctx->d_mail;
         ws.mail_tag = ctx->d_mail_tag;
@@ -616,7 +592,6 @@ struct FrameInFlight {
     int trace_bounce(int b, long long upper);
     int trace_windows(int b, long long upper);
     void light_last();
-    int hand_off(long long &cap);
     void resolve();
     int close();
     int report(long long &cap, long long &sh_cap, ndt_render_stats &st);
@@ -688,7 +663,7 @@ int FrameInFlight::render_frame(long long &cap, long long &sh_cap, ndt_render_st
     if ((rc = frame_init(sh_cap))) return rc;
     if ((rc = trace_primaries())) return rc;
     long long upper = rg.n_primary;         // node count of the bounce
-    for (int b = 0; b < n_levels && b < hand; ++b) {
+    for (int b = 0; b < n_levels; ++b) {
         // (the same bounce limit whatever the light windows: a windowed pass uses its work queues again, but light_window must
         // not change what renders)
         if ((windowed ? b + 2 : queue_slot + 1) > NDT_QUEUE_SLOTS || b + 1 > NDT_MAX_LEVELS)
@@ -718,7 +693,6 @@ int FrameInFlight::render_frame(long long &cap, long long &sh_cap, ndt_render_st
         if ((rc = wait_for_tag(ctx, &ctx->h_mail_tag[n_run], tag, "bounce %d was never published", n_run))) return rc;
         if ((rc = light_beside(n_run - 2))) return rc;
     }
-    if (hybrid && n_run >= hand && hand < n_levels && (rc = hand_off(cap))) return rc;
     HIP_TRY(join_light());                  // the resolve reads the colours every bounce's lighting left
     resolve();
     // (early_pixels: the parts that went to the light stream in this attempt are finished; the final launch takes the others)
@@ -838,10 +812,10 @@ int FrameInFlight::trace_primaries()
     return traced(tj, "primaries + closest 0");
 }
 
-// Hit points, shadow rays of bounce b, and the rays of the next bounce -- in the same launch as the lighting of the previous
-// bounce, which is waiting for the shadow answers the last trace launch produced; or (light_overlap) alone: the next trace launch
-// needs what shade_emit(b) makes, nothing before the resolve needs what shade_finish(b - 1) does, and that goes to the light
-// stream once the stream has passed the trace launch it depends on (render_frame, light_beside)
+// Hit points, shadow rays of bounce b, and the rays of the next bounce -- behind the lighting of the previous bounce, which is
+// waiting for the shadow answers the last trace launch produced; or (light_overlap) alone: the next trace launch needs what
+// shade_emit(b) makes, nothing before the resolve needs what shade_finish(b - 1) does, and that goes to the light stream once
+// the stream has passed the trace launch it depends on (render_frame, light_beside)
 void FrameInFlight::light_and_shade(int b, long long upper)
 {
     if (windowed) {
@@ -850,12 +824,8 @@ void FrameInFlight::light_and_shade(int b, long long upper)
             kt->shade_last(s, ctx->d_blob, sd_win[n_win - 1], shade_ws(pending_upper, pending_finish, s), rg, pending_finish, pending_upper, 0,
                            ctx->windows[n_win - 1].first);
         kt->shade_emit(s, ctx->d_blob, sd_win[0], shade_ws(0, b, s), rg, b, upper);
-    } else if (overlap) {
-        kt->shade_emit(s, ctx->d_blob, sd_pass, shade_ws(0, b, s), rg, b, upper);
-    } else if (pending_finish >= 0 && ctx->shade_pair) {
-        kt->shade_pair(s, ctx->d_blob, sd_pass, shade_ws(pending_upper, pending_finish, s), rg, pending_finish, pending_upper, upper);
     } else {
-        if (pending_finish >= 0)
+        if (!overlap && pending_finish >= 0)
             kt->shade_finish(s, ctx->d_blob, sd_pass, shade_ws(pending_upper, pending_finish, s), rg, pending_finish, pending_upper, 0);
         kt->shade_emit(s, ctx->d_blob, sd_pass, shade_ws(0, b, s), rg, b, upper);
     }
@@ -867,19 +837,18 @@ int FrameInFlight::trace_bounce(int b, long long upper)
 {
     long long next_upper = 2 * upper;           // each node spawns at most two
     if (next_upper > ws.cap) next_upper = ws.cap;
-    const bool last = b + 1 == hand;            // the frame kernel traces bounce `hand`
     TraceJob tj{};
     job_shadow(tj, ws, sd_pass, b, upper, windowed ? ctx->windows[0].n_seg : ctx->n_shadow_lights, NDT_SEG_COUNTERS(ws, b), answer_bank(b));
     job_closest(tj, ws);
     tj.count = next_upper;                      // sizes the grid only
-    tj.dense_level = last ? -1 : b + 1;
+    tj.dense_level = b + 1;
     tj.publish_level = b;
     tj.publish_tag = tag;
     // (light_overlap) the launch writes the bank of answers that shade_finish(b - 3) read: behind it.  That lighting went to the
     // light stream a whole bounce ago (with the tag of bounce b - 1), so in a healthy frame the event is long past, and a wait
     // for a past event puts nothing on the stream
     if (overlap && b >= 3) HIP_TRY(hipStreamWaitEvent(s, ev_lit[b % 3], 0));
-    return traced(tj, "shadow " + std::to_string(b) + (last ? "" : " + closest " + std::to_string(b + 1)), windowed ? &sd_win[0] : nullptr);
+    return traced(tj, "shadow " + std::to_string(b) + " + closest " + std::to_string(b + 1), windowed ? &sd_win[0] : nullptr);
 }
 
 // Light windows 1 .. of bounce b.  Window k: fold the answers of window k-1 into the nodes' colours and emit their shadow rays of
@@ -905,47 +874,18 @@ int FrameInFlight::trace_windows(int b, long long upper)
     return NDT_OK;
 }
 
-// The lighting of the deepest bounce that has nodes: blended on the spot (its nodes have no child nodes), unless the frame
-// kernel renders deeper bounces behind it (hybrid)
+// The lighting of the deepest bounce that has nodes: blended on the spot (its nodes have no child nodes)
 // (light_overlap: on the main stream, like the resolve that follows it)
 void FrameInFlight::light_last()
 {
     if (pending_finish < 0) return;
-    resolve_with_finish = !hybrid && pending_finish >= 1 && pending_finish == n_run - 1;
+    resolve_with_finish = pending_finish >= 1 && pending_finish == n_run - 1;
     if (windowed)
         kt->shade_last(s, ctx->d_blob, sd_win[n_win - 1], shade_ws(pending_upper, pending_finish, s), rg, pending_finish, pending_upper,
                        resolve_with_finish ? 1 : 0, ctx->windows[n_win - 1].first);
     else
         kt->shade_finish(s, ctx->d_blob, sd_pass, shade_ws(pending_upper, pending_finish, s), rg, pending_finish, pending_upper,
                          resolve_with_finish ? 1 : 0);
-}
-
-// Hybrid: the frame kernel renders the forest rooted at the nodes of bounce `hand` (its queues are reset, and it runs).
-// PASS_AGAIN: the 64-aligned cover of the roots does not fit the pool.
-int FrameInFlight::hand_off(long long &cap)
-{
-    int rc;
-    if ((rc = wait_for_tag(ctx, &ctx->h_mail_tag[hand], tag, "bounce %d was never published", hand))) return rc;
-    const LevelRange roots = ctx->h_mail[hand];
-    if (roots.count > 0) {
-        if ((rc = stream_roots(ctx, prof, roots.begin, roots.count, 0, sa))) return rc;
-        if ((long long)sa.root_begin + sa.n_primary > ws.cap) {
-            cap *= 2;
-            return PASS_AGAIN;
-        }
-        launch_stream_init(ctx, ws, sa, 0, nullptr);
-        if (prof) {
-            ev_k0 = get_event(ctx, ev_n++);
-            ev_k1 = get_event(ctx, ev_n++);
-            trace_ev.push_back({ ev_k0, ev_k1 });
-            trace_dbg.push_back("frame kernel, bounces " + std::to_string(hand) + " ..");
-        }
-        kt->frame_stream(s, ctx->d_blob, sd_pass, ws, rg, sa, ctx->tier, ctx->sd.mask_words, ev_k0, ev_k1);
-        ++launches;
-        streamed = true;
-    }
-    n_run = hand;           // the bounces the per-bounce resolve walks
-    return NDT_OK;
 }
 
 // bottom-up colour resolve, deepest bounce first (bounce 0, the primaries: inside k_finish_pixels)
@@ -962,7 +902,7 @@ void FrameInFlight::resolve()
 // k_frame_done is the last kernel of the frame: once its tag is here, the image and the record are complete
 int FrameInFlight::close()
 {
-    launch_stamped(k_frame_done, dim3(1), dim3(64), s, nullptr, ev_end, ws, n_run, ctx->d_done, tag, streamed ? sa.ctl : (const StreamCtl *)nullptr);
+    launch_stamped(k_frame_done, dim3(1), dim3(64), s, nullptr, ev_end, ws, n_run, ctx->d_done, tag);
     HIP_TRY(hipGetLastError());
     int rc = wait_for_tag(ctx, &ctx->h_done[7], tag, "the frame never completed");
     if (rc) return rc;
@@ -975,26 +915,20 @@ int FrameInFlight::report(long long &cap, long long &sh_cap, ndt_render_stats &s
 {
     const unsigned long long *done = ctx->h_done;
     const int overflow = (int)(long long)done[1], sh_wanted = (int)(long long)done[2];
-    const int s_overflow = (int)(long long)done[8], s_abort = (int)(long long)done[9];
-    if (overflow != 0 || s_overflow != 0) {
+    if (overflow != 0) {
         if (ctx->debug_levels)
-            fprintf(stderr, "ndt_hip: overflow: per-bounce kernels %d (needs %d), frame kernel %d; pool %lld nodes, %lld shadow slots\n", overflow,
-                    sh_wanted, s_overflow, cap, sh_cap);
-        if ((overflow & 1) || (s_overflow & 1)) cap *= 2;
-        if ((overflow & 2) || (s_overflow & 2)) {
+            fprintf(stderr, "ndt_hip: overflow: per-bounce kernels %d (needs %d); pool %lld nodes, %lld shadow slots\n", overflow, sh_wanted, cap,
+                    sh_cap);
+        if (overflow & 1) cap *= 2;
+        if (overflow & 2) {
             sh_cap *= 2;
             if (sh_cap < sh_wanted) sh_cap = sh_wanted;
         }
-        // (the frame kernel keeps the shadow rays of ALL its bounces: its segments grow with the node pool, together)
-        const int n_seg = ctx->n_shadow_lights > 0 ? ctx->n_shadow_lights : 1;
-        if (s_overflow != 0 && sh_cap < cap * n_seg) sh_cap = cap * n_seg;
         return PASS_AGAIN;
     }
-    if (s_abort != 0)
-        return fail(NDT_E_STATE, "the frame kernel gave up (abort %d, where %d): a work item never arrived", s_abort & 0xff, s_abort >> 8);
     st = ndt_render_stats{};
     st.rays_primary = n_pixels(rg);
-    st.rays_secondary = (long long)(int)(long long)done[0] - rg.n_primary + (long long)done[10];
+    st.rays_secondary = (long long)(int)(long long)done[0] - rg.n_primary;
     st.rays_shadow = (long long)done[3];
     st.rays_ref_equiv = (long long)done[5];
     st.levels = (int)done[4];
@@ -1008,11 +942,6 @@ int FrameInFlight::report(long long &cap, long long &sh_cap, ndt_render_stats &s
             ms += m;
         }
         st.trace_ms = ms;
-        if (streamed && sa.wave_log && ev_k0) {
-            float km = 0;
-            HIP_TRY(hipEventElapsedTime(&km, ev_k0, ev_k1));
-            print_stream_probe(sa.wave_log, km);
-        }
         if (ctx->debug_levels) HIP_TRY(print_debug(st.levels));
         HIP_TRY(hipEventElapsedTime(&fm, ev_begin, ev_end));
         st.frame_ms = fm;
@@ -1039,15 +968,14 @@ hipError_t FrameInFlight::print_debug(int levels_used)
 }
 
 // Grows the pools and renders again on overflow, at most 8 times
-static int render_pass_levels(ndt_hip_ctx *ctx, const RenderGeom &rg, const SceneDesc &sd_pass, bool prof, bool hybrid, void *d_rgba, void *d_depth,
-                              long long cap, long long sh_cap, ndt_render_stats &st)
+static int render_pass_levels(ndt_hip_ctx *ctx, const RenderGeom &rg, const SceneDesc &sd_pass, bool prof, void *d_rgba, void *d_depth, long long cap,
+                              long long sh_cap, ndt_render_stats &st)
 {
     for (int attempt = 0; attempt < 8; ++attempt) {
         if (cap > 0x7fffff00LL || sh_cap > 0x7fffff00LL) return fail(NDT_E_NOMEM, "ray tree exceeds 2^31 nodes");
         int rc = ensure_workspace(ctx, cap, sh_cap);
         if (rc) return rc;
-        if (hybrid && (rc = ensure_stream_args(ctx))) return rc;
-        FrameInFlight frame(ctx, rg, sd_pass, prof, hybrid, d_rgba, d_depth);
+        FrameInFlight frame(ctx, rg, sd_pass, prof, d_rgba, d_depth);
         if ((rc = frame.render(cap, sh_cap, st)) != PASS_AGAIN) return rc;
     }
     return fail(NDT_E_NOMEM, "ray-tree workspace kept overflowing");
@@ -1079,7 +1007,6 @@ int ndt_impl::render_pass(ndt_hip_ctx *ctx, RenderGeom rg, bool prof, void *d_rg
     // mask of fired lights per node)
     const bool windowed = ctx->windows.size() > 1;
     const bool use_stream = !windowed && (ctx->pipeline == 2 || (ctx->pipeline == 0 && n_primary <= stream_upto));
-    const bool hybrid = !windowed && !use_stream && ctx->pipeline == 3 && ctx->hybrid_level >= 1 && rg.max_depth > ctx->hybrid_level;
     if (use_stream) {
         bool no_room = false;
         const int rc = render_pass_stream(ctx, rg, sd_pass, prof, d_rgba, d_depth, cap, sh_cap, st, no_room);
@@ -1090,5 +1017,5 @@ int ndt_impl::render_pass(ndt_hip_ctx *ctx, RenderGeom rg, bool prof, void *d_rg
         if (cap < ctx->ws.cap) cap = ctx->ws.cap;
         if (sh_cap < ctx->ws.sh_cap) sh_cap = ctx->ws.sh_cap;
     }
-    return render_pass_levels(ctx, rg, sd_pass, prof, hybrid, d_rgba, d_depth, cap, sh_cap, st);
+    return render_pass_levels(ctx, rg, sd_pass, prof, d_rgba, d_depth, cap, sh_cap, st);
 }

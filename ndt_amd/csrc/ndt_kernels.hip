@@ -442,7 +442,7 @@ __global__ void __launch_bounds__(MW == 0 ? NDT_TRACE_T1_MAX_BLOCK : NDT_TRACE_M
             dense_begin = next.begin;
             dense_count = next.count;
         } else {
-            dense_count = 0;        // shadow rays only (the next bounce's nodes go to the frame kernel: hybrid pipeline)
+            dense_count = 0;        // shadow rays only (a later light window of a bounce: trace_windows)
         }
     }
     const long long dense_batches = (dense_count + bs - 1) >> sh;
@@ -1366,35 +1366,6 @@ __global__ void __launch_bounds__(256, NDT_SHADE_WAVES) k_shade_finish(const dou
     }
 }
 
-// lighting of bounce `level` in the first n_finish workgroups, shading of bounce level+1 in the rest.  (The other way
-// round -- the long-lived shading wavefronts first -- was measured: they then all contend for the segment counters at
-// once and live 22-32 us instead of 16-19, and the launch takes 20-30 % longer.)
-__global__ void __launch_bounds__(256, NDT_SHADE_WAVES) k_shade_pair(const double *blob, SceneDesc sd, Workspace ws, RenderGeom rg, int level,
-                                                       unsigned n_finish)
-{
-    __shared__ EmitShared sh;
-    if (blockIdx.x < n_finish) {
-        const LevelRange lr = ws.levels[level];
-        const long long base = (long long)blockIdx.x * blockDim.x;
-        if (base < lr.count) {
-            NDT_SHADE_LOG_BEGIN();
-            shade_finish_node(blob, sd, ws, rg, lr, level, base + threadIdx.x);
-            NDT_SHADE_LOG_END();
-        }
-    } else {
-        const LevelRange lr = ws.levels[level + 1];
-        const long long base = (long long)(blockIdx.x - n_finish) * blockDim.x;
-        if (base < lr.count) {
-            NDT_SHADE_LOG_BEGIN();
-            if (threadIdx.x < 64) sh.seg_total[threadIdx.x] = 0;
-            if (threadIdx.x == 0) sh.spawn_total = 0;
-            __syncthreads();
-            shade_emit_node(blob, sd, ws, rg, lr, level + 1, base + threadIdx.x, &sh);
-            NDT_SHADE_LOG_END();
-        }
-    }
-}
-
 // ------------------------------------------------------------------ light windows (scenes of more than one window)
 //
 // A scene whose lights do not fit in one window of 64 (or of option light_window) is lit window by window:
@@ -1577,13 +1548,6 @@ static void launch_shade_finish(hipStream_t s, const double *blob, SceneDesc sd,
     if (upper <= 0) return;
     hipLaunchKernelGGL(k_shade_finish, dim3(shade_grid(upper)), dim3(256), 0, s, blob, sd, ws, rg, level, resolve_here);
 }
-static void launch_shade_pair(hipStream_t s, const double *blob, SceneDesc sd, Workspace ws, RenderGeom rg, int level,
-                              long long upper_finish, long long upper_emit)
-{
-    const unsigned nf = upper_finish > 0 ? shade_grid(upper_finish) : 0, ne = upper_emit > 0 ? shade_grid(upper_emit) : 0;
-    if (nf + ne == 0) return;
-    hipLaunchKernelGGL(k_shade_pair, dim3(nf + ne), dim3(256), 0, s, blob, sd, ws, rg, level, nf);
-}
 static void launch_shade_window(hipStream_t s, const double *blob, SceneDesc sd_fold, SceneDesc sd_emit, Workspace ws, RenderGeom rg,
                                 int level, long long upper, int li_base_fold, int li_base_emit, int *seg_cnt, int *seg_clear,
                                 int n_seg_emit, int cont)
@@ -1615,7 +1579,6 @@ extern "C" const NdtKernelTable *NDT_CAT(ndt_kernel_table_, NDT_DIMS)()
 {
     using namespace NDT_CAT(ndt_d, NDT_DIMS);
     static const NdtKernelTable table = { NDT_DIMS, launch_primary, launch_trace, launch_shade_emit, launch_shade_finish,
-                                          launch_shade_pair, launch_hitpoints, launch_frame_stream, launch_shade_window,
-                                          launch_shade_last };
+                                          launch_hitpoints, launch_frame_stream, launch_shade_window, launch_shade_last };
     return &table;
 }

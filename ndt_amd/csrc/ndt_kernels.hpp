@@ -181,14 +181,15 @@ struct StreamArgs {
     int *sowner;            // [n_seg * seg_cap]  the node a shadow ray belongs to, -1 = padding slot
     int n_seg;
     int seg_cap;            // slots per light segment (multiple of 64)
-    // The roots of the forest the launch renders: node slots [root_begin, root_begin + n_primary), both multiples of 64.  A
-    // whole frame: the primaries (root_begin = 0).  The deep bounces of a frame whose first bounces went through the
-    // per-bounce kernels: the nodes of the first bounce the frame kernel takes over (render_pass, hybrid pipeline).
+    // The roots of the forest the launch renders: node slots [root_begin, root_begin + n_primary), both multiples of 64.  The
+    // one caller (render_pass_stream) renders whole frames: the roots are the primaries, root_begin = 0.
     int root_begin;
     int n_primary;
-    int roots_are_primaries;    // 1: the roots are the frame's primary rays (depth maps record their hits)
-    // of the root batches' slots only [valid_begin, valid_end) are roots (the first and the last root batch may hold slots
-    // of the bounce before / slots nobody has written: the root range is the 64-aligned cover of a bounce's node range)
+    int roots_are_primaries;    // 1: the roots are the frame's primary rays (depth maps record their hits); always, today
+    // of the root batches' slots only [valid_begin, valid_end) are roots (the last root batch may hold slots nobody has
+    // written; valid_begin = 0).  (root_begin, roots_are_primaries and valid_begin are constants since the frame kernel has no
+    // other caller; taking them out of this by-value argument moved the frame kernel's registers and made 6-D frames
+    // 2-4 % slower, so they stay: profiles/modes_retired.md)
     int valid_begin, valid_end;
     int node_batches;       // cap / 64: entries per shard of sec_ring
     unsigned int *wave_log; // NDT_HIP_STREAM_PROBE: 16 words per wavefront (what it did and when), else nullptr
@@ -212,10 +213,6 @@ struct NdtKernelTable {
     void (*shade_emit)(hipStream_t, const double *blob, SceneDesc, Workspace, RenderGeom, int level, long long upper);
     // resolve_here: `level` is the deepest bounce of the frame, its nodes are blended on the spot (no k_resolve for it)
     void (*shade_finish)(hipStream_t, const double *blob, SceneDesc, Workspace, RenderGeom, int level, long long upper, int resolve_here);
-    // shade_finish(level) and shade_emit(level + 1) in one launch: they touch different nodes, and both are
-    // short latency-bound kernels for the small deep bounces
-    void (*shade_pair)(hipStream_t, const double *blob, SceneDesc, Workspace, RenderGeom, int level, long long upper_finish,
-                       long long upper_emit);
     void (*hitpoints)(hipStream_t, const double *blob, SceneDesc, const double *o, const double *v, long long stride,
                       const int *prim, double *hit, double *nrm, long long count);
     // the whole ray tree of a frame in one persistent launch (ndt_stream.hpp); primaries already in the pool

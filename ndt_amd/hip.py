@@ -365,7 +365,7 @@ class NdtHip:
         self._check(self.lib.ndt_hip_synchronize(self.ctx))
 
     def set_option(self, name, value):
-        """ndt_hip_set_option: "pipeline" (0 auto, 1 levels, 2 stream, 3 hybrid), "hull_box", "face_box", "debug_levels", ..."""
+        """ndt_hip_set_option: "pipeline" (0 auto, 1 levels, 2 stream), "hull_box", "face_box", "debug_levels", ..."""
         self._check(self.lib.ndt_hip_set_option(self.ctx, name.encode(), int(value)))
 
     def multi_path_taken(self):

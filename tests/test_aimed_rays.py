@@ -318,14 +318,17 @@ def test_new_zoo_through_every_pipeline(gpu, name):
     gpu.upload_scene(g.scene)
     outs = []
     try:
-        for pipeline, fused in ((1, 1), (2, 1), (2, 0), (3, 1)):
+        # (the last: the per-bounce pipeline with every launch on the one stream, light_overlap 0)
+        for pipeline, fused, overlap in ((1, 1, 1), (2, 1, 1), (2, 0, 1), (1, 1, 0)):
             gpu.set_option("pipeline", pipeline)
             gpu.set_option("stream_fused", fused)
+            gpu.set_option("light_overlap", overlap)
             img, st = gpu.render(g.width, g.height, g.depth)
             outs.append((img, (st.rays_primary, st.rays_secondary, st.rays_shadow, st.rays_ref_equiv, st.levels)))
     finally:
         gpu.set_option("pipeline", 0)
         gpu.set_option("stream_fused", 1)
+        gpu.set_option("light_overlap", 1)
     for img, counts in outs[1:]:
         assert np.array_equal(img, outs[0][0])
         assert counts == outs[0][1]

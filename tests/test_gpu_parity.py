@@ -195,23 +195,26 @@ def test_one_frame_over_two_gpus(gpu):
 
 @pytest.mark.parametrize("name", ["c3_random4d", "zoo3d_mirror", "c1_hypercube3d", "c5_hypercube6d", "zoo4d"])
 def test_every_pipeline_renders_the_same_frame(gpu, name):
-    """The three ways a pass can be rendered -- one trace launch + shade launches per bounce (levels), the whole ray tree
-    in one persistent launch (stream), the first two bounces per bounce and the deeper ones by the frame kernel (hybrid) --
-    differ in which wavefront computes what and when, never in an operand: the images are the same to the last bit, and so
-    are the ray counts.  (zoo3d_mirror: facing mirrors, 60 bounces deep; the pools are regrown on the way.)"""
+    """The ways a pass can be rendered -- one trace launch + shade launches per bounce (levels), with the lighting of a bounce
+    beside the next trace launch or (light_overlap 0) in front of the next bounce's shading on the one stream; the whole ray
+    tree in one persistent launch (stream), making its own primaries and pixels or not -- differ in which wavefront computes
+    what and when, never in an operand: the images are the same to the last bit, and so are the ray counts.  (zoo3d_mirror:
+    facing mirrors, 60 bounces deep; the pools are regrown on the way.)"""
     g = golden(name)
     gpu.upload_scene(g.scene)
     outs = []
     try:
-        for pipeline, fused in ((1, 1), (2, 1), (2, 0), (3, 1)):
+        for pipeline, fused, overlap in ((1, 1, 1), (2, 1, 1), (2, 0, 1), (1, 1, 0)):
             # (stream_fused 0: the frame kernel between k_primary and k_finish_pixels instead of doing their work itself)
             gpu.set_option("pipeline", pipeline)
             gpu.set_option("stream_fused", fused)
+            gpu.set_option("light_overlap", overlap)
             img, st = gpu.render(g.width, g.height, g.depth)
             outs.append((img, (st.rays_primary, st.rays_secondary, st.rays_shadow, st.rays_ref_equiv, st.levels)))
     finally:
         gpu.set_option("pipeline", 0)
         gpu.set_option("stream_fused", 1)
+        gpu.set_option("light_overlap", 1)
     for img, counts in outs[1:]:
         assert np.array_equal(img, outs[0][0])
         assert counts == outs[0][1]

@@ -109,7 +109,7 @@ def test_many_lights_vs_oracle(gpu, oracle, name, n_lights, w, h, depth):
     assert len(fs.lights) == n_lights
     want, wst = oracle.render(fs, w, h, depth)
     try:
-        for pipeline in (0, 1, 2, 3):
+        for pipeline in (0, 1, 2):
             gpu.set_option("pipeline", pipeline)
             gpu.upload_scene(fs)
             out, st = gpu.render(w, h, depth)
