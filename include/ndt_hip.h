@@ -40,7 +40,8 @@ extern "C" {
 #define NDT_E_INVALID      -1   /* malformed scene / argument */
 #define NDT_E_UNSUPPORTED  -2   /* valid for the reference, but not for the device path */
 #define NDT_E_DEVICE       -3   /* HIP runtime failure */
-#define NDT_E_NOMEM        -4
+#define NDT_E_NOMEM        -4   /* also: a device buffer of the context could not be allocated -- from ndt_hip_render*, the
+                                   multi-context and async paths and ndt_hip_upload_scene too, which answered NDT_E_DEVICE before */
 #define NDT_E_STATE        -5   /* call out of order (no scene uploaded, ...) */
 
 /* Object kinds = the reference's built-in plugins (objects/ *.c `type_name`). */

@@ -118,21 +118,19 @@ extern "C" int ndt_hip_destroy(ndt_hip_ctx *ctx)
     free_workspace(ctx);
     free_stage(ctx);
     free_async(ctx);
-    if (ctx->d_shard) (void)hipFree(ctx->d_shard);
-    if (ctx->d_image) (void)hipFree(ctx->d_image);
-    for (auto &slot : ctx->pool)
-        if (slot.first) (void)hipFree(slot.first);
-    for (auto &slot : ctx->pool2)
-        if (slot.first) (void)hipFree(slot.first);
-    if (ctx->d_blob) (void)hipFree(ctx->d_blob);
-    if (ctx->d_out) (void)hipFree(ctx->d_out);
-    if (ctx->d_fit) (void)hipFree(ctx->d_fit);
+    ctx->d_shard.release();
+    ctx->d_image.release();
+    for (DeviceBuffer &slot : ctx->pool) slot.release();
+    for (DeviceBuffer &slot : ctx->pool2) slot.release();
+    ctx->d_blob.release();
+    ctx->d_out.release();
+    ctx->d_fit.release();
     free_kd(ctx);
     free_png(ctx);
     free_jpeg(ctx);
     free_depth(ctx);
     free_ssaa(ctx);
-    if (ctx->d_eyes) (void)hipFree(ctx->d_eyes);
+    ctx->d_eyes.release();
     if (ctx->h_counters) (void)hipHostFree(ctx->h_counters);
     if (ctx->h_levels) (void)hipHostFree(ctx->h_levels);
     if (ctx->h_mail) (void)hipHostFree(ctx->h_mail);
@@ -222,13 +220,8 @@ extern "C" int ndt_hip_upload_scene(ndt_hip_ctx *ctx, const ndt_flat_scene *fs)
     ctx->kt = table_for(fs->dims);
     if (!ctx->kt) return fail(NDT_E_UNSUPPORTED, "no kernels for %d dimensions", fs->dims);
     HIP_TRY(sync_streams(ctx));          // (the lighting kernels read the blob too)
-    if (ctx->d_blob_words < ctx->blob.size()) {
-        if (ctx->d_blob) HIP_TRY(hipFree(ctx->d_blob));
-        ctx->d_blob = nullptr;
-        HIP_TRY(hipMalloc((void **)&ctx->d_blob, ctx->blob.size() * sizeof(double)));
-        ctx->d_blob_words = ctx->blob.size();
-    }
-    HIP_TRY(hipMemcpyAsync(ctx->d_blob, ctx->blob.data(), ctx->blob.size() * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    if ((rc = ctx->d_blob.reserve(ctx->blob.size() * sizeof(double), ctx->stream, "ndt_hip_upload_scene"))) return rc;
+    HIP_TRY(hipMemcpyAsync(ctx->d_blob.p, ctx->blob.data(), ctx->blob.size() * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     ctx->aperture_radius = fs->cam_aperture_radius;
     ctx->have_scene = true;
@@ -259,18 +252,6 @@ extern "C" int ndt_hip_quantize_device(ndt_hip_ctx *ctx, const void *d_rgba, voi
     hipLaunchKernelGGL(k_quantize, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, (const double *)d_rgba,
                        (unsigned char *)d_rgba8, n);
     HIP_TRY(hipGetLastError());
-    return NDT_OK;
-}
-
-int ndt_impl::ensure_out(ndt_hip_ctx *ctx, size_t bytes)
-{
-    if (ctx->d_out_bytes >= bytes) return NDT_OK;
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    if (ctx->d_out) HIP_TRY(hipFree(ctx->d_out));
-    ctx->d_out = nullptr;
-    ctx->d_out_bytes = 0;
-    HIP_TRY(hipMalloc(&ctx->d_out, bytes));
-    ctx->d_out_bytes = bytes;
     return NDT_OK;
 }
 
@@ -336,8 +317,8 @@ extern "C" int ndt_hip_trace_rays(ndt_hip_ctx *ctx, int64_t n_rays, const double
     tj.queue = ws.counters + NDT_CNT_QUEUE;
     HIP_TRY(hipMemsetAsync(ws.counters + NDT_CNT_QUEUE, 0, NDT_QUEUE_INTS * sizeof(int), s));
     tj.publish_level = -1;
-    ctx->kt->trace(s, ctx->d_blob, ctx->sd, ws, tj, ctx->tier, ctx->sd.mask_words, nullptr, nullptr);
-    ctx->kt->hitpoints(s, ctx->d_blob, ctx->sd, ws.ray_o, ws.ray_v, ws.cap, ws.hit_prim, ws.hit_p, ws.hit_n, cnt);
+    ctx->kt->trace(s, ctx->d_blob.as<double>(), ctx->sd, ws, tj, ctx->tier, ctx->sd.mask_words, nullptr, nullptr);
+    ctx->kt->hitpoints(s, ctx->d_blob.as<double>(), ctx->sd, ws.ray_o, ws.ray_v, ws.cap, ws.hit_prim, ws.hit_p, ws.hit_n, cnt);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(obj, ws.hit_obj, cnt * sizeof(int), hipMemcpyDeviceToHost, s));
     HIP_TRY(hipMemcpyAsync(so.data(), ws.hit_p, so.size() * sizeof(double), hipMemcpyDeviceToHost, s));

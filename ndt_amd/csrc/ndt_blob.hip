@@ -40,7 +40,7 @@ extern "C" int ndt_hip_hcube_face_boxes(const ndt_flat_scene *fs, int32_t object
 
 extern "C" int64_t ndt_hip_hcube_face_tree(const ndt_flat_scene *fs, int32_t object, int64_t cap_nodes, double *rows_out, int32_t *level_off, int32_t *top_out)
 {
-    std::vector<double> hull((size_t)(fs ? fs->dims : 1) * (fs ? fs->dims + 2 : 1));
+    std::vector<double> hull((size_t)(fs && fs->dims > 0 && fs->dims <= NDT_MAX_DIMS ? fs->dims * (fs->dims + 2) : 1));
     const int rc = ndt_hip_hcube_hull_box(fs, object, hull.data());      // validates the arguments
     if (rc <= 0) return rc;
     if (!level_off || !top_out) return fail(NDT_E_INVALID, "null argument");

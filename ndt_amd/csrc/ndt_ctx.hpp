@@ -15,6 +15,7 @@
 //   ndt_jpeg.hip     ndt_hip_encode_jpeg* / ndt_hip_render_jpeg: a frame's JPEG file made on the device; kernels, launcher and C ABI
 //   ndt_depth.hip    ndt_hip_depth_rgba8_device / ndt_hip_render_*_depth: the depth map of `-z` normalised and quantised on the device
 //   ndt_ssaa.hip     ndt_hip_ssaa_fold_device / ndt_hip_render_ssaa*: K x K supersampling, K ordinary renders folded on the device
+//   ndt_buffer.hpp   DeviceBuffer: the grow-only device buffers of the context and of its sinks, their one grow and free path
 #pragma once
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
@@ -29,14 +30,12 @@
 #include <vector>
 
 #include "../../include/ndt_hip.h"
+#include "ndt_buffer.hpp"
 #include "ndt_kernels.hpp"
 
 namespace ndt_impl {
 
 struct CtxWorker;       // ndt_multi.hip: the thread that drives a context inside a multi-context render
-
-// sets the calling thread's ndt_hip_last_error() text and returns `code`
-int fail(int code, const char *fmt, ...) __attribute__((format(printf, 2, 3)));
 
 } // namespace ndt_impl
 using namespace ndt_impl;
@@ -71,28 +70,22 @@ struct KdState {
 
 // ndt_hip_encode_png* (ndt_png.hip): grow-only device buffers, reused by the next frame
 struct PngState {
-    void *d_rgba8 = nullptr, *d_filtered = nullptr, *d_row_filter = nullptr, *d_slots = nullptr, *d_meta = nullptr, *d_offsets = nullptr,
-         *d_file = nullptr, *d_info = nullptr;
-    size_t rgba8_bytes = 0, filtered_bytes = 0, row_filter_bytes = 0, slots_bytes = 0, meta_bytes = 0, offsets_bytes = 0, file_bytes = 0,
-           info_bytes = 0;
+    DeviceBuffer d_rgba8, d_filtered, d_row_filter, d_slots, d_meta, d_offsets, d_file, d_info;
     void *h_info = nullptr;         // pinned: the info record of the last file
-    void *d_rgba16 = nullptr;       // ndt_hip_render_png16: the frame's 16-bit samples in file byte order
-    size_t rgba16_bytes = 0;
+    DeviceBuffer d_rgba16;          // ndt_hip_render_png16: the frame's 16-bit samples in file byte order
 };
 
 // ndt_hip_encode_jpeg* (ndt_jpeg.hip): grow-only device buffers, reused by the next frame
 struct JpegState {
-    void *d_rgba8 = nullptr, *d_coef = nullptr, *d_slots = nullptr, *d_meta = nullptr, *d_offsets = nullptr, *d_file = nullptr, *d_info = nullptr;
-    size_t rgba8_bytes = 0, coef_bytes = 0, slots_bytes = 0, meta_bytes = 0, offsets_bytes = 0, file_bytes = 0, info_bytes = 0;
+    DeviceBuffer d_rgba8, d_coef, d_slots, d_meta, d_offsets, d_file, d_info;
     void *h_info = nullptr;         // pinned: the info record of the last file
 };
 
 // ndt_hip_depth_rgba8_device, ndt_hip_render_*_depth (ndt_depth.hip): grow-only device buffers, reused by the next frame
 struct DepthState {
-    void *d_records = nullptr;      // one {lo, hi, bad} record per workgroup of k_depth_range, and the folded one behind them
-    void *d_rgba8 = nullptr, *d_depth8 = nullptr;       // the two 8-bit images of ndt_hip_render_*_depth
-    void *d_rgba16 = nullptr, *d_grey16 = nullptr;      // the two 16-bit images of ndt_hip_render_png16_depth (file byte order)
-    size_t records_bytes = 0, rgba8_bytes = 0, depth8_bytes = 0, rgba16_bytes = 0, grey16_bytes = 0;
+    DeviceBuffer d_records;         // one {lo, hi, bad} record per workgroup of k_depth_range, and the folded one behind them
+    DeviceBuffer d_rgba8, d_depth8;     // the two 8-bit images of ndt_hip_render_*_depth
+    DeviceBuffer d_rgba16, d_grey16;    // the two 16-bit images of ndt_hip_render_png16_depth (file byte order)
     void *h_result = nullptr;       // pinned: the folded record of the last map
     int launches = 0;               // kernel launches of the last map
     double finish_ms = 0.0;         // host time of the last map: launch to the folded record in host memory
@@ -100,11 +93,10 @@ struct DepthState {
 
 // ndt_hip_render_ssaa* (ndt_ssaa.hip): grow-only device buffers, reused by the next frame
 struct SsaaState {
-    void *d_pass = nullptr;         // one pass of the large frame: rows x K width x 4 doubles, and its depth map behind them when wanted
-    void *d_acc = nullptr;          // the frame of the calls that deliver to host memory or as a file: rows x width x 4 doubles (+ the map)
-    void *d_rgba8 = nullptr, *d_depth8 = nullptr;       // its 8-bit image (written by the last fold) and finished map
-    void *d_rgba16 = nullptr, *d_grey16 = nullptr;      // ndt_hip_render_ssaa_png16*: the 16-bit samples of the accumulator and of the map
-    size_t pass_bytes = 0, acc_bytes = 0, rgba8_bytes = 0, depth8_bytes = 0, rgba16_bytes = 0, grey16_bytes = 0;
+    DeviceBuffer d_pass;            // one pass of the large frame: rows x K width x 4 doubles, and its depth map behind them when wanted
+    DeviceBuffer d_acc;             // the frame of the calls that deliver to host memory or as a file: rows x width x 4 doubles (+ the map)
+    DeviceBuffer d_rgba8, d_depth8;     // its 8-bit image (written by the last fold) and finished map
+    DeviceBuffer d_rgba16, d_grey16;    // ndt_hip_render_ssaa_png16*: the 16-bit samples of the accumulator and of the map
     hipEvent_t ev[16] = {};         // around every fold launch of a frame
     int launches = 0;               // fold launches of the last frame
     int factor = 0;                 // its K
@@ -127,8 +119,7 @@ struct ndt_hip_ctx {
     bool has_area_lights = false;   // LIGHT_DISK / LIGHT_RECT: every render is stochastic (ndt.c:116-147)
     SceneDesc sd{};
     std::vector<double> blob;
-    double *d_blob = nullptr;
-    size_t d_blob_words = 0;
+    DeviceBuffer d_blob;            // the blob on the device
     int tier = 0;
     int n_shadow_lights = 0;        // segments of the shadow queue: the non-ambient lights of the largest light window
     // The scene's lights in windows of at most 64 list entries (option "light_window": 0 auto = 64, else 1 .. 64).  The lighting
@@ -147,8 +138,8 @@ struct ndt_hip_ctx {
     Workspace ws{};
     std::vector<void *> ws_allocs;
     std::vector<void *> sa_allocs;                  // the frame kernel's queues and counters (ensure_stream_args)
-    std::vector<std::pair<void *, size_t>> pool;    // scratch of the multi-pass renderers (AaBuffers)
-    std::vector<std::pair<void *, size_t>> pool2;   // ... of a sampled render nested in an anti-aliased one
+    std::vector<DeviceBuffer> pool;                 // scratch of the multi-pass renderers (AaBuffers)
+    std::vector<DeviceBuffer> pool2;                // ... of a sampled render nested in an anti-aliased one
     long long ws_dims = 0;
     long long ws_slab_words = 0;
     int ws_nseg = 0;
@@ -197,32 +188,25 @@ struct ndt_hip_ctx {
     int shade_probe = -1;           // the k-th shade launch of a frame logs its wavefronts (-1: none)
     long long sa_cap = 0, sa_sh_cap = 0;
     int sa_nseg = 0;
-    void *d_eyes = nullptr;         // the two eye images of a stochastic anaglyph render (ndt_sampled.hip)
-    size_t d_eyes_bytes = 0;
-    void *d_fit = nullptr;          // ndt_hip_fit_spheres: jobs, points and spheres of a batch (grow-only, reused across frames)
-    size_t d_fit_bytes = 0;
+    DeviceBuffer d_eyes;            // the two eye images of a stochastic anaglyph render (ndt_sampled.hip)
+    DeviceBuffer d_fit;             // ndt_hip_fit_spheres: jobs, points and spheres of a batch (grow-only, reused across frames)
     int fit_launches = 0;           // kernel launches of the last ndt_hip_fit_spheres call
     KdState kd;                     // ndt_hip_build_kdtree
     PngState png;                   // ndt_hip_encode_png*, ndt_hip_render_png
     JpegState jpeg;                 // ndt_hip_encode_jpeg*, ndt_hip_render_jpeg
     DepthState depth;               // ndt_hip_depth_rgba8_device, ndt_hip_render_*_depth
     SsaaState ssaa;                 // ndt_hip_render_ssaa*
-    void *d_out = nullptr;          // staging for ndt_hip_render (host output)
-    size_t d_out_bytes = 0;
-    void *d_shard = nullptr;        // ndt_hip_render_multi: this context's rows before they are pushed into the frame
-    size_t d_shard_bytes = 0;
-    void *d_image = nullptr;        // ndt_hip_render_multi (host output): the assembled frame on the first context's device
-    size_t d_image_bytes = 0;
+    DeviceBuffer d_out;             // staging of a frame in doubles (and its map behind it) for the calls that deliver to host memory
+    DeviceBuffer d_shard;           // ndt_hip_render_multi: this context's rows before they are pushed into the frame
+    DeviceBuffer d_image;           // ndt_hip_render_multi (host output): the assembled frame on the first context's device
     // ndt_hip_render_rgba8_async: two quantised frames in HBM, a copy stream, and per buffer the events "quantised" / "copied"
-    void *d_rgba8[2] = { nullptr, nullptr };
-    size_t d_rgba8_bytes[2] = { 0, 0 };
+    DeviceBuffer d_rgba8[2];
     hipStream_t copy_stream = nullptr;
     hipEvent_t ev_quantised[2] = { nullptr, nullptr }, ev_copied[2] = { nullptr, nullptr };
     bool copy_pending[2] = { false, false };
     int rgba8_turn = 0;
     // ndt_hip_render_multi without peer stores: this context's staging buffer and stream ON THE FIRST CONTEXT'S DEVICE
-    void *d_stage = nullptr;
-    size_t d_stage_bytes = 0;
+    DeviceBuffer d_stage;
     hipStream_t stage_stream = nullptr;
     int stage_device = 0;
     long long sample_seed = 0;      // option "sample_seed": selects the set of random streams of the stochastic paths (0: the default set)
@@ -294,9 +278,6 @@ void free_kd(ndt_hip_ctx *ctx);
 
 // ndt_png.hip
 void free_png(ndt_hip_ctx *ctx);
-
-// ndt_api.hip: ctx->d_out, the staging of a frame in doubles (and its map behind it), grown to `bytes`
-int ensure_out(ndt_hip_ctx *ctx, size_t bytes);
 
 // ndt_jpeg.hip
 void free_jpeg(ndt_hip_ctx *ctx);
@@ -385,28 +366,17 @@ __device__ __forceinline__ int block_append_n(int *counter, int n)
 // which synchronises the device.
 struct AaBuffers {
     ndt_hip_ctx *ctx;
-    std::vector<std::pair<void *, size_t>> *from;
+    std::vector<DeviceBuffer> *from;
     size_t next = 0;
     explicit AaBuffers(ndt_hip_ctx *c, bool nested = false) : ctx(c), from(nested ? &c->pool2 : &c->pool) {}
     template <typename T> int get(T **ptr, size_t count)
     {
-        const size_t bytes = (count > 0 ? count : 1) * sizeof(T);
-        if (next == from->size()) from->push_back({ nullptr, 0 });
-        auto &slot = (*from)[next++];
-        if (slot.second < bytes) {
-            if (slot.first) {
-                (void)hipStreamSynchronize(ctx->stream);
-                (void)hipFree(slot.first);
-                slot = { nullptr, 0 };
-            }
-            const size_t want = bytes + bytes / 4;          // some head room: frame-to-frame counts vary
-            void *q = nullptr;
-            hipError_t e = hipMalloc(&q, want);
-            if (e != hipSuccess) return fail(NDT_E_NOMEM, "hipMalloc of %zu bytes: %s", want, hipGetErrorString(e));
-            slot = { q, want };
-        }
-        *ptr = (T *)slot.first;
-        return NDT_OK;
+        if (next == from->size()) from->push_back(DeviceBuffer());
+        DeviceBuffer &slot = (*from)[next++];
+        // with head room: frame-to-frame counts vary
+        const int rc = slot.reserve((count > 0 ? count : 1) * sizeof(T), ctx->stream, "scratch of a multi-pass render", true);
+        *ptr = slot.as<T>();
+        return rc;
     }
 };
 

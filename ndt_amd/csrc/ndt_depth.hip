@@ -132,19 +132,6 @@ __global__ void __launch_bounds__(DEPTH_FINISH_LANES) k_depth_finish(const doubl
     }
 }
 
-int grow(ndt_hip_ctx *ctx, void **buf, size_t *have, size_t want)
-{
-    if (*have >= want) return NDT_OK;
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    if (*buf) HIP_TRY(hipFree(*buf));
-    *buf = nullptr;
-    *have = 0;
-    const hipError_t e = hipMalloc(buf, want);
-    if (e != hipSuccess) return fail(NDT_E_NOMEM, "depth map on the device: hipMalloc of %zu bytes: %s", want, hipGetErrorString(e));
-    *have = want;
-    return NDT_OK;
-}
-
 // ndt_hip_render_depth_device into the context's buffers, then both images in HBM: at 8 bits ds.d_rgba8 (the quantised image)
 // and ds.d_depth8 (the finished map), at 16 ds.d_rgba16 and ds.d_grey16.  *pixels = 0: the shard has no rows (nothing was made).
 int render_both(ndt_hip_ctx *ctx, const ndt_render_params *p, bool sixteen, double *range_out, ndt_render_stats *stats, int *rows_out,
@@ -161,22 +148,22 @@ int render_both(ndt_hip_ctx *ctx, const ndt_render_params *p, bool sixteen, doub
     const size_t img_bytes = pixels * 4 * sizeof(double), bytes = img_bytes + img_bytes / 4;       // the map sits behind the image
     DepthState &ds = ctx->depth;
     int rc;
-    if ((rc = ensure_out(ctx, bytes))) return rc;
+    if ((rc = ctx->d_out.reserve(bytes, ctx->stream, "ndt_hip_render_*_depth"))) return rc;
     if (sixteen) {
-        if ((rc = grow(ctx, &ds.d_rgba16, &ds.rgba16_bytes, pixels * 8))) return rc;
-        if ((rc = grow(ctx, &ds.d_grey16, &ds.grey16_bytes, (pixels * 2 + 3) & ~(size_t)3))) return rc;
+        if ((rc = ds.d_rgba16.reserve(pixels * 8, ctx->stream, "ndt_hip_render_*_depth"))) return rc;
+        if ((rc = ds.d_grey16.reserve((pixels * 2 + 3) & ~(size_t)3, ctx->stream, "ndt_hip_render_*_depth"))) return rc;
     } else {
-        if ((rc = grow(ctx, &ds.d_rgba8, &ds.rgba8_bytes, pixels * 4))) return rc;
-        if ((rc = grow(ctx, &ds.d_depth8, &ds.depth8_bytes, pixels * 4))) return rc;
+        if ((rc = ds.d_rgba8.reserve(pixels * 4, ctx->stream, "ndt_hip_render_*_depth"))) return rc;
+        if ((rc = ds.d_depth8.reserve(pixels * 4, ctx->stream, "ndt_hip_render_*_depth"))) return rc;
     }
-    void *d_depth = (char *)ctx->d_out + img_bytes;
-    if ((rc = ndt_hip_render_depth_device(ctx, p, ctx->d_out, d_depth, stats))) return rc;
+    void *d_depth = ctx->d_out.as<char>() + img_bytes;
+    if ((rc = ndt_hip_render_depth_device(ctx, p, ctx->d_out.p, d_depth, stats))) return rc;
     if (sixteen) {
-        if ((rc = ndt_hip_depth_grey16_device(ctx, d_depth, (int64_t)pixels, ds.d_grey16, range_out))) return rc;
-        return ndt_hip_quantize16_device(ctx, ctx->d_out, ds.d_rgba16, (int64_t)pixels);
+        if ((rc = ndt_hip_depth_grey16_device(ctx, d_depth, (int64_t)pixels, ds.d_grey16.p, range_out))) return rc;
+        return ndt_hip_quantize16_device(ctx, ctx->d_out.p, ds.d_rgba16.p, (int64_t)pixels);
     }
-    if ((rc = ndt_hip_depth_rgba8_device(ctx, d_depth, (int64_t)pixels, ds.d_depth8, range_out))) return rc;
-    return ndt_hip_quantize_device(ctx, ctx->d_out, ds.d_rgba8, (int64_t)pixels);
+    if ((rc = ndt_hip_depth_rgba8_device(ctx, d_depth, (int64_t)pixels, ds.d_depth8.p, range_out))) return rc;
+    return ndt_hip_quantize_device(ctx, ctx->d_out.p, ds.d_rgba8.p, (int64_t)pixels);
 }
 
 // the two launches over a map of n_pixels doubles; `who` names the entry point in errors
@@ -189,9 +176,9 @@ int finish_map(ndt_hip_ctx *ctx, const char *who, bool sixteen, const void *d_de
     ds.finish_ms = 0.0;
     int rc;
     // the records of the largest map there is, and behind them the record the host reads
-    if ((rc = grow(ctx, &ds.d_records, &ds.records_bytes, (size_t)(DEPTH_MAX_RECORDS + 1) * sizeof(DepthRecord)))) return rc;
+    if ((rc = ds.d_records.reserve((size_t)(DEPTH_MAX_RECORDS + 1) * sizeof(DepthRecord), ctx->stream, who))) return rc;
     if (!ds.h_result) HIP_TRY(hipHostMalloc(&ds.h_result, sizeof(DepthRecord), hipHostMallocDefault));
-    DepthRecord *records = (DepthRecord *)ds.d_records, *result = records + DEPTH_MAX_RECORDS;
+    DepthRecord *records = ds.d_records.as<DepthRecord>(), *result = records + DEPTH_MAX_RECORDS;
     const long long n = n_pixels;
     const long long want_records = (n + DEPTH_RANGE_LANES * DEPTH_UNROLL - 1) / (DEPTH_RANGE_LANES * DEPTH_UNROLL);
     const int n_records = (int)(want_records < DEPTH_MAX_RECORDS ? want_records : DEPTH_MAX_RECORDS);
@@ -225,11 +212,11 @@ int finish_map(ndt_hip_ctx *ctx, const char *who, bool sixteen, const void *d_de
 void ndt_impl::free_depth(ndt_hip_ctx *ctx)
 {
     DepthState &ds = ctx->depth;
-    void **bufs[] = { &ds.d_records, &ds.d_rgba8, &ds.d_depth8, &ds.d_rgba16, &ds.d_grey16 };
-    for (void **b : bufs) {
-        if (*b) (void)hipFree(*b);
-        *b = nullptr;
-    }
+    ds.d_records.release();
+    ds.d_rgba8.release();
+    ds.d_depth8.release();
+    ds.d_rgba16.release();
+    ds.d_grey16.release();
     if (ds.h_result) (void)hipHostFree(ds.h_result);
     ds = DepthState();
 }
@@ -263,8 +250,8 @@ extern "C" int ndt_hip_render_rgba8_depth(ndt_hip_ctx *ctx, const ndt_render_par
     size_t pixels = 0;
     int rc = render_both(ctx, p, false, range_out, stats, &rows, &pixels);
     if (rc || pixels == 0) return rc;
-    HIP_TRY(hipMemcpyAsync(rgba8, ctx->depth.d_rgba8, pixels * 4, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(depth8, ctx->depth.d_depth8, pixels * 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(rgba8, ctx->depth.d_rgba8.p, pixels * 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(depth8, ctx->depth.d_depth8.p, pixels * 4, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     return NDT_OK;
 }
@@ -286,9 +273,9 @@ extern "C" int ndt_hip_render_png_depth(ndt_hip_ctx *ctx, const ndt_render_param
     size_t pixels = 0;
     int rc = render_both(ctx, p, false, range_out, render_stats, &rows, &pixels);
     if (rc) return rc;
-    if ((rc = ndt_hip_encode_png_device(ctx, ctx->depth.d_rgba8, p->width, rows, png, cap, stats ? &stats[0] : nullptr))) return rc;
-    if (depth_png) return ndt_hip_encode_png_device(ctx, ctx->depth.d_depth8, p->width, rows, depth_png, depth_cap, stats ? &stats[1] : nullptr);
-    HIP_TRY(hipMemcpyAsync(depth8, ctx->depth.d_depth8, pixels * 4, hipMemcpyDeviceToHost, ctx->stream));
+    if ((rc = ndt_hip_encode_png_device(ctx, ctx->depth.d_rgba8.p, p->width, rows, png, cap, stats ? &stats[0] : nullptr))) return rc;
+    if (depth_png) return ndt_hip_encode_png_device(ctx, ctx->depth.d_depth8.p, p->width, rows, depth_png, depth_cap, stats ? &stats[1] : nullptr);
+    HIP_TRY(hipMemcpyAsync(depth8, ctx->depth.d_depth8.p, pixels * 4, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     return NDT_OK;
 }
@@ -308,6 +295,6 @@ extern "C" int ndt_hip_render_png16_depth(ndt_hip_ctx *ctx, const ndt_render_par
     size_t pixels = 0;
     int rc = render_both(ctx, p, true, range_out, render_stats, &rows, &pixels);
     if (rc) return rc;
-    if ((rc = ndt_hip_encode_png16_device(ctx, ctx->depth.d_rgba16, p->width, rows, 4, png, cap, stats ? &stats[0] : nullptr))) return rc;
-    return ndt_hip_encode_png16_device(ctx, ctx->depth.d_grey16, p->width, rows, 1, depth_png, depth_cap, stats ? &stats[1] : nullptr);
+    if ((rc = ndt_hip_encode_png16_device(ctx, ctx->depth.d_rgba16.p, p->width, rows, 4, png, cap, stats ? &stats[0] : nullptr))) return rc;
+    return ndt_hip_encode_png16_device(ctx, ctx->depth.d_grey16.p, p->width, rows, 1, depth_png, depth_cap, stats ? &stats[1] : nullptr);
 }

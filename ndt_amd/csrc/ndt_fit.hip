@@ -325,17 +325,9 @@ int fit_spheres_device(ndt_hip_ctx *ctx, int dims, long long n_lists, const int6
     const size_t o_jobs = 0, o_pts = o_jobs + sizeof(FitJob) * (size_t)n_lists, o_rad = o_pts + sizeof(double) * (size_t)n_points * dims,
                  o_cen = o_rad + sizeof(double) * (size_t)n_points, o_out = o_cen + sizeof(double) * (size_t)n_lists * dims,
                  total = o_out + sizeof(double) * (size_t)n_lists;
-    if (ctx->d_fit_bytes < total) {
-        HIP_TRY(hipStreamSynchronize(ctx->stream));
-        if (ctx->d_fit) HIP_TRY(hipFree(ctx->d_fit));
-        ctx->d_fit = nullptr;
-        ctx->d_fit_bytes = 0;
-        const size_t want = total + total / 4;          // some head room: frame-to-frame counts vary
-        hipError_t e = hipMalloc(&ctx->d_fit, want);
-        if (e != hipSuccess) return fail(NDT_E_NOMEM, "hipMalloc of %zu bytes: %s", want, hipGetErrorString(e));
-        ctx->d_fit_bytes = want;
-    }
-    char *base = (char *)ctx->d_fit;
+    const int rc = ctx->d_fit.reserve(total, ctx->stream, "ndt_hip_fit_spheres", true);      // head room: frame-to-frame counts vary
+    if (rc) return rc;
+    char *base = ctx->d_fit.as<char>();
     hipStream_t s = ctx->stream;
     HIP_TRY(hipMemcpyAsync(base + o_jobs, jobs.data(), sizeof(FitJob) * (size_t)n_lists, hipMemcpyHostToDevice, s));
     HIP_TRY(hipMemcpyAsync(base + o_pts, points, sizeof(double) * (size_t)n_points * dims, hipMemcpyHostToDevice, s));

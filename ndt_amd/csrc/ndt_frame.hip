@@ -410,7 +410,7 @@ static void launch_finish_pixels(ndt_hip_ctx *ctx, const SceneDesc &sd_pass, con
                                  int resolve0)
 {
     hipLaunchKernelGGL(k_finish_pixels, dim3((unsigned)((rg.n_primary + NDT_FINISH_BLOCK - 1) / NDT_FINISH_BLOCK)), dim3(NDT_FINISH_BLOCK), 0, ctx->stream,
-                       ctx->d_blob, sd_pass, ws, rg, ctx->dims, (double *)d_rgba, (double *)d_depth, resolve0);
+                       ctx->d_blob.as<double>(), sd_pass, ws, rg, ctx->dims, (double *)d_rgba, (double *)d_depth, resolve0);
 }
 
 // early_pixels: the parts in `take` only, on stream `on`
@@ -418,7 +418,7 @@ static void launch_finish_part(ndt_hip_ctx *ctx, hipStream_t on, const SceneDesc
                                void *d_depth, int resolve0, int take)
 {
     hipLaunchKernelGGL(k_finish_part, dim3((unsigned)((rg.n_primary + NDT_FINISH_BLOCK - 1) / NDT_FINISH_BLOCK)), dim3(NDT_FINISH_BLOCK), 0, on,
-                       ctx->d_blob, sd_pass, ws, rg, ctx->dims, (double *)d_rgba, (double *)d_depth, resolve0, take);
+                       ctx->d_blob.as<double>(), sd_pass, ws, rg, ctx->dims, (double *)d_rgba, (double *)d_depth, resolve0, take);
 }
 
 // The frame kernel's arguments for a frame of `count` primaries: the roots of its forest, from slot 0, in batches of 64 (the last
@@ -479,8 +479,8 @@ static int render_pass_stream(ndt_hip_ctx *ctx, const RenderGeom &rg, const Scen
         }
         const unsigned long long tag = ++ctx->frame_tag;
         launch_stream_init(ctx, ws, sa, ev_begin);
-        if (!sa.fused) kt->primary(s, ctx->d_blob, sd_pass, ws, rg);
-        kt->frame_stream(s, ctx->d_blob, sd_pass, ws, rg, sa, ctx->tier, ctx->sd.mask_words, ev_k0, ev_k1);
+        if (!sa.fused) kt->primary(s, ctx->d_blob.as<double>(), sd_pass, ws, rg);
+        kt->frame_stream(s, ctx->d_blob.as<double>(), sd_pass, ws, rg, sa, ctx->tier, ctx->sd.mask_words, ev_k0, ev_k1);
         if (!sa.fused) launch_finish_pixels(ctx, sd_pass, ws, rg, d_rgba, d_depth, 0);
         launch_stamped(k_stream_done, dim3(1), dim3(64), s, nullptr, ev_end, ws, sa, ctx->d_done, tag);
         HIP_TRY(hipGetLastError());
@@ -623,7 +623,7 @@ hipError_t FrameInFlight::join_light()
 // beside trace launch b + 1, and the main stream carries no marker for it.
 int FrameInFlight::light_beside(int b)
 {
-    kt->shade_finish(ls, ctx->d_blob, sd_pass, shade_ws(level_nodes[b], b, ls), rg, b, level_nodes[b], 0);
+    kt->shade_finish(ls, ctx->d_blob.as<double>(), sd_pass, shade_ws(level_nodes[b], b, ls), rg, b, level_nodes[b], 0);
     // (early_pixels 2: the primaries without a child are final now; their pixels go directly behind, ahead of the event)
     int rc;
     if (b == 0 && early >= 2 && (rc = early_pixels_beside(NDT_PART_CHILDLESS))) return rc;
@@ -750,7 +750,7 @@ int FrameInFlight::traced(TraceJob &tj, const std::string &what, const SceneDesc
         trace_ev.push_back({ a, b2 });
         trace_dbg.push_back(what);
     }
-    kt->trace(s, ctx->d_blob, sdj, ws, tj, ctx->tier, ctx->sd.mask_words, a, b2);
+    kt->trace(s, ctx->d_blob.as<double>(), sdj, ws, tj, ctx->tier, ctx->sd.mask_words, a, b2);
     ++launches;
     return NDT_OK;
 }
@@ -800,7 +800,7 @@ int FrameInFlight::trace_primaries()
     // (the variant is built for the planar camera: VR and panorama frames take k_primary)
     const bool fuse_primaries = (ctx->fuse_primaries < 0 ? ctx->dims >= 4 : ctx->fuse_primaries != 0) && ctx->cam_type == 0;
     // (no k_primary: the first trace launch makes the primaries it traces, TraceJob::make_primaries)
-    if (!fuse_primaries) kt->primary(s, ctx->d_blob, sd_pass, ws, rg);
+    if (!fuse_primaries) kt->primary(s, ctx->d_blob.as<double>(), sd_pass, ws, rg);
     TraceJob tj{};
     job_closest(tj, ws);
     tj.count = rg.n_primary;
@@ -821,13 +821,13 @@ void FrameInFlight::light_and_shade(int b, long long upper)
     if (windowed) {
         // (the lighting of the last window of bounce b-1 and the shading of bounce b see different lights: two launches)
         if (pending_finish >= 0)
-            kt->shade_last(s, ctx->d_blob, sd_win[n_win - 1], shade_ws(pending_upper, pending_finish, s), rg, pending_finish, pending_upper, 0,
+            kt->shade_last(s, ctx->d_blob.as<double>(), sd_win[n_win - 1], shade_ws(pending_upper, pending_finish, s), rg, pending_finish, pending_upper, 0,
                            ctx->windows[n_win - 1].first);
-        kt->shade_emit(s, ctx->d_blob, sd_win[0], shade_ws(0, b, s), rg, b, upper);
+        kt->shade_emit(s, ctx->d_blob.as<double>(), sd_win[0], shade_ws(0, b, s), rg, b, upper);
     } else {
         if (!overlap && pending_finish >= 0)
-            kt->shade_finish(s, ctx->d_blob, sd_pass, shade_ws(pending_upper, pending_finish, s), rg, pending_finish, pending_upper, 0);
-        kt->shade_emit(s, ctx->d_blob, sd_pass, shade_ws(0, b, s), rg, b, upper);
+            kt->shade_finish(s, ctx->d_blob.as<double>(), sd_pass, shade_ws(pending_upper, pending_finish, s), rg, pending_finish, pending_upper, 0);
+        kt->shade_emit(s, ctx->d_blob.as<double>(), sd_pass, shade_ws(0, b, s), rg, b, upper);
     }
     pending_finish = -1;
 }
@@ -860,7 +860,7 @@ int FrameInFlight::trace_windows(int b, long long upper)
         int *bank = ws.counters + NDT_CNT_WIN + 64 * (win_emits & 1);
         int *next_bank = ws.counters + NDT_CNT_WIN + 64 * ((win_emits + 1) & 1);
         ++win_emits;
-        kt->shade_window(s, ctx->d_blob, sd_win[k - 1], sd_win[k], shade_ws(upper, b, s), rg, b, upper, ctx->windows[k - 1].first, w.first, bank, next_bank,
+        kt->shade_window(s, ctx->d_blob.as<double>(), sd_win[k - 1], sd_win[k], shade_ws(upper, b, s), rg, b, upper, ctx->windows[k - 1].first, w.first, bank, next_bank,
                          w.n_seg, k > 1 ? 1 : 0);
         if (w.n_seg == 0) continue;
         TraceJob tj{};
@@ -881,10 +881,10 @@ void FrameInFlight::light_last()
     if (pending_finish < 0) return;
     resolve_with_finish = pending_finish >= 1 && pending_finish == n_run - 1;
     if (windowed)
-        kt->shade_last(s, ctx->d_blob, sd_win[n_win - 1], shade_ws(pending_upper, pending_finish, s), rg, pending_finish, pending_upper,
+        kt->shade_last(s, ctx->d_blob.as<double>(), sd_win[n_win - 1], shade_ws(pending_upper, pending_finish, s), rg, pending_finish, pending_upper,
                        resolve_with_finish ? 1 : 0, ctx->windows[n_win - 1].first);
     else
-        kt->shade_finish(s, ctx->d_blob, sd_pass, shade_ws(pending_upper, pending_finish, s), rg, pending_finish, pending_upper,
+        kt->shade_finish(s, ctx->d_blob.as<double>(), sd_pass, shade_ws(pending_upper, pending_finish, s), rg, pending_finish, pending_upper,
                          resolve_with_finish ? 1 : 0);
 }
 
@@ -895,7 +895,7 @@ void FrameInFlight::resolve()
         if (resolve_with_finish && b == n_run - 1) continue;
         long long blocks = (level_nodes[b] + 255) / 256;
         if (blocks > NDT_SHADE_MAX_BLOCKS) blocks = NDT_SHADE_MAX_BLOCKS;
-        hipLaunchKernelGGL(k_resolve, dim3((unsigned)blocks), dim3(256), 0, s, ctx->d_blob, sd_pass, ws, rg.specular, b);
+        hipLaunchKernelGGL(k_resolve, dim3((unsigned)blocks), dim3(256), 0, s, ctx->d_blob.as<double>(), sd_pass, ws, rg.specular, b);
     }
 }
 

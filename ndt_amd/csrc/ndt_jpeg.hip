@@ -529,19 +529,6 @@ __global__ void __launch_bounds__(256) k_jpeg_place(const unsigned char *__restr
 
 // ------------------------------------------------------------------ host
 
-int grow(ndt_hip_ctx *ctx, void **buf, size_t *have, size_t want)
-{
-    if (*have >= want) return NDT_OK;
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    if (*buf) HIP_TRY(hipFree(*buf));
-    *buf = nullptr;
-    *have = 0;
-    const hipError_t e = hipMalloc(buf, want);
-    if (e != hipSuccess) return fail(NDT_E_NOMEM, "ndt_hip_encode_jpeg: hipMalloc of %zu bytes: %s", want, hipGetErrorString(e));
-    *have = want;
-    return NDT_OK;
-}
-
 // Checks size and parameters (who: the entry point's name, for the error text; null: no text) and fills the geometry.
 int geometry(const char *who, int32_t width, int32_t rows, const ndt_jpeg_params *jp, JpegGeom *g)
 {
@@ -580,11 +567,13 @@ extern "C" int64_t ndt_hip_jpeg_bound(int32_t width, int32_t rows, const ndt_jpe
 void ndt_impl::free_jpeg(ndt_hip_ctx *ctx)
 {
     JpegState &js = ctx->jpeg;
-    void **bufs[] = { &js.d_rgba8, &js.d_coef, &js.d_slots, &js.d_meta, &js.d_offsets, &js.d_file, &js.d_info };
-    for (void **b : bufs) {
-        if (*b) (void)hipFree(*b);
-        *b = nullptr;
-    }
+    js.d_rgba8.release();
+    js.d_coef.release();
+    js.d_slots.release();
+    js.d_meta.release();
+    js.d_offsets.release();
+    js.d_file.release();
+    js.d_info.release();
     if (js.h_info) (void)hipHostFree(js.h_info);
     js = JpegState();
 }
@@ -604,23 +593,23 @@ extern "C" int ndt_hip_encode_jpeg_device(ndt_hip_ctx *ctx, const void *d_rgba8,
     JpegState &js = ctx->jpeg;
     const int n_mcus = g.mcu_w * g.mcu_h;           // at most 8192 x 8192
     const long long bound = file_bound(g);
-    if ((rc = grow(ctx, &js.d_coef, &js.coef_bytes, (size_t)n_mcus * g.blocks_per_mcu * 64 * sizeof(short)))) return rc;
-    if ((rc = grow(ctx, &js.d_slots, &js.slots_bytes, (size_t)g.mcu_h * (size_t)g.slot_bytes))) return rc;
-    if ((rc = grow(ctx, &js.d_meta, &js.meta_bytes, (size_t)g.mcu_h * sizeof(IntervalMeta)))) return rc;
-    if ((rc = grow(ctx, &js.d_offsets, &js.offsets_bytes, (size_t)g.mcu_h * sizeof(long long)))) return rc;
-    if ((rc = grow(ctx, &js.d_file, &js.file_bytes, (size_t)bound))) return rc;
-    if ((rc = grow(ctx, &js.d_info, &js.info_bytes, sizeof(JpegInfo)))) return rc;
+    if ((rc = js.d_coef.reserve((size_t)n_mcus * g.blocks_per_mcu * 64 * sizeof(short), ctx->stream, "ndt_hip_encode_jpeg"))) return rc;
+    if ((rc = js.d_slots.reserve((size_t)g.mcu_h * (size_t)g.slot_bytes, ctx->stream, "ndt_hip_encode_jpeg"))) return rc;
+    if ((rc = js.d_meta.reserve((size_t)g.mcu_h * sizeof(IntervalMeta), ctx->stream, "ndt_hip_encode_jpeg"))) return rc;
+    if ((rc = js.d_offsets.reserve((size_t)g.mcu_h * sizeof(long long), ctx->stream, "ndt_hip_encode_jpeg"))) return rc;
+    if ((rc = js.d_file.reserve((size_t)bound, ctx->stream, "ndt_hip_encode_jpeg"))) return rc;
+    if ((rc = js.d_info.reserve(sizeof(JpegInfo), ctx->stream, "ndt_hip_encode_jpeg"))) return rc;
     if (!js.h_info) HIP_TRY(hipHostMalloc(&js.h_info, sizeof(JpegInfo), hipHostMallocDefault));
     hipStream_t s = ctx->stream;
-    hipLaunchKernelGGL(k_jpeg_blocks, dim3((unsigned)((n_mcus + 3) / 4)), dim3(256), 0, s, (const unsigned *)d_rgba8, g, (short *)js.d_coef);
-    hipLaunchKernelGGL(k_jpeg_entropy, dim3((unsigned)g.mcu_h), dim3(JPEG_LANES), 0, s, (const short *)js.d_coef, g, (unsigned char *)js.d_slots,
-                       (IntervalMeta *)js.d_meta);
-    hipLaunchKernelGGL(k_jpeg_assemble, dim3(1), dim3(1024), 0, s, (const IntervalMeta *)js.d_meta, g, (unsigned char *)js.d_file,
-                       (long long *)js.d_offsets, (JpegInfo *)js.d_info);
-    hipLaunchKernelGGL(k_jpeg_place, dim3((unsigned)g.mcu_h), dim3(256), 0, s, (const unsigned char *)js.d_slots, (const IntervalMeta *)js.d_meta,
-                       (const long long *)js.d_offsets, g, (unsigned char *)js.d_file);
+    hipLaunchKernelGGL(k_jpeg_blocks, dim3((unsigned)((n_mcus + 3) / 4)), dim3(256), 0, s, (const unsigned *)d_rgba8, g, js.d_coef.as<short>());
+    hipLaunchKernelGGL(k_jpeg_entropy, dim3((unsigned)g.mcu_h), dim3(JPEG_LANES), 0, s, js.d_coef.as<const short>(), g, js.d_slots.as<unsigned char>(),
+                       js.d_meta.as<IntervalMeta>());
+    hipLaunchKernelGGL(k_jpeg_assemble, dim3(1), dim3(1024), 0, s, js.d_meta.as<const IntervalMeta>(), g, js.d_file.as<unsigned char>(),
+                       js.d_offsets.as<long long>(), js.d_info.as<JpegInfo>());
+    hipLaunchKernelGGL(k_jpeg_place, dim3((unsigned)g.mcu_h), dim3(256), 0, s, js.d_slots.as<const unsigned char>(), js.d_meta.as<const IntervalMeta>(),
+                       js.d_offsets.as<const long long>(), g, js.d_file.as<unsigned char>());
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(js.h_info, js.d_info, sizeof(JpegInfo), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(js.h_info, js.d_info.p, sizeof(JpegInfo), hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
     const JpegInfo info = *(const JpegInfo *)js.h_info;
     if (stats) {
@@ -637,7 +626,7 @@ extern "C" int ndt_hip_encode_jpeg_device(ndt_hip_ctx *ctx, const void *d_rgba8,
         return fail(NDT_E_DEVICE, "ndt_hip_encode_jpeg: the device reports a file of %lld bytes (bound %lld)", info.jpeg_bytes, bound);
     if (info.jpeg_bytes > cap)
         return fail(NDT_E_NOMEM, "ndt_hip_encode_jpeg: the file is %lld bytes, the buffer %lld", info.jpeg_bytes, (long long)cap);
-    HIP_TRY(hipMemcpyAsync(jpg, js.d_file, (size_t)info.jpeg_bytes, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(jpg, js.d_file.p, (size_t)info.jpeg_bytes, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
     if (stats) stats->encode_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     return NDT_OK;
@@ -652,9 +641,9 @@ extern "C" int ndt_hip_encode_jpeg(ndt_hip_ctx *ctx, const uint8_t *rgba8, int32
     if ((rc = geometry("ndt_hip_encode_jpeg", width, rows, jp, &g))) return rc;
     HIP_TRY(hipSetDevice(ctx->device));
     const size_t bytes = (size_t)width * (size_t)rows * 4;
-    if ((rc = grow(ctx, &ctx->jpeg.d_rgba8, &ctx->jpeg.rgba8_bytes, bytes))) return rc;
-    HIP_TRY(hipMemcpyAsync(ctx->jpeg.d_rgba8, rgba8, bytes, hipMemcpyHostToDevice, ctx->stream));
-    return ndt_hip_encode_jpeg_device(ctx, ctx->jpeg.d_rgba8, width, rows, jp, jpg, cap, stats);
+    if ((rc = ctx->jpeg.d_rgba8.reserve(bytes, ctx->stream, "ndt_hip_encode_jpeg"))) return rc;
+    HIP_TRY(hipMemcpyAsync(ctx->jpeg.d_rgba8.p, rgba8, bytes, hipMemcpyHostToDevice, ctx->stream));
+    return ndt_hip_encode_jpeg_device(ctx, ctx->jpeg.d_rgba8.p, width, rows, jp, jpg, cap, stats);
 }
 
 extern "C" int ndt_hip_render_jpeg(ndt_hip_ctx *ctx, const ndt_render_params *p, const ndt_jpeg_params *jp, uint8_t *jpg, int64_t cap,
@@ -668,8 +657,8 @@ extern "C" int ndt_hip_render_jpeg(ndt_hip_ctx *ctx, const ndt_render_params *p,
     int rc;
     if ((rc = geometry("ndt_hip_render_jpeg", p->width, rows, jp, &g))) return rc;
     HIP_TRY(hipSetDevice(ctx->device));
-    if ((rc = grow(ctx, &ctx->jpeg.d_rgba8, &ctx->jpeg.rgba8_bytes, (size_t)p->width * (size_t)rows * 4))) return rc;
+    if ((rc = ctx->jpeg.d_rgba8.reserve((size_t)p->width * (size_t)rows * 4, ctx->stream, "ndt_hip_render_jpeg"))) return rc;
     ndt_hip_ctx *one[1] = { ctx };
-    if ((rc = ndt_hip_render_multi_device(one, 1, p, NDT_IMAGE_RGBA8, ctx->jpeg.d_rgba8, render_stats))) return rc;
-    return ndt_hip_encode_jpeg_device(ctx, ctx->jpeg.d_rgba8, p->width, rows, jp, jpg, cap, stats);
+    if ((rc = ndt_hip_render_multi_device(one, 1, p, NDT_IMAGE_RGBA8, ctx->jpeg.d_rgba8.p, render_stats))) return rc;
+    return ndt_hip_encode_jpeg_device(ctx, ctx->jpeg.d_rgba8.p, p->width, rows, jp, jpg, cap, stats);
 }

@@ -50,18 +50,6 @@ static void launch_push(hipStream_t s, int format, const void *shard, void *dst,
 
 static size_t pixel_bytes(int format) { return format == NDT_IMAGE_RGBA8 ? 4 : 4 * sizeof(double); }
 
-static int ensure_bytes(ndt_hip_ctx *ctx, void **buf, size_t *have, size_t want)
-{
-    if (*have >= want) return NDT_OK;
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    if (*buf) HIP_TRY(hipFree(*buf));
-    *buf = nullptr;
-    *have = 0;
-    HIP_TRY(hipMalloc(buf, want));
-    *have = want;
-    return NDT_OK;
-}
-
 extern "C" int ndt_hip_device_count(void)
 {
     int n = 0;
@@ -108,15 +96,15 @@ extern "C" int ndt_hip_render_rgba8_async(ndt_hip_ctx *ctx, const ndt_render_par
         HIP_TRY(hipEventSynchronize(ctx->ev_copied[k]));
         ctx->copy_pending[k] = false;
     }
-    int rc = ensure_bytes(ctx, &ctx->d_shard, &ctx->d_shard_bytes, pixels * 4 * sizeof(double));
+    int rc = ctx->d_shard.reserve(pixels * 4 * sizeof(double), ctx->stream, "ndt_hip_render_rgba8_async");
     if (rc) return rc;
-    if ((rc = ensure_bytes(ctx, &ctx->d_rgba8[k], &ctx->d_rgba8_bytes[k], pixels * 4))) return rc;
-    if ((rc = ndt_hip_render_device(ctx, p, ctx->d_shard, stats))) return rc;
-    launch_push(ctx->stream, NDT_IMAGE_RGBA8, ctx->d_shard, ctx->d_rgba8[k], p->width, rows, 0, 1);
+    if ((rc = ctx->d_rgba8[k].reserve(pixels * 4, ctx->stream, "ndt_hip_render_rgba8_async"))) return rc;
+    if ((rc = ndt_hip_render_device(ctx, p, ctx->d_shard.p, stats))) return rc;
+    launch_push(ctx->stream, NDT_IMAGE_RGBA8, ctx->d_shard.p, ctx->d_rgba8[k].p, p->width, rows, 0, 1);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord(ctx->ev_quantised[k], ctx->stream));
     HIP_TRY(hipStreamWaitEvent(ctx->copy_stream, ctx->ev_quantised[k], 0));
-    HIP_TRY(hipMemcpyAsync(rgba8, ctx->d_rgba8[k], pixels * 4, hipMemcpyDeviceToHost, ctx->copy_stream));
+    HIP_TRY(hipMemcpyAsync(rgba8, ctx->d_rgba8[k].p, pixels * 4, hipMemcpyDeviceToHost, ctx->copy_stream));
     HIP_TRY(hipEventRecord(ctx->ev_copied[k], ctx->copy_stream));
     ctx->copy_pending[k] = true;
     if (ctx->copy_pending[k ^ 1]) {         // the frame before: it travelled while this one was rendered
@@ -149,11 +137,8 @@ void ndt_impl::free_async(ndt_hip_ctx *ctx)
         (void)hipStreamDestroy(ctx->copy_stream);
         ctx->copy_stream = nullptr;
     }
-    for (int k = 0; k < 2; ++k) {
-        if (ctx->d_rgba8[k]) (void)hipFree(ctx->d_rgba8[k]);
-        ctx->d_rgba8[k] = nullptr;
-        ctx->d_rgba8_bytes[k] = 0;
-    }
+    ctx->d_rgba8[0].release();
+    ctx->d_rgba8[1].release();
 }
 
 // ---- per-context worker threads: a context's frames are enqueued by one thread of its own, so that the contexts of a
@@ -248,9 +233,9 @@ static int render_and_push(ndt_hip_ctx *ctx, ndt_hip_ctx *first, ndt_render_para
         return NDT_OK;
     }
     const size_t shard_bytes = (size_t)rows * sp.width * 4 * sizeof(double);
-    int rc = ensure_bytes(ctx, &ctx->d_shard, &ctx->d_shard_bytes, shard_bytes);
+    int rc = ctx->d_shard.reserve(shard_bytes, ctx->stream, "ndt_hip_render_multi");
     if (rc) return rc;
-    if ((rc = ndt_hip_render_device(ctx, &sp, ctx->d_shard, st))) return rc;
+    if ((rc = ndt_hip_render_device(ctx, &sp, ctx->d_shard.p, st))) return rc;
     int path = NDT_MULTI_STAGED;
     if (ctx->multi_path != 2) {
         if (ctx->device == first->device) {
@@ -268,7 +253,7 @@ static int render_and_push(ndt_hip_ctx *ctx, ndt_hip_ctx *first, ndt_render_para
         }
     }
     if (path != NDT_MULTI_STAGED) {
-        launch_push(ctx->stream, format, ctx->d_shard, d_dst, sp.width, rows, row0_out, step_out);
+        launch_push(ctx->stream, format, ctx->d_shard.p, d_dst, sp.width, rows, row0_out, step_out);
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipStreamSynchronize(ctx->stream));
         ctx->multi_path_taken = path;
@@ -278,34 +263,27 @@ static int render_and_push(ndt_hip_ctx *ctx, ndt_hip_ctx *first, ndt_render_para
     // copies of different contexts do not wait for each other)
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     hipError_t e = hipSetDevice(first->device);
-    if (e == hipSuccess && ctx->d_stage && ctx->stage_device != first->device) {
+    if (e == hipSuccess && ctx->d_stage.p && ctx->stage_device != first->device) {
         // the first context changed devices since the last frame: the old staging area goes
         (void)hipSetDevice(ctx->stage_device);
         (void)hipStreamDestroy(ctx->stage_stream);
-        (void)hipFree(ctx->d_stage);
-        ctx->d_stage = nullptr;
+        ctx->d_stage.release();
         ctx->stage_stream = nullptr;
-        ctx->d_stage_bytes = 0;
         e = hipSetDevice(first->device);
     }
     if (e == hipSuccess && !ctx->stage_stream) {
         e = hipStreamCreateWithFlags(&ctx->stage_stream, hipStreamNonBlocking);
         ctx->stage_device = first->device;
     }
-    if (e == hipSuccess && ctx->d_stage_bytes < shard_bytes) {
-        if (ctx->d_stage) (void)hipFree(ctx->d_stage);
-        ctx->d_stage = nullptr;
-        ctx->d_stage_bytes = 0;
-        e = hipMalloc(&ctx->d_stage, shard_bytes);
-        if (e == hipSuccess) ctx->d_stage_bytes = shard_bytes;
-    }
-    if (e == hipSuccess) e = hipMemcpyPeerAsync(ctx->d_stage, first->device, ctx->d_shard, ctx->device, shard_bytes, ctx->stage_stream);
-    if (e == hipSuccess) {
-        launch_push(ctx->stage_stream, format, ctx->d_stage, d_dst, sp.width, rows, row0_out, step_out);
+    if (e == hipSuccess) rc = ctx->d_stage.reserve(shard_bytes, ctx->stage_stream, "ndt_hip_render_multi (staging)");
+    if (e == hipSuccess && !rc) e = hipMemcpyPeerAsync(ctx->d_stage.p, first->device, ctx->d_shard.p, ctx->device, shard_bytes, ctx->stage_stream);
+    if (e == hipSuccess && !rc) {
+        launch_push(ctx->stage_stream, format, ctx->d_stage.p, d_dst, sp.width, rows, row0_out, step_out);
         e = hipGetLastError();
     }
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stage_stream);
+    if (e == hipSuccess && !rc) e = hipStreamSynchronize(ctx->stage_stream);
     (void)hipSetDevice(ctx->device);
+    if (rc) return rc;
     if (e != hipSuccess) return fail(NDT_E_DEVICE, "staged gather from device %d: %s", ctx->device, hipGetErrorString(e));
     ctx->multi_path_taken = NDT_MULTI_STAGED;
     return NDT_OK;
@@ -316,16 +294,14 @@ extern "C" int ndt_hip_multi_path_taken(ndt_hip_ctx *ctx) { return ctx ? ctx->mu
 // (ndt_hip_destroy) the staging area lives on another device than the context
 void ndt_impl::free_stage(ndt_hip_ctx *ctx)
 {
-    if (!ctx->d_stage && !ctx->stage_stream) return;
+    if (!ctx->d_stage.p && !ctx->stage_stream) return;
     (void)hipSetDevice(ctx->stage_device);
     if (ctx->stage_stream) {
         (void)hipStreamSynchronize(ctx->stage_stream);
         (void)hipStreamDestroy(ctx->stage_stream);
     }
-    if (ctx->d_stage) (void)hipFree(ctx->d_stage);
-    ctx->d_stage = nullptr;
+    ctx->d_stage.release();
     ctx->stage_stream = nullptr;
-    ctx->d_stage_bytes = 0;
     (void)hipSetDevice(ctx->device);
 }
 
@@ -396,10 +372,10 @@ extern "C" int ndt_hip_render_multi(ndt_hip_ctx *const *ctxs, int32_t n_ctx, con
         if (stats) *stats = ndt_render_stats{};
         return NDT_OK;
     }
-    int rc = ensure_bytes(first, &first->d_image, &first->d_image_bytes, bytes);
+    int rc = first->d_image.reserve(bytes, first->stream, "ndt_hip_render_multi");
     if (rc) return rc;
-    if ((rc = ndt_hip_render_multi_device(ctxs, n_ctx, p, format, first->d_image, stats))) return rc;
-    HIP_TRY(hipMemcpyAsync(out, first->d_image, bytes, hipMemcpyDeviceToHost, first->stream));
+    if ((rc = ndt_hip_render_multi_device(ctxs, n_ctx, p, format, first->d_image.p, stats))) return rc;
+    HIP_TRY(hipMemcpyAsync(out, first->d_image.p, bytes, hipMemcpyDeviceToHost, first->stream));
     HIP_TRY(hipStreamSynchronize(first->stream));
     return NDT_OK;
 }

@@ -759,19 +759,6 @@ unsigned crc32_of(const unsigned char *p, size_t len)
     return c ^ 0xffffffffu;
 }
 
-int grow(ndt_hip_ctx *ctx, void **buf, size_t *have, size_t want)
-{
-    if (*have >= want) return NDT_OK;
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    if (*buf) HIP_TRY(hipFree(*buf));
-    *buf = nullptr;
-    *have = 0;
-    const hipError_t e = hipMalloc(buf, want);
-    if (e != hipSuccess) return fail(NDT_E_NOMEM, "ndt_hip_encode_png: hipMalloc of %zu bytes: %s", want, hipGetErrorString(e));
-    *have = want;
-    return NDT_OK;
-}
-
 // the filtered stream's length for pixels of bpp bytes, or -1 for a size the encoder does not take
 long long stream_bytes(int32_t width, int32_t rows, int bpp = 4)
 {
@@ -806,33 +793,33 @@ int encode_device(ndt_hip_ctx *ctx, const char *who, const void *d_image, int32_
     const int n_chunks = (int)((n + PNG_CHUNK - 1) / PNG_CHUNK);
     const long long bound = file_bound(n);
     int rc;
-    if ((rc = grow(ctx, &ps.d_filtered, &ps.filtered_bytes, (size_t)n_chunks * PNG_CHUNK))) return rc;
-    if ((rc = grow(ctx, &ps.d_row_filter, &ps.row_filter_bytes, (size_t)rows))) return rc;
-    if ((rc = grow(ctx, &ps.d_slots, &ps.slots_bytes, (size_t)n_chunks * PNG_SLOT))) return rc;
-    if ((rc = grow(ctx, &ps.d_meta, &ps.meta_bytes, (size_t)n_chunks * sizeof(ChunkMeta)))) return rc;
-    if ((rc = grow(ctx, &ps.d_offsets, &ps.offsets_bytes, (size_t)n_chunks * sizeof(long long)))) return rc;
-    if ((rc = grow(ctx, &ps.d_file, &ps.file_bytes, (size_t)bound))) return rc;
-    if ((rc = grow(ctx, &ps.d_info, &ps.info_bytes, sizeof(PngInfo)))) return rc;
+    if ((rc = ps.d_filtered.reserve((size_t)n_chunks * PNG_CHUNK, ctx->stream, who))) return rc;
+    if ((rc = ps.d_row_filter.reserve((size_t)rows, ctx->stream, who))) return rc;
+    if ((rc = ps.d_slots.reserve((size_t)n_chunks * PNG_SLOT, ctx->stream, who))) return rc;
+    if ((rc = ps.d_meta.reserve((size_t)n_chunks * sizeof(ChunkMeta), ctx->stream, who))) return rc;
+    if ((rc = ps.d_offsets.reserve((size_t)n_chunks * sizeof(long long), ctx->stream, who))) return rc;
+    if ((rc = ps.d_file.reserve((size_t)bound, ctx->stream, who))) return rc;
+    if ((rc = ps.d_info.reserve(sizeof(PngInfo), ctx->stream, who))) return rc;
     if (!ps.h_info) HIP_TRY(hipHostMalloc(&ps.h_info, sizeof(PngInfo), hipHostMallocDefault));
     hipStream_t s = ctx->stream;
     if (f.bpp == 4)
-        hipLaunchKernelGGL(k_png_filter, dim3((unsigned)rows), dim3(256), 0, s, (const unsigned *)d_image, (unsigned char *)ps.d_filtered,
-                           (unsigned char *)ps.d_row_filter, (int)width, (int)rows);
+        hipLaunchKernelGGL(k_png_filter, dim3((unsigned)rows), dim3(256), 0, s, (const unsigned *)d_image, ps.d_filtered.as<unsigned char>(),
+                           ps.d_row_filter.as<unsigned char>(), (int)width, (int)rows);
     else if (f.bpp == 8)
         hipLaunchKernelGGL(k_png_filter_wide<8>, dim3((unsigned)rows), dim3(256), 0, s, (const unsigned char *)d_image,
-                           (unsigned char *)ps.d_filtered, (unsigned char *)ps.d_row_filter, (int)width, (int)rows);
+                           ps.d_filtered.as<unsigned char>(), ps.d_row_filter.as<unsigned char>(), (int)width, (int)rows);
     else
         hipLaunchKernelGGL(k_png_filter_wide<2>, dim3((unsigned)rows), dim3(256), 0, s, (const unsigned char *)d_image,
-                           (unsigned char *)ps.d_filtered, (unsigned char *)ps.d_row_filter, (int)width, (int)rows);
-    hipLaunchKernelGGL(k_png_deflate, dim3((unsigned)n_chunks), dim3(PNG_DEFLATE_LANES), 0, s, (const unsigned char *)ps.d_filtered, n, n_chunks,
-                       (unsigned char *)ps.d_slots, (ChunkMeta *)ps.d_meta);
-    hipLaunchKernelGGL(k_png_assemble, dim3(1), dim3(1024), 0, s, (const ChunkMeta *)ps.d_meta, n_chunks, n, (const unsigned char *)ps.d_row_filter,
-                       (int)width, (int)rows, f.bit_depth, f.colour_type, (unsigned char *)ps.d_file, (long long *)ps.d_offsets,
-                       (PngInfo *)ps.d_info);
-    hipLaunchKernelGGL(k_png_place, dim3((unsigned)n_chunks), dim3(256), 0, s, (const unsigned char *)ps.d_slots, (const ChunkMeta *)ps.d_meta,
-                       (const long long *)ps.d_offsets, (unsigned char *)ps.d_file);
+                           ps.d_filtered.as<unsigned char>(), ps.d_row_filter.as<unsigned char>(), (int)width, (int)rows);
+    hipLaunchKernelGGL(k_png_deflate, dim3((unsigned)n_chunks), dim3(PNG_DEFLATE_LANES), 0, s, ps.d_filtered.as<const unsigned char>(), n, n_chunks,
+                       ps.d_slots.as<unsigned char>(), ps.d_meta.as<ChunkMeta>());
+    hipLaunchKernelGGL(k_png_assemble, dim3(1), dim3(1024), 0, s, ps.d_meta.as<const ChunkMeta>(), n_chunks, n, ps.d_row_filter.as<const unsigned char>(),
+                       (int)width, (int)rows, f.bit_depth, f.colour_type, ps.d_file.as<unsigned char>(), ps.d_offsets.as<long long>(),
+                       ps.d_info.as<PngInfo>());
+    hipLaunchKernelGGL(k_png_place, dim3((unsigned)n_chunks), dim3(256), 0, s, ps.d_slots.as<const unsigned char>(), ps.d_meta.as<const ChunkMeta>(),
+                       ps.d_offsets.as<const long long>(), ps.d_file.as<unsigned char>());
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(ps.h_info, ps.d_info, sizeof(PngInfo), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(ps.h_info, ps.d_info.p, sizeof(PngInfo), hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
     const PngInfo info = *(const PngInfo *)ps.h_info;
     if (stats) {
@@ -848,7 +835,7 @@ int encode_device(ndt_hip_ctx *ctx, const char *who, const void *d_image, int32_
         return fail(NDT_E_DEVICE, "%s: the device reports a file of %lld bytes (bound %lld)", who, info.png_bytes, bound);
     if (info.png_bytes > cap)
         return fail(NDT_E_NOMEM, "%s: the file is %lld bytes, the buffer %lld", who, info.png_bytes, (long long)cap);
-    HIP_TRY(hipMemcpyAsync(png, ps.d_file, (size_t)info.png_bytes, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(png, ps.d_file.p, (size_t)info.png_bytes, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
     // the IDAT chunk's CRC-32 covers its type and data: bytes 37 .. 41 + idat_bytes of the file
     const unsigned crc = crc32_of(png + 37, (size_t)(4 + info.idat_bytes));
@@ -867,9 +854,9 @@ int upload_image(ndt_hip_ctx *ctx, const char *who, const void *image, int32_t w
         return fail(NDT_E_INVALID, "%s: the filtered stream of a %d x %d image exceeds 2^31 - 1 bytes", who, width, rows);
     HIP_TRY(hipSetDevice(ctx->device));
     const size_t bytes = (size_t)width * (size_t)rows * (size_t)f.bpp;
-    int rc = grow(ctx, &ctx->png.d_rgba8, &ctx->png.rgba8_bytes, bytes);
+    int rc = ctx->png.d_rgba8.reserve(bytes, ctx->stream, who);
     if (rc) return rc;
-    HIP_TRY(hipMemcpyAsync(ctx->png.d_rgba8, image, bytes, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(ctx->png.d_rgba8.p, image, bytes, hipMemcpyHostToDevice, ctx->stream));
     return NDT_OK;
 }
 
@@ -893,11 +880,15 @@ extern "C" int64_t ndt_hip_png16_bound(int32_t width, int32_t rows, int32_t chan
 void ndt_impl::free_png(ndt_hip_ctx *ctx)
 {
     PngState &ps = ctx->png;
-    void **bufs[] = { &ps.d_rgba8, &ps.d_rgba16, &ps.d_filtered, &ps.d_row_filter, &ps.d_slots, &ps.d_meta, &ps.d_offsets, &ps.d_file, &ps.d_info };
-    for (void **b : bufs) {
-        if (*b) (void)hipFree(*b);
-        *b = nullptr;
-    }
+    ps.d_rgba8.release();
+    ps.d_rgba16.release();
+    ps.d_filtered.release();
+    ps.d_row_filter.release();
+    ps.d_slots.release();
+    ps.d_meta.release();
+    ps.d_offsets.release();
+    ps.d_file.release();
+    ps.d_info.release();
     if (ps.h_info) (void)hipHostFree(ps.h_info);
     ps = PngState();
 }
@@ -914,7 +905,7 @@ extern "C" int ndt_hip_encode_png(ndt_hip_ctx *ctx, const uint8_t *rgba8, int32_
     if (!png) return fail(NDT_E_INVALID, "ndt_hip_encode_png: NULL argument");
     int rc = upload_image(ctx, "ndt_hip_encode_png", rgba8, width, rows, PNG_RGBA8);
     if (rc) return rc;
-    return ndt_hip_encode_png_device(ctx, ctx->png.d_rgba8, width, rows, png, cap, stats);
+    return ndt_hip_encode_png_device(ctx, ctx->png.d_rgba8.p, width, rows, png, cap, stats);
 }
 
 extern "C" int ndt_hip_encode_png16_device(ndt_hip_ctx *ctx, const void *d_samples, int32_t width, int32_t rows, int32_t channels, uint8_t *png,
@@ -933,7 +924,7 @@ extern "C" int ndt_hip_encode_png16(ndt_hip_ctx *ctx, const uint8_t *samples, in
     if (!png) return fail(NDT_E_INVALID, "ndt_hip_encode_png16: NULL argument");
     int rc = upload_image(ctx, "ndt_hip_encode_png16", samples, width, rows, *f);
     if (rc) return rc;
-    return encode_device(ctx, "ndt_hip_encode_png16", ctx->png.d_rgba8, width, rows, *f, png, cap, stats);
+    return encode_device(ctx, "ndt_hip_encode_png16", ctx->png.d_rgba8.p, width, rows, *f, png, cap, stats);
 }
 
 extern "C" int ndt_hip_render_png(ndt_hip_ctx *ctx, const ndt_render_params *p, uint8_t *png, int64_t cap, ndt_png_stats *stats,
@@ -946,11 +937,11 @@ extern "C" int ndt_hip_render_png(ndt_hip_ctx *ctx, const ndt_render_params *p, 
     if (stream_bytes(p->width, rows) < 0)
         return fail(NDT_E_INVALID, "ndt_hip_render_png: the filtered stream of a %d x %d image exceeds 2^31 - 1 bytes", p->width, rows);
     HIP_TRY(hipSetDevice(ctx->device));
-    int rc = grow(ctx, &ctx->png.d_rgba8, &ctx->png.rgba8_bytes, (size_t)p->width * (size_t)rows * 4);
+    int rc = ctx->png.d_rgba8.reserve((size_t)p->width * (size_t)rows * 4, ctx->stream, "ndt_hip_render_png");
     if (rc) return rc;
     ndt_hip_ctx *one[1] = { ctx };
-    if ((rc = ndt_hip_render_multi_device(one, 1, p, NDT_IMAGE_RGBA8, ctx->png.d_rgba8, render_stats))) return rc;
-    return ndt_hip_encode_png_device(ctx, ctx->png.d_rgba8, p->width, rows, png, cap, stats);
+    if ((rc = ndt_hip_render_multi_device(one, 1, p, NDT_IMAGE_RGBA8, ctx->png.d_rgba8.p, render_stats))) return rc;
+    return ndt_hip_encode_png_device(ctx, ctx->png.d_rgba8.p, p->width, rows, png, cap, stats);
 }
 
 extern "C" int ndt_hip_render_png16(ndt_hip_ctx *ctx, const ndt_render_params *p, uint8_t *png, int64_t cap, ndt_png_stats *stats,
@@ -966,10 +957,10 @@ extern "C" int ndt_hip_render_png16(ndt_hip_ctx *ctx, const ndt_render_params *p
     HIP_TRY(hipSetDevice(ctx->device));
     // the frame in doubles where ndt_hip_render leaves it, its 16-bit samples beside the encoder's buffers
     const size_t pixels = (size_t)p->width * (size_t)rows;
-    int rc = ensure_out(ctx, pixels * 4 * sizeof(double));
+    int rc = ctx->d_out.reserve(pixels * 4 * sizeof(double), ctx->stream, "ndt_hip_render_png16");
     if (rc) return rc;
-    if ((rc = grow(ctx, &ctx->png.d_rgba16, &ctx->png.rgba16_bytes, pixels * 8))) return rc;
-    if ((rc = ndt_hip_render_device(ctx, p, ctx->d_out, render_stats))) return rc;
-    if ((rc = ndt_hip_quantize16_device(ctx, ctx->d_out, ctx->png.d_rgba16, (int64_t)pixels))) return rc;
-    return encode_device(ctx, "ndt_hip_render_png16", ctx->png.d_rgba16, p->width, rows, PNG_RGBA16, png, cap, stats);
+    if ((rc = ctx->png.d_rgba16.reserve(pixels * 8, ctx->stream, "ndt_hip_render_png16"))) return rc;
+    if ((rc = ndt_hip_render_device(ctx, p, ctx->d_out.p, render_stats))) return rc;
+    if ((rc = ndt_hip_quantize16_device(ctx, ctx->d_out.p, ctx->png.d_rgba16.p, (int64_t)pixels))) return rc;
+    return encode_device(ctx, "ndt_hip_render_png16", ctx->png.d_rgba16.p, p->width, rows, PNG_RGBA16, png, cap, stats);
 }

@@ -140,17 +140,11 @@ extern "C" int ndt_hip_render_depth(ndt_hip_ctx *ctx, const ndt_render_params *p
     const size_t img_bytes = (size_t)rows * (size_t)(p->width > 0 ? p->width : 0) * 4 * sizeof(double);
     const size_t bytes = img_bytes + (depth ? img_bytes / 4 : 0);      // the depth map sits behind the image
     if (img_bytes == 0) return ndt_hip_render_depth_device(ctx, p, (void *)rgba, nullptr, stats);
-    if (ctx->d_out_bytes < bytes) {
-        HIP_TRY(hipStreamSynchronize(ctx->stream));
-        if (ctx->d_out) HIP_TRY(hipFree(ctx->d_out));
-        ctx->d_out = nullptr;
-        HIP_TRY(hipMalloc(&ctx->d_out, bytes));
-        ctx->d_out_bytes = bytes;
-    }
-    void *d_depth = depth ? (void *)((char *)ctx->d_out + img_bytes) : nullptr;
-    int rc = ndt_hip_render_depth_device(ctx, p, ctx->d_out, d_depth, stats);
+    int rc = ctx->d_out.reserve(bytes, ctx->stream, "ndt_hip_render");
     if (rc) return rc;
-    HIP_TRY(hipMemcpyAsync(rgba, ctx->d_out, img_bytes, hipMemcpyDeviceToHost, ctx->stream));
+    void *d_depth = depth ? (void *)(ctx->d_out.as<char>() + img_bytes) : nullptr;
+    if ((rc = ndt_hip_render_depth_device(ctx, p, ctx->d_out.p, d_depth, stats))) return rc;
+    HIP_TRY(hipMemcpyAsync(rgba, ctx->d_out.p, img_bytes, hipMemcpyDeviceToHost, ctx->stream));
     if (depth) HIP_TRY(hipMemcpyAsync(depth, d_depth, img_bytes / 4, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     return NDT_OK;

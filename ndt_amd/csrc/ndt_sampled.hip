@@ -262,19 +262,10 @@ int ndt_impl::render_sampled(ndt_hip_ctx *ctx, const ndt_render_params *p, void 
     // frame -- each of those synchronises the device and stalls every other context on it.  (Not from the AaBuffers pools:
     // render_sampled_eye walks those from their start.)
     const size_t eye_bytes = (size_t)n_pixels * 4 * sizeof(double);
-    if (ctx->d_eyes_bytes < 2 * eye_bytes) {
-        if (ctx->d_eyes) {
-            HIP_TRY(hipStreamSynchronize(ctx->stream));
-            (void)hipFree(ctx->d_eyes);
-            ctx->d_eyes = nullptr;
-            ctx->d_eyes_bytes = 0;
-        }
-        hipError_t e = hipMalloc(&ctx->d_eyes, 2 * eye_bytes);
-        if (e != hipSuccess) return fail(NDT_E_NOMEM, "hipMalloc: %s", hipGetErrorString(e));
-        ctx->d_eyes_bytes = 2 * eye_bytes;
-    }
-    double *left = (double *)ctx->d_eyes, *right = left + (size_t)n_pixels * 4;
-    int rc = render_sampled_eye(ctx, p, 0, 0, 0ull, left, total, d_depth);
+    int rc = ctx->d_eyes.reserve(2 * eye_bytes, ctx->stream, "the eyes of a stochastic anaglyph render");
+    if (rc) return rc;
+    double *left = ctx->d_eyes.as<double>(), *right = left + (size_t)n_pixels * 4;
+    rc = render_sampled_eye(ctx, p, 0, 0, 0ull, left, total, d_depth);
     if (!rc) rc = render_sampled_eye(ctx, p, 2, 0, 0x5eed0000000000ffull, right, total, nullptr);
     if (!rc) {
         launch_anaglyph(ctx->stream, left, right, (double *)d_rgba, n_pixels);

@@ -127,19 +127,6 @@ int fold(ndt_hip_ctx *ctx, const void *d_pass, void *d_acc, int width, int rows,
     return NDT_OK;
 }
 
-int grow(ndt_hip_ctx *ctx, void **buf, size_t *have, size_t want)
-{
-    if (*have >= want) return NDT_OK;
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    if (*buf) HIP_TRY(hipFree(*buf));
-    *buf = nullptr;
-    *have = 0;
-    const hipError_t e = hipMalloc(buf, want);
-    if (e != hipSuccess) return fail(NDT_E_NOMEM, "supersampling on the device: hipMalloc of %zu bytes: %s", want, hipGetErrorString(e));
-    *have = want;
-    return NDT_OK;
-}
-
 // what every whole-frame call refuses, before any device work
 int refuse(const char *who, const ndt_hip_ctx *ctx, const ndt_render_params *p, int K, const void *out)
 {
@@ -182,10 +169,10 @@ int render_ssaa(ndt_hip_ctx *ctx, const ndt_render_params *p, int K, void *d_rgb
     }
     const size_t pass_bytes = pixels * K * 4 * sizeof(double);
     int rc;
-    if ((rc = grow(ctx, &ss.d_pass, &ss.pass_bytes, pass_bytes + (d_depth ? pass_bytes / 4 : 0)))) return rc;
+    if ((rc = ss.d_pass.reserve(pass_bytes + (d_depth ? pass_bytes / 4 : 0), ctx->stream, "ndt_hip_render_ssaa*"))) return rc;
     if (!ss.ev[0])
         for (hipEvent_t &e : ss.ev) HIP_TRY(hipEventCreate(&e));
-    void *d_pass_depth = d_depth ? (void *)((char *)ss.d_pass + pass_bytes) : nullptr;
+    void *d_pass_depth = d_depth ? (void *)(ss.d_pass.as<char>() + pass_bytes) : nullptr;
     ndt_render_params q = *p;
     q.width = K * p->width;
     q.height = K * p->height;
@@ -194,12 +181,12 @@ int render_ssaa(ndt_hip_ctx *ctx, const ndt_render_params *p, int K, void *d_rgb
         // rows { K (b + k S) + a } of the large frame: as many as the shard has output rows
         q.row_begin = K * p->row_begin + a;
         ndt_render_stats one{};
-        if ((rc = ndt_hip_render_depth_device(ctx, &q, ss.d_pass, a == 0 ? d_pass_depth : nullptr, &one))) return rc;
+        if ((rc = ndt_hip_render_depth_device(ctx, &q, ss.d_pass.p, a == 0 ? d_pass_depth : nullptr, &one))) return rc;
         add_stats(total, one);
         total.pixels_resampled += one.pixels_resampled;
         total.aa_samples += one.aa_samples;
         HIP_TRY(hipEventRecord(ss.ev[2 * a], ctx->stream));
-        if ((rc = fold(ctx, ss.d_pass, d_rgba, p->width, rows, K, a, d_rgba8, d_pass_depth, d_depth))) return rc;
+        if ((rc = fold(ctx, ss.d_pass.p, d_rgba, p->width, rows, K, a, d_rgba8, d_pass_depth, d_depth))) return rc;
         HIP_TRY(hipEventRecord(ss.ev[2 * a + 1], ctx->stream));
     }
     HIP_TRY(hipStreamSynchronize(ctx->stream));
@@ -224,9 +211,9 @@ int render_ssaa_own(ndt_hip_ctx *ctx, const ndt_render_params *p, int K, bool wa
     *pixels_out = pixels;
     const size_t img_bytes = pixels * 4 * sizeof(double);
     int rc;
-    if ((rc = grow(ctx, &ss.d_acc, &ss.acc_bytes, (img_bytes ? img_bytes : 32) + (want_depth ? img_bytes / 4 : 0)))) return rc;
-    if (want_rgba8 && (rc = grow(ctx, &ss.d_rgba8, &ss.rgba8_bytes, pixels ? pixels * 4 : 4))) return rc;
-    return render_ssaa(ctx, p, K, ss.d_acc, want_depth ? (void *)((char *)ss.d_acc + img_bytes) : nullptr, want_rgba8 ? ss.d_rgba8 : nullptr, stats);
+    if ((rc = ss.d_acc.reserve((img_bytes ? img_bytes : 32) + (want_depth ? img_bytes / 4 : 0), ctx->stream, "ndt_hip_render_ssaa*"))) return rc;
+    if (want_rgba8 && (rc = ss.d_rgba8.reserve(pixels ? pixels * 4 : 4, ctx->stream, "ndt_hip_render_ssaa*"))) return rc;
+    return render_ssaa(ctx, p, K, ss.d_acc.p, want_depth ? (void *)(ss.d_acc.as<char>() + img_bytes) : nullptr, want_rgba8 ? ss.d_rgba8.p : nullptr, stats);
 }
 
 } // namespace
@@ -234,11 +221,12 @@ int render_ssaa_own(ndt_hip_ctx *ctx, const ndt_render_params *p, int K, bool wa
 void ndt_impl::free_ssaa(ndt_hip_ctx *ctx)
 {
     SsaaState &ss = ctx->ssaa;
-    void **bufs[] = { &ss.d_pass, &ss.d_acc, &ss.d_rgba8, &ss.d_depth8, &ss.d_rgba16, &ss.d_grey16 };
-    for (void **b : bufs) {
-        if (*b) (void)hipFree(*b);
-        *b = nullptr;
-    }
+    ss.d_pass.release();
+    ss.d_acc.release();
+    ss.d_rgba8.release();
+    ss.d_depth8.release();
+    ss.d_rgba16.release();
+    ss.d_grey16.release();
     for (hipEvent_t &e : ss.ev)
         if (e) (void)hipEventDestroy(e);
     ss = SsaaState();
@@ -283,8 +271,8 @@ extern "C" int ndt_hip_render_ssaa(ndt_hip_ctx *ctx, const ndt_render_params *p,
     size_t pixels = 0;
     if ((rc = render_ssaa_own(ctx, p, K, depth != nullptr, false, stats, &rows, &pixels)) || pixels == 0) return rc;
     const size_t img_bytes = pixels * 4 * sizeof(double);
-    HIP_TRY(hipMemcpyAsync(rgba, ctx->ssaa.d_acc, img_bytes, hipMemcpyDeviceToHost, ctx->stream));
-    if (depth) HIP_TRY(hipMemcpyAsync(depth, (char *)ctx->ssaa.d_acc + img_bytes, img_bytes / 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(rgba, ctx->ssaa.d_acc.p, img_bytes, hipMemcpyDeviceToHost, ctx->stream));
+    if (depth) HIP_TRY(hipMemcpyAsync(depth, ctx->ssaa.d_acc.as<char>() + img_bytes, img_bytes / 4, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     return NDT_OK;
 }
@@ -296,7 +284,7 @@ extern "C" int ndt_hip_render_ssaa_rgba8(ndt_hip_ctx *ctx, const ndt_render_para
     int rows = 0;
     size_t pixels = 0;
     if ((rc = render_ssaa_own(ctx, p, K, false, true, stats, &rows, &pixels)) || pixels == 0) return rc;
-    HIP_TRY(hipMemcpyAsync(rgba8, ctx->ssaa.d_rgba8, pixels * 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(rgba8, ctx->ssaa.d_rgba8.p, pixels * 4, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     return NDT_OK;
 }
@@ -313,7 +301,7 @@ extern "C" int ndt_hip_render_ssaa_png(ndt_hip_ctx *ctx, const ndt_render_params
     int rows = 0;
     size_t pixels = 0;
     if ((rc = render_ssaa_own(ctx, p, K, false, true, render_stats, &rows, &pixels))) return rc;
-    return ndt_hip_encode_png_device(ctx, ctx->ssaa.d_rgba8, p->width, rows, png, cap, stats);
+    return ndt_hip_encode_png_device(ctx, ctx->ssaa.d_rgba8.p, p->width, rows, png, cap, stats);
 }
 
 extern "C" int ndt_hip_render_ssaa_jpeg(ndt_hip_ctx *ctx, const ndt_render_params *p, int32_t K, const ndt_jpeg_params *jp, uint8_t *jpg,
@@ -329,7 +317,7 @@ extern "C" int ndt_hip_render_ssaa_jpeg(ndt_hip_ctx *ctx, const ndt_render_param
     int rows = 0;
     size_t pixels = 0;
     if ((rc = render_ssaa_own(ctx, p, K, false, true, render_stats, &rows, &pixels))) return rc;
-    return ndt_hip_encode_jpeg_device(ctx, ctx->ssaa.d_rgba8, p->width, rows, jp, jpg, cap, stats);
+    return ndt_hip_encode_jpeg_device(ctx, ctx->ssaa.d_rgba8.p, p->width, rows, jp, jpg, cap, stats);
 }
 
 extern "C" int ndt_hip_render_ssaa_rgba8_depth(ndt_hip_ctx *ctx, const ndt_render_params *p, int32_t K, uint8_t *rgba8, uint8_t *depth8,
@@ -343,10 +331,10 @@ extern "C" int ndt_hip_render_ssaa_rgba8_depth(ndt_hip_ctx *ctx, const ndt_rende
     if (range_out) range_out[0] = range_out[1] = 0.0;
     if ((rc = render_ssaa_own(ctx, p, K, true, true, stats, &rows, &pixels)) || pixels == 0) return rc;
     SsaaState &ss = ctx->ssaa;
-    if ((rc = grow(ctx, &ss.d_depth8, &ss.depth8_bytes, pixels * 4))) return rc;
-    if ((rc = ndt_hip_depth_rgba8_device(ctx, (char *)ss.d_acc + pixels * 4 * sizeof(double), (int64_t)pixels, ss.d_depth8, range_out))) return rc;
-    HIP_TRY(hipMemcpyAsync(rgba8, ss.d_rgba8, pixels * 4, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(depth8, ss.d_depth8, pixels * 4, hipMemcpyDeviceToHost, ctx->stream));
+    if ((rc = ss.d_depth8.reserve(pixels * 4, ctx->stream, "ndt_hip_render_ssaa_rgba8_depth"))) return rc;
+    if ((rc = ndt_hip_depth_rgba8_device(ctx, ss.d_acc.as<char>() + pixels * 4 * sizeof(double), (int64_t)pixels, ss.d_depth8.p, range_out))) return rc;
+    HIP_TRY(hipMemcpyAsync(rgba8, ss.d_rgba8.p, pixels * 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(depth8, ss.d_depth8.p, pixels * 4, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     return NDT_OK;
 }
@@ -367,15 +355,15 @@ static int ssaa_png16(const char *who, ndt_hip_ctx *ctx, const ndt_render_params
     size_t pixels = 0;
     if ((rc = render_ssaa_own(ctx, p, K, depth_png != nullptr, false, render_stats, &rows, &pixels))) return rc;
     SsaaState &ss = ctx->ssaa;
-    if ((rc = grow(ctx, &ss.d_rgba16, &ss.rgba16_bytes, pixels * 8))) return rc;
-    if ((rc = ndt_hip_quantize16_device(ctx, ss.d_acc, ss.d_rgba16, (int64_t)pixels))) return rc;
+    if ((rc = ss.d_rgba16.reserve(pixels * 8, ctx->stream, who))) return rc;
+    if ((rc = ndt_hip_quantize16_device(ctx, ss.d_acc.p, ss.d_rgba16.p, (int64_t)pixels))) return rc;
     if (depth_png) {
-        if ((rc = grow(ctx, &ss.d_grey16, &ss.grey16_bytes, (pixels * 2 + 3) & ~(size_t)3))) return rc;
-        if ((rc = ndt_hip_depth_grey16_device(ctx, (char *)ss.d_acc + pixels * 4 * sizeof(double), (int64_t)pixels, ss.d_grey16, range_out))) return rc;
+        if ((rc = ss.d_grey16.reserve((pixels * 2 + 3) & ~(size_t)3, ctx->stream, who))) return rc;
+        if ((rc = ndt_hip_depth_grey16_device(ctx, ss.d_acc.as<char>() + pixels * 4 * sizeof(double), (int64_t)pixels, ss.d_grey16.p, range_out))) return rc;
     }
-    if ((rc = ndt_hip_encode_png16_device(ctx, ss.d_rgba16, p->width, rows, 4, png, cap, stats))) return rc;
+    if ((rc = ndt_hip_encode_png16_device(ctx, ss.d_rgba16.p, p->width, rows, 4, png, cap, stats))) return rc;
     if (!depth_png) return NDT_OK;
-    return ndt_hip_encode_png16_device(ctx, ss.d_grey16, p->width, rows, 1, depth_png, depth_cap, stats ? &stats[1] : nullptr);
+    return ndt_hip_encode_png16_device(ctx, ss.d_grey16.p, p->width, rows, 1, depth_png, depth_cap, stats ? &stats[1] : nullptr);
 }
 
 extern "C" int ndt_hip_render_ssaa_png16(ndt_hip_ctx *ctx, const ndt_render_params *p, int32_t K, uint8_t *png, int64_t cap, ndt_png_stats *stats,

@@ -282,6 +282,25 @@ def test_hull_box_of_a_non_hcube_is_an_error():
         hcube_hull_box(fs, other)
 
 
+def test_face_tree_refuses_a_scene_of_impossible_dimensions_like_face_groups():
+    """ndt_hip_hcube_face_tree sizes its hull rows from the scene's `dims` before anything has validated them: for a count no
+    scene can have (-1, NDT_MAX_DIMS + 1) it returns the NDT_E_* code ndt_hip_hcube_face_groups returns for the same scene --
+    the call comes back, it does not end the process with a vector's length error thrown across the C boundary."""
+    import ctypes as C
+    from ndt_amd.flat_scene import FlatSceneStruct, MAX_DIMS
+    from ndt_amd.hip import load_library
+    fs = golden("c3_random4d").scene
+    lib = load_library()
+    h = hcubes(fs)[0]
+    for dims in (-1, MAX_DIMS + 1):
+        st = FlatSceneStruct.from_buffer_copy(fs.struct)        # (the golden scene is shared: the copy gets the bad count)
+        st.dims = dims
+        want = lib.ndt_hip_hcube_face_groups(C.byref(st), h, None, None, None, None)
+        top, off = C.c_int32(0), (C.c_int32 * 32)()
+        got = lib.ndt_hip_hcube_face_tree(C.byref(st), h, 0, None, off, C.byref(top))
+        assert want < 0 and got == want, (dims, want, got)
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("name", SCENES + ["zoo9d"])         # (9-D: the hcube of 16 866 faces, the one the index by thin axes is for)
 def test_cull_changes_nothing_on_the_device(oracle, name):
