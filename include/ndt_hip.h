@@ -504,6 +504,52 @@ int ndt_hip_render_ssaa_png16(ndt_hip_ctx *ctx, const ndt_render_params *p, int3
 int ndt_hip_render_ssaa_png16_depth(ndt_hip_ctx *ctx, const ndt_render_params *p, int32_t K, uint8_t *png, int64_t cap, uint8_t *depth_png,
                                     int64_t depth_cap, ndt_png_stats *stats, double *range_out, ndt_render_stats *render_stats);
 
+/* A frame sequence as ONE animated PNG (APNG; `ndt_hip --apng`), the difference between consecutive frames found on the device.
+ * The file is 8-bit RGBA: signature, IHDR, acTL, then per frame an fcTL and one IDAT (frame 0, the default image, the whole
+ * canvas) or one fdAT (every later frame: a sub-rectangle with a zlib stream of its own, made by the encoder of the still files
+ * run on the smaller image), then IEND.  Sequence numbers run 0, 1, 2 ... over fcTL and fdAT together; every frame has dispose
+ * NONE and the delay given at `begin`.  The canvas -- the previous frame -- stays in the context's device memory, and a later
+ * frame is planned there against it:
+ *   changed     a pixel whose 32-bit word differs from the canvas's
+ *   rectangle   the tight bounding box of the changed pixels; nothing changed: the 1 x 1 pixel at (0, 0), blend SOURCE
+ *   blend OVER (1)    when every changed pixel has alpha 255: the unchanged pixels inside the rectangle are sent as 00 00 00 00
+ *               (alpha 0 keeps the canvas, alpha 255 replaces it: the decoded frame is exact)
+ *   blend SOURCE (0)  otherwise: the rectangle's pixels as they are
+ * What crosses PCIe per frame is the plan record and the rectangle's zlib stream.
+ *   ndt_hip_apng_bound   host arithmetic: the most bytes one `add` can append for a width x rows canvas; < 0 (NDT_E_INVALID) exactly
+ *                        where ndt_hip_png_bound is
+ *   ndt_hip_apng_begin   opens the context's session (one at a time; a session still open is dropped): n_frames >= 1 frames are
+ *                        to come -- acTL precedes them, so the count is fixed here --, each shown delay_num / delay_den seconds
+ *                        (0 .. 65535 over 1 .. 65535), the animation played n_plays >= 0 times (0: for ever).  No device work
+ *   ndt_hip_apng_add_device / ndt_hip_apng_add   the next frame, width * rows * 4 bytes in the context's device memory (aligned
+ *                        to 4) or in host memory.  `out` receives exactly the bytes to append to the file; the first call's
+ *                        start with the signature, IHDR and acTL.  Frame 0 takes a device-to-device copy into the canvas and
+ *                        the encoder's 4 launches, a later frame 7 launches
+ *   ndt_hip_render_apng_frame   renders the uploaded scene's shard and adds it from device memory: the 8-bit image never reaches
+ *                        the host.  The shard's width and rows must be the session's.  ssaa 1: the plain frame, every mode of
+ *                        ndt_hip_render_rgba8; ssaa 2 .. 8: the supersampled frame, with the refusals of ndt_hip_render_ssaa_rgba8
+ *   ndt_hip_apng_end     after the n_frames-th frame: IEND into `out`, its length into *bytes; closes the session
+ * NDT_E_INVALID, before any device work and with the cause in the error text: a NULL pointer, a size < 1, n_frames < 1,
+ * delay_den < 1, a delay beyond 65535, no session open, a device pointer off its 4-byte pixels, one `add` more than n_frames,
+ * `end` before the n_frames-th frame (the session stays open).  NDT_E_NOMEM: `cap` is smaller than what is to be appended; the
+ * text and stats->bytes carry the size needed and nothing is written to `out`.  Any error from an `add` closes the session.
+ * stats (may be NULL): frame = its index, bytes = appended, zlib_bytes = the zlib stream's, x y w h blend = its fcTL's,
+ * changed / translucent = pixels that differ from the canvas / ... and have an alpha other than 255 (frame 0: 0 and 0),
+ * launches = kernel launches, encode_ms = host time of the call without the render.  None of the calls falls back. */
+typedef struct ndt_apng_stats {
+    int64_t bytes, zlib_bytes, changed, translucent;
+    int32_t frame, x, y, w, h, blend, launches, reserved;
+    double encode_ms;
+} ndt_apng_stats;
+int64_t ndt_hip_apng_bound(int32_t width, int32_t rows);
+int ndt_hip_apng_begin(ndt_hip_ctx *ctx, int32_t width, int32_t rows, int32_t n_frames, int32_t delay_num, int32_t delay_den,
+                       int32_t n_plays);
+int ndt_hip_apng_add_device(ndt_hip_ctx *ctx, const void *d_rgba8, uint8_t *out, int64_t cap, ndt_apng_stats *stats);
+int ndt_hip_apng_add(ndt_hip_ctx *ctx, const uint8_t *rgba8, uint8_t *out, int64_t cap, ndt_apng_stats *stats);
+int ndt_hip_render_apng_frame(ndt_hip_ctx *ctx, const ndt_render_params *p, int32_t ssaa, uint8_t *out, int64_t cap,
+                              ndt_apng_stats *stats, ndt_render_stats *render_stats);
+int ndt_hip_apng_end(ndt_hip_ctx *ctx, uint8_t *out, int64_t cap, int64_t *bytes);
+
 /* ONE frame over several contexts -- one per GPU of the node, or several on one GPU -- called from one host thread.
  * The rows `p` selects are dealt cyclically to the contexts exactly as the reference deals rows to MPI ranks in
  * MPI_MODE_ROW (ndt.c:812-820: row_start = rank, row_step = size): context k renders rows

@@ -127,6 +127,7 @@ extern "C" int ndt_hip_destroy(ndt_hip_ctx *ctx)
     ctx->d_fit.release();
     free_kd(ctx);
     free_png(ctx);
+    free_apng(ctx);
     free_jpeg(ctx);
     free_depth(ctx);
     free_ssaa(ctx);

@@ -12,6 +12,8 @@
 //   ndt_fit.hip      ndt_hip_fit_spheres: the bounding-sphere fits of a frame (batched Nelder-Mead), kernel and launcher
 //   ndt_kd.hip       ndt_hip_build_kdtree: the kd-tree of a frame's item boxes, level by level; kernels, launcher and C ABI
 //   ndt_png.hip      ndt_hip_encode_png* / ndt_hip_render_png: a frame's PNG file made on the device; kernels, launcher and C ABI
+//   ndt_apng.hip     ndt_hip_apng_* / ndt_hip_render_apng_frame: a frame sequence as one animated PNG, the difference between frames
+//                    found on the device; kernels, launcher and C ABI
 //   ndt_jpeg.hip     ndt_hip_encode_jpeg* / ndt_hip_render_jpeg: a frame's JPEG file made on the device; kernels, launcher and C ABI
 //   ndt_depth.hip    ndt_hip_depth_rgba8_device / ndt_hip_render_*_depth: the depth map of `-z` normalised and quantised on the device
 //   ndt_ssaa.hip     ndt_hip_ssaa_fold_device / ndt_hip_render_ssaa*: K x K supersampling, K ordinary renders folded on the device
@@ -73,6 +75,19 @@ struct PngState {
     DeviceBuffer d_rgba8, d_filtered, d_row_filter, d_slots, d_meta, d_offsets, d_file, d_info;
     void *h_info = nullptr;         // pinned: the info record of the last file
     DeviceBuffer d_rgba16;          // ndt_hip_render_png16: the frame's 16-bit samples in file byte order
+};
+
+// ndt_hip_apng_* (ndt_apng.hip): the open session and its grow-only device buffers, reused by the next frame and the next session
+struct ApngState {
+    DeviceBuffer d_canvas;          // the previous frame: width x rows pixels
+    DeviceBuffer d_frame;           // ndt_hip_apng_add, ndt_hip_render_apng_frame: the frame that arrives
+    DeviceBuffer d_crop;            // a later frame's rectangle as the compact w x h image the encoder takes
+    DeviceBuffer d_rows, d_plan;    // one record per row, and the plan folded from them
+    void *h_plan = nullptr;         // pinned: the plan of the last frame
+    bool open = false;
+    int width = 0, rows = 0, n_frames = 0, delay_num = 0, delay_den = 0, n_plays = 0;
+    int next_frame = 0;             // frames added so far
+    unsigned seq = 0;               // the next fcTL / fdAT sequence number
 };
 
 // ndt_hip_encode_jpeg* (ndt_jpeg.hip): grow-only device buffers, reused by the next frame
@@ -193,6 +208,7 @@ struct ndt_hip_ctx {
     int fit_launches = 0;           // kernel launches of the last ndt_hip_fit_spheres call
     KdState kd;                     // ndt_hip_build_kdtree
     PngState png;                   // ndt_hip_encode_png*, ndt_hip_render_png
+    ApngState apng;                 // ndt_hip_apng_*, ndt_hip_render_apng_frame
     JpegState jpeg;                 // ndt_hip_encode_jpeg*, ndt_hip_render_jpeg
     DepthState depth;               // ndt_hip_depth_rgba8_device, ndt_hip_render_*_depth
     SsaaState ssaa;                 // ndt_hip_render_ssaa*
@@ -278,6 +294,16 @@ void free_kd(ndt_hip_ctx *ctx);
 
 // ndt_png.hip
 void free_png(ndt_hip_ctx *ctx);
+// The file of width x rows 8-bit RGBA pixels at d_rgba8 (the context's device memory, arguments checked by the caller) made in
+// ctx->png.d_file and left there: the encoder's 4 launches.  *zlib_bytes: the length of its zlib stream, which starts at byte
+// PNG_ZLIB_AT of the file.  Returns when the file is complete.
+constexpr int PNG_ZLIB_AT = 41;
+int png_file_device(ndt_hip_ctx *ctx, const char *who, const void *d_rgba8, int32_t width, int32_t rows, long long *zlib_bytes);
+// CRC-32 (the PNG polynomial)
+unsigned crc32_of(const unsigned char *p, size_t len);
+
+// ndt_apng.hip
+void free_apng(ndt_hip_ctx *ctx);
 
 // ndt_jpeg.hip
 void free_jpeg(ndt_hip_ctx *ctx);
@@ -287,6 +313,9 @@ void free_depth(ndt_hip_ctx *ctx);
 
 // ndt_ssaa.hip
 void free_ssaa(ndt_hip_ctx *ctx);
+// ndt_hip_render_ssaa_rgba8 (its refusals under the name `who`) without the download: *d_rgba8 is the frame's 8-bit image in the
+// context's device memory, written by the last fold, valid until the next supersampled frame
+int render_ssaa_rgba8_own(ndt_hip_ctx *ctx, const char *who, const ndt_render_params *p, int K, ndt_render_stats *stats, const void **d_rgba8);
 
 // ndt_aa.hip / ndt_sampled.hip
 int render_antialiased(ndt_hip_ctx *ctx, const ndt_render_params *p, void *d_rgba, ndt_render_stats &total, void *d_depth = nullptr);

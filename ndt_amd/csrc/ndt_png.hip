@@ -741,24 +741,6 @@ struct CrcTables {
     }
 };
 
-unsigned crc32_of(const unsigned char *p, size_t len)
-{
-    static const CrcTables tab;
-    unsigned c = 0xffffffffu;
-    while (len >= 8) {
-        unsigned lo, hi;
-        memcpy(&lo, p, 4);
-        memcpy(&hi, p + 4, 4);
-        lo ^= c;
-        c = tab.t[7][lo & 255u] ^ tab.t[6][(lo >> 8) & 255u] ^ tab.t[5][(lo >> 16) & 255u] ^ tab.t[4][lo >> 24] ^
-            tab.t[3][hi & 255u] ^ tab.t[2][(hi >> 8) & 255u] ^ tab.t[1][(hi >> 16) & 255u] ^ tab.t[0][hi >> 24];
-        p += 8;
-        len -= 8;
-    }
-    while (len--) c = tab.t[0][(c ^ *p++) & 255u] ^ (c >> 8);
-    return c ^ 0xffffffffu;
-}
-
 // the filtered stream's length for pixels of bpp bytes, or -1 for a size the encoder does not take
 long long stream_bytes(int32_t width, int32_t rows, int bpp = 4)
 {
@@ -777,21 +759,16 @@ constexpr PngFormat PNG_RGBA8 = { 4, 8, 6 }, PNG_RGBA16 = { 8, 16, 6 }, PNG_GREY
 // channels 4 -> RGBA16, 1 -> GREY16, anything else -> nullptr
 const PngFormat *format16(int32_t channels) { return channels == 4 ? &PNG_RGBA16 : channels == 1 ? &PNG_GREY16 : nullptr; }
 
-// The file of width x rows pixels of format `f` at d_image (the context's device memory); `who` names the entry point in errors.
-int encode_device(ndt_hip_ctx *ctx, const char *who, const void *d_image, int32_t width, int32_t rows, const PngFormat &f, uint8_t *png,
-                  int64_t cap, ndt_png_stats *stats)
+// The file of width x rows pixels of format `f` at d_image (the context's device memory; arguments checked by the callers) made in
+// ps.d_file: the 4 launches, then its info record in host memory.  `bound`: the largest file the size can give.
+int make_file(ndt_hip_ctx *ctx, const char *who, const void *d_image, int32_t width, int32_t rows, const PngFormat &f, PngInfo &info,
+              int &n_chunks, long long &bound)
 {
-    if (!ctx || !d_image || !png) return fail(NDT_E_INVALID, "%s: NULL argument", who);
-    if (width < 1 || rows < 1) return fail(NDT_E_INVALID, "%s: a %d x %d image", who, width, rows);
-    const long long n = stream_bytes(width, rows, f.bpp);
-    if (n < 0) return fail(NDT_E_INVALID, "%s: the filtered stream of a %d x %d image exceeds 2^31 - 1 bytes", who, width, rows);
-    if (cap < 0) return fail(NDT_E_INVALID, "%s: cap %lld", who, (long long)cap);
-    if (((uintptr_t)d_image & (uintptr_t)(f.bpp - 1)) != 0) return fail(NDT_E_INVALID, "%s: the image is not aligned to its %d-byte pixels", who, f.bpp);
-    const auto t0 = std::chrono::steady_clock::now();
     HIP_TRY(hipSetDevice(ctx->device));
     PngState &ps = ctx->png;
-    const int n_chunks = (int)((n + PNG_CHUNK - 1) / PNG_CHUNK);
-    const long long bound = file_bound(n);
+    const long long n = stream_bytes(width, rows, f.bpp);
+    n_chunks = (int)((n + PNG_CHUNK - 1) / PNG_CHUNK);
+    bound = file_bound(n);
     int rc;
     if ((rc = ps.d_filtered.reserve((size_t)n_chunks * PNG_CHUNK, ctx->stream, who))) return rc;
     if ((rc = ps.d_row_filter.reserve((size_t)rows, ctx->stream, who))) return rc;
@@ -821,7 +798,29 @@ int encode_device(ndt_hip_ctx *ctx, const char *who, const void *d_image, int32_
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(ps.h_info, ps.d_info.p, sizeof(PngInfo), hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
-    const PngInfo info = *(const PngInfo *)ps.h_info;
+    info = *(const PngInfo *)ps.h_info;
+    return NDT_OK;
+}
+
+// The file of width x rows pixels of format `f` at d_image (the context's device memory) in host memory: made by make_file,
+// fetched, its IDAT chunk's CRC-32 set here; `who` names the entry point in errors.
+int encode_device(ndt_hip_ctx *ctx, const char *who, const void *d_image, int32_t width, int32_t rows, const PngFormat &f, uint8_t *png,
+                  int64_t cap, ndt_png_stats *stats)
+{
+    if (!ctx || !d_image || !png) return fail(NDT_E_INVALID, "%s: NULL argument", who);
+    if (width < 1 || rows < 1) return fail(NDT_E_INVALID, "%s: a %d x %d image", who, width, rows);
+    if (stream_bytes(width, rows, f.bpp) < 0)
+        return fail(NDT_E_INVALID, "%s: the filtered stream of a %d x %d image exceeds 2^31 - 1 bytes", who, width, rows);
+    if (cap < 0) return fail(NDT_E_INVALID, "%s: cap %lld", who, (long long)cap);
+    if (((uintptr_t)d_image & (uintptr_t)(f.bpp - 1)) != 0) return fail(NDT_E_INVALID, "%s: the image is not aligned to its %d-byte pixels", who, f.bpp);
+    const auto t0 = std::chrono::steady_clock::now();
+    PngInfo info;
+    int n_chunks = 0;
+    long long bound = 0;
+    int rc = make_file(ctx, who, d_image, width, rows, f, info, n_chunks, bound);
+    if (rc) return rc;
+    PngState &ps = ctx->png;
+    hipStream_t s = ctx->stream;
     if (stats) {
         *stats = ndt_png_stats{};
         stats->png_bytes = info.png_bytes;
@@ -861,6 +860,39 @@ int upload_image(ndt_hip_ctx *ctx, const char *who, const void *image, int32_t w
 }
 
 } // namespace
+
+unsigned ndt_impl::crc32_of(const unsigned char *p, size_t len)
+{
+    static const CrcTables tab;
+    unsigned c = 0xffffffffu;
+    while (len >= 8) {
+        unsigned lo, hi;
+        memcpy(&lo, p, 4);
+        memcpy(&hi, p + 4, 4);
+        lo ^= c;
+        c = tab.t[7][lo & 255u] ^ tab.t[6][(lo >> 8) & 255u] ^ tab.t[5][(lo >> 16) & 255u] ^ tab.t[4][lo >> 24] ^
+            tab.t[3][hi & 255u] ^ tab.t[2][(hi >> 8) & 255u] ^ tab.t[1][(hi >> 16) & 255u] ^ tab.t[0][hi >> 24];
+        p += 8;
+        len -= 8;
+    }
+    while (len--) c = tab.t[0][(c ^ *p++) & 255u] ^ (c >> 8);
+    return c ^ 0xffffffffu;
+}
+
+int ndt_impl::png_file_device(ndt_hip_ctx *ctx, const char *who, const void *d_rgba8, int32_t width, int32_t rows, long long *zlib_bytes)
+{
+    static_assert(PNG_ZLIB_AT == PNG_FILE_HEAD - 2, "the zlib header follows the IDAT chunk's length and type");
+    PngInfo info;
+    int n_chunks = 0;
+    long long bound = 0;
+    int rc = make_file(ctx, who, d_rgba8, width, rows, PNG_RGBA8, info, n_chunks, bound);
+    if (rc) return rc;
+    if (info.png_bytes < PNG_FILE_EXTRA || info.png_bytes > bound || info.idat_bytes != info.png_bytes - (PNG_FILE_EXTRA - 6))
+        return fail(NDT_E_DEVICE, "%s: the device reports a file of %lld bytes with a stream of %lld (bound %lld)", who, info.png_bytes,
+                    info.idat_bytes, bound);
+    *zlib_bytes = info.idat_bytes;
+    return NDT_OK;
+}
 
 extern "C" int64_t ndt_hip_png_bound(int32_t width, int32_t rows)
 {

@@ -289,6 +289,18 @@ extern "C" int ndt_hip_render_ssaa_rgba8(ndt_hip_ctx *ctx, const ndt_render_para
     return NDT_OK;
 }
 
+int ndt_impl::render_ssaa_rgba8_own(ndt_hip_ctx *ctx, const char *who, const ndt_render_params *p, int K, ndt_render_stats *stats,
+                                    const void **d_rgba8)
+{
+    int rc = refuse(who, ctx, p, K, d_rgba8);
+    if (rc) return rc;
+    int rows = 0;
+    size_t pixels = 0;
+    if ((rc = render_ssaa_own(ctx, p, K, false, true, stats, &rows, &pixels))) return rc;
+    *d_rgba8 = ctx->ssaa.d_rgba8.p;
+    return NDT_OK;
+}
+
 extern "C" int ndt_hip_render_ssaa_png(ndt_hip_ctx *ctx, const ndt_render_params *p, int32_t K, uint8_t *png, int64_t cap, ndt_png_stats *stats,
                                        ndt_render_stats *render_stats)
 {

@@ -31,6 +31,7 @@ API_SYMBOLS = [
     "ndt_hip_render_ssaa_jpeg", "ndt_hip_render_ssaa_rgba8_depth", "ndt_hip_ssaa_launches", "ndt_hip_ssaa_ms",
     "ndt_hip_quantize16_device", "ndt_hip_depth_grey16_device", "ndt_hip_png16_bound", "ndt_hip_encode_png16_device", "ndt_hip_encode_png16",
     "ndt_hip_render_png16", "ndt_hip_render_png16_depth", "ndt_hip_render_ssaa_png16", "ndt_hip_render_ssaa_png16_depth",
+    "ndt_hip_apng_bound", "ndt_hip_apng_begin", "ndt_hip_apng_add_device", "ndt_hip_apng_add", "ndt_hip_render_apng_frame", "ndt_hip_apng_end",
 ]
 
 IMAGE_F64, IMAGE_RGBA8 = 0, 1      # enum ndt_image_format
@@ -148,6 +149,14 @@ def load_library():
         lib.ndt_hip_render_ssaa_png16.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
         lib.ndt_hip_render_ssaa_png16_depth.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
                                                         C.c_void_p, C.c_void_p, C.c_void_p]
+    if hasattr(lib, "ndt_hip_apng_bound"):          # (absent from earlier builds, which profiles/ab_libs.sh loads to compare)
+        lib.ndt_hip_apng_bound.argtypes = [C.c_int32, C.c_int32]
+        lib.ndt_hip_apng_bound.restype = C.c_int64
+        lib.ndt_hip_apng_begin.argtypes = [C.c_void_p] + [C.c_int32] * 6
+        lib.ndt_hip_apng_add_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
+        lib.ndt_hip_apng_add.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
+        lib.ndt_hip_render_apng_frame.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
+        lib.ndt_hip_apng_end.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
     _lib = lib
     return lib
 
@@ -162,6 +171,13 @@ class PngStats(C.Structure):
     """ndt_png_stats: what the device encoder says about the file it made"""
     _fields_ = [("png_bytes", C.c_int64), ("idat_bytes", C.c_int64), ("chunks", C.c_int32), ("chunks_stored", C.c_int32),
                 ("launches", C.c_int32), ("rows_filter", C.c_int32 * 3), ("encode_ms", C.c_double)]
+
+
+class ApngStats(C.Structure):
+    """ndt_apng_stats: what the device says about the frame it appended to the animated PNG"""
+    _fields_ = [("bytes", C.c_int64), ("zlib_bytes", C.c_int64), ("changed", C.c_int64), ("translucent", C.c_int64),
+                ("frame", C.c_int32), ("x", C.c_int32), ("y", C.c_int32), ("w", C.c_int32), ("h", C.c_int32), ("blend", C.c_int32),
+                ("launches", C.c_int32), ("reserved", C.c_int32), ("encode_ms", C.c_double)]
 
 
 class JpegParams(C.Structure):
@@ -201,6 +217,14 @@ def png_bound(width, rows):
     n = int(load_library().ndt_hip_png_bound(int(width), int(rows)))
     if n < 0:
         raise ValueError("no PNG of %d x %d: the size is empty or its filtered stream exceeds 2^31 - 1 bytes" % (width, rows))
+    return n
+
+
+def apng_bound(width, rows):
+    """ndt_hip_apng_bound: the most bytes one frame can append to the animated PNG of a width x rows canvas (host arithmetic)."""
+    n = int(load_library().ndt_hip_apng_bound(int(width), int(rows)))
+    if n < 0:
+        raise ValueError("no animated PNG of %d x %d: the size is empty or its filtered stream exceeds 2^31 - 1 bytes" % (width, rows))
     return n
 
 
@@ -560,6 +584,52 @@ class NdtHip:
         self._check(self.lib.ndt_hip_render_ssaa_png16_depth(self.ctx, C.byref(p), int(ssaa), out.ctypes.data, cap, dpng.ctypes.data,
                                                              depth_cap, C.byref(self.png_stats), rng.ctypes.data, C.byref(st)))
         return out[:self.png_stats[0].png_bytes].tobytes(), dpng[:self.png_stats[1].png_bytes].tobytes(), rng, st
+
+    def apng_begin(self, width, rows, n_frames, delay_num=1, delay_den=24, n_plays=0):
+        """ndt_hip_apng_begin: opens the context's animated-PNG session: n_frames frames of width x rows pixels are to come, each
+        shown delay_num / delay_den seconds, played n_plays times (0: for ever)."""
+        self._check(self.lib.ndt_hip_apng_begin(self.ctx, int(width), int(rows), int(n_frames), int(delay_num), int(delay_den), int(n_plays)))
+        self._apng_size = (int(width), int(rows))
+        self.apng_stats = ApngStats()
+
+    _apng_size = (1, 1)             # before the first apng_begin: room enough for the library to say that no session is open
+
+    def _apng_room(self, cap):
+        cap = apng_bound(*self._apng_size) if cap is None else int(cap)
+        self.apng_stats = ApngStats()
+        return np.zeros(max(cap, 1), dtype=np.uint8), cap
+
+    def apng_add(self, rgba8, cap=None):
+        """ndt_hip_apng_add: the session's next frame from a (rows, width, 4) uint8 host image.  Returns the bytes to append to the
+        file; self.apng_stats keeps the ndt_apng_stats.  cap: room offered (default: ndt_hip_apng_bound)."""
+        rgba8 = np.ascontiguousarray(rgba8, dtype=np.uint8)
+        if rgba8.shape != (self._apng_size[1], self._apng_size[0], 4):
+            raise ValueError("a frame of shape %r for a session of %d x %d pixels" % ((rgba8.shape,) + self._apng_size))
+        out, cap = self._apng_room(cap)
+        self._check(self.lib.ndt_hip_apng_add(self.ctx, rgba8.ctypes.data, out.ctypes.data, cap, C.byref(self.apng_stats)))
+        return out[:self.apng_stats.bytes].tobytes()
+
+    def apng_add_device(self, d_rgba8_ptr, cap=None):
+        """ndt_hip_apng_add_device: the same for the session's width * rows * 4 bytes at raw device pointer `d_rgba8_ptr`."""
+        out, cap = self._apng_room(cap)
+        self._check(self.lib.ndt_hip_apng_add_device(self.ctx, C.c_void_p(d_rgba8_ptr), out.ctypes.data, cap, C.byref(self.apng_stats)))
+        return out[:self.apng_stats.bytes].tobytes()
+
+    def render_apng_frame(self, width, height, depth, ssaa=1, cap=None, **kw):
+        """ndt_hip_render_apng_frame: renders the uploaded scene's shard (ssaa 2 .. 8: supersampled) and adds it to the session
+        from device memory.  Returns (the bytes to append, RenderStats); self.apng_stats keeps the ndt_apng_stats."""
+        p = self.params(width, height, depth, **kw)
+        out, cap = self._apng_room(cap)
+        st = RenderStats()
+        self._check(self.lib.ndt_hip_render_apng_frame(self.ctx, C.byref(p), int(ssaa), out.ctypes.data, cap, C.byref(self.apng_stats),
+                                                       C.byref(st)))
+        return out[:self.apng_stats.bytes].tobytes(), st
+
+    def apng_end(self):
+        """ndt_hip_apng_end: the file's last bytes (IEND) after the session's last frame; closes the session."""
+        out, n = np.zeros(16, dtype=np.uint8), C.c_int64(0)
+        self._check(self.lib.ndt_hip_apng_end(self.ctx, out.ctypes.data, out.size, C.byref(n)))
+        return out[:n.value].tobytes()
 
     def encode_jpeg(self, rgba8, quality=95, sampling="420", cap=None):
         """ndt_hip_encode_jpeg: the complete baseline JFIF file of a (rows, width, 4) uint8 host image (alpha ignored), made on

@@ -420,6 +420,24 @@ int ndt_encode_image_png(const unsigned char *rgba8, int width, int height, unsi
 /* host milliseconds the device encoder took in the calling thread's last ndt_render_image_png / ndt_encode_image_png */
 double ndt_render_png_encode_ms(void);
 
+/* A run's frames as ONE animated PNG, the difference between consecutive frames found on the GPU (ndt_hip_apng_*; `ndt_hip
+ * --apng`): the calling thread's first context keeps the previous frame, and what comes back per frame are the bytes to append to
+ * the file -- the rectangle that changed, compressed.
+ *   ndt_apng_begin                n_frames frames of width x height are to come, each shown 1 / fps seconds (fps 1 .. 1000), looped
+ *                                 for ever.  One context renders them, in order: refused while ndt_render_use_devices spreads a
+ *                                 frame over several
+ *   ndt_render_image_apng_frame   renders the next frame (ssaa = 1: the plain frame, with -a when aa_depth >= 0; 2 .. 8: supersampled)
+ *                                 and adds it: *bytes is malloc'ed -- the caller frees it -- and *n_bytes its length.  Prints
+ *                                 `animated PNG frame K: w x h at x,y (B bytes) on GPU D in L launches`
+ *   ndt_apng_end                  after the last frame: the file's closing bytes into out (room for 16), their count into *n_bytes
+ * No fallback: without a device they fail like every render call. */
+int ndt_apng_begin(int width, int height, int n_frames, int fps);
+int ndt_render_image_apng_frame(scene *scn, int width, int height, int samples, int threads, int aa_diff, int aa_depth, int stereo,
+                                int specular, int max_optic_depth, int ssaa, unsigned char **bytes, long long *n_bytes);
+int ndt_apng_end(unsigned char *out, long long *n_bytes);
+/* host milliseconds the calling thread's last ndt_render_image_apng_frame spent on the frame's plan and file bytes */
+double ndt_render_apng_encode_ms(void);
+
 /* The same frame as a complete baseline JPEG file made on the GPU (ndt_hip_render_jpeg: the 8-bit image never leaves the device;
  * `ndt_hip --jpeg`): what the reference's libjpeg writer saves, at `quality` 1 .. 100 (0 = its 95) and `sampling` 0 = 4:2:0 (its
  * default) or 1 = 4:4:4.  *jpg is malloc'ed -- the caller frees it -- and *jpg_bytes its length.  A frame spread over several

@@ -16,8 +16,12 @@
  * K times the size, folded there into a box-filtered average in linear light before anything is quantised (ndt_hip_render_ssaa*);
  * with every output flag, -m s|o|a, -n, -g and -j, not with -a or -m h.  `--png16` (with `--png --deflate gpu`) has the GPU make
  * the PNG at 16 bits a sample from the double framebuffer (ndt_hip_render_png16), and with `-z --depth gpu --depth-png` the map's
- * file as 16-bit grey; on one GPU context a frame (not with -g N > 1).  None falls back: what the device path cannot do ends the
- * run. */
+ * file as 16-bit grey; on one GPU context a frame (not with -g N > 1).  `--apng` writes all frames of `-f a:b` into ONE animated
+ * PNG, images/<scene>/<N>d/<WxH>/<scene>_<WxH>.apng, instead of a file a frame: the GPU keeps the previous frame, finds the
+ * rectangle that changed and compresses only that (ndt_hip_render_apng_frame); `--apng-fps F` (1 .. 1000, default 24) shows each
+ * frame 1 / F seconds.  With --ssaa, -a, -n, -m and --fit / --kd gpu; it is the run's one colour file (not with --png, --jpeg,
+ * --raw, --png16 or -z), and its frames meet one canvas in order (not with -g N > 1 or -j K > 1).  None falls back: what the
+ * device path cannot do ends the run. */
 #include <dlfcn.h>
 #include <getopt.h>
 #include <pthread.h>
@@ -72,12 +76,71 @@ static struct {
     int jpeg, jpeg_quality, jpeg_sampling;      /* --jpeg: the frame's file is a JPEG made on the GPU; quality 1 .. 100, sampling 0 = 4:2:0 / 1 = 4:4:4 */
     int ssaa;                                   /* --ssaa K: every frame supersampled K x K on the GPU (1: the plain frame) */
     int png16;                                  /* --png16: the PNG files carry 16 bits a sample */
+    int apng, apng_fps, apng_frames;            /* --apng: the run's frames in one animated PNG; its frame rate; frames the run renders */
     const char *raw_path;
 } job_opts;
+
+/* --apng: the run's one file, opened at the first frame, appended to per frame, closed by apng_close */
+static FILE *apng_file = NULL;
+static char apng_path[1024];
+static int apng_begun = 0;
+
+static int render_frame_apng(scene *scn)
+{
+    const int width = job_opts.width, height = job_opts.height;
+    unsigned char *bytes = NULL;
+    long long n_bytes = 0;
+    const double t0 = now_s();
+    if (!apng_begun && !ndt_apng_begin(width, height, job_opts.apng_frames, job_opts.apng_fps)) return 0;
+    apng_begun = 1;
+    /* the 8-bit image stays on the device: what comes back are the bytes to append */
+    if (!ndt_render_image_apng_frame(scn, width, height, job_opts.samples, job_opts.threads, job_opts.aa_diff,
+                                     job_opts.ssaa > 1 ? -1 : job_opts.aa_depth, job_opts.stereo, job_opts.specular, job_opts.depth,
+                                     job_opts.ssaa, &bytes, &n_bytes)) return 0;
+    printf("rendering took %.3fs\n", now_s() - t0);
+    const double t_file = now_s();
+    if (!apng_file) {
+        char dir[512];
+        mkdir("images", 0700);
+        snprintf(dir, sizeof(dir), "images/%s", scn->name); mkdir(dir, 0700);
+        snprintf(dir, sizeof(dir), "images/%s/%id", scn->name, job_opts.dims); mkdir(dir, 0700);
+        snprintf(dir, sizeof(dir), "images/%s/%id/%ix%i", scn->name, job_opts.dims, width, height); mkdir(dir, 0700);
+        snprintf(apng_path, sizeof(apng_path), "%s/%s_%ix%i.apng", dir, scn->name, width, height);
+        apng_file = fopen(apng_path, "wb");
+    }
+    const int ok = apng_file && fwrite(bytes, 1, (size_t)n_bytes, apng_file) == (size_t)n_bytes;
+    free(bytes);
+    if (!ok) {
+        fprintf(stderr, "ndt_hip: cannot write %s\n", apng_path);
+        return 0;
+    }
+    printf("\tappended %lld bytes to %s\n", n_bytes, apng_path);
+    if (getenv("NDT_HOST_TIMING"))
+        fprintf(stderr, "ndt_hip: image file %.2f ms (frame planned and compressed on the GPU %.2f, appended %.2f)\n",
+                (now_s() - t_file) * 1e3 + ndt_render_apng_encode_ms(), ndt_render_apng_encode_ms(), (now_s() - t_file) * 1e3);
+    return 1;
+}
+
+/* IEND behind the last frame */
+static int apng_close(void)
+{
+    unsigned char tail[16];
+    long long n = 0;
+    if (!apng_file) return 1;
+    const int ok = ndt_apng_end(tail, &n) && fwrite(tail, 1, (size_t)n, apng_file) == (size_t)n;
+    if (fclose(apng_file) != 0 || !ok) {
+        fprintf(stderr, "ndt_hip: cannot finish %s\n", apng_path);
+        return 0;
+    }
+    apng_file = NULL;
+    printf("\tsaved %s\n", apng_path);
+    return 1;
+}
 
 static int render_frame(scene *scn, int i)
 {
     const int width = job_opts.width, height = job_opts.height;
+    if (job_opts.apng) return render_frame_apng(scn);
     /* the image in doubles only when something asks for it (--raw, the depth map of -z); otherwise the GPU quantises
      * and 4 bytes per pixel come back instead of 32 */
     /* (--depth gpu: the map is finished on the device as well, and -z asks for no doubles) */
@@ -422,6 +485,8 @@ int main(int argc, char **argv)
     int jpeg_sampling = -1; /* --jpeg-sampling 420|444 (default: 4:2:0, libjpeg's) */
     int ssaa = 1;           /* --ssaa K: every frame supersampled K x K on the GPU, 1 .. 8 (default 1: the plain frame) */
     int png16 = 0;          /* --png16: the PNG files at 16 bits a sample, made on the GPU from the doubles (needs --png --deflate gpu) */
+    int apng = 0;           /* --apng: all frames of the run in one animated PNG, the difference between frames found on the GPU */
+    int apng_fps = 0;       /* --apng-fps 1 .. 1000 (default 24): each frame is shown 1 / F seconds */
     char *objects_dir = "objects";      /* -o: where object plugins are looked for (object.c:119; ndt.c passes "objects") */
     static struct option longopts[] = { { "dump-scene", required_argument, NULL, 1000 },
                                         { "raw", required_argument, NULL, 1001 }, { "png", no_argument, NULL, 1002 },
@@ -430,7 +495,8 @@ int main(int argc, char **argv)
                                         { "depth", required_argument, NULL, 1006 }, { "depth-png", no_argument, NULL, 1007 },
                                         { "jpeg", no_argument, NULL, 1008 }, { "jpeg-quality", required_argument, NULL, 1009 },
                                         { "jpeg-sampling", required_argument, NULL, 1010 }, { "ssaa", required_argument, NULL, 1011 },
-                                        { "png16", no_argument, NULL, 1012 },
+                                        { "png16", no_argument, NULL, 1012 }, { "apng", no_argument, NULL, 1013 },
+                                        { "apng-fps", required_argument, NULL, 1014 },
                                         { NULL, 0, NULL, 0 } };
     int ch;
     while ((ch = getopt_long(argc, argv, "a:d:g:r:f:j:l:m:3:n:ps:t:u:o:zh", longopts, NULL)) != -1) {
@@ -528,14 +594,39 @@ int main(int argc, char **argv)
             break;
         }
         case 1012: png16 = 1; break;
+        case 1013: apng = 1; break;
+        case 1014: {
+            char *end = NULL;
+            const long f = strtol(optarg, &end, 10);
+            if (end == optarg || *end || f < 1 || f > 1000) {
+                fprintf(stderr, "%s: --apng-fps takes 1 .. 1000, not '%s'\n", argv[0], optarg);
+                return 1;
+            }
+            apng_fps = (int)f;
+            break;
+        }
         default:
             fprintf(stderr, "usage: %s -s scene.so|builtin:yaml [-d dims] [-r WxH|1080p|4k] [-f last|first:last[:total]] [-l depth]\n"
-                            "          [-a diff,depth] [-n samples] [-m s|o|a|m] [-p] [-z] [-j frames_in_flight] [-g gpus_per_frame] [-u config] [--dump-scene file.ndtscene] [--raw file.f64] [--png [--deflate stored|gpu]] [--jpeg [--jpeg-quality 1..100] [--jpeg-sampling 420|444]] [--fit host|gpu] [--kd host|gpu] [--depth host|gpu [--depth-png]] [--ssaa 1..8] [--png16]\n", argv[0]);
+                            "          [-a diff,depth] [-n samples] [-m s|o|a|m] [-p] [-z] [-j frames_in_flight] [-g gpus_per_frame] [-u config] [--dump-scene file.ndtscene] [--raw file.f64] [--png [--deflate stored|gpu]] [--jpeg [--jpeg-quality 1..100] [--jpeg-sampling 420|444]] [--fit host|gpu] [--kd host|gpu] [--depth host|gpu [--depth-png]] [--ssaa 1..8] [--png16] [--apng [--apng-fps 1..1000]]\n", argv[0]);
             return ch == 'h' ? 0 : 1;
         }
     }
     if (!scene_path || dims < 3 || width < 1 || height < 1) {
         fprintf(stderr, "%s: need -s scene.so, dims >= 3 and a resolution\n", argv[0]);
+        return 1;
+    }
+    if (apng_fps && !apng) {
+        fprintf(stderr, "%s: --apng-fps sets the animated PNG's frame rate: it needs --apng\n", argv[0]);
+        return 1;
+    }
+    if (apng && (png16 || png || jpeg || raw_path || want_depth)) {
+        fprintf(stderr, "%s: --apng with %s: the animated PNG is the run's one colour file; this one is not written beside it: take one\n", argv[0],
+                png16 ? "--png16" : png ? "--png" : jpeg ? "--jpeg" : raw_path ? "--raw" : "-z");
+        return 1;
+    }
+    if (apng && (gpus > 1 || jobs > 1)) {
+        fprintf(stderr, "%s: --apng with %s %d: the frames of an animated PNG meet one canvas on one GPU context, in order: take %s 1\n", argv[0],
+                gpus > 1 ? "-g" : "-j", gpus > 1 ? gpus : jobs, gpus > 1 ? "-g" : "-j");
         return 1;
     }
     if (ssaa > 1 && aa_depth >= 0) {
@@ -630,6 +721,11 @@ int main(int argc, char **argv)
     job_opts.depth_png = depth_png;
     job_opts.ssaa = ssaa;
     job_opts.png16 = png16;
+    job_opts.apng = apng; job_opts.apng_fps = apng_fps ? apng_fps : 24;
+    {
+        const int upto = last < frames - 1 ? last : frames - 1, from = first > 0 ? first : 0;
+        job_opts.apng_frames = upto >= from ? upto - from + 1 : 0;
+    }
     job_opts.jpeg = jpeg; job_opts.jpeg_quality = jpeg_quality; job_opts.jpeg_sampling = jpeg_sampling < 0 ? 0 : jpeg_sampling;
     ndt_render_fit_on_gpu(fit_gpu);
     ndt_render_kd_on_gpu(kd_gpu);
@@ -687,6 +783,7 @@ int main(int argc, char **argv)
         free(workers);
         if (worker_failed) return 1;
     }
+    if (job_opts.apng && !apng_close()) return 1;
     if (rendered > 1) printf("%d frames in %.3fs (%.2f frames/s)\n", rendered, now_s() - t_all, rendered / (now_s() - t_all));
     if (cleanup) cleanup();
     return 0;

@@ -442,6 +442,70 @@ static int render_png16(const ndt_render_params *p, int K, int format, void *out
     return 1;
 }
 
+/* ---- the run's frames as one animated PNG (ndt_hip_apng_*, ndt_hip_render_apng_frame; `ndt_hip --apng`) */
+#define NDT_HOST_IMAGE_APNG 105             /* render_any's `format`; `out` is a png_out: the bytes to append */
+static __thread double g_apng_ms = 0.0;
+
+double ndt_render_apng_encode_ms(void) { return g_apng_ms; }
+
+int ndt_apng_begin(int width, int height, int n_frames, int fps)
+{
+    if (fps < 1 || fps > 1000) {
+        fprintf(stderr, "ndt_apng_begin: %d frames a second is outside 1 .. 1000\n", fps);
+        return 0;
+    }
+    if (g_want_ctx > 1) {
+        fprintf(stderr, "ndt_apng_begin: the frames of an animated PNG meet one canvas on one GPU context, not on %d\n", g_want_ctx);
+        return 0;
+    }
+    if (!have_contexts() || ndt_hip_apng_begin(g_ctx[0], width, height, n_frames, 1, fps, 0) != NDT_OK) {
+        fprintf(stderr, "ndt_apng_begin: %s\n", ndt_hip_last_error());
+        return 0;
+    }
+    return 1;
+}
+
+int ndt_apng_end(unsigned char *out, long long *n_bytes)
+{
+    int64_t n = 0;
+    *n_bytes = 0;
+    if (!have_contexts() || ndt_hip_apng_end(g_ctx[0], out, 16, &n) != NDT_OK) {
+        fprintf(stderr, "ndt_apng_end: %s\n", ndt_hip_last_error());
+        return 0;
+    }
+    *n_bytes = n;
+    return 1;
+}
+
+static int render_apng(const ndt_render_params *p, int K, png_out *po)
+{
+    const int64_t cap = ndt_hip_apng_bound(p->width, p->height);
+    ndt_apng_stats as;
+    if (g_n_ctx > 1) {
+        fprintf(stderr, "ndt_render_image_apng_frame: the frames of an animated PNG meet one canvas on one GPU context, not on %d\n", g_n_ctx);
+        return 0;
+    }
+    unsigned char *buf = cap > 0 ? (unsigned char *)malloc((size_t)cap) : NULL;
+    if (!buf) {
+        fprintf(stderr, "ndt_render_image_apng_frame: no animated PNG of %d x %d\n", p->width, p->height);
+        return 0;
+    }
+    if (ndt_hip_render_apng_frame(g_ctx[0], p, K, buf, cap, &as, NULL) != NDT_OK) {
+        free(buf);
+        return 0;
+    }
+    if (K != 1) {
+        g_ssaa_ms = ndt_hip_ssaa_ms(g_ctx[0]);
+        printf("supersampled %dx%d on GPU %d in %d launches\n", K, K, ndt_hip_device(g_ctx[0]), ndt_hip_ssaa_launches(g_ctx[0]));
+    }
+    g_apng_ms = as.encode_ms;
+    printf("animated PNG frame %d: %d x %d at %d,%d (%lld bytes) on GPU %d in %d launches\n", as.frame, as.w, as.h, as.x, as.y,
+           (long long)as.bytes, ndt_hip_device(g_ctx[0]), as.launches);
+    *po->png = buf;
+    *po->bytes = as.bytes;
+    return 1;
+}
+
 static int render_any(scene *scn, int width, int height, int samples, int aa_diff, int aa_depth, int stereo, int specular,
                       int max_optic_depth, int format, void *out, double *depth, int threads, int ssaa)
 {
@@ -475,7 +539,9 @@ static int render_any(scene *scn, int width, int height, int samples, int aa_dif
             p.aa_diff = aa_diff;
             p.aa_depth = aa_depth;
         }
-        if (format == NDT_HOST_IMAGE_PNG16 || format == NDT_HOST_IMAGE_PNG16_DEPTH) {
+        if (format == NDT_HOST_IMAGE_APNG) {
+            ok = render_apng(&p, ssaa, (png_out *)out);
+        } else if (format == NDT_HOST_IMAGE_PNG16 || format == NDT_HOST_IMAGE_PNG16_DEPTH) {
             ok = render_png16(&p, ssaa, format, out);
         } else if (ssaa != 1) {        /* (0, 9, ... reach the library, which says what is wrong with them) */
             ok = render_ssaa_any(&p, ssaa, format, out, depth);
@@ -558,6 +624,9 @@ static int render_any(scene *scn, int width, int height, int samples, int aa_dif
             fprintf(stderr, "ndt_render_image: bounds + kd-tree + flatten %.2f ms (%s), upload %.2f ms, render + 8-bit image and depth map to host %.2f ms (depth map finished on the GPU %.2f%s)\n",
                     NDT_MS(ts0, ts1), share, NDT_MS(ts1, ts2), NDT_MS(ts2, ts3), g_depth_ms,
                     ((depth_out *)out)->want_png ? ", image files made there" : "");
+        else if (format == NDT_HOST_IMAGE_APNG && ok)
+            fprintf(stderr, "ndt_render_image: bounds + kd-tree + flatten %.2f ms (%s), upload %.2f ms, render + the frame's bytes of the animated PNG to host %.2f ms (plan and file bytes on the GPU %.2f)\n",
+                    NDT_MS(ts0, ts1), share, NDT_MS(ts1, ts2), NDT_MS(ts2, ts3), g_apng_ms);
         else if ((format == NDT_HOST_IMAGE_PNG || format == NDT_HOST_IMAGE_JPEG || format == NDT_HOST_IMAGE_PNG16 ||
                   format == NDT_HOST_IMAGE_PNG16_DEPTH) && ok)
             fprintf(stderr, "ndt_render_image: bounds + kd-tree + flatten %.2f ms (%s), upload %.2f ms, render + image file to host %.2f ms (image file on the GPU %.2f)\n",
@@ -682,4 +751,14 @@ int ndt_render_image_png16_depth(scene *scn, int width, int height, int samples,
         return 0;
     }
     return 1;
+}
+
+/* ---- the next frame of the animated PNG ndt_apng_begin opened (`ndt_hip --apng`); ssaa = 1: the plain frame, with -a when aa_depth >= 0 */
+int ndt_render_image_apng_frame(scene *scn, int width, int height, int samples, int threads, int aa_diff, int aa_depth, int stereo,
+                                int specular, int max_optic_depth, int ssaa, unsigned char **bytes, long long *n_bytes)
+{
+    png_out po = { bytes, n_bytes };
+    *bytes = NULL;
+    *n_bytes = 0;
+    return render_any(scn, width, height, samples, aa_diff, aa_depth, stereo, specular, max_optic_depth, NDT_HOST_IMAGE_APNG, &po, NULL, threads, ssaa);
 }
