@@ -390,116 +390,93 @@ int scene_yaml_count_frames(char *fname);
 
 /* ------------------------------------------------------------------ the accelerated entry */
 
-/* render_image (reference ndt.c:900), mono / samples=1 form: flattens `scn` (objects, the
- * bounding spheres and kd-tree this library builds exactly like ndt.c:1899-1908 does, the aimed
- * camera), uploads it and renders on the GPU through include/ndt_hip.h.  `rgba` receives
- * width*height*4 doubles laid out like the reference's dbl image (image.c:126).
- * Returns 1 like the reference on success, 0 with a message on stderr otherwise. */
+/* One frame: what is asked for (ndt_frame_request), what arrives (ndt_frame), one call (ndt_render_frame).  The call flattens
+ * `scn` (objects, the bounding spheres and kd-tree this library builds exactly like ndt.c:1899-1908 does, the aimed camera),
+ * uploads it and renders on the GPU through include/ndt_hip.h: everything render_image takes (ndt.c:900) is in the request.
+ * `colour` says how the colour image comes back: */
+typedef enum ndt_colour_kind {
+    NDT_COLOUR_F64,         /* rgba: width*height*4 doubles laid out like the reference's dbl image (image.c:126) */
+    NDT_COLOUR_RGBA8,       /* rgba8: width*height*4 bytes, the bytes the reference stores (pixel_d2c on every channel, image.h:36-39;
+                             * quantised on the GPU).  What the driver writes PPM / stored PNG files from */
+    NDT_COLOUR_PNG,         /* file: a complete PNG file compressed on the GPU (`ndt_hip --png --deflate gpu`) */
+    NDT_COLOUR_JPEG,        /* file: the baseline JPEG file the reference's libjpeg writer saves, made on the GPU (`--jpeg`) */
+    NDT_COLOUR_PNG16,       /* file: a PNG file of 16 bits a sample, made on the GPU from the double framebuffer (`--png16`) */
+    NDT_COLOUR_APNG         /* file: the next frame's bytes of the animated PNG ndt_apng_begin opened: the rectangle that
+                             * changed since the previous frame, compressed (`--apng`) */
+} ndt_colour_kind;
+/* ... and `map` how the depth map of `-z` does: */
+typedef enum ndt_map_kind {
+    NDT_MAP_NONE,
+    NDT_MAP_F64,            /* depth: width*height doubles, as render_image leaves them (the caller normalises) */
+    NDT_MAP_DEPTH8,         /* depth8: stretched to 0 .. 1 and quantised on the GPU, width*height*4 bytes g, g, g, 255 (`--depth gpu`) */
+    NDT_MAP_PNG,            /* depth_file: that image as a PNG file compressed on the GPU (`--depth-png`) */
+    NDT_MAP_PNG16           /* depth_file: the map as a 16-bit grey PNG file (`--png16 --depth-png`) */
+} ndt_map_kind;
+/* The pairs a device call serves: doubles with no map or the map in doubles; 8-bit RGBA with none or 8-bit grey; a PNG file with
+ * none, 8-bit grey or a PNG file; a JPEG file and an animated PNG frame with none; a 16-bit PNG file with none or a 16-bit PNG
+ * file.  Any other pair is refused with a message that names both fields. */
+typedef struct ndt_frame_request {
+    int width, height;
+    int samples;                    /* -n */
+    int threads;                    /* host threads that fit the scene's bounding spheres */
+    int aa_diff, aa_depth;          /* Whitted's recursive anti-aliasing, the reference's `-a diff,depth` (ndt.c:1453-1465); aa_depth < 0 = off */
+    int stereo;                     /* the reference's stereo_mode, MONO .. ANAGLYPH_3D (-m) */
+    int specular;                   /* specular_enabled (`-p` clears it) */
+    int max_optic_depth;
+    int ssaa;                       /* 1: the plain frame; 2 .. 8: supersampled ssaa x ssaa on the GPU (`--ssaa K`), the frame of ssaa times
+                                     * the size averaged over ssaa x ssaa blocks in doubles, in linear light, before anything is quantised;
+                                     * not beside aa_depth >= 0 (the library refuses the pair) */
+    ndt_colour_kind colour;
+    ndt_map_kind map;
+    int jpeg_quality, jpeg_sampling;    /* NDT_COLOUR_JPEG: 1 .. 100 (0 = the reference's 95); 0 = 4:2:0 (libjpeg's default), 1 = 4:4:4 */
+} ndt_frame_request;
+/* Everything that arrives is malloc'ed by the library and freed by ndt_frame_free; what was not asked for stays NULL. */
+typedef struct ndt_frame {
+    double *rgba, *depth;
+    unsigned char *rgba8, *depth8;
+    unsigned char *file, *depth_file;
+    long long file_bytes, depth_file_bytes;
+    double range[2];                /* the map's minimum and maximum (a map finished on the GPU) */
+    /* host milliseconds of the frame's device work beside the render: making the file or files, finishing the map, the folds of --ssaa */
+    double file_ms, depth_ms, ssaa_ms;
+} ndt_frame;
+/* Returns 1 like the reference's render_image on success; 0 with a message on stderr otherwise, and then `out` is zeroed: nothing
+ * is left to free.  No fallback: without a device, or with a frame the device path refuses (HIDEF frame packing supersampled, ...),
+ * it fails.  A frame is spread over the calling thread's contexts (ndt_render_use_devices): the rows meet on the host as doubles or
+ * as 8-bit pixels, and a PNG or JPEG file is then encoded from those on the first context; a frame with a map is rendered by one
+ * context whatever was set, and a 16-bit PNG or an animated PNG frame over several contexts is refused.  What the device did is
+ * said on stdout: `compressed PNG of B bytes on GPU D in L launches` (`16-bit PNG`, `depth PNG`, `16-bit depth PNG`), `encoded
+ * JPEG of ...`, `finished depth map [lo, hi] on GPU D in L launches`, `supersampled KxK on GPU D in L launches`, `animated PNG frame
+ * K: w x h at x,y (B bytes) on GPU D in L launches`. */
+int ndt_render_frame(scene *scn, const ndt_frame_request *request, ndt_frame *out);
+/* safe on a zeroed or a half-filled frame; leaves it zeroed */
+void ndt_frame_free(ndt_frame *f);
+
+/* The call shape of the reference's render_image (ndt.c:900), mono / samples=1 form, over ndt_render_frame: `rgba` receives
+ * width*height*4 doubles laid out like the reference's dbl image (image.c:126).  Returns 1 like the reference on success, 0 with a
+ * message on stderr otherwise. */
 int ndt_render_image(scene *scn, int width, int height, int threads, int max_optic_depth, double *rgba);
 /* the same with Whitted's recursive anti-aliasing, the reference's `-a diff,depth` (ndt.c:1453-1465); aa_depth < 0 = off */
 int ndt_render_image_aa(scene *scn, int width, int height, int threads, int aa_diff, int aa_depth, int max_optic_depth,
                         double *rgba);
-/* ... and with everything render_image takes (ndt.c:900): samples (-n), stereo mode (-m), specular_enabled (-p clears it),
- * depth map (-z) */
-int ndt_render_image_full(scene *scn, int width, int height, int samples, int threads, int aa_diff, int aa_depth, int stereo,
-                          int specular, int max_optic_depth, double *rgba, double *depth);
 
-/* The same frame as the bytes the reference stores (pixel_d2c on every channel, image.h:36-39; quantised on the GPU):
- * `rgba8` receives width*height*4 bytes.  What the driver writes PPM / PNG files from. */
-int ndt_render_image_rgba8(scene *scn, int width, int height, int samples, int threads, int aa_diff, int aa_depth, int stereo,
-                           int specular, int max_optic_depth, unsigned char *rgba8);
-
-/* The same frame as a complete PNG file, compressed on the GPU (ndt_hip_render_png: the 8-bit image never leaves the device;
- * `ndt_hip --png --deflate gpu`).  *png is malloc'ed -- the caller frees it -- and *png_bytes its length.  A frame spread over
- * several contexts (ndt_render_use_devices) is gathered on the host and encoded from there on the first context.  Prints
- * `compressed PNG of B bytes on GPU D in L launches`.  No fallback: without a device it fails like every render call. */
-int ndt_render_image_png(scene *scn, int width, int height, int samples, int threads, int aa_diff, int aa_depth, int stereo,
-                         int specular, int max_optic_depth, unsigned char **png, long long *png_bytes);
-/* ... of an 8-bit image that is in host memory already (ndt_hip_encode_png on the calling thread's first context) */
-int ndt_encode_image_png(const unsigned char *rgba8, int width, int height, unsigned char **png, long long *png_bytes);
-/* host milliseconds the device encoder took in the calling thread's last ndt_render_image_png / ndt_encode_image_png */
-double ndt_render_png_encode_ms(void);
+/* An 8-bit image that is in host memory already as a PNG or a JPEG file made on the GPU (ndt_hip_encode_png / ndt_hip_encode_jpeg on
+ * the calling thread's first context): *png / *jpg is malloc'ed -- the caller frees it --, *png_bytes / *jpg_bytes its length, and
+ * *encode_ms (may be NULL) the host milliseconds the device encoder took.  They print the same line as ndt_render_frame. */
+int ndt_encode_image_png(const unsigned char *rgba8, int width, int height, unsigned char **png, long long *png_bytes, double *encode_ms);
+int ndt_encode_image_jpeg(const unsigned char *rgba8, int width, int height, int quality, int sampling, unsigned char **jpg, long long *jpg_bytes,
+                          double *encode_ms);
 
 /* A run's frames as ONE animated PNG, the difference between consecutive frames found on the GPU (ndt_hip_apng_*; `ndt_hip
  * --apng`): the calling thread's first context keeps the previous frame, and what comes back per frame are the bytes to append to
- * the file -- the rectangle that changed, compressed.
- *   ndt_apng_begin                n_frames frames of width x height are to come, each shown 1 / fps seconds (fps 1 .. 1000), looped
- *                                 for ever.  One context renders them, in order: refused while ndt_render_use_devices spreads a
- *                                 frame over several
- *   ndt_render_image_apng_frame   renders the next frame (ssaa = 1: the plain frame, with -a when aa_depth >= 0; 2 .. 8: supersampled)
- *                                 and adds it: *bytes is malloc'ed -- the caller frees it -- and *n_bytes its length.  Prints
- *                                 `animated PNG frame K: w x h at x,y (B bytes) on GPU D in L launches`
- *   ndt_apng_end                  after the last frame: the file's closing bytes into out (room for 16), their count into *n_bytes
+ * the file.
+ *   ndt_apng_begin   n_frames frames of width x height are to come, each shown 1 / fps seconds (fps 1 .. 1000), looped for ever.
+ *                    One context renders them, in order: refused while ndt_render_use_devices spreads a frame over several
+ *   (per frame)      ndt_render_frame with colour NDT_COLOUR_APNG
+ *   ndt_apng_end     after the last frame: the file's closing bytes into out (room for 16), their count into *n_bytes
  * No fallback: without a device they fail like every render call. */
 int ndt_apng_begin(int width, int height, int n_frames, int fps);
-int ndt_render_image_apng_frame(scene *scn, int width, int height, int samples, int threads, int aa_diff, int aa_depth, int stereo,
-                                int specular, int max_optic_depth, int ssaa, unsigned char **bytes, long long *n_bytes);
 int ndt_apng_end(unsigned char *out, long long *n_bytes);
-/* host milliseconds the calling thread's last ndt_render_image_apng_frame spent on the frame's plan and file bytes */
-double ndt_render_apng_encode_ms(void);
-
-/* The same frame as a complete baseline JPEG file made on the GPU (ndt_hip_render_jpeg: the 8-bit image never leaves the device;
- * `ndt_hip --jpeg`): what the reference's libjpeg writer saves, at `quality` 1 .. 100 (0 = its 95) and `sampling` 0 = 4:2:0 (its
- * default) or 1 = 4:4:4.  *jpg is malloc'ed -- the caller frees it -- and *jpg_bytes its length.  A frame spread over several
- * contexts (ndt_render_use_devices) is gathered on the host and encoded from there on the first context.  Prints
- * `encoded JPEG of B bytes on GPU D in L launches`.  No fallback: without a device it fails like every render call. */
-int ndt_render_image_jpeg(scene *scn, int width, int height, int samples, int threads, int aa_diff, int aa_depth, int stereo,
-                          int specular, int max_optic_depth, int quality, int sampling, unsigned char **jpg, long long *jpg_bytes);
-/* ... of an 8-bit image that is in host memory already (ndt_hip_encode_jpeg on the calling thread's first context) */
-int ndt_encode_image_jpeg(const unsigned char *rgba8, int width, int height, int quality, int sampling, unsigned char **jpg, long long *jpg_bytes);
-/* host milliseconds the device encoder took in the calling thread's last ndt_render_image_jpeg / ndt_encode_image_jpeg */
-double ndt_render_jpeg_encode_ms(void);
-
-/* The same frame with the depth map of `-z` beside it, both finished on the GPU (`ndt_hip -z --depth gpu`): the map is
- * stretched to 0 .. 1 and quantised there (ndt_hip_render_rgba8_depth / ndt_hip_render_png_depth) instead of coming back in
- * doubles with the image.  What arrives is what the driver writes its two files from:
- *   want_png = 0                   rgba8 and depth8: width*height*4 bytes each (the map as g, g, g, 255)
- *   want_png = 1, want_depth_png = 0   the image as a complete PNG file compressed on the GPU, the map as depth8
- *   want_png = 1, want_depth_png = 1   both as PNG files
- * The buffers that arrive are malloc'ed -- ndt_depth_frame_free frees them --, the others stay NULL.  range: the map's
- * minimum and maximum.  Prints `finished depth map [lo, hi] on GPU D in L launches`.  One context renders the frame, whatever
- * ndt_render_use_devices says (a map is not split over devices).  No fallback: without a device it fails like every render call. */
-typedef struct ndt_depth_frame {
-    unsigned char *rgba8, *depth8;
-    unsigned char *png, *depth_png;
-    long long png_bytes, depth_png_bytes;
-    double range[2];
-} ndt_depth_frame;
-int ndt_render_image_depth8(scene *scn, int width, int height, int samples, int threads, int aa_diff, int aa_depth, int stereo,
-                            int specular, int max_optic_depth, int want_png, int want_depth_png, ndt_depth_frame *out);
-void ndt_depth_frame_free(ndt_depth_frame *f);
-/* host milliseconds the GPU took to finish the map in the calling thread's last ndt_render_image_depth8 */
-double ndt_render_depth_finish_ms(void);
-
-/* The same frames supersampled ssaa x ssaa on the GPU (`ndt_hip --ssaa K`, K = 1 .. 8; ndt_hip_render_ssaa*): the frame of ssaa
- * times the size, averaged over ssaa x ssaa blocks in doubles, in linear light, before anything is quantised; the map of
- * _full and _depth8 is the plain frame's.  One variant per call above, without the -a arguments (supersampling is not combined
- * with recursive anti-aliasing) and with `ssaa` before the outputs; ssaa = 1 is the plain call.  With ndt_render_use_devices
- * every context renders and folds its own cyclic row shard, one context after the other; the rows meet on the host.  _depth8
- * with files: the two 8-bit images come back and are encoded from host memory.  Each prints `supersampled KxK on GPU D in L
- * launches`.  No fallback: the library's refusals (HIDEF frame packing, an odd width side by side, ...) end the call. */
-int ndt_render_image_ssaa_full(scene *scn, int width, int height, int samples, int threads, int stereo, int specular, int max_optic_depth,
-                               int ssaa, double *rgba, double *depth);
-int ndt_render_image_ssaa_rgba8(scene *scn, int width, int height, int samples, int threads, int stereo, int specular, int max_optic_depth,
-                                int ssaa, unsigned char *rgba8);
-int ndt_render_image_ssaa_png(scene *scn, int width, int height, int samples, int threads, int stereo, int specular, int max_optic_depth,
-                              int ssaa, unsigned char **png, long long *png_bytes);
-int ndt_render_image_ssaa_jpeg(scene *scn, int width, int height, int samples, int threads, int stereo, int specular, int max_optic_depth,
-                               int ssaa, int quality, int sampling, unsigned char **jpg, long long *jpg_bytes);
-int ndt_render_image_ssaa_depth8(scene *scn, int width, int height, int samples, int threads, int stereo, int specular, int max_optic_depth,
-                                 int ssaa, int want_png, int want_depth_png, ndt_depth_frame *out);
-/* The same frames as files of 16 bits a sample, made on the GPU from the double framebuffer (`ndt_hip --png --deflate gpu --png16`;
- * ndt_hip_render_png16*, ndt_hip_render_ssaa_png16*): the image as a 16-bit RGBA PNG and, for _depth, the map beside it as a
- * 16-bit grey PNG -- out->png and out->depth_png arrive, with out->range; ndt_depth_frame_free frees them.  ssaa = 1 is the plain
- * frame (with -a when aa_depth >= 0), ssaa = 2 .. 8 the supersampled one (aa_depth < 0 then).  One context makes the files: after
- * ndt_render_use_devices(n > 1) the calls fail and say so.  Each prints `compressed 16-bit PNG of B bytes on GPU D in L launches`
- * (_depth: and `compressed 16-bit depth PNG of ...`, `finished depth map ...`).  No fallback. */
-int ndt_render_image_png16(scene *scn, int width, int height, int samples, int threads, int aa_diff, int aa_depth, int stereo,
-                           int specular, int max_optic_depth, int ssaa, unsigned char **png, long long *png_bytes);
-int ndt_render_image_png16_depth(scene *scn, int width, int height, int samples, int threads, int aa_diff, int aa_depth, int stereo,
-                                 int specular, int max_optic_depth, int ssaa, ndt_depth_frame *out);
-/* summed device milliseconds of the fold launches of the calling thread's last supersampled frame */
-double ndt_render_ssaa_fold_ms(void);
 
 /* Which GPUs the calling thread's frames are rendered on (the settings are per thread, like the GPU contexts):
  *   ndt_render_use_device(d)     one context on device d -- `ndt_hip -j K` gives worker w device w mod device count,

@@ -1,7 +1,7 @@
 /* ndt_main.c -- minimal frame-loop driver around the GPU path, accepting the flags the
  * BASELINE configs use (reference ndt.c:1450: -d -r -f -l -s -t -u -o).  It loads a scene
  * program exactly like the reference does (dlopen + dlsym scene_setup / scene_frames /
- * scene_cleanup, ndt.c:1654-1664), renders each frame with ndt_render_image and writes
+ * scene_cleanup, ndt.c:1654-1664), renders each frame with ndt_render_frame and writes
  * images/<scene>/<N>d/<WxH>/<scene>_<WxH>_<frame>.ppm (binary PPM of the pixel_d2c bytes), or with `--png` the 8-bit RGBA
  * PNG the reference writes by default (stored blocks from the host, or compressed by the GPU), or with `--jpeg` the baseline JPEG
  * its libjpeg build writes (made by the GPU: ndt_hip_render_jpeg; quality 95 and 4:2:0 like the reference's, or
@@ -56,6 +56,16 @@ static int write_ppm(const char *path, const unsigned char *rgba8, int w, int h)
     return 0;
 }
 
+/* a finished buffer as the file `path` (mode "wb"), or behind what the file holds ("ab"); a file that cannot be written ends the run */
+static int write_bytes(const char *path, const char *mode, const void *bytes, size_t n)
+{
+    FILE *f = fopen(path, mode);
+    int ok = f && fwrite(bytes, 1, n, f) == n;
+    if (f && fclose(f) != 0) ok = 0;
+    if (!ok) fprintf(stderr, "ndt_hip: cannot write %s\n", path);
+    return ok;
+}
+
 /* pixel_d2c on the host: only for images that are in doubles here anyway (--raw, the normalised depth map) */
 static unsigned char *quantise(const double *rgba, long n_values)
 {
@@ -71,54 +81,55 @@ static unsigned char *quantise(const double *rgba, long n_values)
 
 
 /* ---- one frame: flatten, upload, render, save (what follows scene_setup in the reference's frame loop) */
+/* what every frame asks of ndt_render_frame: main turns the flags into it, once */
+static ndt_frame_request frame_request;
+/* ... and what the run needs beside it */
 static struct {
-    int dims, width, height, depth, threads, aa_diff, aa_depth, stereo, specular, want_depth, samples, png, gpus, deflate_gpu, depth_gpu, depth_png;
-    int jpeg, jpeg_quality, jpeg_sampling;      /* --jpeg: the frame's file is a JPEG made on the GPU; quality 1 .. 100, sampling 0 = 4:2:0 / 1 = 4:4:4 */
-    int ssaa;                                   /* --ssaa K: every frame supersampled K x K on the GPU (1: the plain frame) */
-    int png16;                                  /* --png16: the PNG files carry 16 bits a sample */
-    int apng, apng_fps, apng_frames;            /* --apng: the run's frames in one animated PNG; its frame rate; frames the run renders */
+    int dims, gpus;
+    int png;                        /* --png: 8-bit pixels that come back are written as a stored PNG, not a PPM */
+    ndt_colour_kind host_file;      /* NDT_COLOUR_PNG / _JPEG: the frame comes back in doubles (--raw, a host-finished -z) and the file of
+                                     * --png --deflate gpu / --jpeg is encoded on the GPU from the host's bytes; otherwise NDT_COLOUR_F64 */
+    int apng_fps, apng_frames;      /* --apng: the animated PNG's frame rate; frames the run renders */
     const char *raw_path;
 } job_opts;
 
-/* --apng: the run's one file, opened at the first frame, appended to per frame, closed by apng_close */
-static FILE *apng_file = NULL;
+/* images/<scene>/<N>d/<WxH>, made if need be */
+static void image_dir(char *dir, size_t len, const scene *scn)
+{
+    mkdir("images", 0700);
+    snprintf(dir, len, "images/%s", scn->name); mkdir(dir, 0700);
+    snprintf(dir, len, "images/%s/%id", scn->name, job_opts.dims); mkdir(dir, 0700);
+    snprintf(dir, len, "images/%s/%id/%ix%i", scn->name, job_opts.dims, frame_request.width, frame_request.height); mkdir(dir, 0700);
+}
+
+/* --apng: the run's one file, begun at the first frame, appended to per frame, closed by apng_close */
 static char apng_path[1024];
 static int apng_begun = 0;
 
 static int render_frame_apng(scene *scn)
 {
-    const int width = job_opts.width, height = job_opts.height;
-    unsigned char *bytes = NULL;
-    long long n_bytes = 0;
+    const int width = frame_request.width, height = frame_request.height;
+    ndt_frame f;
     const double t0 = now_s();
     if (!apng_begun && !ndt_apng_begin(width, height, job_opts.apng_frames, job_opts.apng_fps)) return 0;
     apng_begun = 1;
     /* the 8-bit image stays on the device: what comes back are the bytes to append */
-    if (!ndt_render_image_apng_frame(scn, width, height, job_opts.samples, job_opts.threads, job_opts.aa_diff,
-                                     job_opts.ssaa > 1 ? -1 : job_opts.aa_depth, job_opts.stereo, job_opts.specular, job_opts.depth,
-                                     job_opts.ssaa, &bytes, &n_bytes)) return 0;
+    if (!ndt_render_frame(scn, &frame_request, &f)) return 0;
     printf("rendering took %.3fs\n", now_s() - t0);
     const double t_file = now_s();
-    if (!apng_file) {
+    const int first = !apng_path[0];
+    if (first) {
         char dir[512];
-        mkdir("images", 0700);
-        snprintf(dir, sizeof(dir), "images/%s", scn->name); mkdir(dir, 0700);
-        snprintf(dir, sizeof(dir), "images/%s/%id", scn->name, job_opts.dims); mkdir(dir, 0700);
-        snprintf(dir, sizeof(dir), "images/%s/%id/%ix%i", scn->name, job_opts.dims, width, height); mkdir(dir, 0700);
+        image_dir(dir, sizeof(dir), scn);
         snprintf(apng_path, sizeof(apng_path), "%s/%s_%ix%i.apng", dir, scn->name, width, height);
-        apng_file = fopen(apng_path, "wb");
     }
-    const int ok = apng_file && fwrite(bytes, 1, (size_t)n_bytes, apng_file) == (size_t)n_bytes;
-    free(bytes);
-    if (!ok) {
-        fprintf(stderr, "ndt_hip: cannot write %s\n", apng_path);
-        return 0;
-    }
-    printf("\tappended %lld bytes to %s\n", n_bytes, apng_path);
-    if (getenv("NDT_HOST_TIMING"))
+    const int ok = write_bytes(apng_path, first ? "wb" : "ab", f.file, (size_t)f.file_bytes);
+    if (ok) printf("\tappended %lld bytes to %s\n", f.file_bytes, apng_path);
+    if (ok && getenv("NDT_HOST_TIMING"))
         fprintf(stderr, "ndt_hip: image file %.2f ms (frame planned and compressed on the GPU %.2f, appended %.2f)\n",
-                (now_s() - t_file) * 1e3 + ndt_render_apng_encode_ms(), ndt_render_apng_encode_ms(), (now_s() - t_file) * 1e3);
-    return 1;
+                (now_s() - t_file) * 1e3 + f.file_ms, f.file_ms, (now_s() - t_file) * 1e3);
+    ndt_frame_free(&f);
+    return ok;
 }
 
 /* IEND behind the last frame */
@@ -126,191 +137,106 @@ static int apng_close(void)
 {
     unsigned char tail[16];
     long long n = 0;
-    if (!apng_file) return 1;
-    const int ok = ndt_apng_end(tail, &n) && fwrite(tail, 1, (size_t)n, apng_file) == (size_t)n;
-    if (fclose(apng_file) != 0 || !ok) {
+    if (!apng_path[0]) return 1;
+    if (!ndt_apng_end(tail, &n) || !write_bytes(apng_path, "ab", tail, (size_t)n)) {
         fprintf(stderr, "ndt_hip: cannot finish %s\n", apng_path);
         return 0;
     }
-    apng_file = NULL;
     printf("\tsaved %s\n", apng_path);
     return 1;
 }
 
-static int render_frame(scene *scn, int i)
+/* the colour file of frame i from what arrived: a file made on the GPU as it is; pixels as a PPM or a stored PNG, or (host_file)
+ * as the file the GPU makes of them */
+static int save_colour(const scene *scn, int i, ndt_frame *f)
 {
-    const int width = job_opts.width, height = job_opts.height;
-    if (job_opts.apng) return render_frame_apng(scn);
-    /* the image in doubles only when something asks for it (--raw, the depth map of -z); otherwise the GPU quantises
-     * and 4 bytes per pixel come back instead of 32 */
-    /* (--depth gpu: the map is finished on the device as well, and -z asks for no doubles) */
-    const int want_f64 = job_opts.raw_path != NULL || (job_opts.want_depth && !job_opts.depth_gpu);
-    double *rgba = want_f64 ? (double *)malloc((size_t)width * height * 4 * sizeof(double)) : NULL;
-    double *depth_map = job_opts.want_depth && !job_opts.depth_gpu ? (double *)malloc((size_t)width * height * sizeof(double)) : NULL;
-    ndt_depth_frame df;                             /* --depth gpu: the 8-bit images or files that arrive */
-    memset(&df, 0, sizeof(df));
-    unsigned char *rgba8 = NULL, *png = NULL;      /* png: the finished file of --png --deflate gpu, or of --jpeg */
-    long long png_bytes = 0;
-    double t0 = now_s();
-    int ok;
-    if (job_opts.png16) {
-        /* the doubles stay on the device: what comes back is the 16-bit file, or two */
-        const int aa_depth = job_opts.ssaa > 1 ? -1 : job_opts.aa_depth;
-        if (job_opts.depth_gpu) {
-            ok = ndt_render_image_png16_depth(scn, width, height, job_opts.samples, job_opts.threads, job_opts.aa_diff, aa_depth,
-                                              job_opts.stereo, job_opts.specular, job_opts.depth, job_opts.ssaa, &df);
-            png = df.png; df.png = NULL;
-            png_bytes = df.png_bytes;
-        } else
-            ok = ndt_render_image_png16(scn, width, height, job_opts.samples, job_opts.threads, job_opts.aa_diff, aa_depth, job_opts.stereo,
-                                        job_opts.specular, job_opts.depth, job_opts.ssaa, &png, &png_bytes);
-    } else if (job_opts.ssaa > 1) {
-        /* the same five ways out, through the supersampled calls */
-        const int K = job_opts.ssaa;
-        if (job_opts.depth_gpu) {
-            ok = ndt_render_image_ssaa_depth8(scn, width, height, job_opts.samples, job_opts.threads, job_opts.stereo, job_opts.specular,
-                                              job_opts.depth, K, job_opts.deflate_gpu, job_opts.depth_png, &df);
-            rgba8 = df.rgba8; df.rgba8 = NULL;
-            png = df.png; df.png = NULL;
-            png_bytes = df.png_bytes;
-        } else if (job_opts.jpeg && !want_f64)
-            ok = ndt_render_image_ssaa_jpeg(scn, width, height, job_opts.samples, job_opts.threads, job_opts.stereo, job_opts.specular,
-                                            job_opts.depth, K, job_opts.jpeg_quality, job_opts.jpeg_sampling, &png, &png_bytes);
-        else if (job_opts.deflate_gpu && !want_f64)
-            ok = ndt_render_image_ssaa_png(scn, width, height, job_opts.samples, job_opts.threads, job_opts.stereo, job_opts.specular,
-                                           job_opts.depth, K, &png, &png_bytes);
-        else if (want_f64) {
-            ok = ndt_render_image_ssaa_full(scn, width, height, job_opts.samples, job_opts.threads, job_opts.stereo, job_opts.specular,
-                                            job_opts.depth, K, rgba, depth_map);
-            if (ok) rgba8 = quantise(rgba, (long)width * height * 4);
-        } else {
-            rgba8 = (unsigned char *)malloc((size_t)width * height * 4);
-            ok = ndt_render_image_ssaa_rgba8(scn, width, height, job_opts.samples, job_opts.threads, job_opts.stereo, job_opts.specular,
-                                             job_opts.depth, K, rgba8);
-        }
-    } else if (job_opts.depth_gpu) {
-        ok = ndt_render_image_depth8(scn, width, height, job_opts.samples, job_opts.threads, job_opts.aa_diff, job_opts.aa_depth,
-                                     job_opts.stereo, job_opts.specular, job_opts.depth, job_opts.deflate_gpu, job_opts.depth_png, &df);
-        /* from here on the image is where the other paths leave it; the map stays in df */
-        rgba8 = df.rgba8; df.rgba8 = NULL;
-        png = df.png; df.png = NULL;
-        png_bytes = df.png_bytes;
-    } else if (job_opts.jpeg && !want_f64) {
-        /* the 8-bit image stays on the device: what comes back is the file */
-        ok = ndt_render_image_jpeg(scn, width, height, job_opts.samples, job_opts.threads, job_opts.aa_diff, job_opts.aa_depth,
-                                   job_opts.stereo, job_opts.specular, job_opts.depth, job_opts.jpeg_quality, job_opts.jpeg_sampling,
-                                   &png, &png_bytes);
-    } else if (job_opts.deflate_gpu && !want_f64) {
-        /* the 8-bit image stays on the device: what comes back is the file */
-        ok = ndt_render_image_png(scn, width, height, job_opts.samples, job_opts.threads, job_opts.aa_diff, job_opts.aa_depth,
-                                  job_opts.stereo, job_opts.specular, job_opts.depth, &png, &png_bytes);
-    } else if (want_f64) {
-        ok = ndt_render_image_full(scn, width, height, job_opts.samples, job_opts.threads, job_opts.aa_diff, job_opts.aa_depth,
-                                   job_opts.stereo, job_opts.specular, job_opts.depth, rgba, depth_map);
-        if (ok) rgba8 = quantise(rgba, (long)width * height * 4);
-    } else {
-        rgba8 = (unsigned char *)malloc((size_t)width * height * 4);
-        ok = ndt_render_image_rgba8(scn, width, height, job_opts.samples, job_opts.threads, job_opts.aa_diff, job_opts.aa_depth,
-                                    job_opts.stereo, job_opts.specular, job_opts.depth, rgba8);
-    }
-    if (!ok) {
-        free(rgba);
-        free(rgba8);
-        free(depth_map);
-        return 0;
-    }
-    printf("rendering took %.3fs\n", now_s() - t0);
+    const int width = frame_request.width, height = frame_request.height;
+    const int on_host = f->file == NULL;       /* the image is in host memory */
+    const ndt_colour_kind kind = on_host ? job_opts.host_file : frame_request.colour;
     const double t_file = now_s();
-    double encode_ms = png ? (job_opts.jpeg ? ndt_render_jpeg_encode_ms() : ndt_render_png_encode_ms()) : 0.0;
-    if ((job_opts.deflate_gpu || job_opts.jpeg) && !png) {
-        /* the image was made on the host (--raw, -z): encoded from there */
-        if (!(job_opts.jpeg ? ndt_encode_image_jpeg(rgba8, width, height, job_opts.jpeg_quality, job_opts.jpeg_sampling, &png, &png_bytes)
-                            : ndt_encode_image_png(rgba8, width, height, &png, &png_bytes))) {
-            free(rgba);
-            free(rgba8);
-            free(depth_map);
-            return 0;
-        }
-        encode_ms = job_opts.jpeg ? ndt_render_jpeg_encode_ms() : ndt_render_png_encode_ms();
-    }
     char dir[512], path[1024];
-    mkdir("images", 0700);
-    snprintf(dir, sizeof(dir), "images/%s", scn->name); mkdir(dir, 0700);
-    snprintf(dir, sizeof(dir), "images/%s/%id", scn->name, job_opts.dims); mkdir(dir, 0700);
-    snprintf(dir, sizeof(dir), "images/%s/%id/%ix%i", scn->name, job_opts.dims, width, height); mkdir(dir, 0700);
-    if (job_opts.jpeg) {
-        snprintf(path, sizeof(path), "%s/%s_%ix%i_%04i.jpg", dir, scn->name, width, height, i);
-        FILE *f = fopen(path, "wb");
-        if (f) { fwrite(png, 1, (size_t)png_bytes, f); fclose(f); }
-    } else if (job_opts.png) {
-        snprintf(path, sizeof(path), "%s/%s_%ix%i_%04i.png", dir, scn->name, width, height, i);
-        if (png) {
-            FILE *f = fopen(path, "wb");
-            if (f) { fwrite(png, 1, (size_t)png_bytes, f); fclose(f); }
-        } else write_png(path, rgba8, width, height);
-    } else {
-        snprintf(path, sizeof(path), "%s/%s_%ix%i_%04i.ppm", dir, scn->name, width, height, i);
-        write_ppm(path, rgba8, width, height);
-    }
+    if (kind == NDT_COLOUR_JPEG && on_host &&
+        !ndt_encode_image_jpeg(f->rgba8, width, height, frame_request.jpeg_quality, frame_request.jpeg_sampling, &f->file, &f->file_bytes, &f->file_ms)) return 0;
+    if (kind == NDT_COLOUR_PNG && on_host && !ndt_encode_image_png(f->rgba8, width, height, &f->file, &f->file_bytes, &f->file_ms)) return 0;
+    image_dir(dir, sizeof(dir), scn);
+    snprintf(path, sizeof(path), "%s/%s_%ix%i_%04i.%s", dir, scn->name, width, height, i,
+             kind == NDT_COLOUR_JPEG ? "jpg" : job_opts.png ? "png" : "ppm");
+    if (f->file) {
+        if (!write_bytes(path, "wb", f->file, (size_t)f->file_bytes)) return 0;
+    } else if (job_opts.png) write_png(path, f->rgba8, width, height);
+    else write_ppm(path, f->rgba8, width, height);
     printf("\tsaved %s\n", path);
     if (getenv("NDT_HOST_TIMING")) {
-        /* with --deflate gpu and the image on the device, the encoder's share is inside "rendering took" */
+        /* a file made where the image is: the encoder's share is inside "rendering took" */
         const double ms = (now_s() - t_file) * 1e3;
-        if (png) fprintf(stderr, "ndt_hip: image file %.2f ms (%s on the GPU %.2f, written %.2f)\n",
-                         want_f64 ? ms : ms + encode_ms, job_opts.jpeg ? "JPEG made" : "compressed", encode_ms, want_f64 ? ms - encode_ms : ms);
+        if (f->file) fprintf(stderr, "ndt_hip: image file %.2f ms (%s on the GPU %.2f, written %.2f)\n", on_host ? ms : ms + f->file_ms,
+                             kind == NDT_COLOUR_JPEG ? "JPEG made" : "compressed", f->file_ms, on_host ? ms - f->file_ms : ms);
         else fprintf(stderr, "ndt_hip: image file %.2f ms (%s, made and written by the host)\n", ms, job_opts.png ? "stored PNG" : "PPM");
     }
-    if (job_opts.depth_gpu) {
-        /* the map arrived normalised and quantised (or as its file): only the writing is left */
-        const double t_depth = now_s();
-        mkdir("depth", 0700);
-        snprintf(path, sizeof(path), "depth/%s_%ix%i_%04i.%s", scn->name, width, height, i, df.depth_png ? "png" : "ppm");
-        if (df.depth_png) {
-            FILE *f = fopen(path, "wb");
-            if (f) { fwrite(df.depth_png, 1, (size_t)df.depth_png_bytes, f); fclose(f); }
-        } else write_ppm(path, df.depth8, width, height);
-        printf("\tsaved %s\n", path);
-        if (getenv("NDT_HOST_TIMING"))
-            fprintf(stderr, "ndt_hip: depth file %.2f ms (map finished on the GPU %.2f, inside \"rendering took\"; %s written by the host)\n",
-                    (now_s() - t_depth) * 1e3, ndt_render_depth_finish_ms(), df.depth_png ? "PNG made there," : "PPM made and");
-        ndt_depth_frame_free(&df);
-    }
-    if (depth_map) {
+    return 1;
+}
+
+/* the map file of -z: depth/<scene>_<WxH>_<frame>.ppm, or .png */
+static int save_map(const scene *scn, int i, const ndt_frame *f)
+{
+    const int width = frame_request.width, height = frame_request.height;
+    const double t_depth = now_s();
+    char path[1024];
+    mkdir("depth", 0700);
+    snprintf(path, sizeof(path), "depth/%s_%ix%i_%04i.%s", scn->name, width, height, i, f->depth_file ? "png" : "ppm");
+    if (f->depth) {
         /* dbl_image_normalize (image.c:1025-1065) stretches the map to 0..1 before it is saved (ndt.c:1010-1016) */
-        double lo = depth_map[0], hi = depth_map[0];
+        double lo = f->depth[0], hi = f->depth[0];
         for (long k = 0; k < (long)width * height; ++k) {
-            if (depth_map[k] < lo) lo = depth_map[k];
-            if (depth_map[k] > hi) hi = depth_map[k];
+            if (f->depth[k] < lo) lo = f->depth[k];
+            if (f->depth[k] > hi) hi = f->depth[k];
         }
         double *norm = (double *)malloc((size_t)width * height * 4 * sizeof(double));
         for (long k = 0; k < (long)width * height; ++k) {
-            const double v = hi > lo ? (depth_map[k] - lo) / (hi - lo) : 0.0;
+            const double v = hi > lo ? (f->depth[k] - lo) / (hi - lo) : 0.0;
             norm[4 * k] = norm[4 * k + 1] = norm[4 * k + 2] = v;
             norm[4 * k + 3] = 1.0;
         }
-        mkdir("depth", 0700);
-        snprintf(path, sizeof(path), "depth/%s_%ix%i_%04i.ppm", scn->name, width, height, i);
         unsigned char *norm8 = quantise(norm, (long)width * height * 4);
         write_ppm(path, norm8, width, height);
         printf("\tsaved %s\n", path);
         free(norm8);
         free(norm);
-        if (job_opts.raw_path) {
-            char dpath[1100];
-            snprintf(dpath, sizeof(dpath), "%s.depth", job_opts.raw_path);
-            FILE *f = fopen(dpath, "wb");
-            if (f) { fwrite(depth_map, sizeof(double), (size_t)width * height, f); fclose(f); }
-        }
+        return 1;
     }
-    if (job_opts.raw_path) {
-        FILE *f = fopen(job_opts.raw_path, "wb");
-        if (f) { fwrite(rgba, sizeof(double), (size_t)width * height * 4, f); fclose(f); }
-    }
-    free(rgba);
-    free(rgba8);
-    free(png);
-    free(depth_map);
+    /* the map arrived normalised and quantised (or as its file): only the writing is left */
+    if (!f->depth_file) write_ppm(path, f->depth8, width, height);
+    else if (!write_bytes(path, "wb", f->depth_file, (size_t)f->depth_file_bytes)) return 0;
+    printf("\tsaved %s\n", path);
+    if (getenv("NDT_HOST_TIMING"))
+        fprintf(stderr, "ndt_hip: depth file %.2f ms (map finished on the GPU %.2f, inside \"rendering took\"; %s written by the host)\n",
+                (now_s() - t_depth) * 1e3, f->depth_ms, f->depth_file ? "PNG made there," : "PPM made and");
     return 1;
+}
+
+/* --raw F: the doubles as they arrived, the map's in F.depth */
+static int save_raw(const ndt_frame *f)
+{
+    const size_t n = (size_t)frame_request.width * frame_request.height;
+    char dpath[1100];
+    snprintf(dpath, sizeof(dpath), "%s.depth", job_opts.raw_path);
+    return (!f->depth || write_bytes(dpath, "wb", f->depth, n * sizeof(double))) &&
+           write_bytes(job_opts.raw_path, "wb", f->rgba, n * 4 * sizeof(double));
+}
+
+static int render_frame(scene *scn, int i)
+{
+    if (frame_request.colour == NDT_COLOUR_APNG) return render_frame_apng(scn);
+    ndt_frame f;
+    const double t0 = now_s();
+    if (!ndt_render_frame(scn, &frame_request, &f)) return 0;
+    /* doubles came back: the host makes the bytes of the colour file */
+    if (f.rgba) f.rgba8 = quantise(f.rgba, (long)frame_request.width * frame_request.height * 4);
+    printf("rendering took %.3fs\n", now_s() - t0);
+    const int ok = save_colour(scn, i, &f) && (frame_request.map == NDT_MAP_NONE || save_map(scn, i, &f)) &&
+                   (!job_opts.raw_path || save_raw(&f));
+    ndt_frame_free(&f);
+    return ok;
 }
 
 /* ---- bounded queue of frames between the scene program (producer) and the render workers */
@@ -712,21 +638,27 @@ int main(int argc, char **argv)
     if (last < 0) last = frames - 1;
     register_objects(objects_dir);
 
-    job_opts.dims = dims; job_opts.width = width; job_opts.height = height; job_opts.depth = depth; job_opts.threads = threads;
-    job_opts.aa_diff = aa_diff; job_opts.aa_depth = aa_depth; job_opts.stereo = stereo; job_opts.specular = specular;
-    job_opts.want_depth = want_depth; job_opts.raw_path = raw_path; job_opts.samples = samples; job_opts.png = png;
+    /* the one place where the flags become the frame request (the refusals above have sorted out what goes together).  The image
+     * comes back in doubles only when something asks for them (--raw, a depth map of -z that the host finishes): the file of
+     * --jpeg or --png --deflate gpu is then encoded from the host's bytes; otherwise the GPU quantises and 4 bytes a pixel come
+     * back instead of 32, or only the file does */
+    const int want_f64 = raw_path != NULL || (want_depth && !depth_gpu);
+    const ndt_colour_kind file_kind = jpeg ? NDT_COLOUR_JPEG : deflate_gpu ? NDT_COLOUR_PNG : NDT_COLOUR_F64;
+    frame_request.width = width; frame_request.height = height; frame_request.samples = samples; frame_request.threads = threads;
+    frame_request.aa_diff = aa_diff; frame_request.aa_depth = aa_depth; frame_request.stereo = stereo; frame_request.specular = specular;
+    frame_request.max_optic_depth = depth; frame_request.ssaa = ssaa;
+    frame_request.jpeg_quality = jpeg_quality; frame_request.jpeg_sampling = jpeg_sampling < 0 ? 0 : jpeg_sampling;
+    frame_request.colour = apng ? NDT_COLOUR_APNG : png16 ? NDT_COLOUR_PNG16 : want_f64 ? NDT_COLOUR_F64
+                         : file_kind != NDT_COLOUR_F64 ? file_kind : NDT_COLOUR_RGBA8;
+    frame_request.map = !want_depth ? NDT_MAP_NONE : !depth_gpu ? NDT_MAP_F64 : png16 ? NDT_MAP_PNG16 : depth_png ? NDT_MAP_PNG : NDT_MAP_DEPTH8;
+    job_opts.dims = dims; job_opts.raw_path = raw_path; job_opts.png = png;
+    job_opts.host_file = want_f64 ? file_kind : NDT_COLOUR_F64;
     job_opts.gpus = gpus > 1 ? gpus : 1;
-    job_opts.deflate_gpu = deflate_gpu;
-    job_opts.depth_gpu = depth_gpu;
-    job_opts.depth_png = depth_png;
-    job_opts.ssaa = ssaa;
-    job_opts.png16 = png16;
-    job_opts.apng = apng; job_opts.apng_fps = apng_fps ? apng_fps : 24;
+    job_opts.apng_fps = apng_fps ? apng_fps : 24;
     {
         const int upto = last < frames - 1 ? last : frames - 1, from = first > 0 ? first : 0;
         job_opts.apng_frames = upto >= from ? upto - from + 1 : 0;
     }
-    job_opts.jpeg = jpeg; job_opts.jpeg_quality = jpeg_quality; job_opts.jpeg_sampling = jpeg_sampling < 0 ? 0 : jpeg_sampling;
     ndt_render_fit_on_gpu(fit_gpu);
     ndt_render_kd_on_gpu(kd_gpu);
     if (job_opts.gpus > 1) {
@@ -772,9 +704,10 @@ int main(int argc, char **argv)
         if (workers) {
             queue_push(scn, i);
         } else {
-            if (!render_frame(scn, i)) return 1;
+            const int ok = render_frame(scn, i);
             scene_free(scn);
             free(scn);
+            if (!ok) return 1;
         }
     }
     if (workers) {
@@ -783,7 +716,7 @@ int main(int argc, char **argv)
         free(workers);
         if (worker_failed) return 1;
     }
-    if (job_opts.apng && !apng_close()) return 1;
+    if (!apng_close()) return 1;
     if (rendered > 1) printf("%d frames in %.3fs (%.2f frames/s)\n", rendered, now_s() - t_all, rendered / (now_s() - t_all));
     if (cleanup) cleanup();
     return 0;

@@ -129,27 +129,52 @@ int ndt_render_image(scene *scn, int width, int height, int threads, int max_opt
     return ndt_render_image_aa(scn, width, height, threads, -1, -1, max_optic_depth, rgba);
 }
 
-/* render_image with the reference's `-a diff,depth` (recursive_aa, ndt.c:44, 1039-1087); aa_depth < 0 = plain */
+/* render_image with the reference's `-a diff,depth` (recursive_aa, ndt.c:44, 1039-1087); aa_depth < 0 = plain: the frame request
+ * of the reference's call shape (mono, one sample, specular on), its doubles copied into the caller's image */
 int ndt_render_image_aa(scene *scn, int width, int height, int threads, int aa_diff, int aa_depth, int max_optic_depth,
                         double *rgba)
 {
-    return ndt_render_image_full(scn, width, height, 1, threads, aa_diff, aa_depth, 0, 1, max_optic_depth, rgba, NULL);
+    ndt_frame_request rq;
+    ndt_frame f;
+    memset(&rq, 0, sizeof(rq));         /* colour: doubles, map: none */
+    rq.width = width; rq.height = height; rq.samples = 1; rq.threads = threads; rq.aa_diff = aa_diff; rq.aa_depth = aa_depth;
+    rq.specular = 1; rq.max_optic_depth = max_optic_depth; rq.ssaa = 1;
+    if (!ndt_render_frame(scn, &rq, &f)) return 0;
+    memcpy(rgba, f.rgba, (size_t)width * height * 4 * sizeof(double));
+    ndt_frame_free(&f);
+    return 1;
 }
 
-/* ---- the frame's PNG file made on the GPU (ndt_hip_render_png / ndt_hip_encode_png) */
-#define NDT_HOST_IMAGE_PNG 100              /* render_any's `format` beside ndt_image_format; `out` is a png_out */
-typedef struct { unsigned char **png; long long *bytes; } png_out;
-static __thread double g_png_ms = 0.0;
-
-double ndt_render_png_encode_ms(void) { return g_png_ms; }
-
-static void say_png(const ndt_png_stats *ps)
+/* ---- the lines a frame's device work is reported with (stdout: tests and people read them) */
+static void say_png(const ndt_png_stats *ps, const char *what)
 {
-    g_png_ms = ps->encode_ms;
-    printf("compressed PNG of %lld bytes on GPU %d in %d launches\n", (long long)ps->png_bytes, ndt_hip_device(g_ctx[0]), ps->launches);
+    printf("compressed %s of %lld bytes on GPU %d in %d launches\n", what, (long long)ps->png_bytes, ndt_hip_device(g_ctx[0]), ps->launches);
 }
 
-int ndt_encode_image_png(const unsigned char *rgba8, int width, int height, unsigned char **png, long long *png_bytes)
+static void say_jpeg(const ndt_jpeg_stats *js)
+{
+    printf("encoded JPEG of %lld bytes on GPU %d in %d launches\n", (long long)js->jpeg_bytes, ndt_hip_device(g_ctx[0]), js->launches);
+}
+
+static void say_map(const double *range)
+{
+    printf("finished depth map [%.17g, %.17g] on GPU %d in %d launches\n", range[0], range[1], ndt_hip_device(g_ctx[0]),
+           ndt_hip_depth_launches(g_ctx[0]));
+}
+
+static void say_ssaa(int K, int launches)
+{
+    printf("supersampled %dx%d on GPU %d in %d launches\n", K, K, ndt_hip_device(g_ctx[0]), launches);
+}
+
+static int out_of_memory(void)
+{
+    fprintf(stderr, "ndt_render_frame: out of memory\n");
+    return 0;
+}
+
+/* ---- an 8-bit image in host memory as a PNG or JPEG file made on the GPU (ndt_hip_encode_png / ndt_hip_encode_jpeg) */
+int ndt_encode_image_png(const unsigned char *rgba8, int width, int height, unsigned char **png, long long *png_bytes, double *encode_ms)
 {
     const int64_t cap = ndt_hip_png_bound(width, height);
     ndt_png_stats ps;
@@ -165,23 +190,11 @@ int ndt_encode_image_png(const unsigned char *rgba8, int width, int height, unsi
         free(buf);
         return 0;
     }
-    say_png(&ps);
+    say_png(&ps, "PNG");
     *png = buf;
     *png_bytes = ps.png_bytes;
+    if (encode_ms) *encode_ms = ps.encode_ms;
     return 1;
-}
-
-/* ---- the frame's JPEG file made on the GPU (ndt_hip_render_jpeg / ndt_hip_encode_jpeg) */
-#define NDT_HOST_IMAGE_JPEG 102             /* render_any's `format`; `out` is a jpeg_out */
-typedef struct { unsigned char **jpg; long long *bytes; ndt_jpeg_params jp; } jpeg_out;
-static __thread double g_jpeg_ms = 0.0;
-
-double ndt_render_jpeg_encode_ms(void) { return g_jpeg_ms; }
-
-static void say_jpeg(const ndt_jpeg_stats *js)
-{
-    g_jpeg_ms = js->encode_ms;
-    printf("encoded JPEG of %lld bytes on GPU %d in %d launches\n", (long long)js->jpeg_bytes, ndt_hip_device(g_ctx[0]), js->launches);
 }
 
 static ndt_jpeg_params jpeg_params_of(int quality, int sampling)
@@ -193,7 +206,8 @@ static ndt_jpeg_params jpeg_params_of(int quality, int sampling)
     return jp;
 }
 
-int ndt_encode_image_jpeg(const unsigned char *rgba8, int width, int height, int quality, int sampling, unsigned char **jpg, long long *jpg_bytes)
+int ndt_encode_image_jpeg(const unsigned char *rgba8, int width, int height, int quality, int sampling, unsigned char **jpg, long long *jpg_bytes,
+                          double *encode_ms)
 {
     const ndt_jpeg_params jp = jpeg_params_of(quality, sampling);
     const int64_t cap = ndt_hip_jpeg_bound(width, height, &jp);
@@ -213,241 +227,11 @@ int ndt_encode_image_jpeg(const unsigned char *rgba8, int width, int height, int
     say_jpeg(&js);
     *jpg = buf;
     *jpg_bytes = js.jpeg_bytes;
+    if (encode_ms) *encode_ms = js.encode_ms;
     return 1;
 }
 
-/* ---- the depth map of -z finished on the GPU (ndt_hip_render_rgba8_depth / ndt_hip_render_png_depth) */
-#define NDT_HOST_IMAGE_DEPTH8 101           /* render_any's `format`; `out` is a depth_out */
-typedef struct { ndt_depth_frame *frame; int want_png, want_depth_png; } depth_out;
-static __thread double g_depth_ms = 0.0;
-
-double ndt_render_depth_finish_ms(void) { return g_depth_ms; }
-
-void ndt_depth_frame_free(ndt_depth_frame *f)
-{
-    free(f->rgba8);
-    free(f->depth8);
-    free(f->png);
-    free(f->depth_png);
-    memset(f, 0, sizeof(*f));
-}
-
-static int render_depth8(const ndt_render_params *p, depth_out *d)
-{
-    ndt_depth_frame *f = d->frame;
-    const size_t bytes = (size_t)p->width * (size_t)p->height * 4;
-    int rc;
-    if (d->want_png) {
-        const int64_t cap = ndt_hip_png_bound(p->width, p->height);
-        ndt_png_stats ps[2];
-        if (cap < 0) {
-            fprintf(stderr, "ndt_render_image_depth8: no PNG of %d x %d\n", p->width, p->height);
-            return 0;
-        }
-        f->png = (unsigned char *)malloc((size_t)cap);
-        if (d->want_depth_png) f->depth_png = (unsigned char *)malloc((size_t)cap);
-        else f->depth8 = (unsigned char *)malloc(bytes);
-        if (!f->png || !(d->want_depth_png ? f->depth_png : f->depth8)) return 0;
-        rc = ndt_hip_render_png_depth(g_ctx[0], p, f->png, cap, f->depth_png, cap, f->depth8, ps, f->range, NULL);
-        if (rc != NDT_OK) return 0;
-        f->png_bytes = ps[0].png_bytes;
-        f->depth_png_bytes = ps[1].png_bytes;
-        g_png_ms = ps[0].encode_ms + ps[1].encode_ms;
-        printf("compressed PNG of %lld bytes on GPU %d in %d launches\n", (long long)ps[0].png_bytes, ndt_hip_device(g_ctx[0]), ps[0].launches);
-        if (d->want_depth_png)
-            printf("compressed depth PNG of %lld bytes on GPU %d in %d launches\n", (long long)ps[1].png_bytes, ndt_hip_device(g_ctx[0]), ps[1].launches);
-    } else {
-        f->rgba8 = (unsigned char *)malloc(bytes);
-        f->depth8 = (unsigned char *)malloc(bytes);
-        if (!f->rgba8 || !f->depth8) return 0;
-        rc = ndt_hip_render_rgba8_depth(g_ctx[0], p, f->rgba8, f->depth8, f->range, NULL);
-        if (rc != NDT_OK) return 0;
-    }
-    g_depth_ms = ndt_hip_depth_ms(g_ctx[0]);
-    printf("finished depth map [%.17g, %.17g] on GPU %d in %d launches\n", f->range[0], f->range[1], ndt_hip_device(g_ctx[0]),
-           ndt_hip_depth_launches(g_ctx[0]));
-    return 1;
-}
-
-/* ---- the frame supersampled K x K on the GPU (ndt_hip_render_ssaa*; `ndt_hip --ssaa K`) */
-static __thread double g_ssaa_ms = 0.0;
-
-double ndt_render_ssaa_fold_ms(void) { return g_ssaa_ms; }
-
-/* the doubles (format NDT_IMAGE_F64) or the bytes (NDT_IMAGE_RGBA8) of the ssaa frame in host memory: from the one context, or
- * from several, each of which renders and folds its own cyclic row shard, context after context */
-static int ssaa_image(const ndt_render_params *p, int K, int format, void *out, int *launches)
-{
-    const size_t px = format == NDT_IMAGE_F64 ? 4 * sizeof(double) : 4;
-    *launches = 0;
-    g_ssaa_ms = 0.0;
-    if (g_n_ctx == 1) {
-        const int rc = format == NDT_IMAGE_F64 ? ndt_hip_render_ssaa(g_ctx[0], p, K, (double *)out, NULL, NULL)
-                                               : ndt_hip_render_ssaa_rgba8(g_ctx[0], p, K, (unsigned char *)out, NULL);
-        *launches = ndt_hip_ssaa_launches(g_ctx[0]);
-        g_ssaa_ms = ndt_hip_ssaa_ms(g_ctx[0]);
-        return rc == NDT_OK;
-    }
-    const size_t row_bytes = (size_t)p->width * px;
-    unsigned char *part = (unsigned char *)malloc(row_bytes * (size_t)((p->height + g_n_ctx - 1) / g_n_ctx));
-    int ok = part != NULL;
-    for (int k = 0; ok && k < g_n_ctx; ++k) {
-        ndt_render_params q = *p;
-        q.row_begin = k;
-        q.row_step = g_n_ctx;
-        const int rows = ndt_hip_shard_rows(p->height, k, g_n_ctx);
-        if (rows < 1) continue;
-        ok = (format == NDT_IMAGE_F64 ? ndt_hip_render_ssaa(g_ctx[k], &q, K, (double *)part, NULL, NULL)
-                                      : ndt_hip_render_ssaa_rgba8(g_ctx[k], &q, K, part, NULL)) == NDT_OK;
-        for (int r = 0; ok && r < rows; ++r)
-            memcpy((unsigned char *)out + (size_t)(k + r * g_n_ctx) * row_bytes, part + (size_t)r * row_bytes, row_bytes);
-        *launches += ndt_hip_ssaa_launches(g_ctx[k]);
-        g_ssaa_ms += ndt_hip_ssaa_ms(g_ctx[k]);
-    }
-    free(part);
-    return ok;
-}
-
-/* every format of render_any for an ssaa frame */
-static int render_ssaa_any(const ndt_render_params *p, int K, int format, void *out, double *depth)
-{
-    const int width = p->width, height = p->height;
-    int ok = 0, launches = 0;
-    if (format == NDT_HOST_IMAGE_PNG || format == NDT_HOST_IMAGE_JPEG) {
-        const int png = format == NDT_HOST_IMAGE_PNG;
-        png_out *po = (png_out *)out;
-        jpeg_out *jo = (jpeg_out *)out;
-        const int64_t cap = png ? ndt_hip_png_bound(width, height) : ndt_hip_jpeg_bound(width, height, &jo->jp);
-        ndt_png_stats ps;
-        ndt_jpeg_stats js;
-        unsigned char *buf = cap > 0 ? (unsigned char *)malloc((size_t)cap) : NULL;
-        if (!buf) {
-            fprintf(stderr, "ndt_render_image_ssaa: no %s of %d x %d\n", png ? "PNG" : "JPEG", width, height);
-            return 0;
-        }
-        if (g_n_ctx == 1) {
-            ok = (png ? ndt_hip_render_ssaa_png(g_ctx[0], p, K, buf, cap, &ps, NULL)
-                      : ndt_hip_render_ssaa_jpeg(g_ctx[0], p, K, &jo->jp, buf, cap, &js, NULL)) == NDT_OK;
-            launches = ndt_hip_ssaa_launches(g_ctx[0]);
-            g_ssaa_ms = ndt_hip_ssaa_ms(g_ctx[0]);
-        } else {
-            /* rows from several contexts: gathered into host memory, encoded from there on the first context */
-            unsigned char *rgba8 = (unsigned char *)malloc((size_t)width * height * 4);
-            ok = rgba8 && ssaa_image(p, K, NDT_IMAGE_RGBA8, rgba8, &launches) &&
-                 (png ? ndt_hip_encode_png(g_ctx[0], rgba8, width, height, buf, cap, &ps)
-                      : ndt_hip_encode_jpeg(g_ctx[0], rgba8, width, height, &jo->jp, buf, cap, &js)) == NDT_OK;
-            free(rgba8);
-        }
-        if (!ok) free(buf);
-        else if (png) {
-            say_png(&ps);
-            *po->png = buf;
-            *po->bytes = ps.png_bytes;
-        } else {
-            say_jpeg(&js);
-            *jo->jpg = buf;
-            *jo->bytes = js.jpeg_bytes;
-        }
-    } else if (format == NDT_HOST_IMAGE_DEPTH8) {
-        /* (one context, like every frame with a map) the two 8-bit images come back; files are encoded from them */
-        depth_out *d = (depth_out *)out;
-        ndt_depth_frame *f = d->frame;
-        const size_t bytes = (size_t)width * (size_t)height * 4;
-        f->rgba8 = (unsigned char *)malloc(bytes);
-        f->depth8 = (unsigned char *)malloc(bytes);
-        ok = f->rgba8 && f->depth8 && ndt_hip_render_ssaa_rgba8_depth(g_ctx[0], p, K, f->rgba8, f->depth8, f->range, NULL) == NDT_OK;
-        launches = ndt_hip_ssaa_launches(g_ctx[0]);
-        g_ssaa_ms = ndt_hip_ssaa_ms(g_ctx[0]);
-        if (ok) {
-            g_depth_ms = ndt_hip_depth_ms(g_ctx[0]);
-            printf("finished depth map [%.17g, %.17g] on GPU %d in %d launches\n", f->range[0], f->range[1], ndt_hip_device(g_ctx[0]),
-                   ndt_hip_depth_launches(g_ctx[0]));
-        }
-        if (ok && d->want_png) {
-            ok = ndt_encode_image_png(f->rgba8, width, height, &f->png, &f->png_bytes);
-            free(f->rgba8);
-            f->rgba8 = NULL;
-            if (ok && d->want_depth_png) {
-                const double image_ms = g_png_ms;
-                ok = ndt_encode_image_png(f->depth8, width, height, &f->depth_png, &f->depth_png_bytes);
-                g_png_ms += image_ms;
-                free(f->depth8);
-                f->depth8 = NULL;
-            }
-        }
-    } else if (depth) {     /* the depth map comes from the one-context call (a map is not split over devices) */
-        ok = format == NDT_IMAGE_F64 && ndt_hip_render_ssaa(g_ctx[0], p, K, (double *)out, depth, NULL) == NDT_OK;
-        launches = ndt_hip_ssaa_launches(g_ctx[0]);
-        g_ssaa_ms = ndt_hip_ssaa_ms(g_ctx[0]);
-    } else
-        ok = ssaa_image(p, K, format, out, &launches);
-    if (ok) printf("supersampled %dx%d on GPU %d in %d launches\n", K, K, ndt_hip_device(g_ctx[0]), launches);
-    return ok;
-}
-
-/* ---- the frame's files at 16 bits a sample (ndt_hip_render_png16*, ndt_hip_render_ssaa_png16*; `ndt_hip --png16`) */
-#define NDT_HOST_IMAGE_PNG16 103            /* render_any's `format`; `out` is a png_out */
-#define NDT_HOST_IMAGE_PNG16_DEPTH 104      /* ... `out` is an ndt_depth_frame: png and depth_png arrive */
-
-static int render_png16(const ndt_render_params *p, int K, int format, void *out)
-{
-    const int width = p->width, height = p->height, with_map = format == NDT_HOST_IMAGE_PNG16_DEPTH;
-    const int64_t cap = ndt_hip_png16_bound(width, height, 4), depth_cap = ndt_hip_png16_bound(width, height, 1);
-    ndt_png_stats ps[2];
-    double range[2] = { 0.0, 0.0 };
-    if (g_n_ctx > 1) {
-        /* (the rows of several contexts meet as 8-bit pixels or as doubles on the host: there is no 16-bit gather) */
-        fprintf(stderr, "ndt_render_image_png16: a 16-bit PNG is made by one GPU context, not by %d\n", g_n_ctx);
-        return 0;
-    }
-    if (cap < 0 || depth_cap < 0) {
-        fprintf(stderr, "ndt_render_image_png16: no 16-bit PNG of %d x %d\n", width, height);
-        return 0;
-    }
-    unsigned char *buf = (unsigned char *)malloc((size_t)cap), *dbuf = with_map ? (unsigned char *)malloc((size_t)depth_cap) : NULL;
-    int ok = buf && (dbuf || !with_map);
-    if (ok && with_map)
-        ok = (K != 1 ? ndt_hip_render_ssaa_png16_depth(g_ctx[0], p, K, buf, cap, dbuf, depth_cap, ps, range, NULL)
-                     : ndt_hip_render_png16_depth(g_ctx[0], p, buf, cap, dbuf, depth_cap, ps, range, NULL)) == NDT_OK;
-    else if (ok)
-        ok = (K != 1 ? ndt_hip_render_ssaa_png16(g_ctx[0], p, K, buf, cap, ps, NULL) : ndt_hip_render_png16(g_ctx[0], p, buf, cap, ps, NULL)) == NDT_OK;
-    if (!ok) {
-        free(buf);
-        free(dbuf);
-        return 0;
-    }
-    if (K != 1) {
-        g_ssaa_ms = ndt_hip_ssaa_ms(g_ctx[0]);
-        printf("supersampled %dx%d on GPU %d in %d launches\n", K, K, ndt_hip_device(g_ctx[0]), ndt_hip_ssaa_launches(g_ctx[0]));
-    }
-    g_png_ms = ps[0].encode_ms + (with_map ? ps[1].encode_ms : 0.0);
-    printf("compressed 16-bit PNG of %lld bytes on GPU %d in %d launches\n", (long long)ps[0].png_bytes, ndt_hip_device(g_ctx[0]), ps[0].launches);
-    if (!with_map) {
-        png_out *po = (png_out *)out;
-        *po->png = buf;
-        *po->bytes = ps[0].png_bytes;
-        return 1;
-    }
-    ndt_depth_frame *f = (ndt_depth_frame *)out;
-    f->png = buf;
-    f->png_bytes = ps[0].png_bytes;
-    f->depth_png = dbuf;
-    f->depth_png_bytes = ps[1].png_bytes;
-    f->range[0] = range[0];
-    f->range[1] = range[1];
-    g_depth_ms = ndt_hip_depth_ms(g_ctx[0]);
-    printf("compressed 16-bit depth PNG of %lld bytes on GPU %d in %d launches\n", (long long)ps[1].png_bytes, ndt_hip_device(g_ctx[0]), ps[1].launches);
-    printf("finished depth map [%.17g, %.17g] on GPU %d in %d launches\n", f->range[0], f->range[1], ndt_hip_device(g_ctx[0]),
-           ndt_hip_depth_launches(g_ctx[0]));
-    return 1;
-}
-
-/* ---- the run's frames as one animated PNG (ndt_hip_apng_*, ndt_hip_render_apng_frame; `ndt_hip --apng`) */
-#define NDT_HOST_IMAGE_APNG 105             /* render_any's `format`; `out` is a png_out: the bytes to append */
-static __thread double g_apng_ms = 0.0;
-
-double ndt_render_apng_encode_ms(void) { return g_apng_ms; }
-
+/* ---- the run's frames as one animated PNG (ndt_hip_apng_*; `ndt_hip --apng`): opened and closed around the frames */
 int ndt_apng_begin(int width, int height, int n_frames, int fps)
 {
     if (fps < 1 || fps > 1000) {
@@ -477,37 +261,254 @@ int ndt_apng_end(unsigned char *out, long long *n_bytes)
     return 1;
 }
 
-static int render_apng(const ndt_render_params *p, int K, png_out *po)
+/* ---- one frame (ndt_render_frame): each routine below brings one group of sinks into the ndt_frame; what it allocates there
+ * and then fails to fill, ndt_render_frame frees */
+void ndt_frame_free(ndt_frame *f)
 {
-    const int64_t cap = ndt_hip_apng_bound(p->width, p->height);
-    ndt_apng_stats as;
-    if (g_n_ctx > 1) {
-        fprintf(stderr, "ndt_render_image_apng_frame: the frames of an animated PNG meet one canvas on one GPU context, not on %d\n", g_n_ctx);
-        return 0;
+    free(f->rgba);
+    free(f->depth);
+    free(f->rgba8);
+    free(f->depth8);
+    free(f->file);
+    free(f->depth_file);
+    memset(f, 0, sizeof(*f));
+}
+
+/* the doubles (format NDT_IMAGE_F64) or the bytes (NDT_IMAGE_RGBA8) of the frame supersampled K x K (ndt_hip_render_ssaa*) in host
+ * memory: from the one context, or from several, each of which renders and folds its own cyclic row shard, context after context */
+static int ssaa_image(const ndt_render_params *p, int K, int format, void *out, int *launches, double *fold_ms)
+{
+    const size_t px = format == NDT_IMAGE_F64 ? 4 * sizeof(double) : 4;
+    *launches = 0;
+    *fold_ms = 0.0;
+    if (g_n_ctx == 1) {
+        const int rc = format == NDT_IMAGE_F64 ? ndt_hip_render_ssaa(g_ctx[0], p, K, (double *)out, NULL, NULL)
+                                               : ndt_hip_render_ssaa_rgba8(g_ctx[0], p, K, (unsigned char *)out, NULL);
+        *launches = ndt_hip_ssaa_launches(g_ctx[0]);
+        *fold_ms = ndt_hip_ssaa_ms(g_ctx[0]);
+        return rc == NDT_OK;
     }
-    unsigned char *buf = cap > 0 ? (unsigned char *)malloc((size_t)cap) : NULL;
+    const size_t row_bytes = (size_t)p->width * px;
+    unsigned char *part = (unsigned char *)malloc(row_bytes * (size_t)((p->height + g_n_ctx - 1) / g_n_ctx));
+    int ok = part != NULL;
+    for (int k = 0; ok && k < g_n_ctx; ++k) {
+        ndt_render_params q = *p;
+        q.row_begin = k;
+        q.row_step = g_n_ctx;
+        const int rows = ndt_hip_shard_rows(p->height, k, g_n_ctx);
+        if (rows < 1) continue;
+        ok = (format == NDT_IMAGE_F64 ? ndt_hip_render_ssaa(g_ctx[k], &q, K, (double *)part, NULL, NULL)
+                                      : ndt_hip_render_ssaa_rgba8(g_ctx[k], &q, K, part, NULL)) == NDT_OK;
+        for (int r = 0; ok && r < rows; ++r)
+            memcpy((unsigned char *)out + (size_t)(k + r * g_n_ctx) * row_bytes, part + (size_t)r * row_bytes, row_bytes);
+        *launches += ndt_hip_ssaa_launches(g_ctx[k]);
+        *fold_ms += ndt_hip_ssaa_ms(g_ctx[k]);
+    }
+    free(part);
+    return ok;
+}
+
+/* colour in doubles or 8-bit RGBA, with the map in doubles beside the doubles if asked: rows of all the thread's contexts, except
+ * that the depth map comes from the one-context call (a map is not split over devices) */
+static int frame_pixels(const ndt_render_params *p, const ndt_frame_request *rq, ndt_frame *f)
+{
+    const int format = rq->colour == NDT_COLOUR_F64 ? NDT_IMAGE_F64 : NDT_IMAGE_RGBA8, K = rq->ssaa;
+    const size_t n = (size_t)p->width * (size_t)p->height;
+    void *out;
+    int ok, launches = 0;
+    if (format == NDT_IMAGE_F64) out = f->rgba = (double *)malloc(n * 4 * sizeof(double));
+    else out = f->rgba8 = (unsigned char *)malloc(n * 4);
+    if (rq->map == NDT_MAP_F64) f->depth = (double *)malloc(n * sizeof(double));
+    if (!out || (rq->map == NDT_MAP_F64 && !f->depth)) return out_of_memory();
+    if (rq->map == NDT_MAP_F64 && K != 1) {     /* (0, 9, ... reach the library, which says what is wrong with them) */
+        ok = ndt_hip_render_ssaa(g_ctx[0], p, K, f->rgba, f->depth, NULL) == NDT_OK;
+        launches = ndt_hip_ssaa_launches(g_ctx[0]);
+        f->ssaa_ms = ndt_hip_ssaa_ms(g_ctx[0]);
+    } else if (rq->map == NDT_MAP_F64)
+        ok = ndt_hip_render_depth(g_ctx[0], p, f->rgba, f->depth, NULL) == NDT_OK;
+    else if (K != 1)
+        ok = ssaa_image(p, K, format, out, &launches, &f->ssaa_ms);
+    else
+        ok = ndt_hip_render_multi(g_ctx, g_n_ctx, p, format, out, NULL) == NDT_OK;
+    if (ok && K != 1) say_ssaa(K, launches);
+    return ok;
+}
+
+/* colour as a PNG or a JPEG file made on the GPU, plain or supersampled.  One context: the file is made where the image is, and
+ * the 8-bit image never leaves the device.  Several: their rows are gathered into host memory as 8-bit pixels and encoded from
+ * there on the first context */
+static int frame_file(const ndt_render_params *p, const ndt_frame_request *rq, ndt_frame *f)
+{
+    const int png = rq->colour == NDT_COLOUR_PNG, K = rq->ssaa, width = p->width, height = p->height;
+    const ndt_jpeg_params jp = jpeg_params_of(rq->jpeg_quality, rq->jpeg_sampling);
+    const int64_t cap = png ? ndt_hip_png_bound(width, height) : ndt_hip_jpeg_bound(width, height, &jp);
+    ndt_png_stats ps;
+    ndt_jpeg_stats js;
+    int ok, launches = 0;
+    unsigned char *buf = f->file = cap > 0 ? (unsigned char *)malloc((size_t)cap) : NULL;
     if (!buf) {
-        fprintf(stderr, "ndt_render_image_apng_frame: no animated PNG of %d x %d\n", p->width, p->height);
+        if (png) fprintf(stderr, "ndt_render_frame: no PNG of %d x %d\n", width, height);
+        else fprintf(stderr, "ndt_render_frame: no JPEG of %d x %d at quality %d, sampling %d\n", width, height, jp.quality, jp.sampling);
         return 0;
     }
-    if (ndt_hip_render_apng_frame(g_ctx[0], p, K, buf, cap, &as, NULL) != NDT_OK) {
-        free(buf);
-        return 0;
+    if (g_n_ctx == 1 && K == 1) {
+        ok = (png ? ndt_hip_render_png(g_ctx[0], p, buf, cap, &ps, NULL) : ndt_hip_render_jpeg(g_ctx[0], p, &jp, buf, cap, &js, NULL)) == NDT_OK;
+    } else if (g_n_ctx == 1) {
+        ok = (png ? ndt_hip_render_ssaa_png(g_ctx[0], p, K, buf, cap, &ps, NULL)
+                  : ndt_hip_render_ssaa_jpeg(g_ctx[0], p, K, &jp, buf, cap, &js, NULL)) == NDT_OK;
+        launches = ndt_hip_ssaa_launches(g_ctx[0]);
+        f->ssaa_ms = ndt_hip_ssaa_ms(g_ctx[0]);
+    } else {
+        unsigned char *rgba8 = (unsigned char *)malloc((size_t)width * height * 4);
+        ok = rgba8 && (K == 1 ? ndt_hip_render_multi(g_ctx, g_n_ctx, p, NDT_IMAGE_RGBA8, rgba8, NULL) == NDT_OK
+                              : ssaa_image(p, K, NDT_IMAGE_RGBA8, rgba8, &launches, &f->ssaa_ms)) &&
+             (png ? ndt_hip_encode_png(g_ctx[0], rgba8, width, height, buf, cap, &ps)
+                  : ndt_hip_encode_jpeg(g_ctx[0], rgba8, width, height, &jp, buf, cap, &js)) == NDT_OK;
+        free(rgba8);
     }
-    if (K != 1) {
-        g_ssaa_ms = ndt_hip_ssaa_ms(g_ctx[0]);
-        printf("supersampled %dx%d on GPU %d in %d launches\n", K, K, ndt_hip_device(g_ctx[0]), ndt_hip_ssaa_launches(g_ctx[0]));
-    }
-    g_apng_ms = as.encode_ms;
-    printf("animated PNG frame %d: %d x %d at %d,%d (%lld bytes) on GPU %d in %d launches\n", as.frame, as.w, as.h, as.x, as.y,
-           (long long)as.bytes, ndt_hip_device(g_ctx[0]), as.launches);
-    *po->png = buf;
-    *po->bytes = as.bytes;
+    if (!ok) return 0;
+    f->file_bytes = png ? ps.png_bytes : js.jpeg_bytes;
+    f->file_ms = png ? ps.encode_ms : js.encode_ms;
+    if (png) say_png(&ps, "PNG");
+    else say_jpeg(&js);
+    if (K != 1) say_ssaa(K, launches);
     return 1;
 }
 
-static int render_any(scene *scn, int width, int height, int samples, int aa_diff, int aa_depth, int stereo, int specular,
-                      int max_optic_depth, int format, void *out, double *depth, int threads, int ssaa)
+/* colour as 8-bit RGBA or a PNG file beside the map of -z finished on the GPU, as 8-bit grey or a PNG file (one context, like
+ * every frame with a map).  The plain frame's files are made where the images are (ndt_hip_render_png_depth); of a supersampled
+ * frame the two 8-bit images come back, and the files asked for are encoded from them */
+static int frame_beside_map8(const ndt_render_params *p, const ndt_frame_request *rq, ndt_frame *f)
+{
+    const int width = p->width, height = p->height, K = rq->ssaa;
+    const int want_png = rq->colour == NDT_COLOUR_PNG, want_depth_png = rq->map == NDT_MAP_PNG;
+    const size_t bytes = (size_t)width * (size_t)height * 4;
+    if (K == 1 && want_png) {
+        const int64_t cap = ndt_hip_png_bound(width, height);
+        ndt_png_stats ps[2];
+        memset(ps, 0, sizeof(ps));
+        if (cap < 0) {
+            fprintf(stderr, "ndt_render_frame: no PNG of %d x %d\n", width, height);
+            return 0;
+        }
+        f->file = (unsigned char *)malloc((size_t)cap);
+        if (want_depth_png) f->depth_file = (unsigned char *)malloc((size_t)cap);
+        else f->depth8 = (unsigned char *)malloc(bytes);
+        if (!f->file || !(want_depth_png ? f->depth_file : f->depth8)) return out_of_memory();
+        if (ndt_hip_render_png_depth(g_ctx[0], p, f->file, cap, f->depth_file, cap, f->depth8, ps, f->range, NULL) != NDT_OK) return 0;
+        f->file_bytes = ps[0].png_bytes;
+        f->depth_file_bytes = ps[1].png_bytes;
+        f->file_ms = ps[0].encode_ms + ps[1].encode_ms;
+        say_png(&ps[0], "PNG");
+        if (want_depth_png) say_png(&ps[1], "depth PNG");
+    } else {
+        f->rgba8 = (unsigned char *)malloc(bytes);
+        f->depth8 = (unsigned char *)malloc(bytes);
+        if (!f->rgba8 || !f->depth8) return out_of_memory();
+        if ((K == 1 ? ndt_hip_render_rgba8_depth(g_ctx[0], p, f->rgba8, f->depth8, f->range, NULL)
+                    : ndt_hip_render_ssaa_rgba8_depth(g_ctx[0], p, K, f->rgba8, f->depth8, f->range, NULL)) != NDT_OK) return 0;
+    }
+    f->depth_ms = ndt_hip_depth_ms(g_ctx[0]);
+    say_map(f->range);
+    if (K == 1) return 1;
+    f->ssaa_ms = ndt_hip_ssaa_ms(g_ctx[0]);
+    if (want_png) {
+        if (!ndt_encode_image_png(f->rgba8, width, height, &f->file, &f->file_bytes, &f->file_ms)) return 0;
+        free(f->rgba8);
+        f->rgba8 = NULL;
+    }
+    if (want_depth_png) {
+        double map_ms = 0.0;
+        if (!ndt_encode_image_png(f->depth8, width, height, &f->depth_file, &f->depth_file_bytes, &map_ms)) return 0;
+        f->file_ms += map_ms;
+        free(f->depth8);
+        f->depth8 = NULL;
+    }
+    say_ssaa(K, ndt_hip_ssaa_launches(g_ctx[0]));
+    return 1;
+}
+
+/* colour as a PNG file of 16 bits a sample, and the map beside it as 16-bit grey if asked (ndt_hip_render_png16*,
+ * ndt_hip_render_ssaa_png16*; `ndt_hip --png16`) */
+static int frame_png16(const ndt_render_params *p, const ndt_frame_request *rq, ndt_frame *f)
+{
+    const int width = p->width, height = p->height, K = rq->ssaa, with_map = rq->map == NDT_MAP_PNG16;
+    const int64_t cap = ndt_hip_png16_bound(width, height, 4), depth_cap = ndt_hip_png16_bound(width, height, 1);
+    ndt_png_stats ps[2];
+    int ok;
+    if (g_n_ctx > 1) {
+        /* (the rows of several contexts meet as 8-bit pixels or as doubles on the host: there is no 16-bit gather) */
+        fprintf(stderr, "ndt_render_frame: a 16-bit PNG is made by one GPU context, not by %d\n", g_n_ctx);
+        return 0;
+    }
+    if (cap < 0 || depth_cap < 0) {
+        fprintf(stderr, "ndt_render_frame: no 16-bit PNG of %d x %d\n", width, height);
+        return 0;
+    }
+    f->file = (unsigned char *)malloc((size_t)cap);
+    if (with_map) f->depth_file = (unsigned char *)malloc((size_t)depth_cap);
+    if (!f->file || (with_map && !f->depth_file)) return out_of_memory();
+    if (with_map)
+        ok = (K != 1 ? ndt_hip_render_ssaa_png16_depth(g_ctx[0], p, K, f->file, cap, f->depth_file, depth_cap, ps, f->range, NULL)
+                     : ndt_hip_render_png16_depth(g_ctx[0], p, f->file, cap, f->depth_file, depth_cap, ps, f->range, NULL)) == NDT_OK;
+    else
+        ok = (K != 1 ? ndt_hip_render_ssaa_png16(g_ctx[0], p, K, f->file, cap, ps, NULL) : ndt_hip_render_png16(g_ctx[0], p, f->file, cap, ps, NULL)) == NDT_OK;
+    if (!ok) return 0;
+    if (K != 1) {
+        f->ssaa_ms = ndt_hip_ssaa_ms(g_ctx[0]);
+        say_ssaa(K, ndt_hip_ssaa_launches(g_ctx[0]));
+    }
+    f->file_bytes = ps[0].png_bytes;
+    f->file_ms = ps[0].encode_ms + (with_map ? ps[1].encode_ms : 0.0);
+    say_png(&ps[0], "16-bit PNG");
+    if (!with_map) return 1;
+    f->depth_file_bytes = ps[1].png_bytes;
+    f->depth_ms = ndt_hip_depth_ms(g_ctx[0]);
+    say_png(&ps[1], "16-bit depth PNG");
+    say_map(f->range);
+    return 1;
+}
+
+/* colour as the next frame's bytes of the animated PNG ndt_apng_begin opened (ndt_hip_render_apng_frame) */
+static int frame_apng(const ndt_render_params *p, const ndt_frame_request *rq, ndt_frame *f)
+{
+    const int64_t cap = ndt_hip_apng_bound(p->width, p->height);
+    const int K = rq->ssaa;
+    ndt_apng_stats as;
+    if (g_n_ctx > 1) {
+        fprintf(stderr, "ndt_render_frame: the frames of an animated PNG meet one canvas on one GPU context, not on %d\n", g_n_ctx);
+        return 0;
+    }
+    f->file = cap > 0 ? (unsigned char *)malloc((size_t)cap) : NULL;
+    if (!f->file) {
+        fprintf(stderr, "ndt_render_frame: no animated PNG of %d x %d\n", p->width, p->height);
+        return 0;
+    }
+    if (ndt_hip_render_apng_frame(g_ctx[0], p, K, f->file, cap, &as, NULL) != NDT_OK) return 0;
+    if (K != 1) {
+        f->ssaa_ms = ndt_hip_ssaa_ms(g_ctx[0]);
+        say_ssaa(K, ndt_hip_ssaa_launches(g_ctx[0]));
+    }
+    f->file_bytes = as.bytes;
+    f->file_ms = as.encode_ms;
+    printf("animated PNG frame %d: %d x %d at %d,%d (%lld bytes) on GPU %d in %d launches\n", as.frame, as.w, as.h, as.x, as.y,
+           (long long)as.bytes, ndt_hip_device(g_ctx[0]), as.launches);
+    return 1;
+}
+
+/* the maps each colour kind comes with (bit m: ndt_map_kind m): the pairs a device call serves */
+#define MAP_BIT(m) (1u << (m))
+static const struct { const char *name; unsigned maps; } colour_kinds[] = {
+    { "doubles", MAP_BIT(NDT_MAP_NONE) | MAP_BIT(NDT_MAP_F64) },
+    { "8-bit RGBA", MAP_BIT(NDT_MAP_NONE) | MAP_BIT(NDT_MAP_DEPTH8) },
+    { "PNG file", MAP_BIT(NDT_MAP_NONE) | MAP_BIT(NDT_MAP_DEPTH8) | MAP_BIT(NDT_MAP_PNG) },
+    { "JPEG file", MAP_BIT(NDT_MAP_NONE) },
+    { "16-bit PNG file", MAP_BIT(NDT_MAP_NONE) | MAP_BIT(NDT_MAP_PNG16) },
+    { "animated PNG frame", MAP_BIT(NDT_MAP_NONE) },
+};
+static const char *const map_kinds[] = { "none", "doubles", "8-bit grey finished on the GPU", "PNG file", "16-bit PNG file" };
+
+int ndt_render_frame(scene *scn, const ndt_frame_request *rq, ndt_frame *f)
 {
     char err[256];
     ndt_flat_builder fb;
@@ -515,10 +516,19 @@ static int render_any(scene *scn, int width, int height, int samples, int aa_dif
     /* (read per call: a static written by concurrent host threads -- ndt_hip -j K -- would be a data race) */
     const int timing = getenv("NDT_HOST_TIMING") != NULL;
     struct timespec ts0, ts1, ts2, ts3;
+    memset(f, 0, sizeof(*f));
+    if ((unsigned)rq->colour > NDT_COLOUR_APNG || (unsigned)rq->map > NDT_MAP_PNG16 || !(colour_kinds[rq->colour].maps & MAP_BIT(rq->map))) {
+        fprintf(stderr, "ndt_render_frame: no device call brings colour (%s) and map (%s) of one frame\n",
+                (unsigned)rq->colour > NDT_COLOUR_APNG ? "unknown" : colour_kinds[rq->colour].name,
+                (unsigned)rq->map > NDT_MAP_PNG16 ? "unknown" : map_kinds[rq->map]);
+        return 0;
+    }
+    /* 1. the scene: flattened, uploaded to every context of the thread (the pthread fan-out of ndt.c:949-975 is the GPU's job now;
+     * `threads` fits the scene's bounding spheres in parallel) */
     if (timing) clock_gettime(CLOCK_MONOTONIC, &ts0);
     ndt_fit_stats fit;
     ndt_kd_stats kds;
-    if (ndt_flatten_scene_gpu(scn, &fb, err, sizeof(err), threads, g_fit_on_gpu, g_kd_on_gpu, &fit, &kds) != 0) {
+    if (ndt_flatten_scene_gpu(scn, &fb, err, sizeof(err), rq->threads, g_fit_on_gpu, g_kd_on_gpu, &fit, &kds) != 0) {
         fprintf(stderr, "ndt_render_image: %s\n", err);
         ndt_flat_builder_free(&fb);
         return 0;
@@ -528,73 +538,25 @@ static int render_any(scene *scn, int width, int height, int samples, int aa_dif
     for (int k = 0; ok && k < g_n_ctx; ++k)
         if (ndt_hip_upload_scene(g_ctx[k], &fb.fs) != NDT_OK) ok = 0;
     if (timing) clock_gettime(CLOCK_MONOTONIC, &ts2);
+    const int map8 = rq->map == NDT_MAP_DEPTH8 || rq->map == NDT_MAP_PNG;
     if (ok) {
         ndt_render_params p;
         memset(&p, 0, sizeof(p));
-        p.width = width; p.height = height; p.max_optic_depth = max_optic_depth; p.samples = samples > 1 ? samples : 1;
-        p.row_begin = 0; p.row_step = 1; p.specular = specular;
-        p.stereo = stereo;
-        if (aa_depth >= 0 && aa_diff < 256) {       /* ndt.c:1040: otherwise the first pass is the image */
+        p.width = rq->width; p.height = rq->height; p.max_optic_depth = rq->max_optic_depth; p.samples = rq->samples > 1 ? rq->samples : 1;
+        p.row_begin = 0; p.row_step = 1; p.specular = rq->specular;
+        p.stereo = rq->stereo;
+        if (rq->aa_depth >= 0 && rq->aa_diff < 256) {       /* ndt.c:1040: otherwise the first pass is the image */
             p.recursive_aa = 1;
-            p.aa_diff = aa_diff;
-            p.aa_depth = aa_depth;
+            p.aa_diff = rq->aa_diff;
+            p.aa_depth = rq->aa_depth;
         }
-        if (format == NDT_HOST_IMAGE_APNG) {
-            ok = render_apng(&p, ssaa, (png_out *)out);
-        } else if (format == NDT_HOST_IMAGE_PNG16 || format == NDT_HOST_IMAGE_PNG16_DEPTH) {
-            ok = render_png16(&p, ssaa, format, out);
-        } else if (ssaa != 1) {        /* (0, 9, ... reach the library, which says what is wrong with them) */
-            ok = render_ssaa_any(&p, ssaa, format, out, depth);
-        } else if (format == NDT_HOST_IMAGE_PNG) {
-            png_out *po = (png_out *)out;
-            const int64_t cap = ndt_hip_png_bound(width, height);
-            ndt_png_stats ps;
-            unsigned char *buf = cap > 0 ? (unsigned char *)malloc((size_t)cap) : NULL;
-            if (!buf) {
-                fprintf(stderr, "ndt_render_image_png: no PNG of %d x %d\n", width, height);
-                ok = 0;
-            } else if (g_n_ctx == 1) {
-                ok = ndt_hip_render_png(g_ctx[0], &p, buf, cap, &ps, NULL) == NDT_OK;
-            } else {
-                /* rows from several contexts: gathered into host memory, encoded from there on the first context */
-                unsigned char *rgba8 = (unsigned char *)malloc((size_t)width * height * 4);
-                ok = rgba8 && ndt_hip_render_multi(g_ctx, g_n_ctx, &p, NDT_IMAGE_RGBA8, rgba8, NULL) == NDT_OK &&
-                     ndt_hip_encode_png(g_ctx[0], rgba8, width, height, buf, cap, &ps) == NDT_OK;
-                free(rgba8);
-            }
-            if (ok) {
-                say_png(&ps);
-                *po->png = buf;
-                *po->bytes = ps.png_bytes;
-            } else free(buf);
-        } else if (format == NDT_HOST_IMAGE_JPEG) {
-            jpeg_out *jo = (jpeg_out *)out;
-            const int64_t cap = ndt_hip_jpeg_bound(width, height, &jo->jp);
-            ndt_jpeg_stats js;
-            unsigned char *buf = cap > 0 ? (unsigned char *)malloc((size_t)cap) : NULL;
-            if (!buf) {
-                fprintf(stderr, "ndt_render_image_jpeg: no JPEG of %d x %d at quality %d, sampling %d\n", width, height, jo->jp.quality, jo->jp.sampling);
-                ok = 0;
-            } else if (g_n_ctx == 1) {
-                ok = ndt_hip_render_jpeg(g_ctx[0], &p, &jo->jp, buf, cap, &js, NULL) == NDT_OK;
-            } else {
-                /* rows from several contexts: gathered into host memory, encoded from there on the first context */
-                unsigned char *rgba8 = (unsigned char *)malloc((size_t)width * height * 4);
-                ok = rgba8 && ndt_hip_render_multi(g_ctx, g_n_ctx, &p, NDT_IMAGE_RGBA8, rgba8, NULL) == NDT_OK &&
-                     ndt_hip_encode_jpeg(g_ctx[0], rgba8, width, height, &jo->jp, buf, cap, &js) == NDT_OK;
-                free(rgba8);
-            }
-            if (ok) {
-                say_jpeg(&js);
-                *jo->jpg = buf;
-                *jo->bytes = js.jpeg_bytes;
-            } else free(buf);
-        } else if (format == NDT_HOST_IMAGE_DEPTH8) {
-            ok = render_depth8(&p, (depth_out *)out);
-        } else if (depth)      /* the depth map comes from the one-context call (a map is not split over devices) */
-            ok = format == NDT_IMAGE_F64 && ndt_hip_render_depth(g_ctx[0], &p, (double *)out, depth, NULL) == NDT_OK;
-        else
-            ok = ndt_hip_render_multi(g_ctx, g_n_ctx, &p, format, out, NULL) == NDT_OK;
+        /* 2. and 3. colour and map in the forms asked for: one device call makes both, so the routine is chosen by the pair */
+        if (rq->colour == NDT_COLOUR_APNG) ok = frame_apng(&p, rq, f);
+        else if (rq->colour == NDT_COLOUR_PNG16) ok = frame_png16(&p, rq, f);
+        else if (map8) ok = frame_beside_map8(&p, rq, f);
+        else if (rq->colour == NDT_COLOUR_PNG || rq->colour == NDT_COLOUR_JPEG) ok = frame_file(&p, rq, f);
+        else ok = frame_pixels(&p, rq, f);
+        /* 4. what is left to report (each routine has said what the device did, in the order it did it) */
         if (ok && g_n_ctx > 1 && !g_paths_said) {
             /* once per thread: how every context's rows reached the frame (an N-GPU run is diagnosable from its log) */
             static const char *const names[] = { "no rows", "same device", "peer stores", "staged copy" };
@@ -620,145 +582,23 @@ static int render_any(scene *scn, int width, int height, int samples, int aa_dif
                      NDT_MS(ts0, ts1) - fit.gather_ms - fit.fit_ms - kds.build_ms);
         else
             snprintf(share, sizeof(share), "host fits %.2f, %s, rest %.2f", fit.fit_ms, tree, NDT_MS(ts0, ts1) - fit.fit_ms - kds.build_ms);
-        if (format == NDT_HOST_IMAGE_DEPTH8 && ok)
-            fprintf(stderr, "ndt_render_image: bounds + kd-tree + flatten %.2f ms (%s), upload %.2f ms, render + 8-bit image and depth map to host %.2f ms (depth map finished on the GPU %.2f%s)\n",
-                    NDT_MS(ts0, ts1), share, NDT_MS(ts1, ts2), NDT_MS(ts2, ts3), g_depth_ms,
-                    ((depth_out *)out)->want_png ? ", image files made there" : "");
-        else if (format == NDT_HOST_IMAGE_APNG && ok)
-            fprintf(stderr, "ndt_render_image: bounds + kd-tree + flatten %.2f ms (%s), upload %.2f ms, render + the frame's bytes of the animated PNG to host %.2f ms (plan and file bytes on the GPU %.2f)\n",
-                    NDT_MS(ts0, ts1), share, NDT_MS(ts1, ts2), NDT_MS(ts2, ts3), g_apng_ms);
-        else if ((format == NDT_HOST_IMAGE_PNG || format == NDT_HOST_IMAGE_JPEG || format == NDT_HOST_IMAGE_PNG16 ||
-                  format == NDT_HOST_IMAGE_PNG16_DEPTH) && ok)
-            fprintf(stderr, "ndt_render_image: bounds + kd-tree + flatten %.2f ms (%s), upload %.2f ms, render + image file to host %.2f ms (image file on the GPU %.2f)\n",
-                    NDT_MS(ts0, ts1), share, NDT_MS(ts1, ts2), NDT_MS(ts2, ts3), format == NDT_HOST_IMAGE_JPEG ? g_jpeg_ms : g_png_ms);
+        char what[200];     /* one fprintf a line: the workers of -j K share stderr */
+        if (map8 && ok)
+            snprintf(what, sizeof(what), "8-bit image and depth map to host %.2f ms (depth map finished on the GPU %.2f%s)", NDT_MS(ts2, ts3),
+                     f->depth_ms, rq->colour == NDT_COLOUR_PNG ? ", image files made there" : "");
+        else if (rq->colour == NDT_COLOUR_APNG && ok)
+            snprintf(what, sizeof(what), "the frame's bytes of the animated PNG to host %.2f ms (plan and file bytes on the GPU %.2f)",
+                     NDT_MS(ts2, ts3), f->file_ms);
+        else if (rq->colour >= NDT_COLOUR_PNG && ok)
+            snprintf(what, sizeof(what), "image file to host %.2f ms (image file on the GPU %.2f)", NDT_MS(ts2, ts3), f->file_ms);
         else
-            fprintf(stderr, "ndt_render_image: bounds + kd-tree + flatten %.2f ms (%s), upload %.2f ms, render + image to host %.2f ms\n",
-                    NDT_MS(ts0, ts1), share, NDT_MS(ts1, ts2), NDT_MS(ts2, ts3));
-        if (ssaa != 1 && ok)
-            fprintf(stderr, "ndt_render_image: of the render, supersampling %dx%d: the folds on the GPU %.2f ms\n", ssaa, ssaa, g_ssaa_ms);
+            snprintf(what, sizeof(what), "image to host %.2f ms", NDT_MS(ts2, ts3));
+        fprintf(stderr, "ndt_render_image: bounds + kd-tree + flatten %.2f ms (%s), upload %.2f ms, render + %s\n", NDT_MS(ts0, ts1), share,
+                NDT_MS(ts1, ts2), what);
+        if (rq->ssaa != 1 && ok)
+            fprintf(stderr, "ndt_render_image: of the render, supersampling %dx%d: the folds on the GPU %.2f ms\n", rq->ssaa, rq->ssaa, f->ssaa_ms);
     }
     ndt_flat_builder_free(&fb);
+    if (!ok) ndt_frame_free(f);
     return ok;
-}
-
-/* everything render_image takes (ndt.c:900): samples = `-n`, stereo = the reference's stereo_mode (MONO ..
- * ANAGLYPH_3D), specular = specular_enabled (`-p` clears it), depth = the depth map of `-z` (width*height doubles) or NULL */
-int ndt_render_image_full(scene *scn, int width, int height, int samples, int threads, int aa_diff, int aa_depth, int stereo,
-                          int specular, int max_optic_depth, double *rgba, double *depth)
-{
-    /* (the pthread fan-out of ndt.c:949-975 is the GPU's job now; `threads` fits the scene's bounding spheres in parallel) */
-    return render_any(scn, width, height, samples, aa_diff, aa_depth, stereo, specular, max_optic_depth, NDT_IMAGE_F64, rgba, depth, threads, 1);
-}
-
-int ndt_render_image_rgba8(scene *scn, int width, int height, int samples, int threads, int aa_diff, int aa_depth, int stereo,
-                           int specular, int max_optic_depth, unsigned char *rgba8)
-{
-    return render_any(scn, width, height, samples, aa_diff, aa_depth, stereo, specular, max_optic_depth, NDT_IMAGE_RGBA8, rgba8, NULL, threads, 1);
-}
-
-int ndt_render_image_depth8(scene *scn, int width, int height, int samples, int threads, int aa_diff, int aa_depth, int stereo,
-                            int specular, int max_optic_depth, int want_png, int want_depth_png, ndt_depth_frame *out)
-{
-    depth_out d = { out, want_png != 0, want_png && want_depth_png };
-    memset(out, 0, sizeof(*out));
-    g_depth_ms = 0.0;
-    if (!render_any(scn, width, height, samples, aa_diff, aa_depth, stereo, specular, max_optic_depth, NDT_HOST_IMAGE_DEPTH8, &d, NULL, threads, 1)) {
-        ndt_depth_frame_free(out);
-        return 0;
-    }
-    return 1;
-}
-
-int ndt_render_image_png(scene *scn, int width, int height, int samples, int threads, int aa_diff, int aa_depth, int stereo,
-                         int specular, int max_optic_depth, unsigned char **png, long long *png_bytes)
-{
-    png_out po = { png, png_bytes };
-    *png = NULL;
-    *png_bytes = 0;
-    return render_any(scn, width, height, samples, aa_diff, aa_depth, stereo, specular, max_optic_depth, NDT_HOST_IMAGE_PNG, &po, NULL, threads, 1);
-}
-
-int ndt_render_image_jpeg(scene *scn, int width, int height, int samples, int threads, int aa_diff, int aa_depth, int stereo,
-                          int specular, int max_optic_depth, int quality, int sampling, unsigned char **jpg, long long *jpg_bytes)
-{
-    jpeg_out jo = { jpg, jpg_bytes, jpeg_params_of(quality, sampling) };
-    *jpg = NULL;
-    *jpg_bytes = 0;
-    return render_any(scn, width, height, samples, aa_diff, aa_depth, stereo, specular, max_optic_depth, NDT_HOST_IMAGE_JPEG, &jo, NULL, threads, 1);
-}
-
-/* ---- the same calls for a frame supersampled ssaa x ssaa on the GPU (no -a beside it: the library refuses the pair) */
-int ndt_render_image_ssaa_full(scene *scn, int width, int height, int samples, int threads, int stereo, int specular, int max_optic_depth,
-                               int ssaa, double *rgba, double *depth)
-{
-    return render_any(scn, width, height, samples, -1, -1, stereo, specular, max_optic_depth, NDT_IMAGE_F64, rgba, depth, threads, ssaa);
-}
-
-int ndt_render_image_ssaa_rgba8(scene *scn, int width, int height, int samples, int threads, int stereo, int specular, int max_optic_depth,
-                                int ssaa, unsigned char *rgba8)
-{
-    return render_any(scn, width, height, samples, -1, -1, stereo, specular, max_optic_depth, NDT_IMAGE_RGBA8, rgba8, NULL, threads, ssaa);
-}
-
-int ndt_render_image_ssaa_png(scene *scn, int width, int height, int samples, int threads, int stereo, int specular, int max_optic_depth,
-                              int ssaa, unsigned char **png, long long *png_bytes)
-{
-    png_out po = { png, png_bytes };
-    *png = NULL;
-    *png_bytes = 0;
-    return render_any(scn, width, height, samples, -1, -1, stereo, specular, max_optic_depth, NDT_HOST_IMAGE_PNG, &po, NULL, threads, ssaa);
-}
-
-int ndt_render_image_ssaa_jpeg(scene *scn, int width, int height, int samples, int threads, int stereo, int specular, int max_optic_depth,
-                               int ssaa, int quality, int sampling, unsigned char **jpg, long long *jpg_bytes)
-{
-    jpeg_out jo = { jpg, jpg_bytes, jpeg_params_of(quality, sampling) };
-    *jpg = NULL;
-    *jpg_bytes = 0;
-    return render_any(scn, width, height, samples, -1, -1, stereo, specular, max_optic_depth, NDT_HOST_IMAGE_JPEG, &jo, NULL, threads, ssaa);
-}
-
-int ndt_render_image_ssaa_depth8(scene *scn, int width, int height, int samples, int threads, int stereo, int specular, int max_optic_depth,
-                                 int ssaa, int want_png, int want_depth_png, ndt_depth_frame *out)
-{
-    depth_out d = { out, want_png != 0, want_png && want_depth_png };
-    memset(out, 0, sizeof(*out));
-    g_depth_ms = 0.0;
-    if (!render_any(scn, width, height, samples, -1, -1, stereo, specular, max_optic_depth, NDT_HOST_IMAGE_DEPTH8, &d, NULL, threads, ssaa)) {
-        ndt_depth_frame_free(out);
-        return 0;
-    }
-    return 1;
-}
-
-/* ---- the frame's files at 16 bits a sample (`ndt_hip --png16`); ssaa = 1: the plain frame, with -a when aa_depth >= 0 */
-int ndt_render_image_png16(scene *scn, int width, int height, int samples, int threads, int aa_diff, int aa_depth, int stereo,
-                           int specular, int max_optic_depth, int ssaa, unsigned char **png, long long *png_bytes)
-{
-    png_out po = { png, png_bytes };
-    *png = NULL;
-    *png_bytes = 0;
-    return render_any(scn, width, height, samples, aa_diff, aa_depth, stereo, specular, max_optic_depth, NDT_HOST_IMAGE_PNG16, &po, NULL, threads, ssaa);
-}
-
-int ndt_render_image_png16_depth(scene *scn, int width, int height, int samples, int threads, int aa_diff, int aa_depth, int stereo,
-                                 int specular, int max_optic_depth, int ssaa, ndt_depth_frame *out)
-{
-    memset(out, 0, sizeof(*out));
-    g_depth_ms = 0.0;
-    if (!render_any(scn, width, height, samples, aa_diff, aa_depth, stereo, specular, max_optic_depth, NDT_HOST_IMAGE_PNG16_DEPTH, out, NULL, threads, ssaa)) {
-        ndt_depth_frame_free(out);
-        return 0;
-    }
-    return 1;
-}
-
-/* ---- the next frame of the animated PNG ndt_apng_begin opened (`ndt_hip --apng`); ssaa = 1: the plain frame, with -a when aa_depth >= 0 */
-int ndt_render_image_apng_frame(scene *scn, int width, int height, int samples, int threads, int aa_diff, int aa_depth, int stereo,
-                                int specular, int max_optic_depth, int ssaa, unsigned char **bytes, long long *n_bytes)
-{
-    png_out po = { bytes, n_bytes };
-    *bytes = NULL;
-    *n_bytes = 0;
-    return render_any(scn, width, height, samples, aa_diff, aa_depth, stereo, specular, max_optic_depth, NDT_HOST_IMAGE_APNG, &po, NULL, threads, ssaa);
 }
