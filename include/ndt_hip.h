@@ -550,6 +550,54 @@ int ndt_hip_render_apng_frame(ndt_hip_ctx *ctx, const ndt_render_params *p, int3
                               ndt_apng_stats *stats, ndt_render_stats *render_stats);
 int ndt_hip_apng_end(ndt_hip_ctx *ctx, uint8_t *out, int64_t cap, int64_t *bytes);
 
+/* The frame as an OpenEXR file made on the device (`ndt_hip --exr`): the double framebuffer as it is, in linear light -- no clamp to
+ * 0 .. 1 and no square root, which every other file passes through -- and the depth map of `-z` unstretched, as a channel of the
+ * same file.  A single-part scanline file of version 2, little-endian: magic 76 2f 31 01, version word 2, the attributes channels,
+ * compression (3: ZIP, 16 scanlines a block), dataWindow and displayWindow (0, 0, width - 1, rows - 1), lineOrder (0),
+ * pixelAspectRatio (1), screenWindowCenter (0, 0), screenWindowWidth (1); one uint64 file offset per block; the blocks in order,
+ * each int32 y of its first line, int32 dataSize, data.  Channels in the file's (alphabetical) order: A B G R, all HALF or all
+ * FLOAT by ndt_exr_params, and Z, always FLOAT, when a map is given.
+ *   FLOAT   (float)x, to nearest even (a double beyond the float range becomes an infinity, as the conversion defines)
+ *   HALF    x clamped to +-65504, then rounded directly to binary16, to nearest even -- not through float, which rounds twice;
+ *           no infinity is written, and a NaN becomes 0x7e00
+ * A block's raw bytes are, per scanline, per channel in that order, `width` samples.  They are compressed as the format defines:
+ * the even bytes, then the odd ones; the delta predictor out[i] = T[i] - T[i-1] + 128; one zlib stream a block, made by the
+ * deflate of the PNG files (independent 32 KiB chunks, a dynamic Huffman code a chunk) with its matches at distance 2, the period
+ * the two byte planes give equal float samples (equal half samples are runs of one byte, which that matches too).  A block whose
+ * stream is not shorter than its raw bytes holds the raw bytes (dataSize = their count): the format's own rule.
+ *   ndt_hip_exr_bound          the largest file for width x rows (host arithmetic: every block raw); < 0 (NDT_E_INVALID) for a bad
+ *                              pixel type, a size below 1 or raw bytes beyond 2^31 - 1
+ *   ndt_hip_encode_exr_device  the file of rows x width x 4 doubles (R G B A) and, when d_depth is not NULL, rows x width doubles
+ *                              of map, both in the context's device memory, aligned to 8 bytes.  4 kernel launches; the host
+ *                              reads an info record, then exactly the file's bytes.  No scene is needed
+ *   ndt_hip_encode_exr         the same from host memory
+ *   ndt_hip_render_exr         ndt_hip_render_device (with_depth: ndt_hip_render_depth_device) and the encoder: recursive_aa,
+ *                              samples and stereo are just another double framebuffer; a row shard gives the file of its rows
+ *   ndt_hip_render_ssaa_exr    the same for the frame supersampled K x K (ndt_hip_render_ssaa_device; Z is sub-sample (0, 0)'s)
+ * ep may be NULL (half).  NDT_E_INVALID: a NULL pointer, a pixel type other than 0, 1, 2, a size below 1, a pointer off its
+ * doubles.  NDT_E_NOMEM: `cap` is below the file; stats->file_bytes and the error text carry the size needed and nothing is
+ * written to `out`.  stats (may be NULL): file_bytes, raw_bytes = the samples' bytes, blocks, blocks_raw = blocks that fell back
+ * to raw bytes, launches, ms = host time of the encoder.  Device buffers belong to the context, only grow and are reused.  None
+ * falls back. */
+typedef struct ndt_exr_params {
+    int32_t pixel_type;             /* 1 half, 2 float; 0 = half */
+    int32_t reserved[3];
+} ndt_exr_params;
+typedef struct ndt_exr_stats {
+    int64_t file_bytes, raw_bytes;
+    int32_t blocks, blocks_raw, launches, pad;
+    double ms;
+} ndt_exr_stats;
+int64_t ndt_hip_exr_bound(int32_t width, int32_t rows, const ndt_exr_params *ep, int32_t with_depth);
+int ndt_hip_encode_exr_device(ndt_hip_ctx *ctx, const void *d_rgba, const void *d_depth, int32_t width, int32_t rows,
+                              const ndt_exr_params *ep, uint8_t *out, int64_t cap, ndt_exr_stats *stats);
+int ndt_hip_encode_exr(ndt_hip_ctx *ctx, const double *rgba, const double *depth, int32_t width, int32_t rows, const ndt_exr_params *ep,
+                       uint8_t *out, int64_t cap, ndt_exr_stats *stats);
+int ndt_hip_render_exr(ndt_hip_ctx *ctx, const ndt_render_params *p, const ndt_exr_params *ep, int32_t with_depth, uint8_t *out,
+                       int64_t cap, ndt_exr_stats *stats, ndt_render_stats *render_stats);
+int ndt_hip_render_ssaa_exr(ndt_hip_ctx *ctx, const ndt_render_params *p, int32_t K, const ndt_exr_params *ep, int32_t with_depth,
+                            uint8_t *out, int64_t cap, ndt_exr_stats *stats, ndt_render_stats *render_stats);
+
 /* ONE frame over several contexts -- one per GPU of the node, or several on one GPU -- called from one host thread.
  * The rows `p` selects are dealt cyclically to the contexts exactly as the reference deals rows to MPI ranks in
  * MPI_MODE_ROW (ndt.c:812-820: row_start = rank, row_step = size): context k renders rows

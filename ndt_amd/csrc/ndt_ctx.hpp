@@ -15,6 +15,9 @@
 //   ndt_apng.hip     ndt_hip_apng_* / ndt_hip_render_apng_frame: a frame sequence as one animated PNG, the difference between frames
 //                    found on the device; kernels, launcher and C ABI
 //   ndt_jpeg.hip     ndt_hip_encode_jpeg* / ndt_hip_render_jpeg: a frame's JPEG file made on the device; kernels, launcher and C ABI
+//   ndt_exr.hip      ndt_hip_encode_exr* / ndt_hip_render_exr: a frame's OpenEXR file (linear half or float samples, the map as its Z
+//                    channel) made on the device; kernels, launcher and C ABI
+//   ndt_deflate.hpp  the deflate of a 32 KiB chunk that ndt_png.hip and ndt_exr.hip share (device code)
 //   ndt_depth.hip    ndt_hip_depth_rgba8_device / ndt_hip_render_*_depth: the depth map of `-z` normalised and quantised on the device
 //   ndt_ssaa.hip     ndt_hip_ssaa_fold_device / ndt_hip_render_ssaa*: K x K supersampling, K ordinary renders folded on the device
 //   ndt_buffer.hpp   DeviceBuffer: the grow-only device buffers of the context and of its sinks, their one grow and free path
@@ -93,6 +96,14 @@ struct ApngState {
 // ndt_hip_encode_jpeg* (ndt_jpeg.hip): grow-only device buffers, reused by the next frame
 struct JpegState {
     DeviceBuffer d_rgba8, d_coef, d_slots, d_meta, d_offsets, d_file, d_info;
+    void *h_info = nullptr;         // pinned: the info record of the last file
+};
+
+// ndt_hip_encode_exr* (ndt_exr.hip): grow-only device buffers, reused by the next frame
+struct ExrState {
+    DeviceBuffer d_in;              // ndt_hip_encode_exr: the doubles (and the map behind them) that arrive from host memory
+    DeviceBuffer d_packed;          // every block's bytes as the format compresses them, each block on a chunk boundary
+    DeviceBuffer d_slots, d_meta, d_offsets, d_blocks, d_file, d_info;
     void *h_info = nullptr;         // pinned: the info record of the last file
 };
 
@@ -210,6 +221,7 @@ struct ndt_hip_ctx {
     PngState png;                   // ndt_hip_encode_png*, ndt_hip_render_png
     ApngState apng;                 // ndt_hip_apng_*, ndt_hip_render_apng_frame
     JpegState jpeg;                 // ndt_hip_encode_jpeg*, ndt_hip_render_jpeg
+    ExrState exr;                   // ndt_hip_encode_exr*, ndt_hip_render_exr, ndt_hip_render_ssaa_exr
     DepthState depth;               // ndt_hip_depth_rgba8_device, ndt_hip_render_*_depth
     SsaaState ssaa;                 // ndt_hip_render_ssaa*
     DeviceBuffer d_out;             // staging of a frame in doubles (and its map behind it) for the calls that deliver to host memory
@@ -307,6 +319,9 @@ void free_apng(ndt_hip_ctx *ctx);
 
 // ndt_jpeg.hip
 void free_jpeg(ndt_hip_ctx *ctx);
+
+// ndt_exr.hip
+void free_exr(ndt_hip_ctx *ctx);
 
 // ndt_depth.hip
 void free_depth(ndt_hip_ctx *ctx);

@@ -32,6 +32,7 @@ API_SYMBOLS = [
     "ndt_hip_quantize16_device", "ndt_hip_depth_grey16_device", "ndt_hip_png16_bound", "ndt_hip_encode_png16_device", "ndt_hip_encode_png16",
     "ndt_hip_render_png16", "ndt_hip_render_png16_depth", "ndt_hip_render_ssaa_png16", "ndt_hip_render_ssaa_png16_depth",
     "ndt_hip_apng_bound", "ndt_hip_apng_begin", "ndt_hip_apng_add_device", "ndt_hip_apng_add", "ndt_hip_render_apng_frame", "ndt_hip_apng_end",
+    "ndt_hip_exr_bound", "ndt_hip_encode_exr_device", "ndt_hip_encode_exr", "ndt_hip_render_exr", "ndt_hip_render_ssaa_exr",
 ]
 
 IMAGE_F64, IMAGE_RGBA8 = 0, 1      # enum ndt_image_format
@@ -157,6 +158,15 @@ def load_library():
         lib.ndt_hip_apng_add.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
         lib.ndt_hip_render_apng_frame.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
         lib.ndt_hip_apng_end.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
+    if hasattr(lib, "ndt_hip_exr_bound"):           # (absent from earlier builds, which profiles/ab_libs.sh loads to compare)
+        lib.ndt_hip_exr_bound.argtypes = [C.c_int32, C.c_int32, C.c_void_p, C.c_int32]
+        lib.ndt_hip_exr_bound.restype = C.c_int64
+        lib.ndt_hip_encode_exr_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64,
+                                                  C.c_void_p]
+        lib.ndt_hip_encode_exr.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
+        lib.ndt_hip_render_exr.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
+        lib.ndt_hip_render_ssaa_exr.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p,
+                                                C.c_void_p]
     _lib = lib
     return lib
 
@@ -189,6 +199,36 @@ class JpegStats(C.Structure):
     """ndt_jpeg_stats: what the device encoder says about the file it made"""
     _fields_ = [("jpeg_bytes", C.c_int64), ("scan_bytes", C.c_int64), ("stuffed_bytes", C.c_int64), ("mcus", C.c_int32),
                 ("intervals", C.c_int32), ("launches", C.c_int32), ("passes_max", C.c_int32), ("encode_ms", C.c_double)]
+
+
+class ExrParams(C.Structure):
+    """ndt_exr_params: pixel_type of the colour channels, 1 half / 2 float (0 = half)"""
+    _fields_ = [("pixel_type", C.c_int32), ("reserved", C.c_int32 * 3)]
+
+
+class ExrStats(C.Structure):
+    """ndt_exr_stats: what the device encoder says about the OpenEXR file it made"""
+    _fields_ = [("file_bytes", C.c_int64), ("raw_bytes", C.c_int64), ("blocks", C.c_int32), ("blocks_raw", C.c_int32),
+                ("launches", C.c_int32), ("pad", C.c_int32), ("ms", C.c_double)]
+
+
+EXR_PIXEL = {"half": 1, "float": 2}
+
+
+def exr_params(pixel="half"):
+    """The ndt_exr_params of pixel "half" or "float"; ValueError for anything else."""
+    if str(pixel) not in EXR_PIXEL:
+        raise ValueError("EXR pixel %r is neither 'half' nor 'float'" % (pixel,))
+    return ExrParams(EXR_PIXEL[str(pixel)])
+
+
+def exr_bound(width, rows, pixel="half", depth_map=False):
+    """ndt_hip_exr_bound: the largest OpenEXR file the device encoder can produce for a width x rows image (host arithmetic)."""
+    ep = exr_params(pixel)
+    n = int(load_library().ndt_hip_exr_bound(int(width), int(rows), C.byref(ep), 1 if depth_map else 0))
+    if n < 0:
+        raise ValueError("no EXR of %d x %d: the size is empty or its samples exceed 2^31 - 1 bytes" % (width, rows))
+    return n
 
 
 JPEG_SAMPLING = {"420": 0, "444": 1}
@@ -584,6 +624,65 @@ class NdtHip:
         self._check(self.lib.ndt_hip_render_ssaa_png16_depth(self.ctx, C.byref(p), int(ssaa), out.ctypes.data, cap, dpng.ctypes.data,
                                                              depth_cap, C.byref(self.png_stats), rng.ctypes.data, C.byref(st)))
         return out[:self.png_stats[0].png_bytes].tobytes(), dpng[:self.png_stats[1].png_bytes].tobytes(), rng, st
+
+    def encode_exr(self, rgba, depth=None, pixel="half", cap=None):
+        """ndt_hip_encode_exr: the complete OpenEXR file of a (rows, width, 4) float64 host image in linear light and, with `depth`,
+        a (rows, width) float64 map as its Z channel, made on this context's GPU.  Returns the file's bytes; self.exr_stats keeps
+        the ndt_exr_stats.  cap: room offered (default: ndt_hip_exr_bound)."""
+        rgba = np.ascontiguousarray(rgba, dtype=np.float64)
+        if rgba.ndim != 3 or rgba.shape[2] != 4:
+            raise ValueError("rgba must be (rows, width, 4)")
+        rows, width = rgba.shape[:2]
+        if depth is not None:
+            depth = np.ascontiguousarray(depth, dtype=np.float64)
+            if depth.shape != (rows, width):
+                raise ValueError("depth must be (rows, width)")
+        ep = exr_params(pixel)
+        cap = exr_bound(width, rows, pixel, depth is not None) if cap is None else int(cap)
+        out = np.zeros(max(cap, 1), dtype=np.uint8)
+        self.exr_stats = ExrStats()
+        self._check(self.lib.ndt_hip_encode_exr(self.ctx, rgba.ctypes.data, depth.ctypes.data if depth is not None else None, width, rows,
+                                                C.byref(ep), out.ctypes.data, cap, C.byref(self.exr_stats)))
+        return out[:self.exr_stats.file_bytes].tobytes()
+
+    def encode_exr_device(self, d_rgba_ptr, d_depth_ptr, width, rows, pixel="half", cap=None):
+        """ndt_hip_encode_exr_device: the same for rows * width * 4 doubles at raw device pointer `d_rgba_ptr` and, unless
+        `d_depth_ptr` is None, rows * width doubles of map there."""
+        ep = exr_params(pixel)
+        cap = exr_bound(width, rows, pixel, d_depth_ptr is not None) if cap is None else int(cap)
+        out = np.zeros(max(cap, 1), dtype=np.uint8)
+        self.exr_stats = ExrStats()
+        self._check(self.lib.ndt_hip_encode_exr_device(self.ctx, C.c_void_p(d_rgba_ptr), C.c_void_p(d_depth_ptr) if d_depth_ptr else None,
+                                                       int(width), int(rows), C.byref(ep), out.ctypes.data, cap, C.byref(self.exr_stats)))
+        return out[:self.exr_stats.file_bytes].tobytes()
+
+    def render_exr(self, width, height, depth, pixel="half", depth_map=False, **kw):
+        """ndt_hip_render_exr: render() with the device's OpenEXR encoder in place of the download; depth_map=True adds the map as
+        the file's Z channel.  Returns (the file's bytes, RenderStats); self.exr_stats keeps the ndt_exr_stats.  The file's height
+        is the row shard's."""
+        p = self.params(width, height, depth, **kw)
+        rows = shard_rows(height, p.row_begin, p.row_step)
+        ep = exr_params(pixel)
+        cap = exr_bound(width, rows, pixel, depth_map)
+        out = np.zeros(cap, dtype=np.uint8)
+        st = RenderStats()
+        self.exr_stats = ExrStats()
+        self._check(self.lib.ndt_hip_render_exr(self.ctx, C.byref(p), C.byref(ep), 1 if depth_map else 0, out.ctypes.data, cap,
+                                                C.byref(self.exr_stats), C.byref(st)))
+        return out[:self.exr_stats.file_bytes].tobytes(), st
+
+    def render_ssaa_exr(self, width, height, depth, ssaa, pixel="half", depth_map=False, **kw):
+        """ndt_hip_render_ssaa_exr: the supersampled frame as an OpenEXR file (Z: sub-sample (0, 0)'s map): (the file's bytes, stats);
+        self.exr_stats keeps the record."""
+        p, rows = self._ssaa_params(width, height, depth, kw)
+        ep = exr_params(pixel)
+        cap = exr_bound(width, rows, pixel, depth_map)
+        out = np.zeros(cap, dtype=np.uint8)
+        st = RenderStats()
+        self.exr_stats = ExrStats()
+        self._check(self.lib.ndt_hip_render_ssaa_exr(self.ctx, C.byref(p), int(ssaa), C.byref(ep), 1 if depth_map else 0, out.ctypes.data,
+                                                     cap, C.byref(self.exr_stats), C.byref(st)))
+        return out[:self.exr_stats.file_bytes].tobytes(), st
 
     def apng_begin(self, width, rows, n_frames, delay_num=1, delay_den=24, n_plays=0):
         """ndt_hip_apng_begin: opens the context's animated-PNG session: n_frames frames of width x rows pixels are to come, each

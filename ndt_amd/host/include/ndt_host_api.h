@@ -401,8 +401,10 @@ typedef enum ndt_colour_kind {
     NDT_COLOUR_PNG,         /* file: a complete PNG file compressed on the GPU (`ndt_hip --png --deflate gpu`) */
     NDT_COLOUR_JPEG,        /* file: the baseline JPEG file the reference's libjpeg writer saves, made on the GPU (`--jpeg`) */
     NDT_COLOUR_PNG16,       /* file: a PNG file of 16 bits a sample, made on the GPU from the double framebuffer (`--png16`) */
-    NDT_COLOUR_APNG         /* file: the next frame's bytes of the animated PNG ndt_apng_begin opened: the rectangle that
+    NDT_COLOUR_APNG,        /* file: the next frame's bytes of the animated PNG ndt_apng_begin opened: the rectangle that
                              * changed since the previous frame, compressed (`--apng`) */
+    NDT_COLOUR_EXR          /* file: an OpenEXR file of the doubles in linear light, half or float samples (exr_pixel), made on the
+                             * GPU (`--exr`); with NDT_MAP_EXR_Z the depth map is its Z channel */
 } ndt_colour_kind;
 /* ... and `map` how the depth map of `-z` does: */
 typedef enum ndt_map_kind {
@@ -410,11 +412,12 @@ typedef enum ndt_map_kind {
     NDT_MAP_F64,            /* depth: width*height doubles, as render_image leaves them (the caller normalises) */
     NDT_MAP_DEPTH8,         /* depth8: stretched to 0 .. 1 and quantised on the GPU, width*height*4 bytes g, g, g, 255 (`--depth gpu`) */
     NDT_MAP_PNG,            /* depth_file: that image as a PNG file compressed on the GPU (`--depth-png`) */
-    NDT_MAP_PNG16           /* depth_file: the map as a 16-bit grey PNG file (`--png16 --depth-png`) */
+    NDT_MAP_PNG16,          /* depth_file: the map as a 16-bit grey PNG file (`--png16 --depth-png`) */
+    NDT_MAP_EXR_Z           /* no file and no pixels of its own: the map as it is, in floats, is the Z channel of the OpenEXR file */
 } ndt_map_kind;
 /* The pairs a device call serves: doubles with no map or the map in doubles; 8-bit RGBA with none or 8-bit grey; a PNG file with
  * none, 8-bit grey or a PNG file; a JPEG file and an animated PNG frame with none; a 16-bit PNG file with none or a 16-bit PNG
- * file.  Any other pair is refused with a message that names both fields. */
+ * file; an OpenEXR file with none or its Z channel.  Any other pair is refused with a message that names both fields. */
 typedef struct ndt_frame_request {
     int width, height;
     int samples;                    /* -n */
@@ -429,6 +432,7 @@ typedef struct ndt_frame_request {
     ndt_colour_kind colour;
     ndt_map_kind map;
     int jpeg_quality, jpeg_sampling;    /* NDT_COLOUR_JPEG: 1 .. 100 (0 = the reference's 95); 0 = 4:2:0 (libjpeg's default), 1 = 4:4:4 */
+    int exr_pixel;                      /* NDT_COLOUR_EXR: the colour channels' samples, 1 half, 2 float (0 = half) */
 } ndt_frame_request;
 /* Everything that arrives is malloc'ed by the library and freed by ndt_frame_free; what was not asked for stays NULL. */
 typedef struct ndt_frame {
@@ -444,9 +448,9 @@ typedef struct ndt_frame {
  * is left to free.  No fallback: without a device, or with a frame the device path refuses (HIDEF frame packing supersampled, ...),
  * it fails.  A frame is spread over the calling thread's contexts (ndt_render_use_devices): the rows meet on the host as doubles or
  * as 8-bit pixels, and a PNG or JPEG file is then encoded from those on the first context; a frame with a map is rendered by one
- * context whatever was set, and a 16-bit PNG or an animated PNG frame over several contexts is refused.  What the device did is
- * said on stdout: `compressed PNG of B bytes on GPU D in L launches` (`16-bit PNG`, `depth PNG`, `16-bit depth PNG`), `encoded
- * JPEG of ...`, `finished depth map [lo, hi] on GPU D in L launches`, `supersampled KxK on GPU D in L launches`, `animated PNG frame
+ * context whatever was set, and a 16-bit PNG, an OpenEXR file or an animated PNG frame over several contexts is refused.  What the
+ * device did is said on stdout: `compressed PNG of B bytes on GPU D in L launches` (`16-bit PNG`, `depth PNG`, `16-bit depth PNG`),
+ * `encoded JPEG of ...`, `encoded EXR of ...`, `finished depth map [lo, hi] on GPU D in L launches`, `supersampled KxK on GPU D in L launches`, `animated PNG frame
  * K: w x h at x,y (B bytes) on GPU D in L launches`. */
 int ndt_render_frame(scene *scn, const ndt_frame_request *request, ndt_frame *out);
 /* safe on a zeroed or a half-filled frame; leaves it zeroed */

@@ -20,8 +20,12 @@
  * PNG, images/<scene>/<N>d/<WxH>/<scene>_<WxH>.apng, instead of a file a frame: the GPU keeps the previous frame, finds the
  * rectangle that changed and compresses only that (ndt_hip_render_apng_frame); `--apng-fps F` (1 .. 1000, default 24) shows each
  * frame 1 / F seconds.  With --ssaa, -a, -n, -m and --fit / --kd gpu; it is the run's one colour file (not with --png, --jpeg,
- * --raw, --png16 or -z), and its frames meet one canvas in order (not with -g N > 1 or -j K > 1).  None falls back: what the
- * device path cannot do ends the run. */
+ * --raw, --png16 or -z), and its frames meet one canvas in order (not with -g N > 1 or -j K > 1).  `--exr` writes every frame as an
+ * OpenEXR file, ....exr where the PNG would be: the doubles as they are, in linear light (no clamp, no square root), as half samples
+ * or with `--exr-pixel float` as floats, ZIP-compressed on the GPU (ndt_hip_render_exr); with `-z` the map is the file's Z channel,
+ * unstretched, and no depth/ file is written.  With --ssaa, -a, -n, -m s|o|a and -j; it is the run's colour file (not with --png,
+ * --jpeg, --raw, --png16 or --apng), the map needs no finish (not with --depth gpu or --depth-png), and one context makes it (not
+ * with -g N > 1).  None falls back: what the device path cannot do ends the run. */
 #include <dlfcn.h>
 #include <getopt.h>
 #include <pthread.h>
@@ -160,7 +164,7 @@ static int save_colour(const scene *scn, int i, ndt_frame *f)
     if (kind == NDT_COLOUR_PNG && on_host && !ndt_encode_image_png(f->rgba8, width, height, &f->file, &f->file_bytes, &f->file_ms)) return 0;
     image_dir(dir, sizeof(dir), scn);
     snprintf(path, sizeof(path), "%s/%s_%ix%i_%04i.%s", dir, scn->name, width, height, i,
-             kind == NDT_COLOUR_JPEG ? "jpg" : job_opts.png ? "png" : "ppm");
+             kind == NDT_COLOUR_EXR ? "exr" : kind == NDT_COLOUR_JPEG ? "jpg" : job_opts.png ? "png" : "ppm");
     if (f->file) {
         if (!write_bytes(path, "wb", f->file, (size_t)f->file_bytes)) return 0;
     } else if (job_opts.png) write_png(path, f->rgba8, width, height);
@@ -170,7 +174,7 @@ static int save_colour(const scene *scn, int i, ndt_frame *f)
         /* a file made where the image is: the encoder's share is inside "rendering took" */
         const double ms = (now_s() - t_file) * 1e3;
         if (f->file) fprintf(stderr, "ndt_hip: image file %.2f ms (%s on the GPU %.2f, written %.2f)\n", on_host ? ms : ms + f->file_ms,
-                             kind == NDT_COLOUR_JPEG ? "JPEG made" : "compressed", f->file_ms, on_host ? ms - f->file_ms : ms);
+                             kind == NDT_COLOUR_JPEG ? "JPEG made" : kind == NDT_COLOUR_EXR ? "EXR made" : "compressed", f->file_ms, on_host ? ms - f->file_ms : ms);
         else fprintf(stderr, "ndt_hip: image file %.2f ms (%s, made and written by the host)\n", ms, job_opts.png ? "stored PNG" : "PPM");
     }
     return 1;
@@ -233,7 +237,7 @@ static int render_frame(scene *scn, int i)
     /* doubles came back: the host makes the bytes of the colour file */
     if (f.rgba) f.rgba8 = quantise(f.rgba, (long)frame_request.width * frame_request.height * 4);
     printf("rendering took %.3fs\n", now_s() - t0);
-    const int ok = save_colour(scn, i, &f) && (frame_request.map == NDT_MAP_NONE || save_map(scn, i, &f)) &&
+    const int ok = save_colour(scn, i, &f) && (frame_request.map == NDT_MAP_NONE || frame_request.map == NDT_MAP_EXR_Z || save_map(scn, i, &f)) &&
                    (!job_opts.raw_path || save_raw(&f));
     ndt_frame_free(&f);
     return ok;
@@ -413,6 +417,8 @@ int main(int argc, char **argv)
     int png16 = 0;          /* --png16: the PNG files at 16 bits a sample, made on the GPU from the doubles (needs --png --deflate gpu) */
     int apng = 0;           /* --apng: all frames of the run in one animated PNG, the difference between frames found on the GPU */
     int apng_fps = 0;       /* --apng-fps 1 .. 1000 (default 24): each frame is shown 1 / F seconds */
+    int exr = 0;            /* --exr: the frame's file is an OpenEXR file of the doubles in linear light, made on the GPU; with -z the map is its Z channel */
+    int exr_pixel = 0;      /* --exr-pixel half|float: the colour channels' samples, 1 / 2 (default: half) */
     char *objects_dir = "objects";      /* -o: where object plugins are looked for (object.c:119; ndt.c passes "objects") */
     static struct option longopts[] = { { "dump-scene", required_argument, NULL, 1000 },
                                         { "raw", required_argument, NULL, 1001 }, { "png", no_argument, NULL, 1002 },
@@ -422,7 +428,8 @@ int main(int argc, char **argv)
                                         { "jpeg", no_argument, NULL, 1008 }, { "jpeg-quality", required_argument, NULL, 1009 },
                                         { "jpeg-sampling", required_argument, NULL, 1010 }, { "ssaa", required_argument, NULL, 1011 },
                                         { "png16", no_argument, NULL, 1012 }, { "apng", no_argument, NULL, 1013 },
-                                        { "apng-fps", required_argument, NULL, 1014 },
+                                        { "apng-fps", required_argument, NULL, 1014 }, { "exr", no_argument, NULL, 1015 },
+                                        { "exr-pixel", required_argument, NULL, 1016 },
                                         { NULL, 0, NULL, 0 } };
     int ch;
     while ((ch = getopt_long(argc, argv, "a:d:g:r:f:j:l:m:3:n:ps:t:u:o:zh", longopts, NULL)) != -1) {
@@ -531,14 +538,38 @@ int main(int argc, char **argv)
             apng_fps = (int)f;
             break;
         }
+        case 1015: exr = 1; break;
+        case 1016:
+            if (!strcmp(optarg, "half")) exr_pixel = 1;
+            else if (!strcmp(optarg, "float")) exr_pixel = 2;
+            else { fprintf(stderr, "%s: --exr-pixel takes half or float, not '%s'\n", argv[0], optarg); return 1; }
+            break;
         default:
             fprintf(stderr, "usage: %s -s scene.so|builtin:yaml [-d dims] [-r WxH|1080p|4k] [-f last|first:last[:total]] [-l depth]\n"
-                            "          [-a diff,depth] [-n samples] [-m s|o|a|m] [-p] [-z] [-j frames_in_flight] [-g gpus_per_frame] [-u config] [--dump-scene file.ndtscene] [--raw file.f64] [--png [--deflate stored|gpu]] [--jpeg [--jpeg-quality 1..100] [--jpeg-sampling 420|444]] [--fit host|gpu] [--kd host|gpu] [--depth host|gpu [--depth-png]] [--ssaa 1..8] [--png16] [--apng [--apng-fps 1..1000]]\n", argv[0]);
+                            "          [-a diff,depth] [-n samples] [-m s|o|a|m] [-p] [-z] [-j frames_in_flight] [-g gpus_per_frame] [-u config] [--dump-scene file.ndtscene] [--raw file.f64] [--png [--deflate stored|gpu]] [--jpeg [--jpeg-quality 1..100] [--jpeg-sampling 420|444]] [--fit host|gpu] [--kd host|gpu] [--depth host|gpu [--depth-png]] [--ssaa 1..8] [--png16] [--apng [--apng-fps 1..1000]] [--exr [--exr-pixel half|float]]\n", argv[0]);
             return ch == 'h' ? 0 : 1;
         }
     }
     if (!scene_path || dims < 3 || width < 1 || height < 1) {
         fprintf(stderr, "%s: need -s scene.so, dims >= 3 and a resolution\n", argv[0]);
+        return 1;
+    }
+    if (exr_pixel && !exr) {
+        fprintf(stderr, "%s: --exr-pixel sets the OpenEXR file's sample type: it needs --exr\n", argv[0]);
+        return 1;
+    }
+    if (exr && (png || jpeg || raw_path || png16 || apng)) {
+        fprintf(stderr, "%s: --exr with %s: the OpenEXR file is the run's colour file; this one is not written beside it: take one\n", argv[0],
+                png16 ? "--png16" : png ? "--png" : jpeg ? "--jpeg" : raw_path ? "--raw" : "--apng");
+        return 1;
+    }
+    if (exr && (depth_gpu || depth_png)) {
+        fprintf(stderr, "%s: --exr with %s: the map of -z is the file's Z channel as it is, in floats: it needs no finish\n", argv[0],
+                depth_gpu ? "--depth gpu" : "--depth-png");
+        return 1;
+    }
+    if (exr && gpus > 1) {
+        fprintf(stderr, "%s: --exr with -g %d: the rows of several contexts are gathered as 8-bit pixels or doubles; a float gather is not built: take -g 1 (or -j)\n", argv[0], gpus);
         return 1;
     }
     if (apng_fps && !apng) {
@@ -642,15 +673,16 @@ int main(int argc, char **argv)
      * comes back in doubles only when something asks for them (--raw, a depth map of -z that the host finishes): the file of
      * --jpeg or --png --deflate gpu is then encoded from the host's bytes; otherwise the GPU quantises and 4 bytes a pixel come
      * back instead of 32, or only the file does */
-    const int want_f64 = raw_path != NULL || (want_depth && !depth_gpu);
+    const int want_f64 = !exr && (raw_path != NULL || (want_depth && !depth_gpu));
     const ndt_colour_kind file_kind = jpeg ? NDT_COLOUR_JPEG : deflate_gpu ? NDT_COLOUR_PNG : NDT_COLOUR_F64;
     frame_request.width = width; frame_request.height = height; frame_request.samples = samples; frame_request.threads = threads;
     frame_request.aa_diff = aa_diff; frame_request.aa_depth = aa_depth; frame_request.stereo = stereo; frame_request.specular = specular;
     frame_request.max_optic_depth = depth; frame_request.ssaa = ssaa;
     frame_request.jpeg_quality = jpeg_quality; frame_request.jpeg_sampling = jpeg_sampling < 0 ? 0 : jpeg_sampling;
-    frame_request.colour = apng ? NDT_COLOUR_APNG : png16 ? NDT_COLOUR_PNG16 : want_f64 ? NDT_COLOUR_F64
+    frame_request.exr_pixel = exr_pixel;
+    frame_request.colour = exr ? NDT_COLOUR_EXR : apng ? NDT_COLOUR_APNG : png16 ? NDT_COLOUR_PNG16 : want_f64 ? NDT_COLOUR_F64
                          : file_kind != NDT_COLOUR_F64 ? file_kind : NDT_COLOUR_RGBA8;
-    frame_request.map = !want_depth ? NDT_MAP_NONE : !depth_gpu ? NDT_MAP_F64 : png16 ? NDT_MAP_PNG16 : depth_png ? NDT_MAP_PNG : NDT_MAP_DEPTH8;
+    frame_request.map = !want_depth ? NDT_MAP_NONE : exr ? NDT_MAP_EXR_Z : !depth_gpu ? NDT_MAP_F64 : png16 ? NDT_MAP_PNG16 : depth_png ? NDT_MAP_PNG : NDT_MAP_DEPTH8;
     job_opts.dims = dims; job_opts.raw_path = raw_path; job_opts.png = png;
     job_opts.host_file = want_f64 ? file_kind : NDT_COLOUR_F64;
     job_opts.gpus = gpus > 1 ? gpus : 1;

@@ -496,6 +496,38 @@ static int frame_apng(const ndt_render_params *p, const ndt_frame_request *rq, n
     return 1;
 }
 
+/* colour as an OpenEXR file of half or float samples in linear light, the map of -z as its Z channel if asked (ndt_hip_render_exr,
+ * ndt_hip_render_ssaa_exr; `ndt_hip --exr`) */
+static int frame_exr(const ndt_render_params *p, const ndt_frame_request *rq, ndt_frame *f)
+{
+    const int K = rq->ssaa, with_map = rq->map == NDT_MAP_EXR_Z;
+    ndt_exr_params ep;
+    ndt_exr_stats es;
+    memset(&ep, 0, sizeof(ep));
+    ep.pixel_type = rq->exr_pixel;
+    const int64_t cap = ndt_hip_exr_bound(p->width, p->height, &ep, with_map);
+    if (g_n_ctx > 1) {
+        /* (the rows of several contexts meet as 8-bit pixels or as doubles on the host: there is no float gather) */
+        fprintf(stderr, "ndt_render_frame: an OpenEXR file is made by one GPU context, not by %d\n", g_n_ctx);
+        return 0;
+    }
+    f->file = cap > 0 ? (unsigned char *)malloc((size_t)cap) : NULL;
+    if (!f->file) {
+        fprintf(stderr, "ndt_render_frame: no OpenEXR file of %d x %d with pixel type %d\n", p->width, p->height, rq->exr_pixel);
+        return 0;
+    }
+    if ((K != 1 ? ndt_hip_render_ssaa_exr(g_ctx[0], p, K, &ep, with_map, f->file, cap, &es, NULL)
+                : ndt_hip_render_exr(g_ctx[0], p, &ep, with_map, f->file, cap, &es, NULL)) != NDT_OK) return 0;
+    if (K != 1) {
+        f->ssaa_ms = ndt_hip_ssaa_ms(g_ctx[0]);
+        say_ssaa(K, ndt_hip_ssaa_launches(g_ctx[0]));
+    }
+    f->file_bytes = es.file_bytes;
+    f->file_ms = es.ms;
+    printf("encoded EXR of %lld bytes on GPU %d in %d launches\n", (long long)es.file_bytes, ndt_hip_device(g_ctx[0]), es.launches);
+    return 1;
+}
+
 /* the maps each colour kind comes with (bit m: ndt_map_kind m): the pairs a device call serves */
 #define MAP_BIT(m) (1u << (m))
 static const struct { const char *name; unsigned maps; } colour_kinds[] = {
@@ -505,8 +537,10 @@ static const struct { const char *name; unsigned maps; } colour_kinds[] = {
     { "JPEG file", MAP_BIT(NDT_MAP_NONE) },
     { "16-bit PNG file", MAP_BIT(NDT_MAP_NONE) | MAP_BIT(NDT_MAP_PNG16) },
     { "animated PNG frame", MAP_BIT(NDT_MAP_NONE) },
+    { "OpenEXR file", MAP_BIT(NDT_MAP_NONE) | MAP_BIT(NDT_MAP_EXR_Z) },
 };
-static const char *const map_kinds[] = { "none", "doubles", "8-bit grey finished on the GPU", "PNG file", "16-bit PNG file" };
+static const char *const map_kinds[] = { "none", "doubles", "8-bit grey finished on the GPU", "PNG file", "16-bit PNG file",
+                                         "the Z channel of the OpenEXR file" };
 
 int ndt_render_frame(scene *scn, const ndt_frame_request *rq, ndt_frame *f)
 {
@@ -517,10 +551,10 @@ int ndt_render_frame(scene *scn, const ndt_frame_request *rq, ndt_frame *f)
     const int timing = getenv("NDT_HOST_TIMING") != NULL;
     struct timespec ts0, ts1, ts2, ts3;
     memset(f, 0, sizeof(*f));
-    if ((unsigned)rq->colour > NDT_COLOUR_APNG || (unsigned)rq->map > NDT_MAP_PNG16 || !(colour_kinds[rq->colour].maps & MAP_BIT(rq->map))) {
+    if ((unsigned)rq->colour > NDT_COLOUR_EXR || (unsigned)rq->map > NDT_MAP_EXR_Z || !(colour_kinds[rq->colour].maps & MAP_BIT(rq->map))) {
         fprintf(stderr, "ndt_render_frame: no device call brings colour (%s) and map (%s) of one frame\n",
-                (unsigned)rq->colour > NDT_COLOUR_APNG ? "unknown" : colour_kinds[rq->colour].name,
-                (unsigned)rq->map > NDT_MAP_PNG16 ? "unknown" : map_kinds[rq->map]);
+                (unsigned)rq->colour > NDT_COLOUR_EXR ? "unknown" : colour_kinds[rq->colour].name,
+                (unsigned)rq->map > NDT_MAP_EXR_Z ? "unknown" : map_kinds[rq->map]);
         return 0;
     }
     /* 1. the scene: flattened, uploaded to every context of the thread (the pthread fan-out of ndt.c:949-975 is the GPU's job now;
@@ -551,7 +585,8 @@ int ndt_render_frame(scene *scn, const ndt_frame_request *rq, ndt_frame *f)
             p.aa_depth = rq->aa_depth;
         }
         /* 2. and 3. colour and map in the forms asked for: one device call makes both, so the routine is chosen by the pair */
-        if (rq->colour == NDT_COLOUR_APNG) ok = frame_apng(&p, rq, f);
+        if (rq->colour == NDT_COLOUR_EXR) ok = frame_exr(&p, rq, f);
+        else if (rq->colour == NDT_COLOUR_APNG) ok = frame_apng(&p, rq, f);
         else if (rq->colour == NDT_COLOUR_PNG16) ok = frame_png16(&p, rq, f);
         else if (map8) ok = frame_beside_map8(&p, rq, f);
         else if (rq->colour == NDT_COLOUR_PNG || rq->colour == NDT_COLOUR_JPEG) ok = frame_file(&p, rq, f);
