@@ -1532,7 +1532,10 @@ struct KdStackLds {
 // coherent rays scan the same leaf in the same order: 80-90 % of the intersections of the 6-D .. 8-D scenes -- its number
 // is made a scalar, so that its records are read with scalar loads into scalar registers: no per-lane addresses, no
 // vector registers for data that is the same in all lanes (in 8-D a vector is 16 of them).  Same arithmetic.
-template <int N, int MW, bool LSTACK = false, bool UNI = false>
+// LAZY_INV (the per-bounce trace kernel): the inverse directions are made where a ray enters the tree, behind the root box test
+// -- a ray that misses the box, the sky, is finished there and never reads them: N divisions of about 12 instructions.  Same
+// inv_of, same values.  (The frame kernel keeps them in front: moving them moved its spills.)
+template <int N, int MW, bool LSTACK = false, bool UNI = false, bool LAZY_INV = false>
 NDT_DEV void trace_kd(const double *blob, const SceneDesc &sd, VisitMask<MW> &mask, const double (&o)[N],
                       const double (&v)[N], double dist_limit, int &out_obj, int &out_prim
 #ifdef NDT_PHASE_TIMING
@@ -1562,7 +1565,7 @@ NDT_DEV void trace_kd(const double *blob, const SceneDesc &sd, VisitMask<MW> &ma
         return r;
     };
     double v_inv[N];
-    if (KEEP_INV) {
+    if (KEEP_INV && !LAZY_INV) {
 #pragma unroll
         for (int i = 0; i < N; ++i) v_inv[i] = inv_of(v[i]);
     }
@@ -1682,6 +1685,16 @@ NDT_DEV void trace_kd(const double *blob, const SceneDesc &sd, VisitMask<MW> &ma
                         if (desc < 0.0 || (voc > 0.0 && voc2 > desc)) dead |= 1ull << id;
                     }
                     mask.w[0] |= dead;
+                }
+                if (KEEP_INV && LAZY_INV) {
+                    // (the copy is pinned here: the divisions are loop-invariant and free of side effects, and the compiler
+                    // moves them back in front of the walk otherwise)
+#pragma unroll
+                    for (int i = 0; i < N; ++i) {
+                        double v_i = v[i];
+                        asm volatile("" : "+v"(v_i));
+                        v_inv[i] = inv_of(v_i);
+                    }
                 }
                 node = 0;
                 ntl = tl;

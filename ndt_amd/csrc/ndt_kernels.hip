@@ -315,7 +315,8 @@ template <int MW> NDT_DEV void init_visit_mask(VisitMask<MW> &mask, const double
 // branch: its code in the kernel cost the launches that do not use it 2-3 % (registers and scratch around the traversal loop).
 // Where the rays of shadow segment s start, when they all start at one point: the position of the s-th light that is not
 // ambient, if it is a point or a spot light (ndt.c:211; light record: ndt_blob.hip) -- else -1 (directional: the nudged hit
-// points; area lights: a point of the light per ray).  s: the same in every lane.
+// points; area lights: a point of the light per ray).  Asked once per wavefront, lane s for segment s, in the prologue of
+// k_trace; a shadow batch takes its segment's answer from that lane.
 NDT_DEV int seg_light_origin(const double *gblob, const SceneDesc &sd, int s)
 {
     unsigned long long rest = ~sd.ambient_bits;
@@ -326,12 +327,102 @@ NDT_DEV int seg_light_origin(const double *gblob, const SceneDesc &sd, int s)
     return (type == NDT_LIGHT_POINT_ || type == NDT_LIGHT_SPOT_) ? w + 5 : -1;
 }
 
+// k_trace's by-value arguments, read again from the kernel-argument segment where the batch loop uses them (LDS tiers).  As
+// values of `job` the two TraceParts are 26 scalar registers that live across the whole batch loop, in 8-register tuples (one
+// wide load each) that the allocator spills and reloads whole -- the kernel is at the scalar ceiling, and a batch reloaded 70 of
+// them lane by lane from a vector register; the PRIM variant keeps `ws` and `job.rg` for primary_node the same way.  From the
+// segment a part is two scalar loads that hit the constant cache, issued when the batch is known and dead behind their use.
+// The arguments stand in order, each at its natural alignment.  The segment's address goes through an empty asm, so that the
+// loads stay where they are written: they are invariant, and would be moved in front of the loop and kept live otherwise.
+typedef __attribute__((address_space(4))) const char *KernargBytes;
+// (the segment of k_trace is this struct: the same members in the same order, laid out by the same rule; the static_assert
+// behind k_trace ties it to the kernel's signature -- whoever changes one is told to change the other)
+struct TraceKernargs {
+    const double *gblob;
+    SceneDesc sd;
+    Workspace ws;
+    TraceJob job;
+};
+constexpr size_t KARG_TRACE_WS = offsetof(TraceKernargs, ws);
+constexpr size_t KARG_TRACE_JOB = offsetof(TraceKernargs, job);
+// Which of round 14's three changes to the batch head a variant of k_trace takes: 1 the arguments from the segment, 2 the light
+// origin of a segment once per wavefront (seg_light_origin), 4 the inverse directions behind the root box test (trace_kd's
+// LAZY_INV).  All of them in the LDS tiers -- but a change goes only where it spills no more vector registers than the kernel
+// without it (the gate; profiles/r14_kernel_resources.txt has the rows).  The exceptions below are
+// what the table of N = 3 .. 12 showed; a variant that takes none is the round 13 kernel instruction for instruction.
+#ifdef NDT_HEAD_STEPS
+constexpr int trace_head_steps(int, int mw, bool, bool) { return mw != 0 ? (NDT_HEAD_STEPS) : 0; }     // (experiments: one setting everywhere)
+#else
+constexpr int trace_head_steps(int n, int mw, bool lstack, bool prim)
+{
+    if (mw == 0) return 0;          // the global-memory tier
+    if (prim) return 7;
+    // (spilled VGPRs, parent -> with all three: the setting that spills no more than the parent; 0 where none does)
+    if (n == 4 && mw == 4 && lstack) return 5;              //   4 ->   8
+    if (n == 4 && mw == 1 && !lstack) return 0;             //   0 ->   4 (and 4 with 1, 5 or 6)
+    if (n == 5 && lstack) return 5;                         //  25 ->  28, 34 -> 35
+    if (n == 6 && mw == 1 && !lstack) return 0;             //  48 ->  52 (49 with 1 or 5)
+    if (n == 8 && mw == 1 && !lstack) return 1;             // 134 -> 140 (137 with 5)
+    if (n == 10 && !lstack) return 5;                       // 430 -> 431, 442 -> 445
+    if (n == 11 && !(mw == 1 && lstack)) return 0;          // 610 -> 625, 619 -> 622, 608 -> 623 (more with 1, 5 and 6 too)
+    return 7;
+}
+#endif
+NDT_DEV KernargBytes karg_here()
+{
+    KernargBytes p = (KernargBytes)__builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(p));
+    return p;
+}
+// (word by word: the members that are not used cost nothing, neighbours become one wide load)
+template <typename T> NDT_DEV T karg_get(KernargBytes p)
+{
+    static_assert(sizeof(T) % 4 == 0 && std::is_trivially_copyable<T>::value, "words");
+    union { T v; unsigned int w[sizeof(T) / 4]; } u;
+#pragma unroll
+    for (size_t i = 0; i < sizeof(T) / 4; ++i) u.w[i] = reinterpret_cast<__attribute__((address_space(4))) const unsigned int *>(p)[i];
+    return u.v;
+}
+// (a pointer member is read as a pointer: one loaded from the constant address space by a kernel is taken to point to global
+// memory, as an argument is; put together from two words it is used with flat instructions -- slower, waited for on two counters)
+#define NDT_KARG_PTR(obj, base, member) \
+    (obj).member = *reinterpret_cast<__attribute__((address_space(4))) decltype((obj).member) const *>((base) + offsetof(decltype(obj), member))
+// in_seg: the same in every lane
+NDT_DEV TracePart karg_trace_part(bool in_seg)
+{
+    const int at = in_seg ? (int)offsetof(TraceJob, seg) : (int)offsetof(TraceJob, dense);
+    const KernargBytes kp = karg_here() + KARG_TRACE_JOB + __builtin_amdgcn_readfirstlane(at);
+    TracePart p = karg_get<TracePart>(kp);
+    NDT_KARG_PTR(p, kp, o); NDT_KARG_PTR(p, kp, v); NDT_KARG_PTR(p, kp, lim); NDT_KARG_PTR(p, kp, valid);
+    NDT_KARG_PTR(p, kp, out_obj); NDT_KARG_PTR(p, kp, out_prim);
+    return p;
+}
+// what primary_node takes from `ws` and `job.rg`
+NDT_DEV Workspace karg_trace_workspace(KernargBytes ka)
+{
+    const KernargBytes kp = ka + KARG_TRACE_WS;
+    Workspace w = karg_get<Workspace>(kp);
+    NDT_KARG_PTR(w, kp, ray_o); NDT_KARG_PTR(w, kp, ray_v); NDT_KARG_PTR(w, kp, frac); NDT_KARG_PTR(w, kp, depth_left);
+    NDT_KARG_PTR(w, kp, hit_obj); NDT_KARG_PTR(w, kp, child_refl); NDT_KARG_PTR(w, kp, child_refr); NDT_KARG_PTR(w, kp, sh_mask);
+    NDT_KARG_PTR(w, kp, count); NDT_KARG_PTR(w, kp, rng_key);
+    return w;
+}
+NDT_DEV RenderGeom karg_trace_geom(KernargBytes ka)
+{
+    const KernargBytes kp = ka + KARG_TRACE_JOB + offsetof(TraceJob, rg);
+    RenderGeom rg = karg_get<RenderGeom>(kp);
+    NDT_KARG_PTR(rg, kp, samples); NDT_KARG_PTR(rg, kp, sample_keys);
+    return rg;
+}
+
 #ifndef NDT_TICKET_AHEAD
 #define NDT_TICKET_AHEAD 256
 #endif
 template <int MW, bool LDS, bool LSTACK = false, bool PRIM = false>
 __global__ void __launch_bounds__(MW == 0 ? NDT_TRACE_T1_MAX_BLOCK : NDT_TRACE_MAX_BLOCK) k_trace(const double *__restrict__ gblob, SceneDesc sd, Workspace ws, TraceJob job)
 {
+    constexpr int STEPS = trace_head_steps(N, MW, LSTACK, PRIM);
+    constexpr bool KARG = (STEPS & 1) != 0, SEG_ONCE = (STEPS & 2) != 0, LAZY = (STEPS & 4) != 0;
     extern __shared__ __attribute__((aligned(16))) double lds_blob[];
     const double *blob = gblob;
     if (LDS) {
@@ -392,10 +483,13 @@ __global__ void __launch_bounds__(MW == 0 ? NDT_TRACE_T1_MAX_BLOCK : NDT_TRACE_M
     const int bs = job.batch;
     const int sh = (bs == 64) ? 6 : (bs == 32) ? 5 : (bs == 16) ? 4 : 3;
     int seg_batches = 0, seg_batches_incl = 0, seg_cnt = 0;     // lane s: inclusive prefix of batches / count of segment s
+    int seg_origin = -1;                                        // lane s: seg_light_origin of segment s (LDS tiers), found once
     if (job.n_seg > 0) {
         seg_cnt = (lane < job.n_seg) ? job.seg_count[lane] : 0;
         const int excl = wave_excl_scan((seg_cnt + bs - 1) >> sh, seg_batches);
         seg_batches_incl = excl + ((seg_cnt + bs - 1) >> sh);
+        // (a segment without rays has no batch to ask, and need not be a light of the list at all)
+        if (SEG_ONCE && job.seg_light_origins && seg_cnt > 0) seg_origin = seg_light_origin(gblob, sd, lane);
     }
     long long dense_count = job.count, dense_begin = job.begin, seg_stride = job.seg_stride;
     if (job.levels) {
@@ -533,7 +627,8 @@ __global__ void __launch_bounds__(MW == 0 ? NDT_TRACE_T1_MAX_BLOCK : NDT_TRACE_M
             // segment of shadow batch sb = number of segments whose inclusive prefix is <= sb
             const int sb = (int)(b - dense_batches);
             const int s = __popcll(__ballot(lane < job.n_seg && seg_batches_incl <= sb));
-            if (MW != 0 && job.seg_light_origins) origin_word = seg_light_origin(gblob, sd, __builtin_amdgcn_readfirstlane(s));
+            if (SEG_ONCE) origin_word = __builtin_amdgcn_readlane(seg_origin, __builtin_amdgcn_readfirstlane(s));
+            else if (MW != 0 && job.seg_light_origins) origin_word = seg_light_origin(gblob, sd, __builtin_amdgcn_readfirstlane(s));
             const int first = (s > 0) ? __shfl(seg_batches_incl, s - 1, 64) : 0;
             const int cnt = __shfl(seg_cnt, s, 64);
             const int idx = (sb - first) * bs + lane;
@@ -543,19 +638,36 @@ __global__ void __launch_bounds__(MW == 0 ? NDT_TRACE_T1_MAX_BLOCK : NDT_TRACE_M
             const long long r = b * bs + lane;
             live = lane < bs && r < dense_count;
             g = dense_begin + (live ? r : 0);
-            if (!PRIM && live && job.dense.valid && job.dense.valid[g] <= 0) live = false;
+            if constexpr (KARG) {
+                if (!PRIM && live) {
+                    const int *valid = karg_trace_part(false).valid;
+                    if (valid && valid[g] <= 0) live = false;
+                }
+            } else {
+                if (!PRIM && live && job.dense.valid && job.dense.valid[g] <= 0) live = false;
+            }
         }
         // The primaries of a pass are made HERE, by the wavefront that traces them (render_pixel + the head of get_pixel_color,
         // ndt.c:578-653, 488-550: primary_node -- what the k_primary launch used to do: 2N doubles a ray written and read back
         // before anything was traced); the node's record still goes to the pool for the kernels behind this one.
         double o[N], v[N];
         const bool make = PRIM && !in_seg;                      // (wave-uniform)
-        if (PRIM && make && live) live = primary_node<false, true>(gblob, sd, ws, job.rg, g, o, v);
+        if (PRIM && make && live) {
+            if (KARG) {
+                const KernargBytes ka = karg_here();
+                live = primary_node<false, true>(gblob, sd, karg_trace_workspace(ka), karg_trace_geom(ka), g, o, v);
+            } else {
+                live = primary_node<false, true>(gblob, sd, ws, job.rg, g, o, v);
+            }
+        }
         // A lane without a ray.  The LDS tiers leave it out of the batch; in the global-memory tier it stays with the
         // wavefront as a helper of the coherent leaf scan (ndt_device.hpp:cls_scan: all 64 lanes fetch), with a ray that is
         // finished before it starts.
         if (live || MW == 0) {
-        const TracePart &part = in_seg ? job.seg : job.dense;
+        // (LDS tiers: the batch's part from the kernel-argument segment -- here what is read in front of the traversal, behind it
+        // where the answers go: karg_trace_part)
+        const TracePart part_here = KARG ? karg_trace_part(in_seg) : TracePart{};
+        const TracePart &part = KARG ? part_here : in_seg ? job.seg : job.dense;
 #ifdef NDT_TRACE_SKIP_KNOB
         if (job.skip_trace == 3) {
             for (int c = 0; c < N; ++c) { o[c] = (double)g; v[c] = 1.0; }
@@ -582,7 +694,7 @@ __global__ void __launch_bounds__(MW == 0 ? NDT_TRACE_T1_MAX_BLOCK : NDT_TRACE_M
             obj = (o[0] + v[0] + lim > 1e300) ? 0 : -1;     // keeps the loads alive
             prim = -1;
         } else
-        trace_kd<N, MW, LSTACK, MW == 0>(blob, sd, mask, o, v, lim, obj, prim, ph, cnt, occ, kstack, cls, live, box_slot);
+        trace_kd<N, MW, LSTACK, MW == 0, LAZY>(blob, sd, mask, o, v, lim, obj, prim, ph, cnt, occ, kstack, cls, live, box_slot);
         out_last = __builtin_readcyclecounter();
         if (ws.dbg && lane == __ffsll((long long)__ballot(1)) - 1) {
             // duration of this batch inside trace_kd: slowest batch of the launch (dbg[40 + is_shadow])
@@ -623,14 +735,17 @@ __global__ void __launch_bounds__(MW == 0 ? NDT_TRACE_T1_MAX_BLOCK : NDT_TRACE_M
             prim = -1;
         } else
 #endif
-        trace_kd<N, MW, LSTACK, MW == 0>(blob, sd, mask, o, v, lim, obj, prim, kstack, cls, live, box_slot);
+        trace_kd<N, MW, LSTACK, MW == 0, LAZY>(blob, sd, mask, o, v, lim, obj, prim, kstack, cls, live, box_slot);
 #endif
 #ifdef NDT_TRACE_SKIP_KNOB
         if (job.skip_trace == 2 && obj == -1) live = false;
 #endif
         if (live) {
-            part.out_obj[g] = obj;
-            part.out_prim[g] = prim;
+            // (read again, not kept: kept, the two addresses are four scalar registers live across the traversal)
+            const TracePart out_here = KARG ? karg_trace_part(in_seg) : TracePart{};
+            const TracePart &out = KARG ? out_here : part;
+            out.out_obj[g] = obj;
+            out.out_prim[g] = prim;
         }
         }
     }
@@ -665,6 +780,10 @@ __global__ void __launch_bounds__(MW == 0 ? NDT_TRACE_T1_MAX_BLOCK : NDT_TRACE_M
     }
 #endif
 }
+
+// (karg_trace_part and its kin read k_trace's kernel-argument segment by TraceKernargs' offsets)
+static_assert(std::is_same<decltype(&k_trace<1, true, true, false>), void (*)(const double *, SceneDesc, Workspace, TraceJob)>::value,
+              "k_trace's parameters changed: change TraceKernargs with them");
 
 // launch knobs of the trace kernel: environment variables in the diagnostic builds (make timing | skipknob), the defaults
 // -- compile-time constants -- in the library
