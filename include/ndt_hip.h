@@ -598,6 +598,58 @@ int ndt_hip_render_exr(ndt_hip_ctx *ctx, const ndt_render_params *p, const ndt_e
 int ndt_hip_render_ssaa_exr(ndt_hip_ctx *ctx, const ndt_render_params *p, int32_t K, const ndt_exr_params *ep, int32_t with_depth,
                             uint8_t *out, int64_t cap, ndt_exr_stats *stats, ndt_render_stats *render_stats);
 
+/* What a pixel shows (`ndt_hip --exr --exr-aov`): the closest hit of every pixel's primary ray -- which object, where in all N
+ * coordinates, and which way the surface faces there -- as planes in pixel order, and as extra channels of the frame's OpenEXR file.
+ * The primary ray is the one a deterministic frame (samples == 1, no recursive_aa) starts from the pixel, the ray whose hit the depth
+ * map records: row shards, NDT_STEREO_SIDE_SIDE / OVER_UNDER with the eye of the pixel's half, every camera type.  Its hit is what
+ * ndt_hip_trace_rays answers for that ray with dist_limit -1, made by the same kernels; a hit within EPSILON of the ray's origin
+ * counts as none (ndt.c:376: the depth map holds 0 there too).  The planes, each rows * width elements a component, [c][rows * width]:
+ *   id         int32: object index + 1, 0 where the ray hits nothing
+ *   position   dims planes of doubles: the hit point; all zero where id == 0
+ *   normal     dims planes of doubles: the normal there as the object's intersect() returns it; all zero where id == 0
+ *   ray_o / ray_v   dims planes each: the ray's origin and unit direction, for every pixel
+ * A NULL member of ndt_feature_planes is not written; at least one must be set.
+ *   ndt_hip_render_features          the planes into host memory
+ *   ndt_hip_render_features_device   ... into the context's device memory (id aligned to 4 bytes, the doubles to 8); returns when
+ *                                    they are complete.  stats (may be NULL): rays_primary, trace_launches = 1
+ *   ndt_hip_features_launches        kernel launches of the context's last feature pass (primaries, trace, hit points, gather: 4)
+ *   ndt_hip_exr_features_bound       ndt_hip_exr_bound for a file with the channels of `features` (a mask of NDT_FEATURE_*) of a
+ *                                    dims-dimensional scene; < 0 (NDT_E_INVALID) also for dims outside 3 .. 12 and a mask that is 0
+ *                                    or has unknown bits
+ *   ndt_hip_encode_exr_features_device   ndt_hip_encode_exr_device with the planes d_planes names (device memory; those of the
+ *                                    mask must be set) as channels.  The file's channel list, in the byte-wise order the format
+ *                                    wants: A B G, N.00 .. N.<dims-1> (normal), P.00 .. P.<dims-1> (position), R, Z (with a map),
+ *                                    id.  N.* and P.* are FLOAT, (float) of the doubles; id is UINT, the plane's 32 bits as they
+ *                                    are; A B G R follow ndt_exr_params.  Only the groups of the mask appear.  UINT samples go
+ *                                    through the two byte planes and the predictor like FLOAT ones.  4 kernel launches
+ *   ndt_hip_render_exr_features      ndt_hip_render_exr, then the feature pass on the same stream, then that encoder.  The colour
+ *                                    and Z channels hold the bits of the file without features
+ *   ndt_hip_render_ssaa_exr_features ... for the supersampled frame: the features are the plain W x H frame's, as Z is
+ * NDT_E_UNSUPPORTED with the cause in the error text, before any device work and with nothing written: recursive_aa (the pixel is
+ * an average of corner samples), samples > 1 (no single primary ray), NDT_STEREO_ANAGLYPH (two rays a pixel), NDT_STEREO_HIDEF.
+ * NDT_E_INVALID and NDT_E_NOMEM as the EXR entries define them: a `cap` below the file gives NDT_E_NOMEM, the size needed in the
+ * error text and in stats->file_bytes, and nothing written.  Device buffers belong to the context, only grow and are reused.
+ * None falls back. */
+enum { NDT_FEATURE_ID = 1, NDT_FEATURE_POSITION = 2, NDT_FEATURE_NORMAL = 4 };
+typedef struct ndt_feature_planes {
+    int32_t *id;
+    double *position, *normal, *ray_o, *ray_v;
+} ndt_feature_planes;
+int ndt_hip_render_features(ndt_hip_ctx *ctx, const ndt_render_params *p, const ndt_feature_planes *planes, ndt_render_stats *stats);
+int ndt_hip_render_features_device(ndt_hip_ctx *ctx, const ndt_render_params *p, const ndt_feature_planes *d_planes,
+                                   ndt_render_stats *stats);
+int ndt_hip_features_launches(ndt_hip_ctx *ctx);
+int64_t ndt_hip_exr_features_bound(int32_t width, int32_t rows, const ndt_exr_params *ep, int32_t with_depth, int32_t dims,
+                                   int32_t features);
+int ndt_hip_encode_exr_features_device(ndt_hip_ctx *ctx, const void *d_rgba, const void *d_depth, const ndt_feature_planes *d_planes,
+                                       int32_t dims, int32_t features, int32_t width, int32_t rows, const ndt_exr_params *ep,
+                                       uint8_t *out, int64_t cap, ndt_exr_stats *stats);
+int ndt_hip_render_exr_features(ndt_hip_ctx *ctx, const ndt_render_params *p, const ndt_exr_params *ep, int32_t with_depth,
+                                int32_t features, uint8_t *out, int64_t cap, ndt_exr_stats *stats, ndt_render_stats *render_stats);
+int ndt_hip_render_ssaa_exr_features(ndt_hip_ctx *ctx, const ndt_render_params *p, int32_t K, const ndt_exr_params *ep,
+                                     int32_t with_depth, int32_t features, uint8_t *out, int64_t cap, ndt_exr_stats *stats,
+                                     ndt_render_stats *render_stats);
+
 /* ONE frame over several contexts -- one per GPU of the node, or several on one GPU -- called from one host thread.
  * The rows `p` selects are dealt cyclically to the contexts exactly as the reference deals rows to MPI ranks in
  * MPI_MODE_ROW (ndt.c:812-820: row_start = rank, row_step = size): context k renders rows

@@ -130,6 +130,7 @@ extern "C" int ndt_hip_destroy(ndt_hip_ctx *ctx)
     free_apng(ctx);
     free_jpeg(ctx);
     free_exr(ctx);
+    free_features(ctx);
     free_depth(ctx);
     free_ssaa(ctx);
     ctx->d_eyes.release();

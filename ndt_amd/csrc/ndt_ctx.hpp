@@ -17,6 +17,7 @@
 //   ndt_jpeg.hip     ndt_hip_encode_jpeg* / ndt_hip_render_jpeg: a frame's JPEG file made on the device; kernels, launcher and C ABI
 //   ndt_exr.hip      ndt_hip_encode_exr* / ndt_hip_render_exr: a frame's OpenEXR file (linear half or float samples, the map as its Z
 //                    channel) made on the device; kernels, launcher and C ABI
+//   ndt_features.hip  ndt_hip_render_features*: the primary hit of every pixel (object, N-D point, normal) as planes in pixel order
 //   ndt_deflate.hpp  the deflate of a 32 KiB chunk that ndt_png.hip and ndt_exr.hip share (device code)
 //   ndt_depth.hip    ndt_hip_depth_rgba8_device / ndt_hip_render_*_depth: the depth map of `-z` normalised and quantised on the device
 //   ndt_ssaa.hip     ndt_hip_ssaa_fold_device / ndt_hip_render_ssaa*: K x K supersampling, K ordinary renders folded on the device
@@ -104,7 +105,14 @@ struct ExrState {
     DeviceBuffer d_in;              // ndt_hip_encode_exr: the doubles (and the map behind them) that arrive from host memory
     DeviceBuffer d_packed;          // every block's bytes as the format compresses them, each block on a chunk boundary
     DeviceBuffer d_slots, d_meta, d_offsets, d_blocks, d_file, d_info;
+    DeviceBuffer d_channels;        // a file with feature channels: its channel table (ndt_exr.hip:ExrChannels)
     void *h_info = nullptr;         // pinned: the info record of the last file
+};
+
+// ndt_hip_render_features*, ndt_hip_render_exr_features (ndt_features.hip): grow-only device buffers, reused by the next frame
+struct FeatureState {
+    DeviceBuffer d_id, d_position, d_normal, d_ray_o, d_ray_v;     // the planes of the calls that deliver to host memory or as a file
+    int launches = 0;               // kernel launches of the last feature pass
 };
 
 // ndt_hip_depth_rgba8_device, ndt_hip_render_*_depth (ndt_depth.hip): grow-only device buffers, reused by the next frame
@@ -222,6 +230,7 @@ struct ndt_hip_ctx {
     ApngState apng;                 // ndt_hip_apng_*, ndt_hip_render_apng_frame
     JpegState jpeg;                 // ndt_hip_encode_jpeg*, ndt_hip_render_jpeg
     ExrState exr;                   // ndt_hip_encode_exr*, ndt_hip_render_exr, ndt_hip_render_ssaa_exr
+    FeatureState features;          // ndt_hip_render_features*, ndt_hip_render_exr_features
     DepthState depth;               // ndt_hip_depth_rgba8_device, ndt_hip_render_*_depth
     SsaaState ssaa;                 // ndt_hip_render_ssaa*
     DeviceBuffer d_out;             // staging of a frame in doubles (and its map behind it) for the calls that deliver to host memory
@@ -322,6 +331,17 @@ void free_jpeg(ndt_hip_ctx *ctx);
 
 // ndt_exr.hip
 void free_exr(ndt_hip_ctx *ctx);
+
+// ndt_features.hip
+void free_features(ndt_hip_ctx *ctx);
+// What the feature entries refuse, under the name `who`, before any device work: NULL arguments, no scene, bad geometry, and the
+// frames that have no single primary ray a pixel (recursive_aa, samples > 1, anaglyph, frame packing).  *rows: the shard's
+int features_check(const char *who, ndt_hip_ctx *ctx, const ndt_render_params *p, int *rows);
+// The feature pass of the rows `p` selects on the context's stream (arguments checked by features_check): the planes of `dst` that
+// are not NULL -- device memory -- are written.  Not synchronised.
+int features_pass(ndt_hip_ctx *ctx, const char *who, const ndt_render_params *p, const ndt_feature_planes &dst);
+// ... into the context's own buffers, the planes of `features` (NDT_FEATURE_*; with_rays: the rays too); *own names them
+int features_own(ndt_hip_ctx *ctx, const char *who, const ndt_render_params *p, int features, bool with_rays, ndt_feature_planes *own);
 
 // ndt_depth.hip
 void free_depth(ndt_hip_ctx *ctx);

@@ -1,9 +1,9 @@
 // ndt_exr.hip -- a frame's OpenEXR file made on the device: ndt_hip_exr_bound / ndt_hip_encode_exr_device / ndt_hip_encode_exr /
-// ndt_hip_render_exr / ndt_hip_render_ssaa_exr.  The frame's doubles are in HBM; what leaves the device is the finished file: a
-// single-part scanline file, channels A B G R (HALF or FLOAT) and, with a depth map, Z (FLOAT), ZIP compression (16 scanlines a
+// ndt_hip_render_exr / ndt_hip_render_ssaa_exr, and their *_features twins.  The frame's doubles are in HBM; what leaves the
+// device is the finished file: a single-part scanline file, channels A B G R (HALF or FLOAT) and, with a depth map, Z (FLOAT), ZIP compression (16 scanlines a
 // block, each block a zlib stream of its own), linear light: no clamp to 0 .. 1 and no square root.
 //
-//   k_exr_pack<HALF>   the doubles (and the map) of a block as the bytes the format compresses: byte planes (the even bytes of the
+//   k_exr_pack<SRC>    the doubles (and the map) of a block as the bytes the format compresses: byte planes (the even bytes of the
 //                      block's raw bytes, then the odd ones), then the delta predictor -- every output byte is a function of two
 //                      source samples, so there is no intermediate image.  Written as aligned words; each block starts on a
 //                      32 KiB chunk boundary, so that the deflate's whole-chunk loads stay inside the buffer
@@ -14,8 +14,15 @@
 //   k_exr_assemble     one workgroup: per block the stream's length, its Adler-32 folded from the chunks' pairs and the raw-fallback
 //                      decision (a stream that is not shorter than the raw bytes: the block holds those, as the format rules), a
 //                      scan of the block sizes, the header, the offset table and the blocks' headers
-//   k_exr_place<HALF>  one workgroup a chunk: its compressed bytes -- or, for a fallback block, the raw bytes made from the
+//   k_exr_place<SRC>   one workgroup a chunk: its compressed bytes -- or, for a fallback block, the raw bytes made from the
 //                      doubles again -- to their place in the file
+//
+// With feature channels (ndt_hip_encode_exr_features_device / ndt_hip_render_exr_features / ndt_hip_render_ssaa_exr_features) the
+// samples come from a channel table in device memory (ExrChannels: per channel its name, pixel type, source, stride, element type
+// and conversion).  k_exr_pack and k_exr_place are templates over where a raw byte comes from: PlainSource<HALF>, the four
+// interleaved colour doubles and the optional map -- the instantiations the plain file had before the table existed, and still
+// has: same registers, no scratch (profiles/exr_features_on_device.txt) --, and ListSource, which reads the table.  k_exr_assemble
+// takes the table for the header; k_exr_deflate and deflate_chunk<2> need only the sizes.
 //
 // No kernel waits for another workgroup, every loop's trip count comes from a size, and the only atomics are the deflate's LDS
 // atomics.  The host reads the info record, then exactly the file's bytes.
@@ -26,13 +33,35 @@
 namespace {
 
 constexpr int EXR_LINES = 16;           // scanlines a block of ZIP compression
-constexpr int EXR_HALF = 1, EXR_FLOAT = 2;      // the format's pixelType
+constexpr int EXR_UINT = 0, EXR_HALF = 1, EXR_FLOAT = 2;        // the format's pixelType
+constexpr int EXR_MAX_CHANNELS = 4 + 1 + 1 + 2 * NDT_MAX_DIMS;  // A B G R, Z, id, N.* and P.*
+constexpr int EXR_ALL_FEATURES = NDT_FEATURE_ID | NDT_FEATURE_POSITION | NDT_FEATURE_NORMAL;
+
+// how a source element becomes a sample: a double to binary16, a double to float, an int32's bits as they are
+enum { EXR_TO_HALF = 0, EXR_TO_FLOAT = 1, EXR_AS_UINT = 2 };
+
+// One channel of a file with a channel list, in the file's order.  Pixel i's element is src[i * stride].
+struct ExrChannel {
+    const void *src;
+    int stride;
+    int is_int;                         // the element type: 0 double, 1 int32
+    int conv;                           // EXR_TO_HALF / EXR_TO_FLOAT / EXR_AS_UINT
+    int pixel_type;                     // the format's
+    int first_unit, bytes;              // of one pixel: the sample bytes of the channels before it in a scanline; its own (2 or 4)
+    char name[8];                       // zero-terminated
+};
+// ... and the list: in device memory (ExrState::d_channels).  unit_channel[u]: the channel that byte u * width of a scanline is in
+struct ExrChannels {
+    int n, units;
+    unsigned char unit_channel[4 * EXR_MAX_CHANNELS];
+    ExrChannel ch[EXR_MAX_CHANNELS];
+};
 
 // what the kernels are told about the file: every quantity fits an int because the raw bytes do
 struct ExrLayout {
-    int width, rows, n_ch;              // channels: 4, or 5 with Z
+    int width, rows, n_ch;              // channels: 4, or 5 with Z; with a channel table, its entries
     int pixel_type;                     // of A B G R
-    int line_bytes, colour_bytes;       // a scanline's raw bytes; those of its colour channels
+    int line_bytes, colour_bytes;       // a scanline's raw bytes; those of its colour channels (the plain file's: 0 with a table)
     int n_blocks, cpb, n_chunks;        // blocks; chunks of a full block; chunks of the file (the last block may have fewer)
     int header_bytes;
     long long raw_bytes;
@@ -65,23 +94,10 @@ __host__ __device__ inline int exr_attr(unsigned char *p, int at, const char *na
     return exr_put32(p, at, (unsigned)size);
 }
 
-// The header -- magic, version, the attributes, the closing zero -- at p (nullptr: nothing is written); returns its length.
-// The one definition: the host takes the length from it, k_exr_assemble the bytes.
-__host__ __device__ inline int exr_header(unsigned char *p, int width, int rows, int n_ch, int pixel_type)
+// what follows the channel list in a header: its closing zero, the other attributes, the header's closing zero
+__host__ __device__ inline int exr_header_rest(unsigned char *p, int at, int width, int rows)
 {
     const unsigned one = 0x3f800000u;   // 1.0f
-    int at = exr_put32(p, 0, 0x01312f76u);
-    at = exr_put32(p, at, 2u);
-    at = exr_attr(p, at, "channels", 8, "chlist", 6, 18 * n_ch + 1);
-    const char names[5] = { 'A', 'B', 'G', 'R', 'Z' };
-    for (int c = 0; c < n_ch; ++c) {
-        const unsigned char name[2] = { (unsigned char)names[c], 0 };
-        at = exr_put(p, at, name, 2);
-        at = exr_put32(p, at, c == 4 ? (unsigned)EXR_FLOAT : (unsigned)pixel_type);
-        at = exr_put32(p, at, 0u);      // pLinear and three reserved bytes
-        at = exr_put32(p, at, 1u);
-        at = exr_put32(p, at, 1u);
-    }
     const unsigned char zip[1] = { 3 }, zero[1] = { 0 };
     at = exr_put(p, at, zero, 1);
     at = exr_attr(p, at, "compression", 11, "compression", 11, 1);
@@ -103,6 +119,49 @@ __host__ __device__ inline int exr_header(unsigned char *p, int width, int rows,
     at = exr_attr(p, at, "screenWindowWidth", 17, "float", 5, 4);
     at = exr_put32(p, at, one);
     return exr_put(p, at, zero, 1);
+}
+
+// The header -- magic, version, the attributes, the closing zero -- at p (nullptr: nothing is written); returns its length.
+// The one definition: the host takes the length from it, k_exr_assemble the bytes.
+__host__ __device__ inline int exr_header(unsigned char *p, int width, int rows, int n_ch, int pixel_type)
+{
+    int at = exr_put32(p, 0, 0x01312f76u);
+    at = exr_put32(p, at, 2u);
+    at = exr_attr(p, at, "channels", 8, "chlist", 6, 18 * n_ch + 1);
+    const char names[5] = { 'A', 'B', 'G', 'R', 'Z' };
+    for (int c = 0; c < n_ch; ++c) {
+        const unsigned char name[2] = { (unsigned char)names[c], 0 };
+        at = exr_put(p, at, name, 2);
+        at = exr_put32(p, at, c == 4 ? (unsigned)EXR_FLOAT : (unsigned)pixel_type);
+        at = exr_put32(p, at, 0u);      // pLinear and three reserved bytes
+        at = exr_put32(p, at, 1u);
+        at = exr_put32(p, at, 1u);
+    }
+    return exr_header_rest(p, at, width, rows);
+}
+
+// ... of a file with a channel list: the table's names and pixel types, in its order
+__host__ __device__ inline int exr_header_list(unsigned char *p, int width, int rows, const ExrChannels *C)
+{
+    int at = exr_put32(p, 0, 0x01312f76u);
+    at = exr_put32(p, at, 2u);
+    int list = 1;
+    for (int c = 0; c < C->n; ++c) {
+        int len = 0;
+        while (C->ch[c].name[len]) ++len;
+        list += len + 1 + 16;
+    }
+    at = exr_attr(p, at, "channels", 8, "chlist", 6, list);
+    for (int c = 0; c < C->n; ++c) {
+        int len = 0;
+        while (C->ch[c].name[len]) ++len;
+        at = exr_put(p, at, C->ch[c].name, len + 1);
+        at = exr_put32(p, at, (unsigned)C->ch[c].pixel_type);
+        at = exr_put32(p, at, 0u);      // pLinear and three reserved bytes
+        at = exr_put32(p, at, 1u);
+        at = exr_put32(p, at, 1u);
+    }
+    return exr_header_rest(p, at, width, rows);
 }
 
 // ------------------------------------------------------------------ samples
@@ -127,27 +186,52 @@ __device__ __forceinline__ unsigned half_bits(double x)
     return e >= -14 ? sign | (((unsigned)(e + 15) << 10) + (q - 1024u)) : sign | q;
 }
 
-// raw byte r of block `block`: per scanline, per channel in list order (A B G R Z), `width` samples, little-endian
+// Where the raw bytes of a block come from.  byte(L, block, r): raw byte r of block `block`: per scanline, per channel in list
+// order, `width` samples, little-endian.
+// The plain file (A B G R Z): four interleaved colour doubles and an optional map
 template <bool HALF>
-__device__ __forceinline__ unsigned raw_byte(const ExrLayout &L, const double *__restrict__ rgba, const double *__restrict__ depth, int block, int r)
-{
-    constexpr int BS = HALF ? 2 : 4;
-    const int line = r / L.line_bytes, q = r - line * L.line_bytes;
-    const long long row = (long long)EXR_LINES * block + line;
-    unsigned bits;
-    int b;
-    if (q < L.colour_bytes) {
-        const int wb = L.width * BS, c = q / wb, rem = q - c * wb, x = rem / BS;
-        b = rem - x * BS;
-        const double v = rgba[(row * L.width + x) * 4 + (3 - c)];      // the framebuffer is R G B A
-        bits = HALF ? half_bits(v) : __float_as_uint((float)v);
-    } else {
-        const int rem = q - L.colour_bytes;
-        b = rem & 3;
-        bits = __float_as_uint((float)depth[row * L.width + (rem >> 2)]);
+struct PlainSource {
+    const double *__restrict__ rgba, *__restrict__ depth;
+    __device__ __forceinline__ unsigned byte(const ExrLayout &L, int block, int r) const
+    {
+        constexpr int BS = HALF ? 2 : 4;
+        const int line = r / L.line_bytes, q = r - line * L.line_bytes;
+        const long long row = (long long)EXR_LINES * block + line;
+        unsigned bits;
+        int b;
+        if (q < L.colour_bytes) {
+            const int wb = L.width * BS, c = q / wb, rem = q - c * wb, x = rem / BS;
+            b = rem - x * BS;
+            const double v = rgba[(row * L.width + x) * 4 + (3 - c)];      // the framebuffer is R G B A
+            bits = HALF ? half_bits(v) : __float_as_uint((float)v);
+        } else {
+            const int rem = q - L.colour_bytes;
+            b = rem & 3;
+            bits = __float_as_uint((float)depth[row * L.width + (rem >> 2)]);
+        }
+        return (bits >> (8 * b)) & 255u;
     }
-    return (bits >> (8 * b)) & 255u;
-}
+};
+// A file with a channel list: the table says where every channel's samples are and what they become
+struct ListSource {
+    const ExrChannels *__restrict__ C;
+    __device__ __forceinline__ unsigned byte(const ExrLayout &L, int block, int r) const
+    {
+        const int line = r / L.line_bytes, q = r - line * L.line_bytes;
+        const long long row = (long long)EXR_LINES * block + line;
+        const ExrChannel &ch = C->ch[C->unit_channel[q / L.width]];
+        const int rem = q - ch.first_unit * L.width, x = ch.bytes == 2 ? rem >> 1 : rem >> 2, b = rem & (ch.bytes - 1);
+        const long long at = (row * L.width + x) * ch.stride;
+        unsigned bits;
+        if (ch.is_int) {
+            bits = (unsigned)((const int *)ch.src)[at];
+        } else {
+            const double v = ((const double *)ch.src)[at];
+            bits = ch.conv == EXR_TO_HALF ? half_bits(v) : __float_as_uint((float)v);
+        }
+        return (bits >> (8 * b)) & 255u;
+    }
+};
 
 __device__ __forceinline__ int block_bytes(const ExrLayout &L, int block)
 {
@@ -158,8 +242,8 @@ __device__ __forceinline__ int block_bytes(const ExrLayout &L, int block)
 // ------------------------------------------------------------------ the block's bytes as the format compresses them
 
 // blockIdx.y: the block; the workgroups of a row share its words
-template <bool HALF>
-__global__ void __launch_bounds__(256) k_exr_pack(ExrLayout L, const double *__restrict__ rgba, const double *__restrict__ depth, unsigned *packed)
+template <class SRC>
+__global__ void __launch_bounds__(256) k_exr_pack(ExrLayout L, SRC src, unsigned *packed)
 {
     const int block = (int)blockIdx.y, n = block_bytes(L, block), half = (n + 1) >> 1, n_words = (n + 3) >> 2;
     unsigned *out = packed + (long long)block * L.cpb * (PNG_CHUNK / 4);
@@ -169,13 +253,13 @@ __global__ void __launch_bounds__(256) k_exr_pack(ExrLayout L, const double *__r
         unsigned before = 0u, val = 0u;
         if (i0 > 0) {
             const int i = i0 - 1;
-            before = raw_byte<HALF>(L, rgba, depth, block, i < half ? 2 * i : 2 * (i - half) + 1);
+            before = src.byte(L, block, i < half ? 2 * i : 2 * (i - half) + 1);
         }
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
             const int i = i0 + k;
             if (i < n) {
-                const unsigned cur = raw_byte<HALF>(L, rgba, depth, block, i < half ? 2 * i : 2 * (i - half) + 1);
+                const unsigned cur = src.byte(L, block, i < half ? 2 * i : 2 * (i - half) + 1);
                 val |= (i == 0 ? cur : (cur - before + 128u) & 255u) << (8 * k);
                 before = cur;
             }
@@ -219,8 +303,9 @@ __device__ __forceinline__ long long block_stream(const ExrLayout &L, const Chun
     return bytes;
 }
 
+// (chans: the channel table of a file with feature channels, or nullptr: the plain file's fixed list)
 __global__ void __launch_bounds__(1024) k_exr_assemble(ExrLayout L, const ChunkMeta *__restrict__ meta, unsigned char *file, long long *offsets,
-                                                       ExrBlock *blocks, ExrInfo *info)
+                                                       ExrBlock *blocks, ExrInfo *info, const ExrChannels *chans)
 {
     __shared__ long long wsum[16];
     const int t = (int)threadIdx.x;
@@ -265,7 +350,8 @@ __global__ void __launch_bounds__(1024) k_exr_assemble(ExrLayout L, const ChunkM
         off += 8 + data;
     }
     if (t == 0) {
-        (void)exr_header(file, L.width, L.rows, L.n_ch, L.pixel_type);
+        if (chans) (void)exr_header_list(file, L.width, L.rows, chans);
+        else (void)exr_header(file, L.width, L.rows, L.n_ch, L.pixel_type);
         info->file_bytes = first + all_size;
         info->raw_bytes = L.raw_bytes;
         info->blocks = L.n_blocks;
@@ -273,8 +359,8 @@ __global__ void __launch_bounds__(1024) k_exr_assemble(ExrLayout L, const ChunkM
     }
 }
 
-template <bool HALF>
-__global__ void __launch_bounds__(256) k_exr_place(ExrLayout L, const double *__restrict__ rgba, const double *__restrict__ depth,
+template <class SRC>
+__global__ void __launch_bounds__(256) k_exr_place(ExrLayout L, SRC src,
                                                    const unsigned char *__restrict__ slots, const ChunkMeta *__restrict__ meta,
                                                    const long long *__restrict__ offsets, const ExrBlock *__restrict__ blocks, unsigned char *file)
 {
@@ -283,7 +369,7 @@ __global__ void __launch_bounds__(256) k_exr_place(ExrLayout L, const double *__
     if (rec.raw) {
         const int r0 = c * PNG_CHUNK, left = block_bytes(L, block) - r0, n = left < PNG_CHUNK ? left : PNG_CHUNK;
         unsigned char *dst = file + rec.data_off + r0;
-        for (int k = (int)threadIdx.x; k < n; k += 256) dst[k] = (unsigned char)raw_byte<HALF>(L, rgba, depth, block, r0 + k);
+        for (int k = (int)threadIdx.x; k < n; k += 256) dst[k] = (unsigned char)src.byte(L, block, r0 + k);
     } else {
         const unsigned char *src = slots + (long long)idx * PNG_SLOT;
         unsigned char *dst = file + offsets[idx];
@@ -302,11 +388,17 @@ int pixel_type_of(const ndt_exr_params *ep)
 }
 
 // the file's layout, or false for a size the encoder does not take: empty, or raw bytes beyond 2^31 - 1
-bool layout_of(int32_t width, int32_t rows, int pixel_type, bool with_depth, ExrLayout &L)
+// (C: the channel table of a file with feature channels -- its channels, not A B G R [Z], make the scanline)
+bool layout_of(int32_t width, int32_t rows, int pixel_type, bool with_depth, ExrLayout &L, const ExrChannels *C = nullptr)
 {
     if (width < 1 || rows < 1 || pixel_type < 0) return false;
     const long long bs = pixel_type == EXR_HALF ? 2 : 4;
-    const long long colour = 4 * bs * (long long)width, line = colour + (with_depth ? 4LL * width : 0), raw = line * (long long)rows;
+    long long colour = 4 * bs * (long long)width, line = colour + (with_depth ? 4LL * width : 0);
+    if (C) {
+        line = (long long)C->units * width;     // the table's channels
+        colour = 0;
+    }
+    const long long raw = line * (long long)rows;
     if (raw > 0x7fffffffLL) return false;
     const long long n_blocks = ((long long)rows + EXR_LINES - 1) / EXR_LINES;
     const long long full = (rows < EXR_LINES ? rows : EXR_LINES) * line, last = raw - (n_blocks - 1) * EXR_LINES * line;
@@ -316,33 +408,75 @@ bool layout_of(int32_t width, int32_t rows, int pixel_type, bool with_depth, Exr
     L.line_bytes = (int)line; L.colour_bytes = (int)colour;
     L.n_blocks = (int)n_blocks; L.cpb = (int)cpb;
     L.n_chunks = (int)((n_blocks - 1) * cpb + (last + PNG_CHUNK - 1) / PNG_CHUNK);
-    L.header_bytes = exr_header(nullptr, width, rows, L.n_ch, pixel_type);
+    if (C) L.n_ch = C->n;
+    L.header_bytes = C ? exr_header_list(nullptr, width, rows, C) : exr_header(nullptr, width, rows, L.n_ch, pixel_type);
     L.raw_bytes = raw;
     return true;
+}
+
+// The channel table of a file with the feature groups of `features`, in the byte-wise order of the names: A B G, N.00 .., P.00 ..,
+// R, Z, id.  Indices have two digits, so that order is the numeric one.  planes may be nullptr (the sizes only).
+void channel_table(ExrChannels &C, int pixel_type, const void *d_rgba, const void *d_depth, bool with_depth, const ndt_feature_planes *planes,
+                   int dims, int features, long long pixels)
+{
+    C = ExrChannels{};
+    auto add = [&C](const char *name, int index, const void *src, int stride, bool is_int, int conv) {
+        ExrChannel &ch = C.ch[C.n];
+        ch.src = src;
+        ch.stride = stride;
+        ch.is_int = is_int ? 1 : 0;
+        ch.conv = conv;
+        ch.pixel_type = conv == EXR_TO_HALF ? EXR_HALF : conv == EXR_TO_FLOAT ? EXR_FLOAT : EXR_UINT;
+        ch.bytes = conv == EXR_TO_HALF ? 2 : 4;
+        ch.first_unit = C.units;
+        if (index < 0) snprintf(ch.name, sizeof(ch.name), "%s", name);
+        else snprintf(ch.name, sizeof(ch.name), "%s.%02d", name, index);
+        for (int k = 0; k < ch.bytes; ++k) C.unit_channel[C.units++] = (unsigned char)C.n;
+        ++C.n;
+    };
+    const int colour = pixel_type == EXR_HALF ? EXR_TO_HALF : EXR_TO_FLOAT;
+    const double *rgba = (const double *)d_rgba;
+    add("A", -1, rgba ? rgba + 3 : nullptr, 4, false, colour);      // the framebuffer is R G B A
+    add("B", -1, rgba ? rgba + 2 : nullptr, 4, false, colour);
+    add("G", -1, rgba ? rgba + 1 : nullptr, 4, false, colour);
+    if (features & NDT_FEATURE_NORMAL)
+        for (int c = 0; c < dims; ++c) add("N", c, planes && planes->normal ? planes->normal + c * pixels : nullptr, 1, false, EXR_TO_FLOAT);
+    if (features & NDT_FEATURE_POSITION)
+        for (int c = 0; c < dims; ++c) add("P", c, planes && planes->position ? planes->position + c * pixels : nullptr, 1, false, EXR_TO_FLOAT);
+    add("R", -1, rgba, 4, false, colour);
+    if (with_depth) add("Z", -1, d_depth, 1, false, EXR_TO_FLOAT);
+    if (features & NDT_FEATURE_ID) add("id", -1, planes ? planes->id : nullptr, 1, true, EXR_AS_UINT);
+}
+
+bool features_ok(int dims, int features)
+{
+    return dims >= NDT_MIN_DIMS && dims <= NDT_MAX_DIMS && features != 0 && (features & ~EXR_ALL_FEATURES) == 0;
 }
 
 // every block raw: the header, an offset and a block header a block, the raw bytes
 long long file_bound(const ExrLayout &L) { return (long long)L.header_bytes + 16LL * L.n_blocks + L.raw_bytes; }
 
-template <bool HALF>
-void launch_all(hipStream_t s, const ExrLayout &L, const double *d_rgba, const double *d_depth, ExrState &ex)
+// (d_chans: the channel table in device memory where SRC reads one, else nullptr)
+template <class SRC>
+void launch_all(hipStream_t s, const ExrLayout &L, SRC src, const ExrChannels *d_chans, ExrState &ex)
 {
     const int words = (int)(((long long)L.cpb * PNG_CHUNK) / 4), across = (words + 255) / 256;
-    hipLaunchKernelGGL(k_exr_pack<HALF>, dim3((unsigned)(across < 256 ? across : 256), (unsigned)L.n_blocks), dim3(256), 0, s, L, d_rgba, d_depth,
+    hipLaunchKernelGGL(k_exr_pack<SRC>, dim3((unsigned)(across < 256 ? across : 256), (unsigned)L.n_blocks), dim3(256), 0, s, L, src,
                        ex.d_packed.as<unsigned>());
     hipLaunchKernelGGL(k_exr_deflate, dim3((unsigned)L.n_chunks), dim3(PNG_DEFLATE_LANES), 0, s, L, ex.d_packed.as<const unsigned char>(),
                        ex.d_slots.as<unsigned char>(), ex.d_meta.as<ChunkMeta>());
     hipLaunchKernelGGL(k_exr_assemble, dim3(1), dim3(1024), 0, s, L, ex.d_meta.as<const ChunkMeta>(), ex.d_file.as<unsigned char>(),
-                       ex.d_offsets.as<long long>(), ex.d_blocks.as<ExrBlock>(), ex.d_info.as<ExrInfo>());
-    hipLaunchKernelGGL(k_exr_place<HALF>, dim3((unsigned)L.n_chunks), dim3(256), 0, s, L, d_rgba, d_depth, ex.d_slots.as<const unsigned char>(),
+                       ex.d_offsets.as<long long>(), ex.d_blocks.as<ExrBlock>(), ex.d_info.as<ExrInfo>(), d_chans);
+    hipLaunchKernelGGL(k_exr_place<SRC>, dim3((unsigned)L.n_chunks), dim3(256), 0, s, L, src, ex.d_slots.as<const unsigned char>(),
                        ex.d_meta.as<const ChunkMeta>(), ex.d_offsets.as<const long long>(), ex.d_blocks.as<const ExrBlock>(),
                        ex.d_file.as<unsigned char>());
 }
 
 // The file of the width x rows doubles at d_rgba (and the map at d_depth, or nullptr) -- the context's device memory -- in host
-// memory; `who` names the entry point in errors.
+// memory; `who` names the entry point in errors.  features != 0: with the feature channels of that mask from d_planes.
 int encode_device(ndt_hip_ctx *ctx, const char *who, const void *d_rgba, const void *d_depth, int32_t width, int32_t rows,
-                  const ndt_exr_params *ep, uint8_t *out, int64_t cap, ndt_exr_stats *stats)
+                  const ndt_exr_params *ep, uint8_t *out, int64_t cap, ndt_exr_stats *stats, const ndt_feature_planes *d_planes = nullptr,
+                  int dims = 0, int features = 0)
 {
     if (stats) *stats = ndt_exr_stats{};
     if (!ctx || !d_rgba || !out) return fail(NDT_E_INVALID, "%s: NULL argument", who);
@@ -351,8 +485,19 @@ int encode_device(ndt_hip_ctx *ctx, const char *who, const void *d_rgba, const v
     if (pixel_type < 0) return fail(NDT_E_INVALID, "%s: pixel type %d: 1 is half, 2 float (0: half)", who, ep->pixel_type);
     if (cap < 0) return fail(NDT_E_INVALID, "%s: cap %lld", who, (long long)cap);
     if ((((uintptr_t)d_rgba | (uintptr_t)d_depth) & 7u) != 0) return fail(NDT_E_INVALID, "%s: the doubles are not aligned to 8 bytes", who);
+    ExrChannels table;
+    if (features) {
+        if (!features_ok(dims, features))
+            return fail(NDT_E_INVALID, "%s: %d dimensions, feature mask %d: 3 .. 12, and a mask of id 1, position 2, normal 4", who, dims, features);
+        if (!d_planes || ((features & NDT_FEATURE_ID) && !d_planes->id) || ((features & NDT_FEATURE_POSITION) && !d_planes->position) ||
+            ((features & NDT_FEATURE_NORMAL) && !d_planes->normal))
+            return fail(NDT_E_INVALID, "%s: a plane of feature mask %d is NULL", who, features);
+        if (((uintptr_t)d_planes->id & 3u) != 0 || (((uintptr_t)d_planes->position | (uintptr_t)d_planes->normal) & 7u) != 0)
+            return fail(NDT_E_INVALID, "%s: a feature plane is not aligned to its elements", who);
+        channel_table(table, pixel_type, d_rgba, d_depth, d_depth != nullptr, d_planes, dims, features, (long long)width * rows);
+    }
     ExrLayout L;
-    if (!layout_of(width, rows, pixel_type, d_depth != nullptr, L))
+    if (!layout_of(width, rows, pixel_type, d_depth != nullptr, L, features ? &table : nullptr))
         return fail(NDT_E_INVALID, "%s: the samples of a %d x %d image exceed 2^31 - 1 bytes", who, width, rows);
     const auto t0 = std::chrono::steady_clock::now();
     HIP_TRY(hipSetDevice(ctx->device));
@@ -368,8 +513,17 @@ int encode_device(ndt_hip_ctx *ctx, const char *who, const void *d_rgba, const v
     if ((rc = ex.d_file.reserve((size_t)bound, s, who))) return rc;
     if ((rc = ex.d_info.reserve(sizeof(ExrInfo), s, who))) return rc;
     if (!ex.h_info) HIP_TRY(hipHostMalloc(&ex.h_info, sizeof(ExrInfo), hipHostMallocDefault));
-    if (pixel_type == EXR_HALF) launch_all<true>(s, L, (const double *)d_rgba, (const double *)d_depth, ex);
-    else launch_all<false>(s, L, (const double *)d_rgba, (const double *)d_depth, ex);
+    if (features) {
+        // (the table leaves this frame before the call goes on: it is copied from pageable memory)
+        if ((rc = ex.d_channels.reserve(sizeof(ExrChannels), s, who))) return rc;
+        HIP_TRY(hipMemcpyAsync(ex.d_channels.p, &table, sizeof(ExrChannels), hipMemcpyHostToDevice, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        launch_all(s, L, ListSource{ ex.d_channels.as<const ExrChannels>() }, ex.d_channels.as<const ExrChannels>(), ex);
+    } else if (pixel_type == EXR_HALF) {
+        launch_all(s, L, PlainSource<true>{ (const double *)d_rgba, (const double *)d_depth }, nullptr, ex);
+    } else {
+        launch_all(s, L, PlainSource<false>{ (const double *)d_rgba, (const double *)d_depth }, nullptr, ex);
+    }
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(ex.h_info, ex.d_info.p, sizeof(ExrInfo), hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
@@ -409,13 +563,24 @@ int check_render(const char *who, ndt_hip_ctx *ctx, const ndt_render_params *p, 
 }
 
 // the frame (K = 0: plain; K >= 1: supersampled K x K) in doubles in ctx->d_out, its map behind it if wanted, then the file of those
+// features != 0: behind the render the feature pass of the plain frame, on the same stream, and its planes as channels
 int render_file(const char *who, ndt_hip_ctx *ctx, const ndt_render_params *p, int32_t K, const ndt_exr_params *ep, int32_t with_depth,
-                uint8_t *out, int64_t cap, ndt_exr_stats *stats, ndt_render_stats *render_stats)
+                uint8_t *out, int64_t cap, ndt_exr_stats *stats, ndt_render_stats *render_stats, int features = 0)
 {
     if (stats) *stats = ndt_exr_stats{};
     int rows = 0;
     int rc = check_render(who, ctx, p, ep, with_depth, out, &rows);
     if (rc) return rc;
+    if (features) {
+        if ((features & ~EXR_ALL_FEATURES) != 0) return fail(NDT_E_INVALID, "%s: feature mask %d: id 1, position 2, normal 4", who, features);
+        int feature_rows = 0;
+        if ((rc = features_check(who, ctx, p, &feature_rows))) return rc;
+        ExrChannels table;
+        ExrLayout L;
+        channel_table(table, pixel_type_of(ep), nullptr, nullptr, with_depth != 0, nullptr, ctx->dims, features, 0);
+        if (!layout_of(p->width, rows, pixel_type_of(ep), with_depth != 0, L, &table))
+            return fail(NDT_E_INVALID, "%s: the samples of a %d x %d image exceed 2^31 - 1 bytes", who, p->width, rows);
+    }
     HIP_TRY(hipSetDevice(ctx->device));
     const size_t pixels = (size_t)p->width * (size_t)rows, img_bytes = pixels * 4 * sizeof(double);
     if ((rc = ctx->d_out.reserve(img_bytes + (with_depth ? pixels * sizeof(double) : 0), ctx->stream, who))) return rc;
@@ -423,7 +588,10 @@ int render_file(const char *who, ndt_hip_ctx *ctx, const ndt_render_params *p, i
     rc = K ? ndt_hip_render_ssaa_device(ctx, p, K, ctx->d_out.p, d_depth, render_stats)
            : ndt_hip_render_depth_device(ctx, p, ctx->d_out.p, d_depth, render_stats);
     if (rc) return rc;
-    return encode_device(ctx, who, ctx->d_out.p, d_depth, p->width, rows, ep, out, cap, stats);
+    if (!features) return encode_device(ctx, who, ctx->d_out.p, d_depth, p->width, rows, ep, out, cap, stats);
+    ndt_feature_planes planes;
+    if ((rc = features_own(ctx, who, p, features, false, &planes))) return rc;
+    return encode_device(ctx, who, ctx->d_out.p, d_depth, p->width, rows, ep, out, cap, stats, &planes, ctx->dims, features);
 }
 
 } // namespace
@@ -439,6 +607,7 @@ void ndt_impl::free_exr(ndt_hip_ctx *ctx)
     ex.d_blocks.release();
     ex.d_file.release();
     ex.d_info.release();
+    ex.d_channels.release();
     if (ex.h_info) (void)hipHostFree(ex.h_info);
     ex = ExrState();
 }
@@ -489,4 +658,45 @@ extern "C" int ndt_hip_render_ssaa_exr(ndt_hip_ctx *ctx, const ndt_render_params
 {
     if (K < 1 || K > 8) return fail(NDT_E_INVALID, "ndt_hip_render_ssaa_exr: ssaa %d is outside 1 .. 8", K);
     return render_file("ndt_hip_render_ssaa_exr", ctx, p, K, ep, with_depth, out, cap, stats, render_stats);
+}
+
+extern "C" int64_t ndt_hip_exr_features_bound(int32_t width, int32_t rows, const ndt_exr_params *ep, int32_t with_depth, int32_t dims,
+                                              int32_t features)
+{
+    const int pixel_type = pixel_type_of(ep);
+    if (pixel_type < 0 || !features_ok(dims, features)) return NDT_E_INVALID;
+    ExrChannels table;
+    ExrLayout L;
+    channel_table(table, pixel_type, nullptr, nullptr, with_depth != 0, nullptr, dims, features, 0);
+    if (!layout_of(width, rows, pixel_type, with_depth != 0, L, &table)) return NDT_E_INVALID;
+    return file_bound(L);
+}
+
+extern "C" int ndt_hip_encode_exr_features_device(ndt_hip_ctx *ctx, const void *d_rgba, const void *d_depth, const ndt_feature_planes *d_planes,
+                                                  int32_t dims, int32_t features, int32_t width, int32_t rows, const ndt_exr_params *ep,
+                                                  uint8_t *out, int64_t cap, ndt_exr_stats *stats)
+{
+    const char *who = "ndt_hip_encode_exr_features_device";
+    if (stats) *stats = ndt_exr_stats{};
+    if (!features_ok(dims, features))
+        return fail(NDT_E_INVALID, "%s: %d dimensions, feature mask %d: 3 .. 12, and a mask of id 1, position 2, normal 4", who, dims, features);
+    return encode_device(ctx, who, d_rgba, d_depth, width, rows, ep, out, cap, stats, d_planes, dims, features);
+}
+
+extern "C" int ndt_hip_render_exr_features(ndt_hip_ctx *ctx, const ndt_render_params *p, const ndt_exr_params *ep, int32_t with_depth,
+                                           int32_t features, uint8_t *out, int64_t cap, ndt_exr_stats *stats, ndt_render_stats *render_stats)
+{
+    const char *who = "ndt_hip_render_exr_features";
+    if (features == 0) return fail(NDT_E_INVALID, "%s: feature mask 0: id 1, position 2, normal 4", who);
+    return render_file(who, ctx, p, 0, ep, with_depth, out, cap, stats, render_stats, features);
+}
+
+extern "C" int ndt_hip_render_ssaa_exr_features(ndt_hip_ctx *ctx, const ndt_render_params *p, int32_t K, const ndt_exr_params *ep,
+                                                int32_t with_depth, int32_t features, uint8_t *out, int64_t cap, ndt_exr_stats *stats,
+                                                ndt_render_stats *render_stats)
+{
+    const char *who = "ndt_hip_render_ssaa_exr_features";
+    if (K < 1 || K > 8) return fail(NDT_E_INVALID, "%s: ssaa %d is outside 1 .. 8", who, K);
+    if (features == 0) return fail(NDT_E_INVALID, "%s: feature mask 0: id 1, position 2, normal 4", who);
+    return render_file(who, ctx, p, K, ep, with_depth, out, cap, stats, render_stats, features);
 }

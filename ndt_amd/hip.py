@@ -33,6 +33,8 @@ API_SYMBOLS = [
     "ndt_hip_render_png16", "ndt_hip_render_png16_depth", "ndt_hip_render_ssaa_png16", "ndt_hip_render_ssaa_png16_depth",
     "ndt_hip_apng_bound", "ndt_hip_apng_begin", "ndt_hip_apng_add_device", "ndt_hip_apng_add", "ndt_hip_render_apng_frame", "ndt_hip_apng_end",
     "ndt_hip_exr_bound", "ndt_hip_encode_exr_device", "ndt_hip_encode_exr", "ndt_hip_render_exr", "ndt_hip_render_ssaa_exr",
+    "ndt_hip_render_features", "ndt_hip_render_features_device", "ndt_hip_features_launches", "ndt_hip_exr_features_bound",
+    "ndt_hip_encode_exr_features_device", "ndt_hip_render_exr_features", "ndt_hip_render_ssaa_exr_features",
 ]
 
 IMAGE_F64, IMAGE_RGBA8 = 0, 1      # enum ndt_image_format
@@ -167,6 +169,18 @@ def load_library():
         lib.ndt_hip_render_exr.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
         lib.ndt_hip_render_ssaa_exr.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p,
                                                 C.c_void_p]
+    if hasattr(lib, "ndt_hip_render_features"):     # (likewise)
+        lib.ndt_hip_render_features.argtypes = [C.c_void_p] * 4
+        lib.ndt_hip_render_features_device.argtypes = [C.c_void_p] * 4
+        lib.ndt_hip_features_launches.argtypes = [C.c_void_p]
+        lib.ndt_hip_exr_features_bound.argtypes = [C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32]
+        lib.ndt_hip_exr_features_bound.restype = C.c_int64
+        lib.ndt_hip_encode_exr_features_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
+                                                           C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
+        lib.ndt_hip_render_exr_features.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int64,
+                                                    C.c_void_p, C.c_void_p]
+        lib.ndt_hip_render_ssaa_exr_features.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p,
+                                                         C.c_int64, C.c_void_p, C.c_void_p]
     _lib = lib
     return lib
 
@@ -228,6 +242,40 @@ def exr_bound(width, rows, pixel="half", depth_map=False):
     n = int(load_library().ndt_hip_exr_bound(int(width), int(rows), C.byref(ep), 1 if depth_map else 0))
     if n < 0:
         raise ValueError("no EXR of %d x %d: the size is empty or its samples exceed 2^31 - 1 bytes" % (width, rows))
+    return n
+
+
+FEATURES = {"id": 1, "position": 2, "normal": 4}        # NDT_FEATURE_*
+
+
+class FeaturePlanes(C.Structure):
+    """ndt_feature_planes: where the planes of a feature pass go (host or device pointers; None: not wanted)"""
+    _fields_ = [("id", C.c_void_p), ("position", C.c_void_p), ("normal", C.c_void_p), ("ray_o", C.c_void_p), ("ray_v", C.c_void_p)]
+
+
+def feature_mask(features):
+    """The NDT_FEATURE_* mask of an iterable of "id" / "position" / "normal" (or of a mask); ValueError for anything else or none."""
+    if isinstance(features, int):
+        mask = features
+    else:
+        mask = 0
+        for name in features:
+            if str(name) not in FEATURES:
+                raise ValueError("feature %r is none of 'id', 'position', 'normal'" % (name,))
+            mask |= FEATURES[str(name)]
+    if mask <= 0 or mask & ~7:
+        raise ValueError("feature mask %r: at least one of id 1, position 2, normal 4" % (mask,))
+    return mask
+
+
+def exr_features_bound(width, rows, dims, features=("id", "position", "normal"), pixel="half", depth_map=False):
+    """ndt_hip_exr_features_bound: exr_bound for a file that also carries the feature channels of a dims-dimensional scene."""
+    ep = exr_params(pixel)
+    n = int(load_library().ndt_hip_exr_features_bound(int(width), int(rows), C.byref(ep), 1 if depth_map else 0, int(dims),
+                                                      feature_mask(features)))
+    if n < 0:
+        raise ValueError("no EXR of %d x %d with the features of %d dimensions: a bad size, or samples beyond 2^31 - 1 bytes"
+                         % (width, rows, dims))
     return n
 
 
@@ -656,33 +704,79 @@ class NdtHip:
                                                        int(width), int(rows), C.byref(ep), out.ctypes.data, cap, C.byref(self.exr_stats)))
         return out[:self.exr_stats.file_bytes].tobytes()
 
-    def render_exr(self, width, height, depth, pixel="half", depth_map=False, **kw):
+    def render_exr(self, width, height, depth, pixel="half", depth_map=False, features=None, cap=None, **kw):
         """ndt_hip_render_exr: render() with the device's OpenEXR encoder in place of the download; depth_map=True adds the map as
-        the file's Z channel.  Returns (the file's bytes, RenderStats); self.exr_stats keeps the ndt_exr_stats.  The file's height
-        is the row shard's."""
+        the file's Z channel.  features (names of FEATURES, e.g. ("id", "position", "normal")): ndt_hip_render_exr_features, the
+        primary hit of every pixel as the channels id, P.*, N.* of the file.  Returns (the file's bytes, RenderStats);
+        self.exr_stats keeps the ndt_exr_stats.  The file's height is the row shard's.  cap: room offered (default: the bound)."""
         p = self.params(width, height, depth, **kw)
         rows = shard_rows(height, p.row_begin, p.row_step)
         ep = exr_params(pixel)
-        cap = exr_bound(width, rows, pixel, depth_map)
-        out = np.zeros(cap, dtype=np.uint8)
+        if cap is None:
+            cap = exr_features_bound(width, rows, self.scene.dims, features, pixel, depth_map) if features else exr_bound(width, rows, pixel, depth_map)
+        out = np.zeros(int(cap), dtype=np.uint8)
         st = RenderStats()
         self.exr_stats = ExrStats()
-        self._check(self.lib.ndt_hip_render_exr(self.ctx, C.byref(p), C.byref(ep), 1 if depth_map else 0, out.ctypes.data, cap,
-                                                C.byref(self.exr_stats), C.byref(st)))
+        if features:
+            self._check(self.lib.ndt_hip_render_exr_features(self.ctx, C.byref(p), C.byref(ep), 1 if depth_map else 0, feature_mask(features),
+                                                             out.ctypes.data, int(cap), C.byref(self.exr_stats), C.byref(st)))
+        else:
+            self._check(self.lib.ndt_hip_render_exr(self.ctx, C.byref(p), C.byref(ep), 1 if depth_map else 0, out.ctypes.data, int(cap),
+                                                    C.byref(self.exr_stats), C.byref(st)))
         return out[:self.exr_stats.file_bytes].tobytes(), st
 
-    def render_ssaa_exr(self, width, height, depth, ssaa, pixel="half", depth_map=False, **kw):
+    def render_ssaa_exr(self, width, height, depth, ssaa, pixel="half", depth_map=False, features=None, **kw):
         """ndt_hip_render_ssaa_exr: the supersampled frame as an OpenEXR file (Z: sub-sample (0, 0)'s map): (the file's bytes, stats);
-        self.exr_stats keeps the record."""
+        self.exr_stats keeps the record.  features: ndt_hip_render_ssaa_exr_features, the plain frame's feature channels beside it."""
         p, rows = self._ssaa_params(width, height, depth, kw)
         ep = exr_params(pixel)
-        cap = exr_bound(width, rows, pixel, depth_map)
+        cap = exr_features_bound(width, rows, self.scene.dims, features, pixel, depth_map) if features else exr_bound(width, rows, pixel, depth_map)
         out = np.zeros(cap, dtype=np.uint8)
         st = RenderStats()
         self.exr_stats = ExrStats()
-        self._check(self.lib.ndt_hip_render_ssaa_exr(self.ctx, C.byref(p), int(ssaa), C.byref(ep), 1 if depth_map else 0, out.ctypes.data,
-                                                     cap, C.byref(self.exr_stats), C.byref(st)))
+        if features:
+            self._check(self.lib.ndt_hip_render_ssaa_exr_features(self.ctx, C.byref(p), int(ssaa), C.byref(ep), 1 if depth_map else 0,
+                                                                  feature_mask(features), out.ctypes.data, cap, C.byref(self.exr_stats),
+                                                                  C.byref(st)))
+        else:
+            self._check(self.lib.ndt_hip_render_ssaa_exr(self.ctx, C.byref(p), int(ssaa), C.byref(ep), 1 if depth_map else 0, out.ctypes.data,
+                                                         cap, C.byref(self.exr_stats), C.byref(st)))
         return out[:self.exr_stats.file_bytes].tobytes(), st
+
+    def render_features(self, width, height, depth, rays=False, **kw):
+        """ndt_hip_render_features: what every pixel of the frame shows -- the closest hit of its primary ray.  Returns a dict of
+        arrays: "id" (rows, width) int32, object index + 1 and 0 for no hit; "position" and "normal" (dims, rows, width) float64,
+        zero where id is 0; with rays=True also "ray_o" and "ray_v" (dims, rows, width), the rays themselves.  kw: as render()'s
+        (row shards, stereo 1 / 2); frames without one primary ray a pixel (aa, samples > 1, anaglyph) are refused."""
+        p = self.params(width, height, depth, **kw)
+        rows = shard_rows(height, p.row_begin, p.row_step)
+        d = self.scene.dims
+        out = {"id": np.zeros((rows, width), dtype=np.int32), "position": np.zeros((d, rows, width)), "normal": np.zeros((d, rows, width))}
+        if rays:
+            out["ray_o"], out["ray_v"] = np.zeros((d, rows, width)), np.zeros((d, rows, width))
+        planes = FeaturePlanes(*[out[k].ctypes.data if k in out else None for k in ("id", "position", "normal", "ray_o", "ray_v")])
+        st = RenderStats()
+        self._check(self.lib.ndt_hip_render_features(self.ctx, C.byref(p), C.byref(planes), C.byref(st)))
+        return out
+
+    def features_launches(self):
+        """ndt_hip_features_launches: kernel launches of the context's last feature pass."""
+        return int(self.lib.ndt_hip_features_launches(self.ctx))
+
+    def encode_exr_features_device(self, d_rgba_ptr, d_depth_ptr, d_planes, dims, features, width, rows, pixel="half", cap=None):
+        """ndt_hip_encode_exr_features_device: the file of device doubles at `d_rgba_ptr` (and the map at `d_depth_ptr`, or None)
+        with the feature channels of `features` taken from the device planes `d_planes` names: a dict "id" / "position" / "normal"
+        of raw device pointers.  Returns the file's bytes; self.exr_stats keeps the record."""
+        ep = exr_params(pixel)
+        mask = feature_mask(features)
+        cap = exr_features_bound(width, rows, dims, mask, pixel, d_depth_ptr is not None) if cap is None else int(cap)
+        out = np.zeros(max(cap, 1), dtype=np.uint8)
+        planes = FeaturePlanes(d_planes.get("id"), d_planes.get("position"), d_planes.get("normal"), None, None)
+        self.exr_stats = ExrStats()
+        self._check(self.lib.ndt_hip_encode_exr_features_device(self.ctx, C.c_void_p(d_rgba_ptr), C.c_void_p(d_depth_ptr) if d_depth_ptr else None,
+                                                                C.byref(planes), int(dims), mask, int(width), int(rows), C.byref(ep),
+                                                                out.ctypes.data, cap, C.byref(self.exr_stats)))
+        return out[:self.exr_stats.file_bytes].tobytes()
 
     def apng_begin(self, width, rows, n_frames, delay_num=1, delay_den=24, n_plays=0):
         """ndt_hip_apng_begin: opens the context's animated-PNG session: n_frames frames of width x rows pixels are to come, each

@@ -433,6 +433,10 @@ typedef struct ndt_frame_request {
     ndt_map_kind map;
     int jpeg_quality, jpeg_sampling;    /* NDT_COLOUR_JPEG: 1 .. 100 (0 = the reference's 95); 0 = 4:2:0 (libjpeg's default), 1 = 4:4:4 */
     int exr_pixel;                      /* NDT_COLOUR_EXR: the colour channels' samples, 1 half, 2 float (0 = half) */
+    int exr_features;                   /* NDT_COLOUR_EXR only: a mask of NDT_FEATURE_ID / _POSITION / _NORMAL (include/ndt_hip.h): what every
+                                         * pixel's primary ray hits -- object, N-D point, normal -- as extra channels id, P.*, N.* of the file
+                                         * (`--exr-aov`); 0 = none.  Refused with any other colour kind, and where a pixel has no single
+                                         * primary ray: aa_depth >= 0, samples > 1, anaglyph, frame packing */
 } ndt_frame_request;
 /* Everything that arrives is malloc'ed by the library and freed by ndt_frame_free; what was not asked for stays NULL. */
 typedef struct ndt_frame {
@@ -443,6 +447,7 @@ typedef struct ndt_frame {
     double range[2];                /* the map's minimum and maximum (a map finished on the GPU) */
     /* host milliseconds of the frame's device work beside the render: making the file or files, finishing the map, the folds of --ssaa */
     double file_ms, depth_ms, ssaa_ms;
+    int feature_channels, feature_launches;     /* exr_features: the channels it added to the file, and the kernel launches of the feature pass */
 } ndt_frame;
 /* Returns 1 like the reference's render_image on success; 0 with a message on stderr otherwise, and then `out` is zeroed: nothing
  * is left to free.  No fallback: without a device, or with a frame the device path refuses (HIDEF frame packing supersampled, ...),
@@ -450,7 +455,7 @@ typedef struct ndt_frame {
  * as 8-bit pixels, and a PNG or JPEG file is then encoded from those on the first context; a frame with a map is rendered by one
  * context whatever was set, and a 16-bit PNG, an OpenEXR file or an animated PNG frame over several contexts is refused.  What the
  * device did is said on stdout: `compressed PNG of B bytes on GPU D in L launches` (`16-bit PNG`, `depth PNG`, `16-bit depth PNG`),
- * `encoded JPEG of ...`, `encoded EXR of ...`, `finished depth map [lo, hi] on GPU D in L launches`, `supersampled KxK on GPU D in L launches`, `animated PNG frame
+ * `encoded JPEG of ...`, `encoded EXR of ...`, `added K feature channels on GPU D in L launches`, `finished depth map [lo, hi] on GPU D in L launches`, `supersampled KxK on GPU D in L launches`, `animated PNG frame
  * K: w x h at x,y (B bytes) on GPU D in L launches`. */
 int ndt_render_frame(scene *scn, const ndt_frame_request *request, ndt_frame *out);
 /* safe on a zeroed or a half-filled frame; leaves it zeroed */

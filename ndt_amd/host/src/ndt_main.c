@@ -25,7 +25,11 @@
  * or with `--exr-pixel float` as floats, ZIP-compressed on the GPU (ndt_hip_render_exr); with `-z` the map is the file's Z channel,
  * unstretched, and no depth/ file is written.  With --ssaa, -a, -n, -m s|o|a and -j; it is the run's colour file (not with --png,
  * --jpeg, --raw, --png16 or --apng), the map needs no finish (not with --depth gpu or --depth-png), and one context makes it (not
- * with -g N > 1).  None falls back: what the device path cannot do ends the run. */
+ * with -g N > 1).  `--exr --exr-aov id,position,normal` (or `all`; any order, repeats allowed) adds what every pixel shows to that
+ * file: the object its primary ray hits (channel id, UINT: object index + 1, 0 for none), the hit point in all N coordinates (P.00 ..,
+ * FLOAT) and the normal there (N.00 .., FLOAT), found on the GPU by a feature pass beside the render (ndt_hip_render_exr_features).
+ * With -z, --ssaa, -m s|o, -j, --fit gpu and --kd gpu; not with -a, -n above 1 or -m a|h, where a pixel has no single primary ray.
+ * None falls back: what the device path cannot do ends the run. */
 #include <dlfcn.h>
 #include <getopt.h>
 #include <pthread.h>
@@ -419,6 +423,8 @@ int main(int argc, char **argv)
     int apng_fps = 0;       /* --apng-fps 1 .. 1000 (default 24): each frame is shown 1 / F seconds */
     int exr = 0;            /* --exr: the frame's file is an OpenEXR file of the doubles in linear light, made on the GPU; with -z the map is its Z channel */
     int exr_pixel = 0;      /* --exr-pixel half|float: the colour channels' samples, 1 / 2 (default: half) */
+    int exr_aov = 0;        /* --exr-aov id,position,normal|all: what every pixel's primary ray hits, as channels id, P.*, N.* of the OpenEXR file (a mask of NDT_FEATURE_*) */
+    int exr_aov_given = 0;
     char *objects_dir = "objects";      /* -o: where object plugins are looked for (object.c:119; ndt.c passes "objects") */
     static struct option longopts[] = { { "dump-scene", required_argument, NULL, 1000 },
                                         { "raw", required_argument, NULL, 1001 }, { "png", no_argument, NULL, 1002 },
@@ -429,7 +435,7 @@ int main(int argc, char **argv)
                                         { "jpeg-sampling", required_argument, NULL, 1010 }, { "ssaa", required_argument, NULL, 1011 },
                                         { "png16", no_argument, NULL, 1012 }, { "apng", no_argument, NULL, 1013 },
                                         { "apng-fps", required_argument, NULL, 1014 }, { "exr", no_argument, NULL, 1015 },
-                                        { "exr-pixel", required_argument, NULL, 1016 },
+                                        { "exr-pixel", required_argument, NULL, 1016 }, { "exr-aov", required_argument, NULL, 1017 },
                                         { NULL, 0, NULL, 0 } };
     int ch;
     while ((ch = getopt_long(argc, argv, "a:d:g:r:f:j:l:m:3:n:ps:t:u:o:zh", longopts, NULL)) != -1) {
@@ -544,9 +550,29 @@ int main(int argc, char **argv)
             else if (!strcmp(optarg, "float")) exr_pixel = 2;
             else { fprintf(stderr, "%s: --exr-pixel takes half or float, not '%s'\n", argv[0], optarg); return 1; }
             break;
+        case 1017: {
+            /* words separated by commas, in any order, repeats allowed */
+            const char *w = optarg;
+            exr_aov_given = 1;
+            for (;;) {
+                const size_t len = strcspn(w, ",");
+                if (len == 2 && !strncmp(w, "id", 2)) exr_aov |= NDT_FEATURE_ID;
+                else if (len == 8 && !strncmp(w, "position", 8)) exr_aov |= NDT_FEATURE_POSITION;
+                else if (len == 6 && !strncmp(w, "normal", 6)) exr_aov |= NDT_FEATURE_NORMAL;
+                else if (len == 3 && !strncmp(w, "all", 3)) exr_aov |= NDT_FEATURE_ID | NDT_FEATURE_POSITION | NDT_FEATURE_NORMAL;
+                else {
+                    if (len == 0) fprintf(stderr, "%s: --exr-aov takes a list of id, position, normal (or all): an empty word in '%s'\n", argv[0], optarg);
+                    else fprintf(stderr, "%s: --exr-aov takes a list of id, position, normal (or all), not '%.*s'\n", argv[0], (int)len, w);
+                    return 1;
+                }
+                if (!w[len]) break;
+                w += len + 1;
+            }
+            break;
+        }
         default:
             fprintf(stderr, "usage: %s -s scene.so|builtin:yaml [-d dims] [-r WxH|1080p|4k] [-f last|first:last[:total]] [-l depth]\n"
-                            "          [-a diff,depth] [-n samples] [-m s|o|a|m] [-p] [-z] [-j frames_in_flight] [-g gpus_per_frame] [-u config] [--dump-scene file.ndtscene] [--raw file.f64] [--png [--deflate stored|gpu]] [--jpeg [--jpeg-quality 1..100] [--jpeg-sampling 420|444]] [--fit host|gpu] [--kd host|gpu] [--depth host|gpu [--depth-png]] [--ssaa 1..8] [--png16] [--apng [--apng-fps 1..1000]] [--exr [--exr-pixel half|float]]\n", argv[0]);
+                            "          [-a diff,depth] [-n samples] [-m s|o|a|m] [-p] [-z] [-j frames_in_flight] [-g gpus_per_frame] [-u config] [--dump-scene file.ndtscene] [--raw file.f64] [--png [--deflate stored|gpu]] [--jpeg [--jpeg-quality 1..100] [--jpeg-sampling 420|444]] [--fit host|gpu] [--kd host|gpu] [--depth host|gpu [--depth-png]] [--ssaa 1..8] [--png16] [--apng [--apng-fps 1..1000]] [--exr [--exr-pixel half|float] [--exr-aov id,position,normal|all]]\n", argv[0]);
             return ch == 'h' ? 0 : 1;
         }
     }
@@ -556,6 +582,23 @@ int main(int argc, char **argv)
     }
     if (exr_pixel && !exr) {
         fprintf(stderr, "%s: --exr-pixel sets the OpenEXR file's sample type: it needs --exr\n", argv[0]);
+        return 1;
+    }
+    if (exr_aov_given && !exr) {
+        fprintf(stderr, "%s: --exr-aov adds channels to the OpenEXR file: it needs --exr\n", argv[0]);
+        return 1;
+    }
+    if (exr_aov_given && aa_depth >= 0) {
+        fprintf(stderr, "%s: --exr-aov with -a: an anti-aliased pixel is an average of corner samples, not one primary ray: no hit to record\n", argv[0]);
+        return 1;
+    }
+    if (exr_aov_given && samples > 1) {
+        fprintf(stderr, "%s: --exr-aov with -n %d: a pixel of several samples has no single primary ray: take -n 1\n", argv[0], samples);
+        return 1;
+    }
+    if (exr_aov_given && (stereo == 3 || stereo == 4)) {
+        fprintf(stderr, "%s: --exr-aov with -m %s: %s: take -m s or -m o\n", argv[0], stereo == 3 ? "a" : "h",
+                stereo == 3 ? "an anaglyph pixel has two primary rays, one an eye" : "a frame-packed image has no feature channels");
         return 1;
     }
     if (exr && (png || jpeg || raw_path || png16 || apng)) {
@@ -680,6 +723,7 @@ int main(int argc, char **argv)
     frame_request.max_optic_depth = depth; frame_request.ssaa = ssaa;
     frame_request.jpeg_quality = jpeg_quality; frame_request.jpeg_sampling = jpeg_sampling < 0 ? 0 : jpeg_sampling;
     frame_request.exr_pixel = exr_pixel;
+    frame_request.exr_features = exr_aov;
     frame_request.colour = exr ? NDT_COLOUR_EXR : apng ? NDT_COLOUR_APNG : png16 ? NDT_COLOUR_PNG16 : want_f64 ? NDT_COLOUR_F64
                          : file_kind != NDT_COLOUR_F64 ? file_kind : NDT_COLOUR_RGBA8;
     frame_request.map = !want_depth ? NDT_MAP_NONE : exr ? NDT_MAP_EXR_Z : !depth_gpu ? NDT_MAP_F64 : png16 ? NDT_MAP_PNG16 : depth_png ? NDT_MAP_PNG : NDT_MAP_DEPTH8;

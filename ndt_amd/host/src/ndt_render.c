@@ -497,15 +497,22 @@ static int frame_apng(const ndt_render_params *p, const ndt_frame_request *rq, n
 }
 
 /* colour as an OpenEXR file of half or float samples in linear light, the map of -z as its Z channel if asked (ndt_hip_render_exr,
- * ndt_hip_render_ssaa_exr; `ndt_hip --exr`) */
-static int frame_exr(const ndt_render_params *p, const ndt_frame_request *rq, ndt_frame *f)
+ * ndt_hip_render_ssaa_exr; `ndt_hip --exr`); with exr_features the primary hit of every pixel as further channels of it
+ * (ndt_hip_render_exr_features, ndt_hip_render_ssaa_exr_features; `--exr-aov`) */
+static int frame_exr(const ndt_render_params *p, const ndt_frame_request *rq, ndt_frame *f, int dims)
 {
     const int K = rq->ssaa, with_map = rq->map == NDT_MAP_EXR_Z;
     ndt_exr_params ep;
     ndt_exr_stats es;
     memset(&ep, 0, sizeof(ep));
     ep.pixel_type = rq->exr_pixel;
-    const int64_t cap = ndt_hip_exr_bound(p->width, p->height, &ep, with_map);
+    const int features = rq->exr_features;
+    if (features & ~(NDT_FEATURE_ID | NDT_FEATURE_POSITION | NDT_FEATURE_NORMAL)) {
+        fprintf(stderr, "ndt_render_frame: exr_features %d: a mask of id 1, position 2, normal 4\n", features);
+        return 0;
+    }
+    const int64_t cap = features ? ndt_hip_exr_features_bound(p->width, p->height, &ep, with_map, dims, features)
+                                 : ndt_hip_exr_bound(p->width, p->height, &ep, with_map);
     if (g_n_ctx > 1) {
         /* (the rows of several contexts meet as 8-bit pixels or as doubles on the host: there is no float gather) */
         fprintf(stderr, "ndt_render_frame: an OpenEXR file is made by one GPU context, not by %d\n", g_n_ctx);
@@ -516,8 +523,12 @@ static int frame_exr(const ndt_render_params *p, const ndt_frame_request *rq, nd
         fprintf(stderr, "ndt_render_frame: no OpenEXR file of %d x %d with pixel type %d\n", p->width, p->height, rq->exr_pixel);
         return 0;
     }
-    if ((K != 1 ? ndt_hip_render_ssaa_exr(g_ctx[0], p, K, &ep, with_map, f->file, cap, &es, NULL)
-                : ndt_hip_render_exr(g_ctx[0], p, &ep, with_map, f->file, cap, &es, NULL)) != NDT_OK) return 0;
+    if (features) {
+        /* (no fallback: a frame the feature pass refuses -- -a, -n, anaglyph -- fails with the library's message) */
+        if ((K != 1 ? ndt_hip_render_ssaa_exr_features(g_ctx[0], p, K, &ep, with_map, features, f->file, cap, &es, NULL)
+                    : ndt_hip_render_exr_features(g_ctx[0], p, &ep, with_map, features, f->file, cap, &es, NULL)) != NDT_OK) return 0;
+    } else if ((K != 1 ? ndt_hip_render_ssaa_exr(g_ctx[0], p, K, &ep, with_map, f->file, cap, &es, NULL)
+                       : ndt_hip_render_exr(g_ctx[0], p, &ep, with_map, f->file, cap, &es, NULL)) != NDT_OK) return 0;
     if (K != 1) {
         f->ssaa_ms = ndt_hip_ssaa_ms(g_ctx[0]);
         say_ssaa(K, ndt_hip_ssaa_launches(g_ctx[0]));
@@ -525,6 +536,11 @@ static int frame_exr(const ndt_render_params *p, const ndt_frame_request *rq, nd
     f->file_bytes = es.file_bytes;
     f->file_ms = es.ms;
     printf("encoded EXR of %lld bytes on GPU %d in %d launches\n", (long long)es.file_bytes, ndt_hip_device(g_ctx[0]), es.launches);
+    if (features) {
+        f->feature_channels = (features & NDT_FEATURE_ID ? 1 : 0) + (features & NDT_FEATURE_POSITION ? dims : 0) + (features & NDT_FEATURE_NORMAL ? dims : 0);
+        f->feature_launches = ndt_hip_features_launches(g_ctx[0]);
+        printf("added %d feature channels on GPU %d in %d launches\n", f->feature_channels, ndt_hip_device(g_ctx[0]), f->feature_launches);
+    }
     return 1;
 }
 
@@ -557,6 +573,10 @@ int ndt_render_frame(scene *scn, const ndt_frame_request *rq, ndt_frame *f)
                 (unsigned)rq->map > NDT_MAP_EXR_Z ? "unknown" : map_kinds[rq->map]);
         return 0;
     }
+    if (rq->exr_features && rq->colour != NDT_COLOUR_EXR) {
+        fprintf(stderr, "ndt_render_frame: exr_features are channels of the OpenEXR file: colour (%s) has none\n", colour_kinds[rq->colour].name);
+        return 0;
+    }
     /* 1. the scene: flattened, uploaded to every context of the thread (the pthread fan-out of ndt.c:949-975 is the GPU's job now;
      * `threads` fits the scene's bounding spheres in parallel) */
     if (timing) clock_gettime(CLOCK_MONOTONIC, &ts0);
@@ -585,7 +605,7 @@ int ndt_render_frame(scene *scn, const ndt_frame_request *rq, ndt_frame *f)
             p.aa_depth = rq->aa_depth;
         }
         /* 2. and 3. colour and map in the forms asked for: one device call makes both, so the routine is chosen by the pair */
-        if (rq->colour == NDT_COLOUR_EXR) ok = frame_exr(&p, rq, f);
+        if (rq->colour == NDT_COLOUR_EXR) ok = frame_exr(&p, rq, f, fb.fs.dims);
         else if (rq->colour == NDT_COLOUR_APNG) ok = frame_apng(&p, rq, f);
         else if (rq->colour == NDT_COLOUR_PNG16) ok = frame_png16(&p, rq, f);
         else if (map8) ok = frame_beside_map8(&p, rq, f);
