@@ -137,7 +137,7 @@ NDT_DEV bool primary_node(const double *blob, const SceneDesc &sd, const Workspa
         prim_sti<COH>(ws.hit_obj + g, -1);
         return false;
     }
-    // (jittered samples: the PIXEL decides the half, the jitter comes after -- i + dx/2 and j - dy/2 lie in [i, i+1) and (j-1, j])
+    // (jittered samples: the PIXEL decides the half, the jitter comes after, below)
     const double half_i = rg.pixel_halves ? floor(ip) : ip, half_j = rg.pixel_halves ? ceil(jp) : jp;
     if (rg.stereo == 1) {           // SIDE_SIDE_3D, x_scale = 0.5 (ndt.c:591-601)
         if (half_i < rg.img_w / 2) { ip = ip / 0.5; eye = 0; }
@@ -161,8 +161,16 @@ NDT_DEV bool primary_node(const double *blob, const SceneDesc &sd, const Workspa
             return false;
         }
     }
-    const double x = ip / (double)rg.img_w - 0.5;               // ndt.c:632
-    const double y = -(jp / y_div - 0.5);                       // ndt.c:633 (629 for HIDEF_3D)
+    double x = ip / (double)rg.img_w - 0.5;                     // ndt.c:632
+    double y = -(jp / y_div - 0.5);                             // ndt.c:633 (629 for HIDEF_3D)
+    if (rg.samples && rg.pixel_halves == 2) {
+        // -n > 1: the jitter inside the pixel, added to x and y AFTER the split of a side-by-side / over-under image, 1/width x
+        // 1/height of the IMAGE (ndt.c:482-483, 505-514; a frame-packed eye image is 1080 lines of its 2205) -- the reference's
+        // own two operations, so that the ray is the reference's to the bit
+        const unsigned long long key = rg.sample_keys[g];
+        x = x + ndt_rng_uniform(key, 1000) * (1.0 / (double)rg.img_w);
+        y = y + ndt_rng_uniform(key, 1001) * (1.0 / (double)rg.img_h);
+    }
     double pixel[N], temp[N], cam[N];
     blob_vec<N>(blob, sd.off_cam, pos);
     const double focal = blob[sd.off_cam + 4 * N];

@@ -17,12 +17,14 @@ __device__ __forceinline__ unsigned long long ns_sample_key(unsigned long long p
     return ndt_rng_mix(pixel * 0x100000001b3ull + round);
 }
 
-// sample r of the active pixels: (i + dx, j - dy) and the lens offsets (ndt.c:505-514, 527-541)
+// sample r of the active pixels: the pixel (i, j), its stream key and the lens offsets (ndt.c:527-541); the jitter inside the pixel
+// (ndt.c:505-514) is drawn from the key where the primary ray is made (primary_node), so that x and y are the reference's
+// `orig_x + dx * pix_width`, `orig_y + dy * pix_height` to the bit
 // (`per` consecutive samples per pixel in one pass: sample a*per + r is the pixel's sample number round + r)
 // pos (or nullptr): the positions of a list render -- "pixel" k is image position (pos[2k], pos[2k+1]); its streams are named by
 // the position itself, so that they do not depend on which shard, level or task asked for it
 __global__ void k_ns_samples(const int *active, int n_active, int per, int width, int row_begin, int row_step, unsigned int round0,
-                             double aperture, int jitter, int lens, double xs, double ys, double *samples, unsigned long long *keys,
+                             double aperture, int lens, double *samples, unsigned long long *keys,
                              unsigned long long seed, const double *pos)
 {
     const long long a = (long long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -45,11 +47,7 @@ __global__ void k_ns_samples(const int *active, int n_active, int per, int width
     // draw an ENSEMBLE of device images and compare it with the oracle's, two samples of the same distribution)
     const unsigned long long key = ns_sample_key(id, round) ^ ndt_rng_mix(seed * 0x9e3779b97f4a7c15ull + 0x632be59bd9b4e019ull) * (seed != 0ull);
     keys[a] = key;
-    double dx = 0.0, dy = 0.0, ax = 0.0, ay = 0.0;
-    if (jitter) {       // -n > 1 without recursive anti-aliasing (ndt.c:505)
-        dx = ndt_rng_uniform(key, 1000);
-        dy = ndt_rng_uniform(key, 1001);
-    }
+    double ax = 0.0, ay = 0.0;
     if (lens) {         // -n > 1 or recursive anti-aliasing (ndt.c:528); with neither the area lights are all that is random
         unsigned int k = 1002;
         do {        // reject samples outside the unit disk
@@ -59,11 +57,8 @@ __global__ void k_ns_samples(const int *active, int n_active, int per, int width
         } while (ax * ax + ay * ay > 1.0 && k < 1064);
     }
     double *q = samples + 4ll * a;
-    // x = orig_x + dx/width, y = orig_y + dy/height (y grows upwards).  The jitter is added AFTER render_pixel has split a
-    // side-by-side / over-under image (ndt.c:590-612 before :505-514): in the squeezed direction it spans 1/width of the
-    // eye's image, half a pixel of the packed one -- xs / ys = 0.5 there, so that k_primary's "/ 0.5" gives it back whole
-    q[0] = i + dx * xs;
-    q[1] = j - dy * ys;
+    q[0] = i;
+    q[1] = j;
     q[2] = ax * aperture;
     q[3] = ay * aperture;
 }
@@ -202,10 +197,7 @@ static int render_sampled_eye(ndt_hip_ctx *ctx, const ndt_render_params *p, int 
             if (d_depth && (rc = buf.get(&sdepth, cap_samples + 64))) return rc;
         }
         hipLaunchKernelGGL(k_ns_samples, dim3((unsigned)((n_s + 255) / 256)), dim3(256), 0, s, list[flip], n_active, (int)per, W,
-                           p->row_begin, p->row_step, round, ctx->aperture_radius, (p->samples > 1 && !sl) ? 1 : 0, (p->samples > 1 || sl) ? 1 : 0,
-                           // (the jitter is 1/width x 1/height of the IMAGE; a frame-packed eye image is 1080 lines of its 2205, ndt.c:482-483, 629)
-                           stereo == NDT_STEREO_SIDE_SIDE ? 0.5 : 1.0, stereo == NDT_STEREO_OVER_UNDER ? 0.5 : stereo == NDT_STEREO_HIDEF ? 1080.0 / H : 1.0,
-                           samples, keys, (unsigned long long)ctx->sample_seed + salt, sl ? sl->d_pos : nullptr);
+                           p->row_begin, p->row_step, round, ctx->aperture_radius, (p->samples > 1 || sl) ? 1 : 0, samples, keys, (unsigned long long)ctx->sample_seed + salt, sl ? sl->d_pos : nullptr);
         RenderGeom gs{};
         gs.samples = samples;
         gs.n_samples = (int)n_s;
@@ -222,7 +214,7 @@ static int render_sampled_eye(ndt_hip_ctx *ctx, const ndt_render_params *p, int 
         gs.stereo = stereo;
         gs.lens = 1;
         gs.raw_samples = 1;
-        gs.pixel_halves = sl ? 0 : 1;
+        gs.pixel_halves = sl ? 0 : p->samples > 1 ? 2 : 1;      // (2: -n > 1 without recursive anti-aliasing -- jittered, ndt.c:505)
         gs.sample_keys = keys;
         ndt_render_stats st{};
         if ((rc = render_pass(ctx, gs, p->profile != 0, colours, st, d_depth ? sdepth : nullptr))) return rc;

@@ -18,7 +18,9 @@
  * (-ffp-contract=off), dot products summed in the SSE2 lane-pair order of vectNd.h:215-227
  * (even components in lane 0, odd components in lane 1, lanes added last).
  */
+#ifndef _GNU_SOURCE
 #define _GNU_SOURCE
+#endif
 #include <float.h>
 #include <math.h>
 #include <pthread.h>
@@ -1002,7 +1004,101 @@ typedef struct {
     int stochastic;         /* samples > 1 or area lights: every pass of the adaptive loop is a different ray tree */
     int aa_lens;            /* recursive anti-aliasing with an aperture: every sample draws a lens point (ndt.c:528) */
     double pix_w, pix_h;    /* 1/width, 1/height of the image being rendered (ndt.c:482-483) */
+    /* stream replay (ndt_oracle_set_streams mode 1): the device's counter-based streams instead of drand48 */
+    int replay;
+    int list;                       /* the image positions of an anti-aliased render name their streams themselves */
+    unsigned long long seed;        /* sample_seed */
+    unsigned long long salt;        /* the eye's salt */
+    unsigned long long id;          /* the image position's stream id */
+    unsigned long long sample_key;  /* the current sample's key: jitter and lens */
+    unsigned long long node_key;    /* the current ray's key: area lights; handed down get_ray_color's recursion */
+    int node_kind;                  /* 0 primary, 1 reflected child, 2 refracted child */
+    struct replay_report *rep;
 } tctx;
+
+/* ---- the device's random streams, restated (DESIGN.md "The stream contract"; ndt_device.hpp, ndt_sampled.hip, light_setup).
+ * Every number is a hash of (key, index); a key depends only on the image position, the sample number, sample_seed + the
+ * eye's salt, the path of reflected / refracted children and the light's place in the list -- nothing on order. */
+enum { DRAW_JITTER, DRAW_LENS, DRAW_LENS_REJECT, DRAW_LENS_CAP, DRAW_DISK, DRAW_DISK_REJECT, DRAW_DISK_CAP, DRAW_RECT,
+       DRAW_AREA_PRIMARY, DRAW_AREA_REFLECTED, DRAW_AREA_REFRACTED, DRAW_KINDS };
+
+typedef struct replay_report {
+    long long samples;              /* samples the adaptive loops consumed */
+    double margin;                  /* smallest |clr_diff - 1/256| over the loops' continuation decisions */
+    double aa_margin;               /* smallest |var - threshold| over the anti-aliasing's subdivision decisions */
+    long long draws[DRAW_KINDS];
+} replay_report;
+
+static unsigned long long stream_mix(unsigned long long z)
+{
+    z += 0x9e3779b97f4a7c15ull;                 /* splitmix64's finaliser */
+    z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ull;
+    z = (z ^ (z >> 27)) * 0x94d049bb133111ebull;
+    return z ^ (z >> 31);
+}
+
+static double stream_uniform(unsigned long long key, unsigned int k)
+{
+    return (double)(stream_mix(key + k) >> 11) * (1.0 / 9007199254740992.0);       /* [0, 1) */
+}
+
+static unsigned long long stream_sample_key(unsigned long long id, unsigned int round, unsigned long long seed)
+{
+    unsigned long long key = stream_mix(id * 0x100000001b3ull + round);
+    if (seed != 0ull) key ^= stream_mix(seed * 0x9e3779b97f4a7c15ull + 0x632be59bd9b4e019ull);
+    return key;
+}
+
+/* a list render's positions (the samples of -a): two doubles, exact on both sides */
+static unsigned long long stream_list_id(double i, double j)
+{
+    unsigned long long bi, bj;
+    memcpy(&bi, &i, sizeof(bi));
+    memcpy(&bj, &j, sizeof(bj));
+    return stream_mix(bi) ^ stream_mix(bj + 0x7f4a7c159e3779b9ull);
+}
+
+/* the lens point: indices 1002, 1003, then +2 per rejected try; the try at 1062 / 1063 is kept whatever it is */
+static int stream_lens(unsigned long long key, double *ax, double *ay)
+{
+    unsigned int k = 1002;
+    int tries = 0;
+    do {
+        *ax = 2 * stream_uniform(key, k) - 1.0;
+        *ay = 2 * stream_uniform(key, k + 1) - 1.0;
+        k += 2;
+        ++tries;
+    } while (*ax * *ax + *ay * *ay > 1.0 && k < 1064);
+    return tries;
+}
+
+/* the point of area light `li` (its 0-based place in the whole list) seen from the ray `node`: indices 0, 1, then +2 per
+ * rejected try (disk only); the try at 62 / 63 is kept whatever it is */
+static int stream_light(unsigned long long node, int li, int disk, double *x, double *y)
+{
+    const unsigned long long lk = stream_mix(node ^ (0x51ed270b27b4f3cfull * (unsigned long long)(li + 1)));
+    unsigned int k = 0;
+    int tries = 0;
+    do {
+        *x = 2 * stream_uniform(lk, k) - 1.0;
+        *y = 2 * stream_uniform(lk, k + 1) - 1.0;
+        k += 2;
+        ++tries;
+    } while (disk && *x * *x + *y * *y > 1.0 && k < 64);
+    return tries;
+}
+
+/* the same, for the tests that restate the contract a second time */
+unsigned long long ndt_oracle_stream_mix(unsigned long long z) { return stream_mix(z); }
+double ndt_oracle_stream_uniform(unsigned long long key, unsigned int k) { return stream_uniform(key, k); }
+unsigned long long ndt_oracle_stream_sample_key(unsigned long long id, unsigned int round, unsigned long long seed)
+{
+    return stream_sample_key(id, round, seed);
+}
+unsigned long long ndt_oracle_stream_list_id(double i, double j) { return stream_list_id(i, j); }
+unsigned long long ndt_oracle_stream_child_key(unsigned long long node, int kind) { return stream_mix(node ^ (unsigned long long)kind); }
+int ndt_oracle_stream_lens(unsigned long long key, double *ax, double *ay) { return stream_lens(key, ax, ay); }
+int ndt_oracle_stream_light(unsigned long long node, int li, int disk, double *x, double *y) { return stream_light(node, li, disk, x, y); }
 
 typedef struct { double r, g, b, a; } pix;
 
@@ -1043,6 +1139,15 @@ static void apply_lights(tctx *T, int obj_idx, const double *src, const double *
              * here on the sample is a point light */
             const double *u1 = fs->vecs + L->area_off, *v1 = u1 + n;
             double x, y, temp[ND];
+            if (T->replay) {
+                const int disk = lgt_type == NDT_LIGHT_DISK;
+                const int tries = stream_light(T->node_key, i, disk, &x, &y);
+                long long *d = T->rep->draws;
+                d[disk ? DRAW_DISK : DRAW_RECT] += 1;
+                d[DRAW_DISK_REJECT] += tries - 1;
+                if (disk && x * x + y * y > 1.0) d[DRAW_DISK_CAP] += 1;
+                d[T->node_kind == 0 ? DRAW_AREA_PRIMARY : T->node_kind == 1 ? DRAW_AREA_REFLECTED : DRAW_AREA_REFRACTED] += 1;
+            } else
             do {
                 x = 2 * drand48() - 1.0;
                 y = 2 * drand48() - 1.0;
@@ -1176,6 +1281,9 @@ static int get_ray_color_d(tctx *T, const double *src, const double *unit_look, 
         if (trace_dist > EPS) *depth = 1.0 / trace_dist;
         if (obj_ptr < 0) *depth = 0.0;
     }
+    /* stream replay: this ray's key; the reflected child gets mix(key ^ 1), the refracted child mix(key ^ 2) */
+    const unsigned long long node_key = T->node_key;
+    const int node_kind = T->node_kind;
     if (obj_ptr >= 0 && trace_dist > EPS) {
         const pobj *obj = &S->objs[obj_ptr];
         apply_lights(T, obj_ptr, src, unit_look, hit, hit_normal, &clr);
@@ -1187,7 +1295,11 @@ static int get_ray_color_d(tctx *T, const double *src, const double *unit_look, 
             if (hitr_r != 0.0 || hitr_g != 0.0 || hitr_b != 0.0) {
                 v_reflect(unit_look, hit_normal, new_ray, 1.0, n);
                 v_unitize(new_ray, n);
+                T->node_key = stream_mix(node_key ^ 0x1ull);
+                T->node_kind = 1;
                 get_ray_color(T, hit, new_ray, &ref, contrib * pixel_frac, max_depth - 1, 0);
+                T->node_key = node_key;
+                T->node_kind = node_kind;
                 if (T->specular) {
                     clr.r = (1 - hitr_r) * (clr.r) + (hitr_r)*ref.r;
                     clr.g = (1 - hitr_g) * (clr.g) + (hitr_g)*ref.g;
@@ -1204,7 +1316,11 @@ static int get_ray_color_d(tctx *T, const double *src, const double *unit_look, 
         if (obj->transparent) {
             v_refract(unit_look, hit_normal, new_ray, obj->refract_index, n);
             v_unitize(new_ray, n);
+            T->node_key = stream_mix(node_key ^ 0x2ull);
+            T->node_kind = 2;
             get_ray_color(T, hit, new_ray, &ref, (1 - contrib) * pixel_frac, max_depth - 1, 0);
+            T->node_key = node_key;
+            T->node_kind = node_kind;
             clr.r += (1.0 - hitr_r) * ref.r;
             clr.g += (1.0 - hitr_g) * ref.g;
             clr.b += (1.0 - hitr_b) * ref.b;
@@ -1299,11 +1415,6 @@ enum { CAM_LEFT = 0, CAM_CENTER = 1, CAM_RIGHT = 2 };      /* camera_mode, ndt.c
 
 static void get_pixel_color_m(tctx *T, double x, double y, pix *clr, int max_optic_depth, int literal, int *k_out,
                               int mode, double *depth);
-static void get_pixel_color(tctx *T, double x, double y, pix *clr, int max_optic_depth, int literal, int *k_out)
-{
-    get_pixel_color_m(T, x, y, clr, max_optic_depth, literal, k_out, CAM_CENTER, NULL);
-}
-
 static void get_pixel_color_m(tctx *T, double x, double y, pix *clr, int max_optic_depth, int literal, int *k_out,
                               int mode, double *depth)
 {
@@ -1323,11 +1434,24 @@ static void get_pixel_color_m(tctx *T, double x, double y, pix *clr, int max_opt
     ray_counts before = T->cnt, one = { 0, 0, 0 };
     for (int i = 0; i < min_samples || (i < max_samples && clr_diff > max_diff); ++i) {
         if (i == 0 || literal) {
+            if (T->replay) {
+                /* sample i of this image position: its own stream */
+                T->sample_key = stream_sample_key(T->id, (unsigned int)i, T->seed + T->salt);
+                T->node_key = T->sample_key;
+                T->node_kind = 0;
+            }
             v_copy(virtCam, mode == CAM_LEFT ? S->cam_left_eye : mode == CAM_RIGHT ? S->cam_right_eye : S->cam_pos, n);   /* ndt.c:491-502 */
             if (samples > 1) {
                 /* jitter inside the pixel (ndt.c:505-514); the reference's global drand48 stream */
-                double dx = drand48();
-                double dy = drand48();
+                double dx, dy;
+                if (T->replay) {
+                    dx = stream_uniform(T->sample_key, 1000);
+                    dy = stream_uniform(T->sample_key, 1001);
+                    T->rep->draws[DRAW_JITTER] += 1;
+                } else {
+                    dx = drand48();
+                    dy = drand48();
+                }
                 x = orig_x + dx * T->pix_w;
                 y = orig_y + dy * T->pix_h;
             }
@@ -1342,6 +1466,12 @@ static void get_pixel_color_m(tctx *T, double x, double y, pix *clr, int max_opt
                  * disk, also drawn when the aperture is 0 (the offsets are then zero vectors; in the anti-aliasing mode the
                  * draws are then skipped here -- nothing else reads the stream) */
                 double ax, ay;
+                if (T->replay) {
+                    const int tries = stream_lens(T->sample_key, &ax, &ay);
+                    T->rep->draws[DRAW_LENS] += 1;
+                    T->rep->draws[DRAW_LENS_REJECT] += tries - 1;
+                    if (ax * ax + ay * ay > 1.0) T->rep->draws[DRAW_LENS_CAP] += 1;
+                } else
                 do {
                     ax = 2 * drand48() - 1.0;
                     ay = 2 * drand48() - 1.0;
@@ -1375,7 +1505,11 @@ static void get_pixel_color_m(tctx *T, double x, double y, pix *clr, int max_opt
         t_clr.b += l_clr.b;
         t_clr.a += l_clr.a;
         t_samples += 1;
+        /* the decision the loop's test takes next wherever it rests on clr_diff: how far from its threshold */
+        if (T->replay && i + 1 >= min_samples && i + 1 < max_samples && fabs(clr_diff - max_diff) < T->rep->margin)
+            T->rep->margin = fabs(clr_diff - max_diff);
     }
+    if (T->replay) T->rep->samples += t_samples;
     clr->r = t_clr.r / t_samples;
     clr->g = t_clr.g / t_samples;
     clr->b = t_clr.b / t_samples;
@@ -1404,6 +1538,9 @@ typedef struct {
     long long resampled, aa_samples;
     double *depth;          /* depth map (1/distance of the primary hit), or NULL */
     int stochastic;
+    int replay;             /* stream replay: the streams' seed, and what the render reports */
+    unsigned long long seed;
+    replay_report rep;
 } job;
 
 /* render_pixel (ndt.c:578-653, MONO) + get_pixel_color: the sample at image position (i, j), both in
@@ -1432,6 +1569,11 @@ static void render_pixel_d(job *J, tctx *T, int width, int height, double i, dou
         if (j < height / 2) { jp = jp / 0.5; mode = CAM_LEFT; }
         else { jp = (jp - height / 2) / 0.5; mode = CAM_RIGHT; }
     }
+    if (T->replay) {
+        /* the position's streams: the pixel's number in the (packed) image, or the position itself in a list render */
+        T->id = T->list ? stream_list_id(i, j) : (unsigned long long)j * (unsigned long long)width + (unsigned long long)i;
+        T->salt = 0ull;
+    }
     double x = ip / (double)width - 0.5;
     double y = -(jp / (double)height - 0.5);
     if (stereo == NDT_STEREO_HIDEF) {               /* frame packing, ndt.c:614-631: left eye, 45 blank lines, right eye */
@@ -1450,7 +1592,9 @@ static void render_pixel_d(job *J, tctx *T, int width, int height, double i, dou
     if (stereo == NDT_STEREO_ANAGLYPH) {            /* ndt.c:636-647 */
         pix left, right;
         one_eye(J, T, x, y, &left, CAM_LEFT, depth);
+        T->salt = 0x5eed0000000000ffull;        /* the right eye of an anaglyph draws from streams of its own */
         one_eye(J, T, x, y, &right, CAM_RIGHT, NULL);
+        T->salt = 0ull;
         clr->r = 0.299 * left.r + 0.587 * left.g + 0.114 * left.b;
         clr->g = 0;
         clr->b = 0.299 * right.r + 0.587 * right.g + 0.114 * right.b;
@@ -1476,6 +1620,12 @@ static void tctx_open(tctx *T, job *J)
     T->aa_lens = J->p->recursive_aa && J->S->fs->cam_aperture_radius != 0.0;
     T->pix_w = 1.0 / (J->p->width + (J->p->recursive_aa ? 1 : 0));
     T->pix_h = 1.0 / (J->p->height + (J->p->recursive_aa ? 1 : 0));
+    T->replay = J->replay;
+    T->list = J->p->recursive_aa != 0;
+    T->seed = J->seed;
+    T->salt = T->id = T->sample_key = T->node_key = 0ull;
+    T->node_kind = 0;
+    T->rep = &J->rep;
 }
 
 /* render_lines_thread / render_line, ndt.c:803 / 735 */
@@ -1523,6 +1673,12 @@ static void avg4(const pix *p1, const pix *p2, const pix *p3, const pix *p4, pix
     }
 }
 
+/* stream replay: how far a subdivision decision lies from its threshold (the colours it tests are noisy ones) */
+static void aa_decision(job *J, double var, double threshold)
+{
+    if (J->replay && fabs(var - threshold) < J->rep.aa_margin) J->rep.aa_margin = fabs(var - threshold);
+}
+
 /* recursive_resample, ndt.c:655-707.  width/height are the first pass's (image + 1). */
 static void recursive_resample(job *J, tctx *T, int width, int height, double x, double y, double step,
                                const pix *p1, const pix *p2, const pix *p3, const pix *p4, pix *res)
@@ -1544,12 +1700,16 @@ static void recursive_resample(job *J, tctx *T, int width, int height, double x,
     double var1 = 0, var2 = 0, var3 = 0, var4 = 0;
     double threshold = J->p->aa_diff / 255.0;
     avg4(p1, &p6, &p7, &p5, &sp1, &var1);
+    aa_decision(J, var1, threshold);
     if (var1 > threshold) recursive_resample(J, T, width, height, x, y, hs, p1, &p6, &p7, &p5, &sp1);
     avg4(p2, &p6, &p8, &p5, &sp2, &var2);
+    aa_decision(J, var2, threshold);
     if (var2 > threshold) recursive_resample(J, T, width, height, x + hs, y, hs, &p6, p2, &p5, &p8, &sp2);
     avg4(p3, &p9, &p7, &p5, &sp3, &var3);
+    aa_decision(J, var3, threshold);
     if (var3 > threshold) recursive_resample(J, T, width, height, x, y + hs, hs, &p7, &p5, p3, &p9, &sp3);
     avg4(p4, &p9, &p8, &p5, &sp4, &var4);
+    aa_decision(J, var4, threshold);
     if (var4 > threshold) recursive_resample(J, T, width, height, x + hs, y + hs, hs, &p5, &p8, &p9, p4, &sp4);
     avg4(&sp1, &sp2, &sp3, &sp4, res, NULL);
 }
@@ -1609,6 +1769,7 @@ static void *resample_rows(void *arg)
             for (int k = 0; k < 4; ++k) { c[k].r = q[k][0]; c[k].g = q[k][1]; c[k].b = q[k][2]; c[k].a = q[k][3]; }
             double var = 0.0;
             avg4(&c[0], &c[1], &c[2], &c[3], &clr, &var);
+            aa_decision(J, var, p->aa_diff / 255.0);
             if (var > p->aa_diff / 255.0) {
                 J->resampled += 1;
                 recursive_resample(J, &T, width + 1, height + 1, i, j, 1.0, &c[0], &c[1], &c[2], &c[3], &clr);
@@ -1673,6 +1834,28 @@ void ndt_oracle_set_seed48(unsigned short s0, unsigned short s1, unsigned short 
     g_seed48[0] = s0; g_seed48[1] = s1; g_seed48[2] = s2;
 }
 
+/* Where the random numbers of a stochastic render come from.  Mode 0: the reference's global drand48 stream (above).
+ * Mode 1, stream replay: the device's counter-based streams for `sample_seed` -- every stochastic render then has one right
+ * answer, the device's, value for value; nothing depends on order, so the render may use its threads. */
+static int g_stream_mode = 0;
+static unsigned long long g_stream_seed = 0ull;
+void ndt_oracle_set_streams(int mode, unsigned long long sample_seed)
+{
+    g_stream_mode = mode;
+    g_stream_seed = sample_seed;
+}
+
+/* what the last mode-1 render reports */
+static replay_report g_report;
+long long ndt_oracle_replay_samples(void) { return g_report.samples; }
+double ndt_oracle_replay_margin(void) { return g_report.margin; }
+double ndt_oracle_replay_aa_margin(void) { return g_report.aa_margin; }
+int ndt_oracle_replay_draws(long long *out, int n)
+{
+    for (int k = 0; k < n && k < DRAW_KINDS; ++k) out[k] = g_report.draws[k];
+    return DRAW_KINDS;
+}
+
 int ndt_oracle_render_depth(const ndt_flat_scene *fs, const ndt_render_params *p, double *rgba, double *depth,
                             ndt_render_stats *stats, int threads, int flags);
 int ndt_oracle_render(const ndt_flat_scene *fs, const ndt_render_params *p, double *rgba, ndt_render_stats *stats,
@@ -1696,7 +1879,8 @@ int ndt_oracle_render_depth(const ndt_flat_scene *fs, const ndt_render_params *p
     for (int i = 0; i < fs->n_lights; ++i)
         if (fs->lights[i].type == NDT_LIGHT_DISK || fs->lights[i].type == NDT_LIGHT_RECT) stochastic = 1;
     if (p->recursive_aa && fs->cam_aperture_radius != 0.0) stochastic = 1;     /* the lens is sampled in this mode too (ndt.c:528) */
-    if (stochastic) {
+    const int replay = g_stream_mode == 1;
+    if (stochastic && !replay) {
         /* the random numbers come from one global stream in pixel order: one thread, starting where the
          * reference run that made the fixture stood (ndt_oracle_set_seed48) */
         unsigned short x0[3] = { g_seed48[0], g_seed48[1], g_seed48[2] };
@@ -1713,6 +1897,9 @@ int ndt_oracle_render_depth(const ndt_flat_scene *fs, const ndt_render_params *p
         jobs[i].literal = flags & 1;
         jobs[i].depth = depth;
         jobs[i].stochastic = stochastic;
+        jobs[i].replay = replay;
+        jobs[i].seed = g_stream_seed;
+        jobs[i].rep.margin = jobs[i].rep.aa_margin = DBL_MAX;
     }
     ray_counts cnt1 = { 0, 0, 0 };
     double *pass1 = NULL;
@@ -1749,6 +1936,16 @@ int ndt_oracle_render_depth(const ndt_flat_scene *fs, const ndt_render_params *p
             stats->aa_samples += jobs[i].aa_samples;
         }
         stats->frame_ms = 1e3 * ((t1.tv_sec - t0.tv_sec) + 1e-6 * (t1.tv_usec - t0.tv_usec));
+    }
+    if (replay) {
+        memset(&g_report, 0, sizeof(g_report));
+        g_report.margin = g_report.aa_margin = DBL_MAX;
+        for (int i = 0; i < threads; ++i) {
+            g_report.samples += jobs[i].rep.samples;
+            if (jobs[i].rep.margin < g_report.margin) g_report.margin = jobs[i].rep.margin;
+            if (jobs[i].rep.aa_margin < g_report.aa_margin) g_report.aa_margin = jobs[i].rep.aa_margin;
+            for (int k = 0; k < DRAW_KINDS; ++k) g_report.draws[k] += jobs[i].rep.draws[k];
+        }
     }
     free(jobs);
     free(pass1);
