@@ -650,6 +650,63 @@ int ndt_hip_render_ssaa_exr_features(ndt_hip_ctx *ctx, const ndt_render_params *
                                      int32_t with_depth, int32_t features, uint8_t *out, int64_t cap, ndt_exr_stats *stats,
                                      ndt_render_stats *render_stats);
 
+/* A sampled frame denoised on the device (`ndt_hip --denoise`): an edge-avoiding a-trous wavelet over the double framebuffer, in
+ * linear light, before pixel_d2c, guided by the planes of ndt_hip_render_features -- one stage between the render and the sink, as
+ * supersampling is.  Defined to the bit.  Inputs: rgba = [rows][width][4] doubles; id = [rows * width] int32; position, normal =
+ * [dims][rows * width] doubles.  Iteration it = 0 .. iterations - 1 has step s = 1 << it, sc = sigma_colour / (double)(1 << it),
+ * inv_c = 1.0 / (sc * sc), inv_p = 1.0 / (sigma_plane * sigma_plane) (host doubles), and reads image `cur`, writes `next`.  For pixel
+ * p = (y, x) with me = id[p]: me == 0 copies cur[p] bit for bit.  Otherwise num[4] = 0, den = 0, and the 25 taps are visited j outer,
+ * i inner (j, i = 0 .. 4): q = (y + (j - 2) s, x + (i - 2) s), h = H[j] * H[i], H = {1/16, 1/4, 3/8, 1/4, 1/16}.
+ *   the centre tap (j == 2 and i == 2): w = h, always taken
+ *   any other tap is skipped when q lies outside the image (no wrap, no clamp) or id[q] != me; otherwise, every sum over the
+ *   components k = 0 .. dims - 1 in ascending order, one operation at a time:
+ *       d_k = position[k][q] - position[k][p];  dd = sum d_k * d_k;  nd = sum normal[k][p] * d_k;
+ *       dot = sum normal[k][p] * normal[k][q];  wn = dot > 0 ? dot : 0, then squared normal_power_log2 times
+ *       wp = dd > 0 ? 1.0 - ((nd * nd) / dd) * inv_p : 1.0     (the squared sine of the angle by which q leaves p's tangent
+ *                                                               hyperplane over sigma_plane^2: scale-free, no exp)
+ *       cc = (q.r - p.r)^2 + (q.g - p.g)^2 + (q.b - p.b)^2 on `cur`, left to right;  wc = 1.0 / (1.0 + cc * inv_c)
+ *       w = ((h * wn) * wp) * wc, and the tap is skipped unless w > 0 (which drops a NaN too)
+ *   a taken tap: num[c] = num[c] + w * cur[q][c] for the four channels, then den = den + w;   finally next[p][c] = num[c] / den.
+ * Only + - * / and comparisons on doubles, none contracted: a restatement in plain C or numpy gives the same 64-bit patterns.
+ *   ndt_hip_denoise_device           the filter alone on the context's device memory: d_rgba_in and d_rgba_out rows x width x 4
+ *                                    doubles aligned to 16 bytes (they may be the same), the id, position and normal members of
+ *                                    d_planes set and aligned to their elements.  One launch an iteration; synchronous; no scene needed
+ *   ndt_hip_render_denoised_device   on the context's one stream: the frame `p` asks for, any samples, through ndt_hip_render_device;
+ *                                    the feature pass of a copy of `p` whose samples is 1 -- the guide of a pixel is the hit of
+ *                                    the ray a deterministic frame starts from it; then the iterations into d_rgba (aligned to 16)
+ *   ndt_hip_render_denoised          the same into host memory
+ *   ndt_hip_render_denoised_rgba8 / _png / _jpeg / _exr   the same doubles through ndt_hip_quantize_device and the encoders of
+ *                                    the 8-bit files, or through ndt_hip_encode_exr_device (colour only)
+ *   ndt_hip_denoise_launches / ndt_hip_denoise_ms   kernel launches of the context's last call (4 + iterations after a rendered
+ *                                    frame, iterations after ndt_hip_denoise_device), and the iterations' summed device time
+ * dp == NULL: the defaults (a first guess from a synthetic frame).  NDT_E_UNSUPPORTED with the cause in the error text, before any
+ * device work and with nothing written: recursive_aa; any stereo mode but mono (a stencil must not cross the seam between two
+ * eyes); row_begin != 0 or row_step != 1 (a cyclic shard has no neighbouring rows).  NDT_E_INVALID: parameters out of range, a NaN
+ * sigma, NULL or misaligned pointers or planes, dims outside 3 .. 12.  The device buffers belong to the context, only grow and are
+ * reused.  None falls back. */
+typedef struct ndt_denoise_params {
+    int32_t iterations;             /* 1 .. 6; default 4 */
+    int32_t normal_power_log2;      /* 0 .. 8; default 5: the normals' dot product to the power 32 */
+    double  sigma_colour;           /* finite, > 0; default 0.25 */
+    double  sigma_plane;            /* finite, > 0; default 0.25 */
+} ndt_denoise_params;
+int ndt_hip_denoise_device(ndt_hip_ctx *ctx, const void *d_rgba_in, const ndt_feature_planes *d_planes, int32_t dims, int32_t width,
+                           int32_t rows, const ndt_denoise_params *dp, void *d_rgba_out);
+int ndt_hip_render_denoised_device(ndt_hip_ctx *ctx, const ndt_render_params *p, const ndt_denoise_params *dp, void *d_rgba,
+                                   ndt_render_stats *stats);
+int ndt_hip_render_denoised(ndt_hip_ctx *ctx, const ndt_render_params *p, const ndt_denoise_params *dp, double *rgba,
+                            ndt_render_stats *stats);
+int ndt_hip_render_denoised_rgba8(ndt_hip_ctx *ctx, const ndt_render_params *p, const ndt_denoise_params *dp, uint8_t *rgba8,
+                                  ndt_render_stats *stats);
+int ndt_hip_render_denoised_png(ndt_hip_ctx *ctx, const ndt_render_params *p, const ndt_denoise_params *dp, uint8_t *png, int64_t cap,
+                                ndt_png_stats *stats, ndt_render_stats *render_stats);
+int ndt_hip_render_denoised_jpeg(ndt_hip_ctx *ctx, const ndt_render_params *p, const ndt_denoise_params *dp, const ndt_jpeg_params *jp,
+                                 uint8_t *jpg, int64_t cap, ndt_jpeg_stats *stats, ndt_render_stats *render_stats);
+int ndt_hip_render_denoised_exr(ndt_hip_ctx *ctx, const ndt_render_params *p, const ndt_denoise_params *dp, const ndt_exr_params *ep,
+                                uint8_t *out, int64_t cap, ndt_exr_stats *stats, ndt_render_stats *render_stats);
+int ndt_hip_denoise_launches(ndt_hip_ctx *ctx);
+double ndt_hip_denoise_ms(ndt_hip_ctx *ctx);
+
 /* ONE frame over several contexts -- one per GPU of the node, or several on one GPU -- called from one host thread.
  * The rows `p` selects are dealt cyclically to the contexts exactly as the reference deals rows to MPI ranks in
  * MPI_MODE_ROW (ndt.c:812-820: row_start = rank, row_step = size): context k renders rows

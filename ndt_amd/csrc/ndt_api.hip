@@ -133,6 +133,7 @@ extern "C" int ndt_hip_destroy(ndt_hip_ctx *ctx)
     free_features(ctx);
     free_depth(ctx);
     free_ssaa(ctx);
+    free_denoise(ctx);
     ctx->d_eyes.release();
     if (ctx->h_counters) (void)hipHostFree(ctx->h_counters);
     if (ctx->h_levels) (void)hipHostFree(ctx->h_levels);

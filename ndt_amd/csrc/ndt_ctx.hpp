@@ -21,6 +21,8 @@
 //   ndt_deflate.hpp  the deflate of a 32 KiB chunk that ndt_png.hip and ndt_exr.hip share (device code)
 //   ndt_depth.hip    ndt_hip_depth_rgba8_device / ndt_hip_render_*_depth: the depth map of `-z` normalised and quantised on the device
 //   ndt_ssaa.hip     ndt_hip_ssaa_fold_device / ndt_hip_render_ssaa*: K x K supersampling, K ordinary renders folded on the device
+//   ndt_denoise.hip  ndt_hip_denoise_device / ndt_hip_render_denoised*: the edge-avoiding a-trous filter over the double framebuffer,
+//                    guided by the feature planes; kernel, launcher and C ABI
 //   ndt_buffer.hpp   DeviceBuffer: the grow-only device buffers of the context and of its sinks, their one grow and free path
 #pragma once
 #include <hip/hip_runtime.h>
@@ -137,6 +139,17 @@ struct SsaaState {
     double fold_ms = 0.0;           // their summed device time
 };
 
+// ndt_hip_denoise_device, ndt_hip_render_denoised* (ndt_denoise.hip): grow-only device buffers, reused by the next frame
+struct DenoiseState {
+    DeviceBuffer d_ping, d_pong;    // what the iterations between the first image and the last one write: rows x width x 4 doubles each
+    DeviceBuffer d_frame;           // ndt_hip_render_denoised*: the frame as rendered
+    DeviceBuffer d_out, d_rgba8;    // ... denoised, for the calls that deliver to host memory or as a file, and its 8-bit image
+    hipEvent_t ev[12] = {};         // around every iteration's launch
+    int launches = 0;               // kernel launches of the last call: the feature pass's and the iterations'
+    int iterations = 0;             // iterations of the last call
+    double ms = 0.0;                // their summed device time
+};
+
 struct ndt_hip_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -233,6 +246,7 @@ struct ndt_hip_ctx {
     FeatureState features;          // ndt_hip_render_features*, ndt_hip_render_exr_features
     DepthState depth;               // ndt_hip_depth_rgba8_device, ndt_hip_render_*_depth
     SsaaState ssaa;                 // ndt_hip_render_ssaa*
+    DenoiseState denoise;           // ndt_hip_denoise_device, ndt_hip_render_denoised*
     DeviceBuffer d_out;             // staging of a frame in doubles (and its map behind it) for the calls that deliver to host memory
     DeviceBuffer d_shard;           // ndt_hip_render_multi: this context's rows before they are pushed into the frame
     DeviceBuffer d_image;           // ndt_hip_render_multi (host output): the assembled frame on the first context's device
@@ -351,6 +365,9 @@ void free_ssaa(ndt_hip_ctx *ctx);
 // ndt_hip_render_ssaa_rgba8 (its refusals under the name `who`) without the download: *d_rgba8 is the frame's 8-bit image in the
 // context's device memory, written by the last fold, valid until the next supersampled frame
 int render_ssaa_rgba8_own(ndt_hip_ctx *ctx, const char *who, const ndt_render_params *p, int K, ndt_render_stats *stats, const void **d_rgba8);
+
+// ndt_denoise.hip
+void free_denoise(ndt_hip_ctx *ctx);
 
 // ndt_aa.hip / ndt_sampled.hip
 int render_antialiased(ndt_hip_ctx *ctx, const ndt_render_params *p, void *d_rgba, ndt_render_stats &total, void *d_depth = nullptr);

@@ -1,0 +1,373 @@
+// ndt_denoise.hip -- a sampled frame denoised on the device (`ndt_hip --denoise`): an edge-avoiding a-trous wavelet over the double
+// framebuffer, in linear light, before pixel_d2c, guided by what ndt_hip_render_features knows of every pixel -- the object its
+// primary ray hits, the N-D hit point and the N-D normal there.  ndt_hip_denoise_device / ndt_hip_render_denoised*.
+//
+// Iteration it = 0 .. iterations - 1 has step s = 1 << it and reads image `cur`, writes `next`.  A pixel p whose id is 0 is copied.
+// Every other pixel is the weighted mean of the 5 x 5 taps q = p + (j - 2, i - 2) * s (j outer, i inner) of the B3 spline
+// H = {1/16, 1/4, 3/8, 1/4, 1/16}: the centre with weight h = H[j] H[i], always; any other tap only inside the image (no wrap, no
+// clamp), only on the same object, and with
+//     w = ((h * wn) * wp) * wc      wn = max(n_p . n_q, 0) squared normal_power_log2 times
+//                                   wp = 1 - ((n_p . d)^2 / (d . d)) / sigma_plane^2,  d = P_q - P_p (1 where d . d is not > 0)
+//                                   wc = 1 / (1 + |rgb_q - rgb_p|^2 / (sigma_colour / s)^2)
+// when w > 0 (a NaN is dropped with that).  Sums run over components in ascending order, one operation at a time; include/ndt_hip.h
+// has the definition to the bit, and under -ffp-contract=off a numpy restatement gives the same 64-bit patterns.
+//
+//   k_denoise_atrous<N>   one launch an iteration, one lane a pixel, consecutive lanes on consecutive pixels: every plane load and
+//                         every 32-byte colour load is contiguous across the wavefront at any step.  The centre's normal and
+//                         position stay in registers; a tap's guide planes are not loaded when its id differs or it lies outside.
+// No atomics, no LDS, no workgroup waits for another, trip counts come from sizes.  The iterations ping-pong between two buffers of
+// the context; the last one writes the destination.
+#include "ndt_ctx.hpp"
+#include <limits.h>
+
+namespace {
+
+constexpr int DENOISE_LANES = 256;
+constexpr int FEATURES_ALL = NDT_FEATURE_ID | NDT_FEATURE_POSITION | NDT_FEATURE_NORMAL;
+
+template <int N>
+__global__ void __launch_bounds__(DENOISE_LANES) k_denoise_atrous(const double2 *__restrict__ cur, double2 *__restrict__ next,
+                                                                  const int *__restrict__ id, const double *__restrict__ position,
+                                                                  const double *__restrict__ normal, int width, int rows, int step,
+                                                                  double inv_c, double inv_p, int normal_power_log2)
+{
+    const long long n_pixels = (long long)rows * width;
+    const long long p = (long long)blockIdx.x * DENOISE_LANES + threadIdx.x;
+    if (p >= n_pixels) return;
+    const int y = (int)(p / width), x = (int)(p - (long long)y * width);
+    const double2 p_rg = cur[2 * p], p_ba = cur[2 * p + 1];
+    const int me = id[p];
+    if (me == 0) {
+        next[2 * p] = p_rg;
+        next[2 * p + 1] = p_ba;
+        return;
+    }
+    double pn[N], pp[N];
+#pragma unroll
+    for (int k = 0; k < N; ++k) {
+        pn[k] = normal[(long long)k * n_pixels + p];
+        pp[k] = position[(long long)k * n_pixels + p];
+    }
+    double num0 = 0.0, num1 = 0.0, num2 = 0.0, num3 = 0.0, den = 0.0;
+#pragma unroll 1
+    for (int j = 0; j < 5; ++j) {
+        const double hj = j == 2 ? 0.375 : (j == 1 || j == 3) ? 0.25 : 0.0625;
+        const int qy = y + (j - 2) * step;
+#pragma unroll
+        for (int i = 0; i < 5; ++i) {
+            const double h = hj * (i == 2 ? 0.375 : (i == 1 || i == 3) ? 0.25 : 0.0625);
+            const int qx = x + (i - 2) * step;
+            double w = h;
+            double2 q_rg = p_rg, q_ba = p_ba;
+            if (j != 2 || i != 2) {
+                if (qy < 0 || qy >= rows || qx < 0 || qx >= width) continue;
+                const long long q = (long long)qy * width + qx;
+                if (id[q] != me) continue;
+                double dd = 0.0, nd = 0.0, dot = 0.0;
+#pragma unroll
+                for (int k = 0; k < N; ++k) {
+                    const double d = position[(long long)k * n_pixels + q] - pp[k];
+                    dd = dd + d * d;
+                    nd = nd + pn[k] * d;
+                    dot = dot + pn[k] * normal[(long long)k * n_pixels + q];
+                }
+                double wn = dot > 0 ? dot : 0;
+                for (int e = 0; e < normal_power_log2; ++e) wn = wn * wn;
+                const double wp = dd > 0 ? 1.0 - ((nd * nd) / dd) * inv_p : 1.0;
+                q_rg = cur[2 * q];
+                q_ba = cur[2 * q + 1];
+                const double dr = q_rg.x - p_rg.x, dg = q_rg.y - p_rg.y, db = q_ba.x - p_ba.x;
+                const double cc = (dr * dr + dg * dg) + db * db;
+                const double wc = 1.0 / (1.0 + cc * inv_c);
+                w = ((h * wn) * wp) * wc;
+                if (!(w > 0)) continue;
+            }
+            num0 = num0 + w * q_rg.x;
+            num1 = num1 + w * q_rg.y;
+            num2 = num2 + w * q_ba.x;
+            num3 = num3 + w * q_ba.y;
+            den = den + w;
+        }
+    }
+    next[2 * p] = make_double2(num0 / den, num1 / den);
+    next[2 * p + 1] = make_double2(num2 / den, num3 / den);
+}
+
+template <int N>
+void launch_atrous(hipStream_t s, unsigned grid, const void *cur, void *next, const ndt_feature_planes &g, int width, int rows, int step,
+                   double inv_c, double inv_p, int normal_power_log2)
+{
+    hipLaunchKernelGGL(k_denoise_atrous<N>, dim3(grid), dim3(DENOISE_LANES), 0, s, (const double2 *)cur, (double2 *)next, (const int *)g.id,
+                       (const double *)g.position, (const double *)g.normal, width, rows, step, inv_c, inv_p, normal_power_log2);
+}
+
+ndt_denoise_params params_of(const ndt_denoise_params *dp)
+{
+    if (dp) return *dp;
+    ndt_denoise_params d;
+    d.iterations = 4;
+    d.normal_power_log2 = 5;
+    d.sigma_colour = 0.25;
+    d.sigma_plane = 0.25;
+    return d;
+}
+
+int check_params(const char *who, const ndt_denoise_params &d)
+{
+    if (d.iterations < 1 || d.iterations > 6) return fail(NDT_E_INVALID, "%s: %d iterations are outside 1 .. 6", who, d.iterations);
+    if (d.normal_power_log2 < 0 || d.normal_power_log2 > 8)
+        return fail(NDT_E_INVALID, "%s: normal_power_log2 %d is outside 0 .. 8", who, d.normal_power_log2);
+    if (!(d.sigma_colour > 0) || !isfinite(d.sigma_colour))
+        return fail(NDT_E_INVALID, "%s: sigma_colour %g: a finite number above 0", who, d.sigma_colour);
+    if (!(d.sigma_plane > 0) || !isfinite(d.sigma_plane)) return fail(NDT_E_INVALID, "%s: sigma_plane %g: a finite number above 0", who, d.sigma_plane);
+    return NDT_OK;
+}
+
+// The iterations for checked arguments, asynchronous on the context's stream: d_in -> ping -> pong -> ... -> d_out.  d_out may be
+// d_in: a single iteration then goes through ping and a copy.
+int iterate(ndt_hip_ctx *ctx, const char *who, const void *d_in, const ndt_feature_planes &g, int dims, int width, int rows,
+            const ndt_denoise_params &d, void *d_out)
+{
+    DenoiseState &dn = ctx->denoise;
+    hipStream_t s = ctx->stream;
+    const long long n_pixels = (long long)rows * width;
+    const long long grid = (n_pixels + DENOISE_LANES - 1) / DENOISE_LANES;
+    if (grid > INT_MAX) return fail(NDT_E_UNSUPPORTED, "%s: %d x %d pixels are more than one launch takes", who, width, rows);
+    const size_t img_bytes = (size_t)n_pixels * 4 * sizeof(double);
+    const bool through_copy = d.iterations == 1 && d_in == d_out;
+    int rc;
+    if ((d.iterations > 1 || through_copy) && (rc = dn.d_ping.reserve(img_bytes, s, who))) return rc;
+    if (d.iterations > 2 && (rc = dn.d_pong.reserve(img_bytes, s, who))) return rc;
+    if (!dn.ev[0])
+        for (hipEvent_t &e : dn.ev) HIP_TRY(hipEventCreate(&e));
+    const double inv_p = 1.0 / (d.sigma_plane * d.sigma_plane);
+    const void *cur = d_in;
+    for (int it = 0; it < d.iterations; ++it) {
+        const bool last = it == d.iterations - 1;
+        void *next = last && !through_copy ? d_out : (it & 1) ? dn.d_pong.p : dn.d_ping.p;
+        const double sc = d.sigma_colour / (double)(1 << it);
+        const double inv_c = 1.0 / (sc * sc);
+        const int step = 1 << it;
+        HIP_TRY(hipEventRecord(dn.ev[2 * it], s));
+        switch (dims) {
+        case 3: launch_atrous<3>(s, (unsigned)grid, cur, next, g, width, rows, step, inv_c, inv_p, d.normal_power_log2); break;
+        case 4: launch_atrous<4>(s, (unsigned)grid, cur, next, g, width, rows, step, inv_c, inv_p, d.normal_power_log2); break;
+        case 5: launch_atrous<5>(s, (unsigned)grid, cur, next, g, width, rows, step, inv_c, inv_p, d.normal_power_log2); break;
+        case 6: launch_atrous<6>(s, (unsigned)grid, cur, next, g, width, rows, step, inv_c, inv_p, d.normal_power_log2); break;
+        case 7: launch_atrous<7>(s, (unsigned)grid, cur, next, g, width, rows, step, inv_c, inv_p, d.normal_power_log2); break;
+        case 8: launch_atrous<8>(s, (unsigned)grid, cur, next, g, width, rows, step, inv_c, inv_p, d.normal_power_log2); break;
+        case 9: launch_atrous<9>(s, (unsigned)grid, cur, next, g, width, rows, step, inv_c, inv_p, d.normal_power_log2); break;
+        case 10: launch_atrous<10>(s, (unsigned)grid, cur, next, g, width, rows, step, inv_c, inv_p, d.normal_power_log2); break;
+        case 11: launch_atrous<11>(s, (unsigned)grid, cur, next, g, width, rows, step, inv_c, inv_p, d.normal_power_log2); break;
+        default: launch_atrous<12>(s, (unsigned)grid, cur, next, g, width, rows, step, inv_c, inv_p, d.normal_power_log2); break;
+        }
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipEventRecord(dn.ev[2 * it + 1], s));
+        ++dn.launches;
+        cur = next;
+    }
+    if (through_copy) HIP_TRY(hipMemcpyAsync(d_out, dn.d_ping.p, img_bytes, hipMemcpyDeviceToDevice, s));
+    dn.iterations = d.iterations;
+    return NDT_OK;
+}
+
+// after the stream has been synchronised: the summed device time of the last call's iterations
+int collect_ms(ndt_hip_ctx *ctx)
+{
+    DenoiseState &dn = ctx->denoise;
+    dn.ms = 0.0;
+    for (int it = 0; it < dn.iterations; ++it) {
+        float ms = 0.0f;
+        HIP_TRY(hipEventElapsedTime(&ms, dn.ev[2 * it], dn.ev[2 * it + 1]));
+        dn.ms += ms;
+    }
+    return NDT_OK;
+}
+
+// what every whole-frame call refuses, before any device work; *d the parameters in force, *rows the frame's
+int refuse(const char *who, ndt_hip_ctx *ctx, const ndt_render_params *p, const ndt_denoise_params *dp, const void *out, ndt_denoise_params *d,
+           int *rows)
+{
+    if (!ctx || !p || !out) return fail(NDT_E_INVALID, "%s: NULL argument", who);
+    *d = params_of(dp);
+    int rc = check_params(who, *d);
+    if (rc) return rc;
+    if (p->recursive_aa)
+        return fail(NDT_E_UNSUPPORTED, "%s: no denoiser behind recursive_aa (-a): its pixels are averages of corner samples, the guides are one ray's", who);
+    if (p->stereo != NDT_STEREO_MONO)
+        return fail(NDT_E_UNSUPPORTED, "%s: no denoiser for stereo mode %d: a stencil must not cross the seam between two eyes", who, p->stereo);
+    if (p->row_begin != 0 || p->row_step != 1)
+        return fail(NDT_E_UNSUPPORTED, "%s: no denoiser for a row shard (row_begin %d, row_step %d): a cyclic shard has no neighbouring rows", who,
+                    p->row_begin, p->row_step);
+    if (p->samples < 1) return fail(NDT_E_INVALID, "%s: samples=%d", who, p->samples);
+    ndt_render_params q = *p;
+    q.samples = 1;
+    return features_check(who, ctx, &q, rows);
+}
+
+// The denoised frame of checked arguments in d_rgba (device, aligned to 16 bytes): the frame `p` asks for into the context's frame
+// buffer, the feature pass of the same frame with samples = 1 into the context's planes, the iterations.  Returns when complete.
+int render_denoised(const char *who, ndt_hip_ctx *ctx, const ndt_render_params *p, const ndt_denoise_params &d, int rows, void *d_rgba,
+                    ndt_render_stats *stats)
+{
+    HIP_TRY(hipSetDevice(ctx->device));
+    DenoiseState &dn = ctx->denoise;
+    dn.launches = 0;
+    dn.iterations = 0;
+    dn.ms = 0.0;
+    const size_t img_bytes = (size_t)rows * (size_t)p->width * 4 * sizeof(double);
+    int rc;
+    if ((rc = dn.d_frame.reserve(img_bytes, ctx->stream, who))) return rc;
+    if ((rc = ndt_hip_render_device(ctx, p, dn.d_frame.p, stats))) return rc;
+    ndt_render_params q = *p;
+    q.samples = 1;
+    ndt_feature_planes planes;
+    if ((rc = features_own(ctx, who, &q, FEATURES_ALL, false, &planes))) return rc;
+    dn.launches = ctx->features.launches;
+    if ((rc = iterate(ctx, who, dn.d_frame.p, planes, ctx->dims, p->width, rows, d, d_rgba))) return rc;
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return collect_ms(ctx);
+}
+
+// ... into the context's own buffer dn.d_out, and its 8-bit image into dn.d_rgba8 when wanted (queued behind it, not synchronised)
+int render_denoised_own(const char *who, ndt_hip_ctx *ctx, const ndt_render_params *p, const ndt_denoise_params &d, int rows, bool want_rgba8,
+                        ndt_render_stats *stats)
+{
+    HIP_TRY(hipSetDevice(ctx->device));
+    DenoiseState &dn = ctx->denoise;
+    const size_t pixels = (size_t)rows * (size_t)p->width;
+    int rc;
+    if ((rc = dn.d_out.reserve(pixels * 4 * sizeof(double), ctx->stream, who))) return rc;
+    if (want_rgba8 && (rc = dn.d_rgba8.reserve(pixels * 4, ctx->stream, who))) return rc;
+    if ((rc = render_denoised(who, ctx, p, d, rows, dn.d_out.p, stats))) return rc;
+    if (want_rgba8 && (rc = ndt_hip_quantize_device(ctx, dn.d_out.p, dn.d_rgba8.p, (int64_t)pixels))) return rc;
+    return NDT_OK;
+}
+
+} // namespace
+
+void ndt_impl::free_denoise(ndt_hip_ctx *ctx)
+{
+    DenoiseState &dn = ctx->denoise;
+    dn.d_ping.release();
+    dn.d_pong.release();
+    dn.d_frame.release();
+    dn.d_out.release();
+    dn.d_rgba8.release();
+    for (hipEvent_t &e : dn.ev)
+        if (e) (void)hipEventDestroy(e);
+    dn = DenoiseState();
+}
+
+extern "C" int ndt_hip_denoise_device(ndt_hip_ctx *ctx, const void *d_rgba_in, const ndt_feature_planes *d_planes, int32_t dims, int32_t width,
+                                      int32_t rows, const ndt_denoise_params *dp, void *d_rgba_out)
+{
+    const char *who = "ndt_hip_denoise_device";
+    if (!ctx || !d_rgba_in || !d_planes || !d_rgba_out) return fail(NDT_E_INVALID, "%s: NULL argument", who);
+    const ndt_denoise_params d = params_of(dp);
+    int rc = check_params(who, d);
+    if (rc) return rc;
+    if (dims < NDT_MIN_DIMS || dims > NDT_MAX_DIMS) return fail(NDT_E_INVALID, "%s: %d dimensions are outside %d .. %d", who, dims, NDT_MIN_DIMS, NDT_MAX_DIMS);
+    if (width < 1 || rows < 1) return fail(NDT_E_INVALID, "%s: a frame of %d x %d pixels", who, width, rows);
+    if (!d_planes->id || !d_planes->position || !d_planes->normal)
+        return fail(NDT_E_INVALID, "%s: a NULL plane: id, position and normal guide the filter", who);
+    if (((uintptr_t)d_rgba_in & 15u) != 0 || ((uintptr_t)d_rgba_out & 15u) != 0 || ((uintptr_t)d_planes->id & 3u) != 0 ||
+        (((uintptr_t)d_planes->position | (uintptr_t)d_planes->normal) & 7u) != 0)
+        return fail(NDT_E_INVALID, "%s: misaligned: the images to 16 bytes, the planes to their elements", who);
+    HIP_TRY(hipSetDevice(ctx->device));
+    DenoiseState &dn = ctx->denoise;
+    dn.launches = 0;
+    dn.iterations = 0;
+    dn.ms = 0.0;
+    if ((rc = iterate(ctx, who, d_rgba_in, *d_planes, dims, width, rows, d, d_rgba_out))) return rc;
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return collect_ms(ctx);
+}
+
+extern "C" int ndt_hip_denoise_launches(ndt_hip_ctx *ctx) { return ctx ? ctx->denoise.launches : 0; }
+extern "C" double ndt_hip_denoise_ms(ndt_hip_ctx *ctx) { return ctx ? ctx->denoise.ms : 0.0; }
+
+extern "C" int ndt_hip_render_denoised_device(ndt_hip_ctx *ctx, const ndt_render_params *p, const ndt_denoise_params *dp, void *d_rgba,
+                                              ndt_render_stats *stats)
+{
+    const char *who = "ndt_hip_render_denoised_device";
+    ndt_denoise_params d;
+    int rows = 0;
+    int rc = refuse(who, ctx, p, dp, d_rgba, &d, &rows);
+    if (rc) return rc;
+    if (((uintptr_t)d_rgba & 15u) != 0) return fail(NDT_E_INVALID, "%s: misaligned: the image must be aligned to 16 bytes", who);
+    return render_denoised(who, ctx, p, d, rows, d_rgba, stats);
+}
+
+extern "C" int ndt_hip_render_denoised(ndt_hip_ctx *ctx, const ndt_render_params *p, const ndt_denoise_params *dp, double *rgba,
+                                       ndt_render_stats *stats)
+{
+    const char *who = "ndt_hip_render_denoised";
+    ndt_denoise_params d;
+    int rows = 0;
+    int rc = refuse(who, ctx, p, dp, rgba, &d, &rows);
+    if (rc) return rc;
+    if ((rc = render_denoised_own(who, ctx, p, d, rows, false, stats))) return rc;
+    HIP_TRY(hipMemcpyAsync(rgba, ctx->denoise.d_out.p, (size_t)rows * (size_t)p->width * 4 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return NDT_OK;
+}
+
+extern "C" int ndt_hip_render_denoised_rgba8(ndt_hip_ctx *ctx, const ndt_render_params *p, const ndt_denoise_params *dp, uint8_t *rgba8,
+                                             ndt_render_stats *stats)
+{
+    const char *who = "ndt_hip_render_denoised_rgba8";
+    ndt_denoise_params d;
+    int rows = 0;
+    int rc = refuse(who, ctx, p, dp, rgba8, &d, &rows);
+    if (rc) return rc;
+    if ((rc = render_denoised_own(who, ctx, p, d, rows, true, stats))) return rc;
+    HIP_TRY(hipMemcpyAsync(rgba8, ctx->denoise.d_rgba8.p, (size_t)rows * (size_t)p->width * 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return NDT_OK;
+}
+
+extern "C" int ndt_hip_render_denoised_png(ndt_hip_ctx *ctx, const ndt_render_params *p, const ndt_denoise_params *dp, uint8_t *png, int64_t cap,
+                                           ndt_png_stats *stats, ndt_render_stats *render_stats)
+{
+    const char *who = "ndt_hip_render_denoised_png";
+    ndt_denoise_params d;
+    int rows = 0;
+    int rc = refuse(who, ctx, p, dp, png, &d, &rows);
+    if (rc) return rc;
+    if (ndt_hip_png_bound(p->width, rows) < 0)
+        return fail(NDT_E_INVALID, "%s: the filtered stream of a %d x %d image exceeds 2^31 - 1 bytes", who, p->width, rows);
+    if ((rc = render_denoised_own(who, ctx, p, d, rows, true, render_stats))) return rc;
+    return ndt_hip_encode_png_device(ctx, ctx->denoise.d_rgba8.p, p->width, rows, png, cap, stats);
+}
+
+extern "C" int ndt_hip_render_denoised_jpeg(ndt_hip_ctx *ctx, const ndt_render_params *p, const ndt_denoise_params *dp, const ndt_jpeg_params *jp,
+                                            uint8_t *jpg, int64_t cap, ndt_jpeg_stats *stats, ndt_render_stats *render_stats)
+{
+    const char *who = "ndt_hip_render_denoised_jpeg";
+    ndt_denoise_params d;
+    int rows = 0;
+    int rc = refuse(who, ctx, p, dp, jpg, &d, &rows);
+    if (rc) return rc;
+    if (ndt_hip_jpeg_bound(p->width, rows, jp) < 0)
+        return fail(NDT_E_INVALID, "%s: no JPEG of %d x %d with these parameters (a side above 65535, a quality outside 0 .. 100, a sampling outside 0 .. 1 or a reserved word set)",
+                    who, p->width, rows);
+    if ((rc = render_denoised_own(who, ctx, p, d, rows, true, render_stats))) return rc;
+    return ndt_hip_encode_jpeg_device(ctx, ctx->denoise.d_rgba8.p, p->width, rows, jp, jpg, cap, stats);
+}
+
+extern "C" int ndt_hip_render_denoised_exr(ndt_hip_ctx *ctx, const ndt_render_params *p, const ndt_denoise_params *dp, const ndt_exr_params *ep,
+                                           uint8_t *out, int64_t cap, ndt_exr_stats *stats, ndt_render_stats *render_stats)
+{
+    const char *who = "ndt_hip_render_denoised_exr";
+    if (stats) *stats = ndt_exr_stats{};
+    ndt_denoise_params d;
+    int rows = 0;
+    int rc = refuse(who, ctx, p, dp, out, &d, &rows);
+    if (rc) return rc;
+    if (ndt_hip_exr_bound(p->width, rows, ep, 0) < 0)
+        return fail(NDT_E_INVALID, "%s: no EXR of %d x %d with these parameters (a pixel type other than 0, 1, 2, or samples beyond 2^31 - 1 bytes)", who,
+                    p->width, rows);
+    if ((rc = render_denoised_own(who, ctx, p, d, rows, false, render_stats))) return rc;
+    return ndt_hip_encode_exr_device(ctx, ctx->denoise.d_out.p, nullptr, p->width, rows, ep, out, cap, stats);
+}

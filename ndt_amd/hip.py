@@ -35,6 +35,8 @@ API_SYMBOLS = [
     "ndt_hip_exr_bound", "ndt_hip_encode_exr_device", "ndt_hip_encode_exr", "ndt_hip_render_exr", "ndt_hip_render_ssaa_exr",
     "ndt_hip_render_features", "ndt_hip_render_features_device", "ndt_hip_features_launches", "ndt_hip_exr_features_bound",
     "ndt_hip_encode_exr_features_device", "ndt_hip_render_exr_features", "ndt_hip_render_ssaa_exr_features",
+    "ndt_hip_denoise_device", "ndt_hip_render_denoised_device", "ndt_hip_render_denoised", "ndt_hip_render_denoised_rgba8",
+    "ndt_hip_render_denoised_png", "ndt_hip_render_denoised_jpeg", "ndt_hip_render_denoised_exr", "ndt_hip_denoise_launches", "ndt_hip_denoise_ms",
 ]
 
 IMAGE_F64, IMAGE_RGBA8 = 0, 1      # enum ndt_image_format
@@ -181,6 +183,17 @@ def load_library():
                                                     C.c_void_p, C.c_void_p]
         lib.ndt_hip_render_ssaa_exr_features.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p,
                                                          C.c_int64, C.c_void_p, C.c_void_p]
+    if hasattr(lib, "ndt_hip_denoise_device"):      # (likewise)
+        lib.ndt_hip_denoise_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
+        lib.ndt_hip_render_denoised_device.argtypes = [C.c_void_p] * 5
+        lib.ndt_hip_render_denoised.argtypes = [C.c_void_p] * 5
+        lib.ndt_hip_render_denoised_rgba8.argtypes = [C.c_void_p] * 5
+        lib.ndt_hip_render_denoised_png.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
+        lib.ndt_hip_render_denoised_jpeg.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
+        lib.ndt_hip_render_denoised_exr.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
+        lib.ndt_hip_denoise_launches.argtypes = [C.c_void_p]
+        lib.ndt_hip_denoise_ms.argtypes = [C.c_void_p]
+        lib.ndt_hip_denoise_ms.restype = C.c_double
     _lib = lib
     return lib
 
@@ -277,6 +290,16 @@ def exr_features_bound(width, rows, dims, features=("id", "position", "normal"),
         raise ValueError("no EXR of %d x %d with the features of %d dimensions: a bad size, or samples beyond 2^31 - 1 bytes"
                          % (width, rows, dims))
     return n
+
+
+class DenoiseParams(C.Structure):
+    """ndt_denoise_params: iterations 1 .. 6, normal_power_log2 0 .. 8, the two sigmas finite and above 0"""
+    _fields_ = [("iterations", C.c_int32), ("normal_power_log2", C.c_int32), ("sigma_colour", C.c_double), ("sigma_plane", C.c_double)]
+
+
+def denoise_params(iterations=4, sigma_colour=0.25, sigma_plane=0.25, normal_power_log2=5):
+    """The ndt_denoise_params of these values (the defaults are the library's); the library checks their ranges."""
+    return DenoiseParams(int(iterations), int(normal_power_log2), float(sigma_colour), float(sigma_plane))
 
 
 JPEG_SAMPLING = {"420": 0, "444": 1}
@@ -777,6 +800,70 @@ class NdtHip:
                                                                 C.byref(planes), int(dims), mask, int(width), int(rows), C.byref(ep),
                                                                 out.ctypes.data, cap, C.byref(self.exr_stats)))
         return out[:self.exr_stats.file_bytes].tobytes()
+
+    def denoise(self, d_rgba_in_ptr, d_planes, dims, width, rows, d_rgba_out_ptr=None, **dn):
+        """ndt_hip_denoise_device: the edge-avoiding a-trous filter alone, on rows x width x 4 device doubles at `d_rgba_in_ptr`,
+        guided by the device planes `d_planes` names (a dict "id" / "position" / "normal" of raw device pointers), into
+        `d_rgba_out_ptr` (default: in place).  dn: iterations, sigma_colour, sigma_plane, normal_power_log2."""
+        dp = denoise_params(**dn)
+        planes = FeaturePlanes(d_planes.get("id"), d_planes.get("position"), d_planes.get("normal"), None, None)
+        out = d_rgba_in_ptr if d_rgba_out_ptr is None else d_rgba_out_ptr
+        self._check(self.lib.ndt_hip_denoise_device(self.ctx, C.c_void_p(d_rgba_in_ptr), C.byref(planes), int(dims), int(width), int(rows),
+                                                    C.byref(dp), C.c_void_p(out)))
+
+    def denoise_launches(self):
+        """ndt_hip_denoise_launches: kernel launches of the context's last denoised frame (the feature pass's and the iterations')."""
+        return int(self.lib.ndt_hip_denoise_launches(self.ctx))
+
+    def denoise_ms(self):
+        """ndt_hip_denoise_ms: summed device time of its iterations."""
+        return float(self.lib.ndt_hip_denoise_ms(self.ctx))
+
+    def render_denoised(self, width, height, depth, sink=None, iterations=4, sigma_colour=0.25, sigma_plane=0.25, normal_power_log2=5,
+                        d_rgba_ptr=None, quality=95, sampling="420", pixel="half", cap=None, **kw):
+        """ndt_hip_render_denoised*: the frame render(**kw) gives (samples and all), denoised on the device by the a-trous filter,
+        guided by the feature pass of the same frame with samples = 1.  sink None: ((rows, width, 4) float64, RenderStats);
+        "device": left at raw device pointer `d_rgba_ptr`, returns the stats; "rgba8": the (rows, width, 4) uint8 image;
+        "png" / "jpeg" / "exr": the file's bytes (self.png_stats / jpeg_stats / exr_stats keep the record) -- each with the stats."""
+        p = self.params(width, height, depth, **kw)
+        rows = shard_rows(height, p.row_begin, p.row_step)
+        dp = denoise_params(iterations, sigma_colour, sigma_plane, normal_power_log2)
+        st = RenderStats()
+        if sink is None:
+            out = np.zeros((rows, width, 4), dtype=np.float64)
+            self._check(self.lib.ndt_hip_render_denoised(self.ctx, C.byref(p), C.byref(dp), out.ctypes.data, C.byref(st)))
+            return out, st
+        if sink == "device":
+            self._check(self.lib.ndt_hip_render_denoised_device(self.ctx, C.byref(p), C.byref(dp), C.c_void_p(d_rgba_ptr), C.byref(st)))
+            return st
+        if sink == "rgba8":
+            out = np.zeros((rows, width, 4), dtype=np.uint8)
+            self._check(self.lib.ndt_hip_render_denoised_rgba8(self.ctx, C.byref(p), C.byref(dp), out.ctypes.data, C.byref(st)))
+            return out, st
+        if sink == "png":
+            cap = png_bound(width, rows) if cap is None else int(cap)
+            out = np.zeros(max(cap, 1), dtype=np.uint8)
+            self.png_stats = PngStats()
+            self._check(self.lib.ndt_hip_render_denoised_png(self.ctx, C.byref(p), C.byref(dp), out.ctypes.data, cap, C.byref(self.png_stats),
+                                                             C.byref(st)))
+            return out[:self.png_stats.png_bytes].tobytes(), st
+        if sink == "jpeg":
+            jp = jpeg_params(quality, sampling)
+            cap = jpeg_bound(width, rows, quality, sampling) if cap is None else int(cap)
+            out = np.zeros(max(cap, 1), dtype=np.uint8)
+            self.jpeg_stats = JpegStats()
+            self._check(self.lib.ndt_hip_render_denoised_jpeg(self.ctx, C.byref(p), C.byref(dp), C.byref(jp), out.ctypes.data, cap,
+                                                              C.byref(self.jpeg_stats), C.byref(st)))
+            return out[:self.jpeg_stats.jpeg_bytes].tobytes(), st
+        if sink == "exr":
+            ep = exr_params(pixel)
+            cap = exr_bound(width, rows, pixel) if cap is None else int(cap)
+            out = np.zeros(max(cap, 1), dtype=np.uint8)
+            self.exr_stats = ExrStats()
+            self._check(self.lib.ndt_hip_render_denoised_exr(self.ctx, C.byref(p), C.byref(dp), C.byref(ep), out.ctypes.data, cap,
+                                                             C.byref(self.exr_stats), C.byref(st)))
+            return out[:self.exr_stats.file_bytes].tobytes(), st
+        raise ValueError("sink %r is none of None, 'device', 'rgba8', 'png', 'jpeg', 'exr'" % (sink,))
 
     def apng_begin(self, width, rows, n_frames, delay_num=1, delay_den=24, n_plays=0):
         """ndt_hip_apng_begin: opens the context's animated-PNG session: n_frames frames of width x rows pixels are to come, each

@@ -437,6 +437,13 @@ typedef struct ndt_frame_request {
                                          * pixel's primary ray hits -- object, N-D point, normal -- as extra channels id, P.*, N.* of the file
                                          * (`--exr-aov`); 0 = none.  Refused with any other colour kind, and where a pixel has no single
                                          * primary ray: aa_depth >= 0, samples > 1, anaglyph, frame packing */
+    /* `--denoise`: the frame denoised on the GPU between the render and the sink by the edge-avoiding a-trous filter of
+     * ndt_hip_render_denoised* (include/ndt_hip.h), guided by the feature pass of the same frame.  The four are ndt_denoise_params';
+     * denoise_iterations 0 = off (the others are then ignored), 1 .. 6 = on.  With the colour kinds doubles, 8-bit RGBA, PNG file,
+     * JPEG file and OpenEXR file, any samples, one context; refused with a message that names the cause beside aa_depth >= 0, a
+     * stereo mode, ssaa above 1, a map, exr_features, a 16-bit or animated PNG and a frame spread over several contexts */
+    int denoise_iterations, denoise_normal_power_log2;
+    double denoise_sigma_colour, denoise_sigma_plane;
 } ndt_frame_request;
 /* Everything that arrives is malloc'ed by the library and freed by ndt_frame_free; what was not asked for stays NULL. */
 typedef struct ndt_frame {
@@ -448,6 +455,8 @@ typedef struct ndt_frame {
     /* host milliseconds of the frame's device work beside the render: making the file or files, finishing the map, the folds of --ssaa */
     double file_ms, depth_ms, ssaa_ms;
     int feature_channels, feature_launches;     /* exr_features: the channels it added to the file, and the kernel launches of the feature pass */
+    int denoise_launches;                       /* denoise_iterations: kernel launches of the feature pass and the iterations */
+    double denoise_ms;                          /* ... and the iterations' summed device time */
 } ndt_frame;
 /* Returns 1 like the reference's render_image on success; 0 with a message on stderr otherwise, and then `out` is zeroed: nothing
  * is left to free.  No fallback: without a device, or with a frame the device path refuses (HIDEF frame packing supersampled, ...),
@@ -455,7 +464,7 @@ typedef struct ndt_frame {
  * as 8-bit pixels, and a PNG or JPEG file is then encoded from those on the first context; a frame with a map is rendered by one
  * context whatever was set, and a 16-bit PNG, an OpenEXR file or an animated PNG frame over several contexts is refused.  What the
  * device did is said on stdout: `compressed PNG of B bytes on GPU D in L launches` (`16-bit PNG`, `depth PNG`, `16-bit depth PNG`),
- * `encoded JPEG of ...`, `encoded EXR of ...`, `added K feature channels on GPU D in L launches`, `finished depth map [lo, hi] on GPU D in L launches`, `supersampled KxK on GPU D in L launches`, `animated PNG frame
+ * `encoded JPEG of ...`, `encoded EXR of ...`, `added K feature channels on GPU D in L launches`, `finished depth map [lo, hi] on GPU D in L launches`, `supersampled KxK on GPU D in L launches`, `denoised in K iterations on GPU D in L launches`, `animated PNG frame
  * K: w x h at x,y (B bytes) on GPU D in L launches`. */
 int ndt_render_frame(scene *scn, const ndt_frame_request *request, ndt_frame *out);
 /* safe on a zeroed or a half-filled frame; leaves it zeroed */

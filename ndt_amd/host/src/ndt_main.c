@@ -29,6 +29,12 @@
  * file: the object its primary ray hits (channel id, UINT: object index + 1, 0 for none), the hit point in all N coordinates (P.00 ..,
  * FLOAT) and the normal there (N.00 .., FLOAT), found on the GPU by a feature pass beside the render (ndt_hip_render_exr_features).
  * With -z, --ssaa, -m s|o, -j, --fit gpu and --kd gpu; not with -a, -n above 1 or -m a|h, where a pixel has no single primary ray.
+ * `--denoise [K]` (1 .. 6 iterations, default 4) denoises every frame on the GPU between the render and the sink: an edge-avoiding
+ * a-trous wavelet over the doubles, in linear light, before anything is quantised, guided by the object, N-D hit point and N-D
+ * normal of every pixel's primary ray (ndt_hip_render_denoised*); `--denoise-colour X`, `--denoise-plane X` (above 0, default 0.25
+ * each) and `--denoise-normal E` (0 .. 8, default 5) set its three weights.  With the default stored PNG, --png [--deflate gpu],
+ * --jpeg, --exr, --raw, -n, -j, --fit gpu and --kd gpu; not with -a, -m other than mono, -g N > 1, --ssaa above 1, --apng, --png16,
+ * -z or --exr-aov.
  * None falls back: what the device path cannot do ends the run. */
 #include <dlfcn.h>
 #include <getopt.h>
@@ -425,6 +431,10 @@ int main(int argc, char **argv)
     int exr_pixel = 0;      /* --exr-pixel half|float: the colour channels' samples, 1 / 2 (default: half) */
     int exr_aov = 0;        /* --exr-aov id,position,normal|all: what every pixel's primary ray hits, as channels id, P.*, N.* of the OpenEXR file (a mask of NDT_FEATURE_*) */
     int exr_aov_given = 0;
+    int denoise = 0;        /* --denoise [K]: every frame denoised on the GPU by K iterations of the a-trous filter, 1 .. 6 (default 4); 0: off */
+    int denoise_normal = 5; /* --denoise-normal E: the normals' dot product squared E times, 0 .. 8 */
+    double denoise_colour = 0.25, denoise_plane = 0.25;     /* --denoise-colour X, --denoise-plane X: sigma_colour, sigma_plane, above 0 */
+    const char *denoise_tuned = NULL;       /* the first --denoise-* flag given */
     char *objects_dir = "objects";      /* -o: where object plugins are looked for (object.c:119; ndt.c passes "objects") */
     static struct option longopts[] = { { "dump-scene", required_argument, NULL, 1000 },
                                         { "raw", required_argument, NULL, 1001 }, { "png", no_argument, NULL, 1002 },
@@ -436,6 +446,8 @@ int main(int argc, char **argv)
                                         { "png16", no_argument, NULL, 1012 }, { "apng", no_argument, NULL, 1013 },
                                         { "apng-fps", required_argument, NULL, 1014 }, { "exr", no_argument, NULL, 1015 },
                                         { "exr-pixel", required_argument, NULL, 1016 }, { "exr-aov", required_argument, NULL, 1017 },
+                                        { "denoise", optional_argument, NULL, 1018 }, { "denoise-colour", required_argument, NULL, 1019 },
+                                        { "denoise-plane", required_argument, NULL, 1020 }, { "denoise-normal", required_argument, NULL, 1021 },
                                         { NULL, 0, NULL, 0 } };
     int ch;
     while ((ch = getopt_long(argc, argv, "a:d:g:r:f:j:l:m:3:n:ps:t:u:o:zh", longopts, NULL)) != -1) {
@@ -570,14 +582,90 @@ int main(int argc, char **argv)
             }
             break;
         }
+        case 1018: {
+            /* --denoise, --denoise=K or --denoise K: a following word that starts with a digit is the count */
+            const char *arg = optarg;
+            if (!arg && optind < argc && argv[optind][0] >= '0' && argv[optind][0] <= '9') arg = argv[optind++];
+            denoise = 4;
+            if (arg) {
+                char *end = NULL;
+                const long k = strtol(arg, &end, 10);
+                if (end == arg || *end || k < 1 || k > 6) {
+                    fprintf(stderr, "%s: --denoise takes 1 .. 6 iterations, not '%s'\n", argv[0], arg);
+                    return 1;
+                }
+                denoise = (int)k;
+            }
+            break;
+        }
+        case 1019:
+        case 1020: {
+            char *end = NULL;
+            const double x = strtod(optarg, &end);
+            const char *flag = ch == 1019 ? "--denoise-colour" : "--denoise-plane";
+            if (end == optarg || *end || !(x > 0) || !isfinite(x)) {
+                fprintf(stderr, "%s: %s takes a finite number above 0, not '%s'\n", argv[0], flag, optarg);
+                return 1;
+            }
+            if (ch == 1019) denoise_colour = x;
+            else denoise_plane = x;
+            if (!denoise_tuned) denoise_tuned = flag;
+            break;
+        }
+        case 1021: {
+            char *end = NULL;
+            const long e = strtol(optarg, &end, 10);
+            if (end == optarg || *end || e < 0 || e > 8) {
+                fprintf(stderr, "%s: --denoise-normal takes 0 .. 8, not '%s'\n", argv[0], optarg);
+                return 1;
+            }
+            denoise_normal = (int)e;
+            if (!denoise_tuned) denoise_tuned = "--denoise-normal";
+            break;
+        }
         default:
             fprintf(stderr, "usage: %s -s scene.so|builtin:yaml [-d dims] [-r WxH|1080p|4k] [-f last|first:last[:total]] [-l depth]\n"
-                            "          [-a diff,depth] [-n samples] [-m s|o|a|m] [-p] [-z] [-j frames_in_flight] [-g gpus_per_frame] [-u config] [--dump-scene file.ndtscene] [--raw file.f64] [--png [--deflate stored|gpu]] [--jpeg [--jpeg-quality 1..100] [--jpeg-sampling 420|444]] [--fit host|gpu] [--kd host|gpu] [--depth host|gpu [--depth-png]] [--ssaa 1..8] [--png16] [--apng [--apng-fps 1..1000]] [--exr [--exr-pixel half|float] [--exr-aov id,position,normal|all]]\n", argv[0]);
+                            "          [-a diff,depth] [-n samples] [-m s|o|a|m] [-p] [-z] [-j frames_in_flight] [-g gpus_per_frame] [-u config] [--dump-scene file.ndtscene] [--raw file.f64] [--png [--deflate stored|gpu]] [--jpeg [--jpeg-quality 1..100] [--jpeg-sampling 420|444]] [--fit host|gpu] [--kd host|gpu] [--depth host|gpu [--depth-png]] [--ssaa 1..8] [--png16] [--apng [--apng-fps 1..1000]] [--exr [--exr-pixel half|float] [--exr-aov id,position,normal|all]]\n"
+                            "          [--denoise [1..6] [--denoise-colour X] [--denoise-plane X] [--denoise-normal 0..8]]: every frame denoised on the GPU, with the stored PNG, --png [--deflate gpu], --jpeg, --exr, --raw, -n, -j, --fit gpu, --kd gpu; refused with -a, -m s|o|a|h, -g N > 1, --ssaa above 1, --apng, --png16, -z, --exr-aov\n", argv[0]);
             return ch == 'h' ? 0 : 1;
         }
     }
     if (!scene_path || dims < 3 || width < 1 || height < 1) {
         fprintf(stderr, "%s: need -s scene.so, dims >= 3 and a resolution\n", argv[0]);
+        return 1;
+    }
+    if (denoise_tuned && !denoise) {
+        fprintf(stderr, "%s: %s sets a weight of the denoiser: it needs --denoise\n", argv[0], denoise_tuned);
+        return 1;
+    }
+    if (denoise && aa_depth >= 0) {
+        fprintf(stderr, "%s: --denoise with -a: an anti-aliased pixel is an average of corner samples, and the denoiser's guides are one primary ray's: take -n\n", argv[0]);
+        return 1;
+    }
+    if (denoise && stereo != 0) {
+        fprintf(stderr, "%s: --denoise with -m %s: a stencil must not cross the seam between two eyes; that is not built: take -m m\n", argv[0],
+                stereo == 1 ? "s" : stereo == 2 ? "o" : stereo == 3 ? "a" : "h");
+        return 1;
+    }
+    if (denoise && gpus > 1) {
+        fprintf(stderr, "%s: --denoise with -g %d: a cyclic row shard has no neighbouring rows to filter over: take -g 1 (or -j)\n", argv[0], gpus);
+        return 1;
+    }
+    if (denoise && ssaa > 1) {
+        fprintf(stderr, "%s: --denoise with --ssaa %d: the guides are the plain frame's, not a supersampled one's: take one\n", argv[0], ssaa);
+        return 1;
+    }
+    if (denoise && (apng || png16)) {
+        fprintf(stderr, "%s: --denoise with %s: the denoised frame leaves as a PPM, --png, --jpeg, --exr or --raw: take one of those\n", argv[0],
+                apng ? "--apng" : "--png16");
+        return 1;
+    }
+    if (denoise && want_depth) {
+        fprintf(stderr, "%s: --denoise with -z: no depth map is made beside a denoised frame: take one\n", argv[0]);
+        return 1;
+    }
+    if (denoise && exr_aov_given) {
+        fprintf(stderr, "%s: --denoise with --exr-aov: the denoised file carries colour only: take one\n", argv[0]);
         return 1;
     }
     if (exr_pixel && !exr) {
@@ -724,6 +812,8 @@ int main(int argc, char **argv)
     frame_request.jpeg_quality = jpeg_quality; frame_request.jpeg_sampling = jpeg_sampling < 0 ? 0 : jpeg_sampling;
     frame_request.exr_pixel = exr_pixel;
     frame_request.exr_features = exr_aov;
+    frame_request.denoise_iterations = denoise; frame_request.denoise_normal_power_log2 = denoise_normal;
+    frame_request.denoise_sigma_colour = denoise_colour; frame_request.denoise_sigma_plane = denoise_plane;
     frame_request.colour = exr ? NDT_COLOUR_EXR : apng ? NDT_COLOUR_APNG : png16 ? NDT_COLOUR_PNG16 : want_f64 ? NDT_COLOUR_F64
                          : file_kind != NDT_COLOUR_F64 ? file_kind : NDT_COLOUR_RGBA8;
     frame_request.map = !want_depth ? NDT_MAP_NONE : exr ? NDT_MAP_EXR_Z : !depth_gpu ? NDT_MAP_F64 : png16 ? NDT_MAP_PNG16 : depth_png ? NDT_MAP_PNG : NDT_MAP_DEPTH8;

@@ -544,6 +544,88 @@ static int frame_exr(const ndt_render_params *p, const ndt_frame_request *rq, nd
     return 1;
 }
 
+/* `--denoise`: the frame denoised on the GPU behind the render (ndt_hip_render_denoised*): colour in doubles, as 8-bit RGBA, or as
+ * a PNG, JPEG or OpenEXR file made there of the denoised doubles; one context, no map */
+static ndt_denoise_params denoise_params_of(const ndt_frame_request *rq)
+{
+    ndt_denoise_params dp;
+    memset(&dp, 0, sizeof(dp));
+    dp.iterations = rq->denoise_iterations;
+    dp.normal_power_log2 = rq->denoise_normal_power_log2;
+    dp.sigma_colour = rq->denoise_sigma_colour;
+    dp.sigma_plane = rq->denoise_sigma_plane;
+    return dp;
+}
+
+/* what a denoised frame does not go with, by name, before the scene is flattened or a device asked for */
+static int denoise_refused(const ndt_frame_request *rq)
+{
+    const char *why = NULL;
+    if (rq->aa_depth >= 0 && rq->aa_diff < 256) why = "recursive anti-aliasing (aa_depth >= 0): its pixels are averages of corner samples";
+    else if (rq->stereo != 0) why = "a stereo mode: a stencil must not cross the seam between two eyes";
+    else if (rq->ssaa != 1) why = "ssaa above 1: the guides are the plain frame's";
+    else if (rq->map != NDT_MAP_NONE) why = "a depth map";
+    else if (rq->exr_features) why = "exr_features";
+    else if (rq->colour == NDT_COLOUR_PNG16 || rq->colour == NDT_COLOUR_APNG) why = "a 16-bit or an animated PNG";
+    else if (g_want_ctx > 1) why = "a frame spread over several GPU contexts: a cyclic row shard has no neighbouring rows";
+    if (why) fprintf(stderr, "ndt_render_frame: denoise_iterations %d with %s: not built; there is no fallback\n", rq->denoise_iterations, why);
+    return why != NULL;
+}
+
+static int frame_denoised(const ndt_render_params *p, const ndt_frame_request *rq, ndt_frame *f)
+{
+    const int width = p->width, height = p->height;
+    const size_t n = (size_t)width * (size_t)height;
+    const ndt_denoise_params dp = denoise_params_of(rq);
+    int ok;
+    if (rq->colour == NDT_COLOUR_F64) {
+        if (!(f->rgba = (double *)malloc(n * 4 * sizeof(double)))) return out_of_memory();
+        ok = ndt_hip_render_denoised(g_ctx[0], p, &dp, f->rgba, NULL) == NDT_OK;
+    } else if (rq->colour == NDT_COLOUR_RGBA8) {
+        if (!(f->rgba8 = (unsigned char *)malloc(n * 4))) return out_of_memory();
+        ok = ndt_hip_render_denoised_rgba8(g_ctx[0], p, &dp, f->rgba8, NULL) == NDT_OK;
+    } else if (rq->colour == NDT_COLOUR_EXR) {
+        ndt_exr_params ep;
+        ndt_exr_stats es;
+        memset(&ep, 0, sizeof(ep));
+        ep.pixel_type = rq->exr_pixel;
+        const int64_t cap = ndt_hip_exr_bound(width, height, &ep, 0);
+        f->file = cap > 0 ? (unsigned char *)malloc((size_t)cap) : NULL;
+        if (!f->file) {
+            fprintf(stderr, "ndt_render_frame: no OpenEXR file of %d x %d with pixel type %d\n", width, height, rq->exr_pixel);
+            return 0;
+        }
+        if (!(ok = ndt_hip_render_denoised_exr(g_ctx[0], p, &dp, &ep, f->file, cap, &es, NULL) == NDT_OK)) return 0;
+        f->file_bytes = es.file_bytes;
+        f->file_ms = es.ms;
+        printf("encoded EXR of %lld bytes on GPU %d in %d launches\n", (long long)es.file_bytes, ndt_hip_device(g_ctx[0]), es.launches);
+    } else {
+        const int png = rq->colour == NDT_COLOUR_PNG;
+        const ndt_jpeg_params jp = jpeg_params_of(rq->jpeg_quality, rq->jpeg_sampling);
+        const int64_t cap = png ? ndt_hip_png_bound(width, height) : ndt_hip_jpeg_bound(width, height, &jp);
+        ndt_png_stats ps;
+        ndt_jpeg_stats js;
+        f->file = cap > 0 ? (unsigned char *)malloc((size_t)cap) : NULL;
+        if (!f->file) {
+            if (png) fprintf(stderr, "ndt_render_frame: no PNG of %d x %d\n", width, height);
+            else fprintf(stderr, "ndt_render_frame: no JPEG of %d x %d at quality %d, sampling %d\n", width, height, jp.quality, jp.sampling);
+            return 0;
+        }
+        ok = (png ? ndt_hip_render_denoised_png(g_ctx[0], p, &dp, f->file, cap, &ps, NULL)
+                  : ndt_hip_render_denoised_jpeg(g_ctx[0], p, &dp, &jp, f->file, cap, &js, NULL)) == NDT_OK;
+        if (!ok) return 0;
+        f->file_bytes = png ? ps.png_bytes : js.jpeg_bytes;
+        f->file_ms = png ? ps.encode_ms : js.encode_ms;
+        if (png) say_png(&ps, "PNG");
+        else say_jpeg(&js);
+    }
+    if (!ok) return 0;
+    f->denoise_launches = ndt_hip_denoise_launches(g_ctx[0]);
+    f->denoise_ms = ndt_hip_denoise_ms(g_ctx[0]);
+    printf("denoised in %d iterations on GPU %d in %d launches\n", dp.iterations, ndt_hip_device(g_ctx[0]), f->denoise_launches);
+    return 1;
+}
+
 /* the maps each colour kind comes with (bit m: ndt_map_kind m): the pairs a device call serves */
 #define MAP_BIT(m) (1u << (m))
 static const struct { const char *name; unsigned maps; } colour_kinds[] = {
@@ -577,6 +659,7 @@ int ndt_render_frame(scene *scn, const ndt_frame_request *rq, ndt_frame *f)
         fprintf(stderr, "ndt_render_frame: exr_features are channels of the OpenEXR file: colour (%s) has none\n", colour_kinds[rq->colour].name);
         return 0;
     }
+    if (rq->denoise_iterations != 0 && denoise_refused(rq)) return 0;
     /* 1. the scene: flattened, uploaded to every context of the thread (the pthread fan-out of ndt.c:949-975 is the GPU's job now;
      * `threads` fits the scene's bounding spheres in parallel) */
     if (timing) clock_gettime(CLOCK_MONOTONIC, &ts0);
@@ -605,7 +688,8 @@ int ndt_render_frame(scene *scn, const ndt_frame_request *rq, ndt_frame *f)
             p.aa_depth = rq->aa_depth;
         }
         /* 2. and 3. colour and map in the forms asked for: one device call makes both, so the routine is chosen by the pair */
-        if (rq->colour == NDT_COLOUR_EXR) ok = frame_exr(&p, rq, f, fb.fs.dims);
+        if (rq->denoise_iterations != 0) ok = frame_denoised(&p, rq, f);
+        else if (rq->colour == NDT_COLOUR_EXR) ok = frame_exr(&p, rq, f, fb.fs.dims);
         else if (rq->colour == NDT_COLOUR_APNG) ok = frame_apng(&p, rq, f);
         else if (rq->colour == NDT_COLOUR_PNG16) ok = frame_png16(&p, rq, f);
         else if (map8) ok = frame_beside_map8(&p, rq, f);
@@ -650,6 +734,8 @@ int ndt_render_frame(scene *scn, const ndt_frame_request *rq, ndt_frame *f)
             snprintf(what, sizeof(what), "image to host %.2f ms", NDT_MS(ts2, ts3));
         fprintf(stderr, "ndt_render_image: bounds + kd-tree + flatten %.2f ms (%s), upload %.2f ms, render + %s\n", NDT_MS(ts0, ts1), share,
                 NDT_MS(ts1, ts2), what);
+        if (rq->denoise_iterations != 0 && ok)
+            fprintf(stderr, "ndt_render_image: behind the render, the denoiser's %d iterations on the GPU %.2f ms\n", rq->denoise_iterations, f->denoise_ms);
         if (rq->ssaa != 1 && ok)
             fprintf(stderr, "ndt_render_image: of the render, supersampling %dx%d: the folds on the GPU %.2f ms\n", rq->ssaa, rq->ssaa, f->ssaa_ms);
     }
