@@ -707,6 +707,86 @@ int ndt_hip_render_denoised_exr(ndt_hip_ctx *ctx, const ndt_render_params *p, co
 int ndt_hip_denoise_launches(ndt_hip_ctx *ctx);
 double ndt_hip_denoise_ms(ndt_hip_ctx *ctx);
 
+/* Ambient occlusion of a frame on the device (`ndt_hip --ao`): how open the surface a pixel shows is to its surroundings, in all N
+ * coordinates -- geometry only, from the planes of ndt_hip_render_features.  One stage between the render and the sink, as the
+ * denoiser is.  Inputs, of the rows `p` selects: id = [rows * width] int32; position, normal, ray_v = [dims][rows * width] doubles, the
+ * feature planes of the deterministic frame (samples == 1).  Output: ao = [rows * width] doubles in 0 .. 1, 1.0 = open.
+ * For pixel p = (row j of the image, column i) with id[p] != 0, every sum over the components k = 0 .. dims - 1 in ascending order,
+ * one operation at a time, starting from 0.0:
+ *     len = sqrt(sum normal[k][p]^2).  !(len > 0) or len not finite: ao[p] = 1.0, and the pixel sends no rays.
+ *     n'_k = normal[k][p] / len, every component negated when sum n'_k * ray_v[k][p] > 0: the hemisphere faces the viewer.
+ *     origin = position[.][p] itself, as a reflection ray's is (ndt.c:398-402); the intersectors reject t <= EPSILON themselves.
+ * Sample s = 0 .. samples - 1 has its own counter-based stream (ndt_device.hpp: ndt_rng_mix is splitmix64's finaliser):
+ *     key = ndt_rng_mix(ndt_rng_mix((j * width + i) * 0x100000001b3 + s) ^ 0x616f2d72617973 ^ ndt_rng_mix(seed)),
+ *     u_m = ndt_rng_uniform(key, m) = (ndt_rng_mix(key + m) >> 11) * 2^-53,   m = 0 .. 2 * ceil(dims / 2) - 1
+ * -- of the image pixel, not the shard's; independent of sharding, of batching and of `samples`: sample s of a call is sample s of
+ * every call with more; the constant keeps the streams apart from those of samples > 1.  The direction is uniform over the hemisphere:
+ *     pair m: r = sqrt(-2.0 * log(1.0 - u_2m)), a = (2.0 * M_PI) * u_2m+1, g_2m = r * cos(a), g_2m+1 = r * sin(a)  (Box-Muller; the
+ *     last of an odd dims is not used);   d_k = g_k / sqrt(sum g_k^2);   c = sum d_k * n'_k;   c < 0: d = -d, c = -c.
+ * log, cos and sin are the device's, so a restatement elsewhere need not give their last bits: every entry can return the directions
+ * it used ([samples][dims][rows * width] doubles, zero where the pixel sends no rays), and everything behind them is defined to the bit:
+ *     radius == 0: the ray (origin, d) is occluded <=> ndt_hip_trace_rays answers an object >= 0 for it with dist_limit 0
+ *     radius > 0:  ... <=> its closest hit (dist_limit -1) exists and v_dist(hit, origin) < radius, v_dist = the root of (the even
+ *                  components' sum of squared differences + the odd ones') as vectNd_dot sums (vectNd.h:215-227)
+ *     den = sum_s c_s;  num = sum_s (occluded_s ? 0 : c_s), both over s ascending;   ao[p] = den > 0 ? num / den : 1.0
+ * and ao[p] = 1.0 where id[p] == 0.  The cosine-weighted share of the hemisphere that is open.
+ *   ndt_hip_ao_device            the pass alone: d_planes' id, position, normal and ray_v (device memory, aligned to their elements)
+ *                                of the rows `p` selects of the uploaded scene, into d_ao and, unless NULL, d_dirs (device, 8 bytes).
+ *                                Per batch of samples 3 kernel launches (rays, trace, fold), 4 with a radius (hit points); synchronous
+ *   ndt_hip_render_ao_device     the feature pass of a copy of `p` whose samples is 1, then that pass
+ *   ndt_hip_render_ao            the same into host memory (dirs may be NULL)
+ *   ndt_hip_ao_apply_device      out.rgb = in.rgb * ((1.0 - strength) + strength * ao), alpha copied; rows x width x 4 doubles aligned
+ *                                to 16 bytes, out may be in.  strength 0 leaves the image bit for bit.  One launch; no scene needed
+ *   ndt_hip_render_ao_shaded_device   ndt_hip_render_device for `p` as given (any samples), the pass of its deterministic twin, the
+ *                                apply with ap->strength, into d_rgba (16 bytes); d_ao, unless NULL, receives the plane
+ *   ndt_hip_render_ao_shaded     the same into host memory (ao may be NULL);  _rgba8 / _png / _jpeg: the same doubles through
+ *                                ndt_hip_quantize_device and the encoders of the 8-bit files
+ *   ndt_hip_exr_ao_bound         ndt_hip_exr_features_bound for a file that also carries the channel AO; the mask may be 0
+ *   ndt_hip_encode_exr_ao_device ndt_hip_encode_exr_features_device with the FLOAT channel AO, (float) of the plane d_ao: the channel
+ *                                list in the format's byte-wise order is A AO B G N.* P.* R Z id.  The mask may be 0
+ *   ndt_hip_render_exr_ao        ndt_hip_render_depth_device, the pass, the colour multiplied as by the apply (strength 0: the colour,
+ *                                Z and feature channels hold the bits of the file without AO), the feature planes, that encoder
+ *   ndt_hip_ao_launches / ndt_hip_ao_ms   kernel launches of the context's last call (the feature pass's 4 and the apply's 1 included
+ *                                where they run), and the device time of its pass
+ * Option "ao_batch" (ndt_hip_set_option) sets how many samples share a trace launch; the plane does not depend on it.
+ * ap == NULL: the defaults (a first guess, not measured against anything).  NDT_E_UNSUPPORTED with the cause in the error text, before
+ * any device work and with nothing written: recursive_aa, NDT_STEREO_ANAGLYPH, NDT_STEREO_HIDEF; samples > 1 for ndt_hip_ao_device,
+ * whose planes are one deterministic frame's (every other entry makes them itself).  NDT_E_INVALID: parameters out of range, a NaN, NULL or misaligned
+ * pointers, dims outside 3 .. 12.  NDT_E_STATE: no scene.  Row shards and NDT_STEREO_SIDE_SIDE / OVER_UNDER work: a pixel needs no
+ * neighbour.  The device buffers belong to the context, only grow and are reused.  None falls back. */
+typedef struct ndt_ao_params {
+    int32_t  samples;               /* 1 .. 256; default 16 */
+    int32_t  reserved;              /* must be 0 */
+    double   radius;                /* finite, >= 0; 0 (default): no limit, any hit occludes */
+    uint64_t seed;                  /* default 0 */
+    double   strength;              /* 0 .. 1; default 1 */
+} ndt_ao_params;
+int ndt_hip_ao_device(ndt_hip_ctx *ctx, const ndt_render_params *p, const ndt_feature_planes *d_planes, const ndt_ao_params *ap, void *d_ao,
+                      void *d_dirs);
+int ndt_hip_render_ao_device(ndt_hip_ctx *ctx, const ndt_render_params *p, const ndt_ao_params *ap, void *d_ao, void *d_dirs,
+                             ndt_render_stats *stats);
+int ndt_hip_render_ao(ndt_hip_ctx *ctx, const ndt_render_params *p, const ndt_ao_params *ap, double *ao, double *dirs,
+                      ndt_render_stats *stats);
+int ndt_hip_ao_apply_device(ndt_hip_ctx *ctx, const void *d_rgba_in, const void *d_ao, int64_t n_pixels, double strength, void *d_rgba_out);
+int ndt_hip_render_ao_shaded_device(ndt_hip_ctx *ctx, const ndt_render_params *p, const ndt_ao_params *ap, void *d_rgba, void *d_ao,
+                                    ndt_render_stats *stats);
+int ndt_hip_render_ao_shaded(ndt_hip_ctx *ctx, const ndt_render_params *p, const ndt_ao_params *ap, double *rgba, double *ao,
+                             ndt_render_stats *stats);
+int ndt_hip_render_ao_shaded_rgba8(ndt_hip_ctx *ctx, const ndt_render_params *p, const ndt_ao_params *ap, uint8_t *rgba8,
+                                   ndt_render_stats *stats);
+int ndt_hip_render_ao_shaded_png(ndt_hip_ctx *ctx, const ndt_render_params *p, const ndt_ao_params *ap, uint8_t *png, int64_t cap,
+                                 ndt_png_stats *stats, ndt_render_stats *render_stats);
+int ndt_hip_render_ao_shaded_jpeg(ndt_hip_ctx *ctx, const ndt_render_params *p, const ndt_ao_params *ap, const ndt_jpeg_params *jp,
+                                  uint8_t *jpg, int64_t cap, ndt_jpeg_stats *stats, ndt_render_stats *render_stats);
+int64_t ndt_hip_exr_ao_bound(int32_t width, int32_t rows, const ndt_exr_params *ep, int32_t with_depth, int32_t dims, int32_t features);
+int ndt_hip_encode_exr_ao_device(ndt_hip_ctx *ctx, const void *d_rgba, const void *d_depth, const ndt_feature_planes *d_planes,
+                                 const void *d_ao, int32_t dims, int32_t features, int32_t width, int32_t rows, const ndt_exr_params *ep,
+                                 uint8_t *out, int64_t cap, ndt_exr_stats *stats);
+int ndt_hip_render_exr_ao(ndt_hip_ctx *ctx, const ndt_render_params *p, const ndt_exr_params *ep, int32_t with_depth, int32_t features,
+                          const ndt_ao_params *ap, uint8_t *out, int64_t cap, ndt_exr_stats *stats, ndt_render_stats *render_stats);
+int ndt_hip_ao_launches(ndt_hip_ctx *ctx);
+double ndt_hip_ao_ms(ndt_hip_ctx *ctx);
+
 /* ONE frame over several contexts -- one per GPU of the node, or several on one GPU -- called from one host thread.
  * The rows `p` selects are dealt cyclically to the contexts exactly as the reference deals rows to MPI ranks in
  * MPI_MODE_ROW (ndt.c:812-820: row_start = rank, row_step = size): context k renders rows
@@ -768,6 +848,8 @@ int ndt_hip_multi_path_taken(ndt_hip_ctx *ctx);
  *                     list entries a window (ambient ones included).  A scene of more than one window renders every pass
  *                     with the per-bounce kernels, whatever "pipeline" says, and pays a shading and a trace launch per
  *                     bounce and extra window.  Neutral: it exists so that tests can run the window path on any scene
+ *   "ao_batch"        ambient occlusion (ndt_hip_render_ao*): samples that share one trace launch.  0 (default) auto: as many as fit
+ *                     2^23 workspace slots, at least one; n in 1 .. 256: exactly n (the last launch takes what is left).  Same plane
  *   "debug_levels"    profiled renders print the bounces and the duration of every trace launch
  *   "exit_probe" / "shade_probe" / "stream_probe"   profiled renders log the life of every wavefront of the trace
  *                     launches / of the k-th shade launch (value k + 1) / of the frame kernel

@@ -61,7 +61,7 @@ extern "C" int ndt_hip_create(int device, ndt_hip_ctx **out)
     ctx->device = device;
     {
         // the environment is read here, once: nothing on the render or upload path looks at it
-        static const char *const names[] = { "stream_below", "stream_below_list", "hull_box", "face_box", "face_tree", "face_groups", "item_sets", "gate_prepass", "gate_prepass_below", "item_boxes", "leaf_history", "leaf_scan", "leaf_scan_group", "multi_path", "sample_seed", "stream_fused", "fuse_primaries", "light_overlap", "early_pixels", "light_window", "debug_levels",
+        static const char *const names[] = { "stream_below", "stream_below_list", "hull_box", "face_box", "face_tree", "face_groups", "item_sets", "gate_prepass", "gate_prepass_below", "item_boxes", "leaf_history", "leaf_scan", "leaf_scan_group", "multi_path", "sample_seed", "stream_fused", "fuse_primaries", "light_overlap", "early_pixels", "light_window", "ao_batch", "debug_levels",
                                              "exit_probe", "shade_probe", "stream_probe", "test_small_pool" };
         const char *pl = getenv("NDT_HIP_PIPELINE");
         if (pl) (void)ndt_hip_set_option(ctx, "pipeline", !strcmp(pl, "levels") ? 1 : !strcmp(pl, "stream") ? 2 : 0);
@@ -134,6 +134,7 @@ extern "C" int ndt_hip_destroy(ndt_hip_ctx *ctx)
     free_depth(ctx);
     free_ssaa(ctx);
     free_denoise(ctx);
+    free_ao(ctx);
     ctx->d_eyes.release();
     if (ctx->h_counters) (void)hipHostFree(ctx->h_counters);
     if (ctx->h_levels) (void)hipHostFree(ctx->h_levels);
@@ -182,6 +183,10 @@ extern "C" int ndt_hip_set_option(ndt_hip_ctx *ctx, const char *name, int64_t va
         if (value < 0 || value > 64) return fail(NDT_E_INVALID, "light_window %lld (0 auto, 1 .. 64)", (long long)value);
         ctx->light_window = (int)value;
         if (ctx->have_scene) light_windows(ctx);
+    }
+    else if (!strcmp(name, "ao_batch")) {
+        if (value < 0 || value > 256) return fail(NDT_E_INVALID, "ao_batch %lld (0 auto, 1 .. 256 samples a trace launch)", (long long)value);
+        ctx->ao_batch = (int)value;
     }
     else if (!strcmp(name, "debug_levels")) ctx->debug_levels = on;
     else if (!strcmp(name, "exit_probe")) ctx->exit_probe = on;

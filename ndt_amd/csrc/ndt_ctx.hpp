@@ -23,6 +23,8 @@
 //   ndt_ssaa.hip     ndt_hip_ssaa_fold_device / ndt_hip_render_ssaa*: K x K supersampling, K ordinary renders folded on the device
 //   ndt_denoise.hip  ndt_hip_denoise_device / ndt_hip_render_denoised*: the edge-avoiding a-trous filter over the double framebuffer,
 //                    guided by the feature planes; kernel, launcher and C ABI
+//   ndt_ao.hip       ndt_hip_ao_device / ndt_hip_render_ao* / ndt_hip_render_exr_ao: ambient occlusion from the feature planes -- the
+//                    sample rays, the trace kernel as it is, the fold into a plane, the plane applied to a frame; kernels and C ABI
 //   ndt_buffer.hpp   DeviceBuffer: the grow-only device buffers of the context and of its sinks, their one grow and free path
 #pragma once
 #include <hip/hip_runtime.h>
@@ -150,6 +152,18 @@ struct DenoiseState {
     double ms = 0.0;                // their summed device time
 };
 
+// ndt_hip_ao_device, ndt_hip_render_ao*, ndt_hip_render_exr_ao (ndt_ao.hip): grow-only device buffers, reused by the next frame
+struct AoState {
+    DeviceBuffer d_cos;             // the cosine of every slot of a batch: per x n_primary doubles
+    DeviceBuffer d_acc;             // num and den of every pixel slot between the batches of a call: 2 x n_primary doubles
+    DeviceBuffer d_plane, d_dirs;   // the plane and the directions of the calls that deliver to host memory or as a file
+    DeviceBuffer d_frame, d_rgba8;  // ndt_hip_render_ao_shaded*: the frame in doubles, and its 8-bit image
+    hipEvent_t ev[2] = {};          // around the pass
+    bool timed = false;             // ... recorded by the last call
+    int launches = 0;               // kernel launches of the last call
+    double ms = 0.0;                // device time of its pass
+};
+
 struct ndt_hip_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -247,6 +261,8 @@ struct ndt_hip_ctx {
     DepthState depth;               // ndt_hip_depth_rgba8_device, ndt_hip_render_*_depth
     SsaaState ssaa;                 // ndt_hip_render_ssaa*
     DenoiseState denoise;           // ndt_hip_denoise_device, ndt_hip_render_denoised*
+    AoState ao;                     // ndt_hip_ao_device, ndt_hip_render_ao*, ndt_hip_render_exr_ao
+    int ao_batch = 0;               // option "ao_batch": AO samples a trace launch; 0 auto (ndt_ao.hip:AO_AUTO_SLOTS)
     DeviceBuffer d_out;             // staging of a frame in doubles (and its map behind it) for the calls that deliver to host memory
     DeviceBuffer d_shard;           // ndt_hip_render_multi: this context's rows before they are pushed into the frame
     DeviceBuffer d_image;           // ndt_hip_render_multi (host output): the assembled frame on the first context's device
@@ -346,6 +362,12 @@ void free_jpeg(ndt_hip_ctx *ctx);
 // ndt_exr.hip
 void free_exr(ndt_hip_ctx *ctx);
 
+// The file of ndt_hip_encode_exr_features_device with the FLOAT channel AO from the rows x width doubles at d_ao (device memory)
+// between A and B; features may be 0 (d_planes is then not read)
+int exr_encode_ao_device(ndt_hip_ctx *ctx, const char *who, const void *d_rgba, const void *d_depth, const ndt_feature_planes *d_planes,
+                         const void *d_ao, int dims, int features, int32_t width, int32_t rows, const ndt_exr_params *ep, uint8_t *out,
+                         int64_t cap, ndt_exr_stats *stats);
+
 // ndt_features.hip
 void free_features(ndt_hip_ctx *ctx);
 // What the feature entries refuse, under the name `who`, before any device work: NULL arguments, no scene, bad geometry, and the
@@ -368,6 +390,9 @@ int render_ssaa_rgba8_own(ndt_hip_ctx *ctx, const char *who, const ndt_render_pa
 
 // ndt_denoise.hip
 void free_denoise(ndt_hip_ctx *ctx);
+
+// ndt_ao.hip
+void free_ao(ndt_hip_ctx *ctx);
 
 // ndt_aa.hip / ndt_sampled.hip
 int render_antialiased(ndt_hip_ctx *ctx, const ndt_render_params *p, void *d_rgba, ndt_render_stats &total, void *d_depth = nullptr);

@@ -34,7 +34,7 @@ namespace {
 
 constexpr int EXR_LINES = 16;           // scanlines a block of ZIP compression
 constexpr int EXR_UINT = 0, EXR_HALF = 1, EXR_FLOAT = 2;        // the format's pixelType
-constexpr int EXR_MAX_CHANNELS = 4 + 1 + 1 + 2 * NDT_MAX_DIMS;  // A B G R, Z, id, N.* and P.*
+constexpr int EXR_MAX_CHANNELS = 4 + 1 + 1 + 1 + 2 * NDT_MAX_DIMS;  // A B G R, AO, Z, id, N.* and P.*
 constexpr int EXR_ALL_FEATURES = NDT_FEATURE_ID | NDT_FEATURE_POSITION | NDT_FEATURE_NORMAL;
 
 // how a source element becomes a sample: a double to binary16, a double to float, an int32's bits as they are
@@ -415,9 +415,10 @@ bool layout_of(int32_t width, int32_t rows, int pixel_type, bool with_depth, Exr
 }
 
 // The channel table of a file with the feature groups of `features`, in the byte-wise order of the names: A B G, N.00 .., P.00 ..,
-// R, Z, id.  Indices have two digits, so that order is the numeric one.  planes may be nullptr (the sizes only).
+// R, Z, id.  Indices have two digits, so that order is the numeric one.  planes may be nullptr (the sizes only).  with_ao: the FLOAT
+// channel AO of the plane d_ao (ndt_ao.hip) between A and B.
 void channel_table(ExrChannels &C, int pixel_type, const void *d_rgba, const void *d_depth, bool with_depth, const ndt_feature_planes *planes,
-                   int dims, int features, long long pixels)
+                   int dims, int features, long long pixels, bool with_ao = false, const void *d_ao = nullptr)
 {
     C = ExrChannels{};
     auto add = [&C](const char *name, int index, const void *src, int stride, bool is_int, int conv) {
@@ -437,6 +438,7 @@ void channel_table(ExrChannels &C, int pixel_type, const void *d_rgba, const voi
     const int colour = pixel_type == EXR_HALF ? EXR_TO_HALF : EXR_TO_FLOAT;
     const double *rgba = (const double *)d_rgba;
     add("A", -1, rgba ? rgba + 3 : nullptr, 4, false, colour);      // the framebuffer is R G B A
+    if (with_ao) add("AO", -1, d_ao, 1, false, EXR_TO_FLOAT);
     add("B", -1, rgba ? rgba + 2 : nullptr, 4, false, colour);
     add("G", -1, rgba ? rgba + 1 : nullptr, 4, false, colour);
     if (features & NDT_FEATURE_NORMAL)
@@ -473,10 +475,11 @@ void launch_all(hipStream_t s, const ExrLayout &L, SRC src, const ExrChannels *d
 }
 
 // The file of the width x rows doubles at d_rgba (and the map at d_depth, or nullptr) -- the context's device memory -- in host
-// memory; `who` names the entry point in errors.  features != 0: with the feature channels of that mask from d_planes.
+// memory; `who` names the entry point in errors.  features != 0: with the feature channels of that mask from d_planes.  d_ao: with
+// the channel AO of that plane (features may then be 0).
 int encode_device(ndt_hip_ctx *ctx, const char *who, const void *d_rgba, const void *d_depth, int32_t width, int32_t rows,
                   const ndt_exr_params *ep, uint8_t *out, int64_t cap, ndt_exr_stats *stats, const ndt_feature_planes *d_planes = nullptr,
-                  int dims = 0, int features = 0)
+                  int dims = 0, int features = 0, const void *d_ao = nullptr)
 {
     if (stats) *stats = ndt_exr_stats{};
     if (!ctx || !d_rgba || !out) return fail(NDT_E_INVALID, "%s: NULL argument", who);
@@ -486,6 +489,9 @@ int encode_device(ndt_hip_ctx *ctx, const char *who, const void *d_rgba, const v
     if (cap < 0) return fail(NDT_E_INVALID, "%s: cap %lld", who, (long long)cap);
     if ((((uintptr_t)d_rgba | (uintptr_t)d_depth) & 7u) != 0) return fail(NDT_E_INVALID, "%s: the doubles are not aligned to 8 bytes", who);
     ExrChannels table;
+    const bool listed = features != 0 || d_ao != nullptr;
+    if (((uintptr_t)d_ao & 7u) != 0) return fail(NDT_E_INVALID, "%s: the AO plane is not aligned to 8 bytes", who);
+    if (d_ao && !features) channel_table(table, pixel_type, d_rgba, d_depth, d_depth != nullptr, nullptr, dims, 0, (long long)width * rows, true, d_ao);
     if (features) {
         if (!features_ok(dims, features))
             return fail(NDT_E_INVALID, "%s: %d dimensions, feature mask %d: 3 .. 12, and a mask of id 1, position 2, normal 4", who, dims, features);
@@ -494,10 +500,10 @@ int encode_device(ndt_hip_ctx *ctx, const char *who, const void *d_rgba, const v
             return fail(NDT_E_INVALID, "%s: a plane of feature mask %d is NULL", who, features);
         if (((uintptr_t)d_planes->id & 3u) != 0 || (((uintptr_t)d_planes->position | (uintptr_t)d_planes->normal) & 7u) != 0)
             return fail(NDT_E_INVALID, "%s: a feature plane is not aligned to its elements", who);
-        channel_table(table, pixel_type, d_rgba, d_depth, d_depth != nullptr, d_planes, dims, features, (long long)width * rows);
+        channel_table(table, pixel_type, d_rgba, d_depth, d_depth != nullptr, d_planes, dims, features, (long long)width * rows, d_ao != nullptr, d_ao);
     }
     ExrLayout L;
-    if (!layout_of(width, rows, pixel_type, d_depth != nullptr, L, features ? &table : nullptr))
+    if (!layout_of(width, rows, pixel_type, d_depth != nullptr, L, listed ? &table : nullptr))
         return fail(NDT_E_INVALID, "%s: the samples of a %d x %d image exceed 2^31 - 1 bytes", who, width, rows);
     const auto t0 = std::chrono::steady_clock::now();
     HIP_TRY(hipSetDevice(ctx->device));
@@ -513,7 +519,7 @@ int encode_device(ndt_hip_ctx *ctx, const char *who, const void *d_rgba, const v
     if ((rc = ex.d_file.reserve((size_t)bound, s, who))) return rc;
     if ((rc = ex.d_info.reserve(sizeof(ExrInfo), s, who))) return rc;
     if (!ex.h_info) HIP_TRY(hipHostMalloc(&ex.h_info, sizeof(ExrInfo), hipHostMallocDefault));
-    if (features) {
+    if (listed) {
         // (the table leaves this frame before the call goes on: it is copied from pageable memory)
         if ((rc = ex.d_channels.reserve(sizeof(ExrChannels), s, who))) return rc;
         HIP_TRY(hipMemcpyAsync(ex.d_channels.p, &table, sizeof(ExrChannels), hipMemcpyHostToDevice, s));
@@ -670,6 +676,41 @@ extern "C" int64_t ndt_hip_exr_features_bound(int32_t width, int32_t rows, const
     channel_table(table, pixel_type, nullptr, nullptr, with_depth != 0, nullptr, dims, features, 0);
     if (!layout_of(width, rows, pixel_type, with_depth != 0, L, &table)) return NDT_E_INVALID;
     return file_bound(L);
+}
+
+// what the AO entries take: a mask of the three groups, or none
+static bool ao_features_ok(int dims, int features)
+{
+    return dims >= NDT_MIN_DIMS && dims <= NDT_MAX_DIMS && features >= 0 && (features & ~EXR_ALL_FEATURES) == 0;
+}
+
+extern "C" int64_t ndt_hip_exr_ao_bound(int32_t width, int32_t rows, const ndt_exr_params *ep, int32_t with_depth, int32_t dims, int32_t features)
+{
+    const int pixel_type = pixel_type_of(ep);
+    if (pixel_type < 0 || !ao_features_ok(dims, features)) return NDT_E_INVALID;
+    ExrChannels table;
+    ExrLayout L;
+    channel_table(table, pixel_type, nullptr, nullptr, with_depth != 0, nullptr, dims, features, 0, true, nullptr);
+    if (!layout_of(width, rows, pixel_type, with_depth != 0, L, &table)) return NDT_E_INVALID;
+    return file_bound(L);
+}
+
+int ndt_impl::exr_encode_ao_device(ndt_hip_ctx *ctx, const char *who, const void *d_rgba, const void *d_depth, const ndt_feature_planes *d_planes,
+                                   const void *d_ao, int dims, int features, int32_t width, int32_t rows, const ndt_exr_params *ep, uint8_t *out,
+                                   int64_t cap, ndt_exr_stats *stats)
+{
+    if (stats) *stats = ndt_exr_stats{};
+    if (!d_ao) return fail(NDT_E_INVALID, "%s: NULL argument", who);
+    if (!ao_features_ok(dims, features))
+        return fail(NDT_E_INVALID, "%s: %d dimensions, feature mask %d: 3 .. 12, and a mask of id 1, position 2, normal 4, or 0", who, dims, features);
+    return encode_device(ctx, who, d_rgba, d_depth, width, rows, ep, out, cap, stats, d_planes, dims, features, d_ao);
+}
+
+extern "C" int ndt_hip_encode_exr_ao_device(ndt_hip_ctx *ctx, const void *d_rgba, const void *d_depth, const ndt_feature_planes *d_planes,
+                                            const void *d_ao, int32_t dims, int32_t features, int32_t width, int32_t rows,
+                                            const ndt_exr_params *ep, uint8_t *out, int64_t cap, ndt_exr_stats *stats)
+{
+    return exr_encode_ao_device(ctx, "ndt_hip_encode_exr_ao_device", d_rgba, d_depth, d_planes, d_ao, dims, features, width, rows, ep, out, cap, stats);
 }
 
 extern "C" int ndt_hip_encode_exr_features_device(ndt_hip_ctx *ctx, const void *d_rgba, const void *d_depth, const ndt_feature_planes *d_planes,

@@ -37,6 +37,9 @@ API_SYMBOLS = [
     "ndt_hip_encode_exr_features_device", "ndt_hip_render_exr_features", "ndt_hip_render_ssaa_exr_features",
     "ndt_hip_denoise_device", "ndt_hip_render_denoised_device", "ndt_hip_render_denoised", "ndt_hip_render_denoised_rgba8",
     "ndt_hip_render_denoised_png", "ndt_hip_render_denoised_jpeg", "ndt_hip_render_denoised_exr", "ndt_hip_denoise_launches", "ndt_hip_denoise_ms",
+    "ndt_hip_ao_device", "ndt_hip_render_ao_device", "ndt_hip_render_ao", "ndt_hip_ao_apply_device", "ndt_hip_render_ao_shaded_device",
+    "ndt_hip_render_ao_shaded", "ndt_hip_render_ao_shaded_rgba8", "ndt_hip_render_ao_shaded_png", "ndt_hip_render_ao_shaded_jpeg",
+    "ndt_hip_exr_ao_bound", "ndt_hip_encode_exr_ao_device", "ndt_hip_render_exr_ao", "ndt_hip_ao_launches", "ndt_hip_ao_ms",
 ]
 
 IMAGE_F64, IMAGE_RGBA8 = 0, 1      # enum ndt_image_format
@@ -194,6 +197,26 @@ def load_library():
         lib.ndt_hip_denoise_launches.argtypes = [C.c_void_p]
         lib.ndt_hip_denoise_ms.argtypes = [C.c_void_p]
         lib.ndt_hip_denoise_ms.restype = C.c_double
+    if hasattr(lib, "ndt_hip_ao_device"):           # (likewise)
+        lib.ndt_hip_ao_device.argtypes = [C.c_void_p] * 6
+        lib.ndt_hip_render_ao_device.argtypes = [C.c_void_p] * 6
+        lib.ndt_hip_render_ao.argtypes = [C.c_void_p] * 6
+        lib.ndt_hip_ao_apply_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_double, C.c_void_p]
+        lib.ndt_hip_render_ao_shaded_device.argtypes = [C.c_void_p] * 6
+        lib.ndt_hip_render_ao_shaded.argtypes = [C.c_void_p] * 6
+        lib.ndt_hip_render_ao_shaded_rgba8.argtypes = [C.c_void_p] * 5
+        lib.ndt_hip_render_ao_shaded_png.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
+        lib.ndt_hip_render_ao_shaded_jpeg.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
+                                                      C.c_void_p]
+        lib.ndt_hip_exr_ao_bound.argtypes = [C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32]
+        lib.ndt_hip_exr_ao_bound.restype = C.c_int64
+        lib.ndt_hip_encode_exr_ao_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
+                                                     C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
+        lib.ndt_hip_render_exr_ao.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64,
+                                              C.c_void_p, C.c_void_p]
+        lib.ndt_hip_ao_launches.argtypes = [C.c_void_p]
+        lib.ndt_hip_ao_ms.argtypes = [C.c_void_p]
+        lib.ndt_hip_ao_ms.restype = C.c_double
     _lib = lib
     return lib
 
@@ -300,6 +323,27 @@ class DenoiseParams(C.Structure):
 def denoise_params(iterations=4, sigma_colour=0.25, sigma_plane=0.25, normal_power_log2=5):
     """The ndt_denoise_params of these values (the defaults are the library's); the library checks their ranges."""
     return DenoiseParams(int(iterations), int(normal_power_log2), float(sigma_colour), float(sigma_plane))
+
+
+class AoParams(C.Structure):
+    """ndt_ao_params: samples 1 .. 256, radius finite and >= 0 (0: no limit), any seed, strength 0 .. 1"""
+    _fields_ = [("samples", C.c_int32), ("reserved", C.c_int32), ("radius", C.c_double), ("seed", C.c_uint64), ("strength", C.c_double)]
+
+
+def ao_params(samples=16, radius=0.0, seed=0, strength=1.0):
+    """The ndt_ao_params of these values (the defaults are the library's); the library checks their ranges."""
+    return AoParams(int(samples), 0, float(radius), int(seed) & 0xffffffffffffffff, float(strength))
+
+
+def exr_ao_bound(width, rows, dims, features=None, pixel="half", depth_map=False):
+    """ndt_hip_exr_ao_bound: exr_features_bound for a file that also carries the channel AO; features may be None (no feature channel)."""
+    ep = exr_params(pixel)
+    n = int(load_library().ndt_hip_exr_ao_bound(int(width), int(rows), C.byref(ep), 1 if depth_map else 0, int(dims),
+                                                feature_mask(features) if features else 0))
+    if n < 0:
+        raise ValueError("no EXR of %d x %d with AO and the features of %d dimensions: a bad size, or samples beyond 2^31 - 1 bytes"
+                         % (width, rows, dims))
+    return n
 
 
 JPEG_SAMPLING = {"420": 0, "444": 1}
@@ -727,14 +771,26 @@ class NdtHip:
                                                        int(width), int(rows), C.byref(ep), out.ctypes.data, cap, C.byref(self.exr_stats)))
         return out[:self.exr_stats.file_bytes].tobytes()
 
-    def render_exr(self, width, height, depth, pixel="half", depth_map=False, features=None, cap=None, **kw):
+    def render_exr(self, width, height, depth, pixel="half", depth_map=False, features=None, cap=None, ao=None, **kw):
         """ndt_hip_render_exr: render() with the device's OpenEXR encoder in place of the download; depth_map=True adds the map as
         the file's Z channel.  features (names of FEATURES, e.g. ("id", "position", "normal")): ndt_hip_render_exr_features, the
         primary hit of every pixel as the channels id, P.*, N.* of the file.  Returns (the file's bytes, RenderStats);
-        self.exr_stats keeps the ndt_exr_stats.  The file's height is the row shard's.  cap: room offered (default: the bound)."""
+        self.exr_stats keeps the ndt_exr_stats.  The file's height is the row shard's.  cap: room offered (default: the bound).
+        ao (a dict of ao_params' arguments, or True for the defaults): ndt_hip_render_exr_ao, the file with the channel AO, its colour
+        multiplied by the plane at the dict's strength; features may then be None."""
         p = self.params(width, height, depth, **kw)
         rows = shard_rows(height, p.row_begin, p.row_step)
         ep = exr_params(pixel)
+        if ao is not None and ao is not False:
+            ap = ao_params(**({} if ao is True else dict(ao)))
+            cap = exr_ao_bound(width, rows, self.scene.dims, features, pixel, depth_map) if cap is None else int(cap)
+            out = np.zeros(max(cap, 1), dtype=np.uint8)
+            st = RenderStats()
+            self.exr_stats = ExrStats()
+            self._check(self.lib.ndt_hip_render_exr_ao(self.ctx, C.byref(p), C.byref(ep), 1 if depth_map else 0,
+                                                       feature_mask(features) if features else 0, C.byref(ap), out.ctypes.data, cap,
+                                                       C.byref(self.exr_stats), C.byref(st)))
+            return out[:self.exr_stats.file_bytes].tobytes(), st
         if cap is None:
             cap = exr_features_bound(width, rows, self.scene.dims, features, pixel, depth_map) if features else exr_bound(width, rows, pixel, depth_map)
         out = np.zeros(int(cap), dtype=np.uint8)
@@ -864,6 +920,88 @@ class NdtHip:
                                                              C.byref(self.exr_stats), C.byref(st)))
             return out[:self.exr_stats.file_bytes].tobytes(), st
         raise ValueError("sink %r is none of None, 'device', 'rgba8', 'png', 'jpeg', 'exr'" % (sink,))
+
+    def render_ao(self, width, height, depth, samples=16, radius=0.0, seed=0, dirs=False, frame_samples=1, **kw):
+        """ndt_hip_render_ao: the ambient occlusion of the frame render(**kw) gives -- for every pixel the cosine-weighted share of
+        `samples` rays from its primary hit, over the hemisphere of the N-D normal that faces the viewer, that get away (radius 0) or
+        meet nothing nearer than `radius`.  Returns the (rows, width) float64 plane, 1.0 = open and where nothing shows; with
+        dirs=True (plane, directions), the directions (samples, dims, rows, width) the device used, zero where a pixel sends none.
+        kw: as render()'s (row shards, stereo 1 / 2); `samples` here counts AO rays, the frame's own `-n` is frame_samples (the pass is
+        the deterministic frame's whatever it is)."""
+        p = self.params(width, height, depth, samples=frame_samples, **kw)
+        rows = shard_rows(height, p.row_begin, p.row_step)
+        ap = ao_params(samples, radius, seed)
+        plane = np.zeros((rows, width), dtype=np.float64)
+        used = np.zeros((max(int(samples), 0), self.scene.dims, rows, width), dtype=np.float64) if dirs else None
+        st = RenderStats()
+        self._check(self.lib.ndt_hip_render_ao(self.ctx, C.byref(p), C.byref(ap), plane.ctypes.data, used.ctypes.data if dirs else None,
+                                               C.byref(st)))
+        return (plane, used) if dirs else plane
+
+    def ao_device(self, d_planes, d_ao_ptr, width, height, depth, samples=16, radius=0.0, seed=0, d_dirs_ptr=None, **kw):
+        """ndt_hip_ao_device: the pass alone, from the device planes `d_planes` names (a dict "id" / "position" / "normal" / "ray_v" of
+        raw device pointers: the feature planes of the rows kw selects) into rows * width doubles at `d_ao_ptr` and, unless None,
+        samples * dims * rows * width doubles of directions at `d_dirs_ptr`."""
+        p = self.params(width, height, depth, **kw)
+        ap = ao_params(samples, radius, seed)
+        planes = FeaturePlanes(d_planes.get("id"), d_planes.get("position"), d_planes.get("normal"), None, d_planes.get("ray_v"))
+        self._check(self.lib.ndt_hip_ao_device(self.ctx, C.byref(p), C.byref(planes), C.byref(ap), C.c_void_p(d_ao_ptr),
+                                               C.c_void_p(d_dirs_ptr) if d_dirs_ptr else None))
+
+    def ao_apply_device(self, d_rgba_in_ptr, d_ao_ptr, n_pixels, strength=1.0, d_rgba_out_ptr=None):
+        """ndt_hip_ao_apply_device: rgb * ((1 - strength) + strength * ao) on n_pixels x 4 device doubles, the alpha copied, into
+        `d_rgba_out_ptr` (default: in place)."""
+        out = d_rgba_in_ptr if d_rgba_out_ptr is None else d_rgba_out_ptr
+        self._check(self.lib.ndt_hip_ao_apply_device(self.ctx, C.c_void_p(d_rgba_in_ptr), C.c_void_p(d_ao_ptr), int(n_pixels), float(strength),
+                                                     C.c_void_p(out)))
+
+    def ao_launches(self):
+        """ndt_hip_ao_launches: kernel launches of the context's last ambient-occlusion call."""
+        return int(self.lib.ndt_hip_ao_launches(self.ctx))
+
+    def ao_ms(self):
+        """ndt_hip_ao_ms: device time of its pass."""
+        return float(self.lib.ndt_hip_ao_ms(self.ctx))
+
+    def render_ao_shaded(self, width, height, depth, sink=None, samples=16, radius=0.0, seed=0, strength=1.0, d_rgba_ptr=None, d_ao_ptr=None,
+                         quality=95, sampling="420", cap=None, frame_samples=1, **kw):
+        """ndt_hip_render_ao_shaded*: the frame render(samples=frame_samples, **kw) gives, its colour multiplied by (1 - strength) +
+        strength * ao, the ambient occlusion of `samples` rays a pixel.  sink
+        None: ((rows, width, 4) float64, the (rows, width) plane, RenderStats); "device": left at raw device pointers `d_rgba_ptr`
+        (and the plane at `d_ao_ptr` unless None), returns the stats; "rgba8": the (rows, width, 4) uint8 image; "png" / "jpeg":
+        the file's bytes (self.png_stats / jpeg_stats keep the record) -- each with the stats."""
+        p = self.params(width, height, depth, samples=frame_samples, **kw)
+        rows = shard_rows(height, p.row_begin, p.row_step)
+        ap = ao_params(samples, radius, seed, strength)
+        st = RenderStats()
+        if sink is None:
+            out, plane = np.zeros((rows, width, 4), dtype=np.float64), np.zeros((rows, width), dtype=np.float64)
+            self._check(self.lib.ndt_hip_render_ao_shaded(self.ctx, C.byref(p), C.byref(ap), out.ctypes.data, plane.ctypes.data, C.byref(st)))
+            return out, plane, st
+        if sink == "device":
+            self._check(self.lib.ndt_hip_render_ao_shaded_device(self.ctx, C.byref(p), C.byref(ap), C.c_void_p(d_rgba_ptr),
+                                                                 C.c_void_p(d_ao_ptr) if d_ao_ptr else None, C.byref(st)))
+            return st
+        if sink == "rgba8":
+            out = np.zeros((rows, width, 4), dtype=np.uint8)
+            self._check(self.lib.ndt_hip_render_ao_shaded_rgba8(self.ctx, C.byref(p), C.byref(ap), out.ctypes.data, C.byref(st)))
+            return out, st
+        if sink == "png":
+            cap = png_bound(width, rows) if cap is None else int(cap)
+            out = np.zeros(max(cap, 1), dtype=np.uint8)
+            self.png_stats = PngStats()
+            self._check(self.lib.ndt_hip_render_ao_shaded_png(self.ctx, C.byref(p), C.byref(ap), out.ctypes.data, cap, C.byref(self.png_stats),
+                                                              C.byref(st)))
+            return out[:self.png_stats.png_bytes].tobytes(), st
+        if sink == "jpeg":
+            jp = jpeg_params(quality, sampling)
+            cap = jpeg_bound(width, rows, quality, sampling) if cap is None else int(cap)
+            out = np.zeros(max(cap, 1), dtype=np.uint8)
+            self.jpeg_stats = JpegStats()
+            self._check(self.lib.ndt_hip_render_ao_shaded_jpeg(self.ctx, C.byref(p), C.byref(ap), C.byref(jp), out.ctypes.data, cap,
+                                                               C.byref(self.jpeg_stats), C.byref(st)))
+            return out[:self.jpeg_stats.jpeg_bytes].tobytes(), st
+        raise ValueError("sink %r is none of None, 'device', 'rgba8', 'png', 'jpeg'" % (sink,))
 
     def apng_begin(self, width, rows, n_frames, delay_num=1, delay_den=24, n_plays=0):
         """ndt_hip_apng_begin: opens the context's animated-PNG session: n_frames frames of width x rows pixels are to come, each

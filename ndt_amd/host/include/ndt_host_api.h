@@ -444,6 +444,15 @@ typedef struct ndt_frame_request {
      * stereo mode, ssaa above 1, a map, exr_features, a 16-bit or animated PNG and a frame spread over several contexts */
     int denoise_iterations, denoise_normal_power_log2;
     double denoise_sigma_colour, denoise_sigma_plane;
+    /* `--ao`: the frame's colour multiplied on the GPU, between the render and the sink, by its ambient occlusion (ndt_hip_render_ao_shaded*,
+     * include/ndt_hip.h).  The four are ndt_ao_params'; ao_samples 0 = off (the others are then ignored), 1 .. 256 = on.  With the
+     * colour kinds doubles, 8-bit RGBA, PNG file, JPEG file and OpenEXR file -- which also gets the channel AO, beside exr_features and
+     * the map as its Z channel (ndt_hip_render_exr_ao) --, any samples, stereo side by side or over / under, one context; refused with
+     * a message that names the cause beside aa_depth >= 0, anaglyph and frame packing, ssaa above 1, any other map, a 16-bit or
+     * animated PNG, denoise_iterations and a frame spread over several contexts */
+    int ao_samples;
+    double ao_radius, ao_strength;
+    unsigned long long ao_seed;
 } ndt_frame_request;
 /* Everything that arrives is malloc'ed by the library and freed by ndt_frame_free; what was not asked for stays NULL. */
 typedef struct ndt_frame {
@@ -457,6 +466,8 @@ typedef struct ndt_frame {
     int feature_channels, feature_launches;     /* exr_features: the channels it added to the file, and the kernel launches of the feature pass */
     int denoise_launches;                       /* denoise_iterations: kernel launches of the feature pass and the iterations */
     double denoise_ms;                          /* ... and the iterations' summed device time */
+    int ao_launches;                            /* ao_samples: kernel launches of the feature pass, the occlusion pass and the apply */
+    double ao_ms;                               /* ... and the device time of the occlusion pass */
 } ndt_frame;
 /* Returns 1 like the reference's render_image on success; 0 with a message on stderr otherwise, and then `out` is zeroed: nothing
  * is left to free.  No fallback: without a device, or with a frame the device path refuses (HIDEF frame packing supersampled, ...),
@@ -464,7 +475,7 @@ typedef struct ndt_frame {
  * as 8-bit pixels, and a PNG or JPEG file is then encoded from those on the first context; a frame with a map is rendered by one
  * context whatever was set, and a 16-bit PNG, an OpenEXR file or an animated PNG frame over several contexts is refused.  What the
  * device did is said on stdout: `compressed PNG of B bytes on GPU D in L launches` (`16-bit PNG`, `depth PNG`, `16-bit depth PNG`),
- * `encoded JPEG of ...`, `encoded EXR of ...`, `added K feature channels on GPU D in L launches`, `finished depth map [lo, hi] on GPU D in L launches`, `supersampled KxK on GPU D in L launches`, `denoised in K iterations on GPU D in L launches`, `animated PNG frame
+ * `encoded JPEG of ...`, `encoded EXR of ...`, `added K feature channels on GPU D in L launches`, `finished depth map [lo, hi] on GPU D in L launches`, `supersampled KxK on GPU D in L launches`, `denoised in K iterations on GPU D in L launches`, `ambient occlusion of K samples on GPU D in L launches`, `animated PNG frame
  * K: w x h at x,y (B bytes) on GPU D in L launches`. */
 int ndt_render_frame(scene *scn, const ndt_frame_request *request, ndt_frame *out);
 /* safe on a zeroed or a half-filled frame; leaves it zeroed */

@@ -35,8 +35,16 @@
  * each) and `--denoise-normal E` (0 .. 8, default 5) set its three weights.  With the default stored PNG, --png [--deflate gpu],
  * --jpeg, --exr, --raw, -n, -j, --fit gpu and --kd gpu; not with -a, -m other than mono, -g N > 1, --ssaa above 1, --apng, --png16,
  * -z or --exr-aov.
+ * `--ao [K]` (1 .. 256 samples, default 16) shades every frame by its ambient occlusion, found on the GPU between the render and the
+ * sink: from the N-D hit point of every pixel's primary ray K rays over the hemisphere of the N-D normal there, and the colour
+ * multiplied by the cosine-weighted share of them that get away (ndt_hip_render_ao_shaded*); `--ao-radius R` (finite, 0 or above;
+ * default 0: any hit occludes) lets only hits nearer than R occlude, `--ao-strength S` (0 .. 1, default 1) blends the factor towards
+ * 1, `--ao-seed X` picks another set of sample streams.  With the default PPM, --png [--deflate gpu], --jpeg, --raw and --exr [-z]
+ * [--exr-aov ...], whose file also gets the FLOAT channel AO (ndt_hip_render_exr_ao); with -n, -m s|o, -j, --fit gpu and --kd gpu; not
+ * with -a, -m a|h, -g N > 1, --ssaa above 1, --apng, --png16, --denoise, --depth gpu or -z without --exr.
  * None falls back: what the device path cannot do ends the run. */
 #include <dlfcn.h>
+#include <errno.h>
 #include <getopt.h>
 #include <pthread.h>
 #include <sys/stat.h>
@@ -435,6 +443,10 @@ int main(int argc, char **argv)
     int denoise_normal = 5; /* --denoise-normal E: the normals' dot product squared E times, 0 .. 8 */
     double denoise_colour = 0.25, denoise_plane = 0.25;     /* --denoise-colour X, --denoise-plane X: sigma_colour, sigma_plane, above 0 */
     const char *denoise_tuned = NULL;       /* the first --denoise-* flag given */
+    int ao = 0;             /* --ao [K]: every frame shaded by its ambient occlusion of K samples a pixel, found on the GPU, 1 .. 256 (default 16); 0: off */
+    double ao_radius = 0.0, ao_strength = 1.0;      /* --ao-radius R: finite, 0 (any hit occludes) or above; --ao-strength S: 0 .. 1 */
+    unsigned long long ao_seed = 0;                 /* --ao-seed X */
+    const char *ao_tuned = NULL;            /* the first --ao-* flag given */
     char *objects_dir = "objects";      /* -o: where object plugins are looked for (object.c:119; ndt.c passes "objects") */
     static struct option longopts[] = { { "dump-scene", required_argument, NULL, 1000 },
                                         { "raw", required_argument, NULL, 1001 }, { "png", no_argument, NULL, 1002 },
@@ -448,6 +460,8 @@ int main(int argc, char **argv)
                                         { "exr-pixel", required_argument, NULL, 1016 }, { "exr-aov", required_argument, NULL, 1017 },
                                         { "denoise", optional_argument, NULL, 1018 }, { "denoise-colour", required_argument, NULL, 1019 },
                                         { "denoise-plane", required_argument, NULL, 1020 }, { "denoise-normal", required_argument, NULL, 1021 },
+                                        { "ao", optional_argument, NULL, 1022 }, { "ao-radius", required_argument, NULL, 1023 },
+                                        { "ao-strength", required_argument, NULL, 1024 }, { "ao-seed", required_argument, NULL, 1025 },
                                         { NULL, 0, NULL, 0 } };
     int ch;
     while ((ch = getopt_long(argc, argv, "a:d:g:r:f:j:l:m:3:n:ps:t:u:o:zh", longopts, NULL)) != -1) {
@@ -623,15 +637,95 @@ int main(int argc, char **argv)
             if (!denoise_tuned) denoise_tuned = "--denoise-normal";
             break;
         }
+        case 1022: {
+            /* --ao, --ao=K or --ao K: a following word that starts with a digit is the count */
+            const char *arg = optarg;
+            if (!arg && optind < argc && argv[optind][0] >= '0' && argv[optind][0] <= '9') arg = argv[optind++];
+            ao = 16;
+            if (arg) {
+                char *end = NULL;
+                const long k = strtol(arg, &end, 10);
+                if (end == arg || *end || k < 1 || k > 256) {
+                    fprintf(stderr, "%s: --ao takes 1 .. 256 samples, not '%s'\n", argv[0], arg);
+                    return 1;
+                }
+                ao = (int)k;
+            }
+            break;
+        }
+        case 1023:
+        case 1024: {
+            char *end = NULL;
+            const double x = strtod(optarg, &end);
+            if (end == optarg || *end || !(x >= 0) || !isfinite(x) || (ch == 1024 && x > 1)) {
+                if (ch == 1023) fprintf(stderr, "%s: --ao-radius takes a finite number, 0 or above, not '%s'\n", argv[0], optarg);
+                else fprintf(stderr, "%s: --ao-strength takes 0 .. 1, not '%s'\n", argv[0], optarg);
+                return 1;
+            }
+            if (ch == 1023) ao_radius = x;
+            else ao_strength = x;
+            if (!ao_tuned) ao_tuned = ch == 1023 ? "--ao-radius" : "--ao-strength";
+            break;
+        }
+        case 1025: {
+            char *end = NULL;
+            errno = 0;
+            ao_seed = strtoull(optarg, &end, 0);
+            if (end == optarg || *end || errno || optarg[0] == '-') {
+                fprintf(stderr, "%s: --ao-seed takes an unsigned 64-bit number, not '%s'\n", argv[0], optarg);
+                return 1;
+            }
+            if (!ao_tuned) ao_tuned = "--ao-seed";
+            break;
+        }
         default:
             fprintf(stderr, "usage: %s -s scene.so|builtin:yaml [-d dims] [-r WxH|1080p|4k] [-f last|first:last[:total]] [-l depth]\n"
                             "          [-a diff,depth] [-n samples] [-m s|o|a|m] [-p] [-z] [-j frames_in_flight] [-g gpus_per_frame] [-u config] [--dump-scene file.ndtscene] [--raw file.f64] [--png [--deflate stored|gpu]] [--jpeg [--jpeg-quality 1..100] [--jpeg-sampling 420|444]] [--fit host|gpu] [--kd host|gpu] [--depth host|gpu [--depth-png]] [--ssaa 1..8] [--png16] [--apng [--apng-fps 1..1000]] [--exr [--exr-pixel half|float] [--exr-aov id,position,normal|all]]\n"
-                            "          [--denoise [1..6] [--denoise-colour X] [--denoise-plane X] [--denoise-normal 0..8]]: every frame denoised on the GPU, with the stored PNG, --png [--deflate gpu], --jpeg, --exr, --raw, -n, -j, --fit gpu, --kd gpu; refused with -a, -m s|o|a|h, -g N > 1, --ssaa above 1, --apng, --png16, -z, --exr-aov\n", argv[0]);
+                            "          [--denoise [1..6] [--denoise-colour X] [--denoise-plane X] [--denoise-normal 0..8]]: every frame denoised on the GPU, with the stored PNG, --png [--deflate gpu], --jpeg, --exr, --raw, -n, -j, --fit gpu, --kd gpu; refused with -a, -m s|o|a|h, -g N > 1, --ssaa above 1, --apng, --png16, -z, --exr-aov\n"
+                            "          [--ao [1..256] [--ao-radius R] [--ao-strength 0..1] [--ao-seed X]]: every frame shaded by its ambient occlusion, found on the GPU, with the PPM, --png [--deflate gpu], --jpeg, --raw, --exr [-z] [--exr-aov ...] (which gets the channel AO), -n, -m s|o, -j, --fit gpu, --kd gpu; refused with -a, -m a|h, -g N > 1, --ssaa above 1, --apng, --png16, --denoise, --depth gpu, -z without --exr\n", argv[0]);
             return ch == 'h' ? 0 : 1;
         }
     }
     if (!scene_path || dims < 3 || width < 1 || height < 1) {
         fprintf(stderr, "%s: need -s scene.so, dims >= 3 and a resolution\n", argv[0]);
+        return 1;
+    }
+    if (ao_tuned && !ao) {
+        fprintf(stderr, "%s: %s sets a parameter of the ambient occlusion: it needs --ao\n", argv[0], ao_tuned);
+        return 1;
+    }
+    if (ao && aa_depth >= 0) {
+        fprintf(stderr, "%s: --ao with -a: an anti-aliased pixel is an average of corner samples, and the occlusion starts from one primary ray's hit: take -n\n", argv[0]);
+        return 1;
+    }
+    if (ao && (stereo == 3 || stereo == 4)) {
+        fprintf(stderr, "%s: --ao with -m %s: %s: take -m s or -m o\n", argv[0], stereo == 3 ? "a" : "h",
+                stereo == 3 ? "an anaglyph pixel has two primary rays, one an eye" : "a frame-packed image has no feature pass");
+        return 1;
+    }
+    if (ao && gpus > 1) {
+        fprintf(stderr, "%s: --ao with -g %d: the stage runs on the context that holds the whole frame; over several it is not built: take -g 1 (or -j)\n", argv[0], gpus);
+        return 1;
+    }
+    if (ao && ssaa > 1) {
+        fprintf(stderr, "%s: --ao with --ssaa %d: the occlusion is the plain frame's, not a supersampled one's: take one\n", argv[0], ssaa);
+        return 1;
+    }
+    if (ao && (apng || png16)) {
+        fprintf(stderr, "%s: --ao with %s: the shaded frame leaves as a PPM, --png, --jpeg, --exr or --raw: take one of those\n", argv[0],
+                apng ? "--apng" : "--png16");
+        return 1;
+    }
+    if (ao && denoise) {
+        fprintf(stderr, "%s: --ao with --denoise: one stage stands between the render and the sink: take one\n", argv[0]);
+        return 1;
+    }
+    if (ao && depth_gpu) {
+        fprintf(stderr, "%s: --ao with --depth gpu: no depth map is finished beside a shaded frame: take --exr -z, whose file carries it as Z\n", argv[0]);
+        return 1;
+    }
+    if (ao && want_depth && !exr) {
+        fprintf(stderr, "%s: --ao with -z: beside a shaded frame the depth map is the Z channel of the OpenEXR file only: it needs --exr\n", argv[0]);
         return 1;
     }
     if (denoise_tuned && !denoise) {
@@ -814,6 +908,7 @@ int main(int argc, char **argv)
     frame_request.exr_features = exr_aov;
     frame_request.denoise_iterations = denoise; frame_request.denoise_normal_power_log2 = denoise_normal;
     frame_request.denoise_sigma_colour = denoise_colour; frame_request.denoise_sigma_plane = denoise_plane;
+    frame_request.ao_samples = ao; frame_request.ao_radius = ao_radius; frame_request.ao_strength = ao_strength; frame_request.ao_seed = ao_seed;
     frame_request.colour = exr ? NDT_COLOUR_EXR : apng ? NDT_COLOUR_APNG : png16 ? NDT_COLOUR_PNG16 : want_f64 ? NDT_COLOUR_F64
                          : file_kind != NDT_COLOUR_F64 ? file_kind : NDT_COLOUR_RGBA8;
     frame_request.map = !want_depth ? NDT_MAP_NONE : exr ? NDT_MAP_EXR_Z : !depth_gpu ? NDT_MAP_F64 : png16 ? NDT_MAP_PNG16 : depth_png ? NDT_MAP_PNG : NDT_MAP_DEPTH8;

@@ -626,6 +626,96 @@ static int frame_denoised(const ndt_render_params *p, const ndt_frame_request *r
     return 1;
 }
 
+/* `--ao`: the frame's colour multiplied on the GPU by its ambient occlusion (ndt_hip_render_ao_shaded*): in doubles, as 8-bit RGBA,
+ * as a PNG or JPEG file made there, or as the OpenEXR file with the channel AO, the feature channels and the map as Z
+ * (ndt_hip_render_exr_ao); one context */
+static ndt_ao_params ao_params_of(const ndt_frame_request *rq)
+{
+    ndt_ao_params ap;
+    memset(&ap, 0, sizeof(ap));
+    ap.samples = rq->ao_samples;
+    ap.radius = rq->ao_radius;
+    ap.seed = rq->ao_seed;
+    ap.strength = rq->ao_strength;
+    return ap;
+}
+
+/* what a frame with ambient occlusion does not go with, by name, before the scene is flattened or a device asked for */
+static int ao_refused(const ndt_frame_request *rq)
+{
+    const char *why = NULL;
+    if (rq->aa_depth >= 0 && rq->aa_diff < 256) why = "recursive anti-aliasing (aa_depth >= 0): its pixels are averages of corner samples";
+    else if (rq->stereo == 3 || rq->stereo == 4) why = "anaglyph or frame-packed stereo: no single primary ray a pixel";
+    else if (rq->ssaa != 1) why = "ssaa above 1: the occlusion is the plain frame's";
+    else if (rq->map != NDT_MAP_NONE && rq->map != NDT_MAP_EXR_Z) why = "a depth map that is not the Z channel of the OpenEXR file";
+    else if (rq->colour == NDT_COLOUR_PNG16 || rq->colour == NDT_COLOUR_APNG) why = "a 16-bit or an animated PNG";
+    else if (rq->denoise_iterations != 0) why = "denoise_iterations: one stage stands between the render and the sink";
+    else if (g_want_ctx > 1) why = "a frame spread over several GPU contexts";
+    else if (rq->ao_samples < 1 || rq->ao_samples > 256) why = "a sample count outside 1 .. 256";
+    if (why) fprintf(stderr, "ndt_render_frame: ao_samples %d with %s: not built; there is no fallback\n", rq->ao_samples, why);
+    return why != NULL;
+}
+
+static int frame_ao(const ndt_render_params *p, const ndt_frame_request *rq, ndt_frame *f, int dims)
+{
+    const int width = p->width, height = p->height;
+    const size_t n = (size_t)width * (size_t)height;
+    const ndt_ao_params ap = ao_params_of(rq);
+    int ok;
+    if (rq->colour == NDT_COLOUR_F64) {
+        if (!(f->rgba = (double *)malloc(n * 4 * sizeof(double)))) return out_of_memory();
+        ok = ndt_hip_render_ao_shaded(g_ctx[0], p, &ap, f->rgba, NULL, NULL) == NDT_OK;
+    } else if (rq->colour == NDT_COLOUR_RGBA8) {
+        if (!(f->rgba8 = (unsigned char *)malloc(n * 4))) return out_of_memory();
+        ok = ndt_hip_render_ao_shaded_rgba8(g_ctx[0], p, &ap, f->rgba8, NULL) == NDT_OK;
+    } else if (rq->colour == NDT_COLOUR_EXR) {
+        const int with_map = rq->map == NDT_MAP_EXR_Z, features = rq->exr_features;
+        ndt_exr_params ep;
+        ndt_exr_stats es;
+        memset(&ep, 0, sizeof(ep));
+        ep.pixel_type = rq->exr_pixel;
+        const int64_t cap = ndt_hip_exr_ao_bound(width, height, &ep, with_map, dims, features);
+        f->file = cap > 0 ? (unsigned char *)malloc((size_t)cap) : NULL;
+        if (!f->file) {
+            fprintf(stderr, "ndt_render_frame: no OpenEXR file of %d x %d with pixel type %d and exr_features %d\n", width, height, rq->exr_pixel, features);
+            return 0;
+        }
+        if (!(ok = ndt_hip_render_exr_ao(g_ctx[0], p, &ep, with_map, features, &ap, f->file, cap, &es, NULL) == NDT_OK)) return 0;
+        f->file_bytes = es.file_bytes;
+        f->file_ms = es.ms;
+        printf("encoded EXR of %lld bytes on GPU %d in %d launches\n", (long long)es.file_bytes, ndt_hip_device(g_ctx[0]), es.launches);
+        if (features) {
+            f->feature_channels = (features & NDT_FEATURE_ID ? 1 : 0) + (features & NDT_FEATURE_POSITION ? dims : 0) + (features & NDT_FEATURE_NORMAL ? dims : 0);
+            f->feature_launches = ndt_hip_features_launches(g_ctx[0]);
+            printf("added %d feature channels on GPU %d in %d launches\n", f->feature_channels, ndt_hip_device(g_ctx[0]), f->feature_launches);
+        }
+    } else {
+        const int png = rq->colour == NDT_COLOUR_PNG;
+        const ndt_jpeg_params jp = jpeg_params_of(rq->jpeg_quality, rq->jpeg_sampling);
+        const int64_t cap = png ? ndt_hip_png_bound(width, height) : ndt_hip_jpeg_bound(width, height, &jp);
+        ndt_png_stats ps;
+        ndt_jpeg_stats js;
+        f->file = cap > 0 ? (unsigned char *)malloc((size_t)cap) : NULL;
+        if (!f->file) {
+            if (png) fprintf(stderr, "ndt_render_frame: no PNG of %d x %d\n", width, height);
+            else fprintf(stderr, "ndt_render_frame: no JPEG of %d x %d at quality %d, sampling %d\n", width, height, jp.quality, jp.sampling);
+            return 0;
+        }
+        ok = (png ? ndt_hip_render_ao_shaded_png(g_ctx[0], p, &ap, f->file, cap, &ps, NULL)
+                  : ndt_hip_render_ao_shaded_jpeg(g_ctx[0], p, &ap, &jp, f->file, cap, &js, NULL)) == NDT_OK;
+        if (!ok) return 0;
+        f->file_bytes = png ? ps.png_bytes : js.jpeg_bytes;
+        f->file_ms = png ? ps.encode_ms : js.encode_ms;
+        if (png) say_png(&ps, "PNG");
+        else say_jpeg(&js);
+    }
+    if (!ok) return 0;
+    f->ao_launches = ndt_hip_ao_launches(g_ctx[0]);
+    f->ao_ms = ndt_hip_ao_ms(g_ctx[0]);
+    printf("ambient occlusion of %d samples on GPU %d in %d launches\n", ap.samples, ndt_hip_device(g_ctx[0]), f->ao_launches);
+    return 1;
+}
+
 /* the maps each colour kind comes with (bit m: ndt_map_kind m): the pairs a device call serves */
 #define MAP_BIT(m) (1u << (m))
 static const struct { const char *name; unsigned maps; } colour_kinds[] = {
@@ -660,6 +750,7 @@ int ndt_render_frame(scene *scn, const ndt_frame_request *rq, ndt_frame *f)
         return 0;
     }
     if (rq->denoise_iterations != 0 && denoise_refused(rq)) return 0;
+    if (rq->ao_samples != 0 && ao_refused(rq)) return 0;
     /* 1. the scene: flattened, uploaded to every context of the thread (the pthread fan-out of ndt.c:949-975 is the GPU's job now;
      * `threads` fits the scene's bounding spheres in parallel) */
     if (timing) clock_gettime(CLOCK_MONOTONIC, &ts0);
@@ -689,6 +780,7 @@ int ndt_render_frame(scene *scn, const ndt_frame_request *rq, ndt_frame *f)
         }
         /* 2. and 3. colour and map in the forms asked for: one device call makes both, so the routine is chosen by the pair */
         if (rq->denoise_iterations != 0) ok = frame_denoised(&p, rq, f);
+        else if (rq->ao_samples != 0) ok = frame_ao(&p, rq, f, fb.fs.dims);
         else if (rq->colour == NDT_COLOUR_EXR) ok = frame_exr(&p, rq, f, fb.fs.dims);
         else if (rq->colour == NDT_COLOUR_APNG) ok = frame_apng(&p, rq, f);
         else if (rq->colour == NDT_COLOUR_PNG16) ok = frame_png16(&p, rq, f);
@@ -736,6 +828,8 @@ int ndt_render_frame(scene *scn, const ndt_frame_request *rq, ndt_frame *f)
                 NDT_MS(ts1, ts2), what);
         if (rq->denoise_iterations != 0 && ok)
             fprintf(stderr, "ndt_render_image: behind the render, the denoiser's %d iterations on the GPU %.2f ms\n", rq->denoise_iterations, f->denoise_ms);
+        if (rq->ao_samples != 0 && ok)
+            fprintf(stderr, "ndt_render_image: behind the render, the ambient occlusion of %d samples on the GPU %.2f ms\n", rq->ao_samples, f->ao_ms);
         if (rq->ssaa != 1 && ok)
             fprintf(stderr, "ndt_render_image: of the render, supersampling %dx%d: the folds on the GPU %.2f ms\n", rq->ssaa, rq->ssaa, f->ssaa_ms);
     }
