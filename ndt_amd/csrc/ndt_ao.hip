@@ -224,11 +224,13 @@ int check_params(const char *who, const ndt_ao_params &a)
     return NDT_OK;
 }
 
-// What every entry that takes a frame refuses, before any device work; *a the parameters in force, *rows the shard's.  any_samples:
+// What every entry that takes a frame refuses, before any device work; *a the parameters in force, *v the frame's width and the shard's rows.  any_samples:
 // the entry renders `p` as given and takes the AO pass of its deterministic twin (samples = 1)
-int refuse(const char *who, ndt_hip_ctx *ctx, const ndt_render_params *p, const ndt_ao_params *ap, bool any_samples, ndt_ao_params *a, int *rows)
+int refuse(const char *who, ndt_hip_ctx *ctx, const ndt_render_params *p, const ndt_ao_params *ap, const void *out, bool any_samples,
+           ndt_ao_params *a, FrameView *v)
 {
-    if (!ctx || !p) return fail(NDT_E_INVALID, "%s: NULL argument", who);
+    if (!ctx || !p || !out) return fail(NDT_E_INVALID, "%s: NULL argument", who);
+    *v = FrameView{ nullptr, nullptr, nullptr, p->width, 0 };
     *a = params_of(ap);
     int rc = check_params(who, *a);
     if (rc) return rc;
@@ -245,7 +247,7 @@ int refuse(const char *who, ndt_hip_ctx *ctx, const ndt_render_params *p, const 
         return fail(NDT_E_UNSUPPORTED, "%s: samples = %d: the pass starts from the one primary ray of a deterministic frame", who, p->samples);
     ndt_render_params q = *p;
     q.samples = 1;
-    return features_check(who, ctx, &q, rows);
+    return features_check(who, ctx, &q, &v->rows);
 }
 
 // The pass for checked arguments, asynchronous on the context's stream: the planes of `pl` (device memory: id, position, normal and
@@ -391,8 +393,8 @@ extern "C" int ndt_hip_ao_device(ndt_hip_ctx *ctx, const ndt_render_params *p, c
     const char *who = "ndt_hip_ao_device";
     if (!d_planes || !d_ao) return fail(NDT_E_INVALID, "%s: NULL argument", who);
     ndt_ao_params a;
-    int rows = 0;
-    int rc = refuse(who, ctx, p, ap, false, &a, &rows);
+    FrameView v;
+    int rc = refuse(who, ctx, p, ap, d_ao, false, &a, &v);
     if (rc) return rc;
     if (!d_planes->id || !d_planes->position || !d_planes->normal || !d_planes->ray_v)
         return fail(NDT_E_INVALID, "%s: a NULL plane: the pass starts from id, position, normal and ray_v", who);
@@ -408,10 +410,9 @@ extern "C" int ndt_hip_render_ao_device(ndt_hip_ctx *ctx, const ndt_render_param
                                         ndt_render_stats *stats)
 {
     const char *who = "ndt_hip_render_ao_device";
-    if (!d_ao) return fail(NDT_E_INVALID, "%s: NULL argument", who);
     ndt_ao_params a;
-    int rows = 0;
-    int rc = refuse(who, ctx, p, ap, true, &a, &rows);
+    FrameView v;
+    int rc = refuse(who, ctx, p, ap, d_ao, true, &a, &v);
     if (rc) return rc;
     if ((((uintptr_t)d_ao | (uintptr_t)d_dirs) & 7u) != 0) return fail(NDT_E_INVALID, "%s: misaligned: the plane and the directions to 8 bytes", who);
     ndt_feature_planes planes;
@@ -420,7 +421,7 @@ extern "C" int ndt_hip_render_ao_device(ndt_hip_ctx *ctx, const ndt_render_param
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     if (stats) {
         *stats = ndt_render_stats{};
-        stats->rays_primary = p->max_optic_depth > 0 ? (int64_t)rows * p->width : 0;
+        stats->rays_primary = p->max_optic_depth > 0 ? (int64_t)v.rows * p->width : 0;
         stats->trace_launches = p->max_optic_depth > 0 ? 1 : 0;
     }
     return collect_ms(ctx);
@@ -430,14 +431,13 @@ extern "C" int ndt_hip_render_ao(ndt_hip_ctx *ctx, const ndt_render_params *p, c
                                  ndt_render_stats *stats)
 {
     const char *who = "ndt_hip_render_ao";
-    if (!ao_plane) return fail(NDT_E_INVALID, "%s: NULL argument", who);
     ndt_ao_params a;
-    int rows = 0;
-    int rc = refuse(who, ctx, p, ap, true, &a, &rows);
+    FrameView v;
+    int rc = refuse(who, ctx, p, ap, ao_plane, true, &a, &v);
     if (rc) return rc;
     HIP_TRY(hipSetDevice(ctx->device));
     AoState &ao = ctx->ao;
-    const size_t pixels = (size_t)rows * (size_t)p->width, dir_bytes = pixels * (size_t)a.samples * (size_t)ctx->dims * sizeof(double);
+    const size_t pixels = (size_t)v.rows * (size_t)p->width, dir_bytes = pixels * (size_t)a.samples * (size_t)ctx->dims * sizeof(double);
     if ((rc = ao.d_plane.reserve(pixels * sizeof(double), ctx->stream, who))) return rc;
     if (dirs && (rc = ao.d_dirs.reserve(dir_bytes, ctx->stream, who))) return rc;
     if ((rc = ndt_hip_render_ao_device(ctx, p, &a, ao.d_plane.p, dirs ? ao.d_dirs.p : nullptr, stats))) return rc;
@@ -468,15 +468,14 @@ extern "C" int ndt_hip_render_ao_shaded_device(ndt_hip_ctx *ctx, const ndt_rende
                                                ndt_render_stats *stats)
 {
     const char *who = "ndt_hip_render_ao_shaded_device";
-    if (!d_rgba) return fail(NDT_E_INVALID, "%s: NULL argument", who);
     ndt_ao_params a;
-    int rows = 0;
-    int rc = refuse(who, ctx, p, ap, true, &a, &rows);
+    FrameView v;
+    int rc = refuse(who, ctx, p, ap, d_rgba, true, &a, &v);
     if (rc) return rc;
     if (((uintptr_t)d_rgba & 15u) != 0 || ((uintptr_t)d_ao & 7u) != 0)
         return fail(NDT_E_INVALID, "%s: misaligned: the image to 16 bytes, the plane to 8", who);
     HIP_TRY(hipSetDevice(ctx->device));
-    const long long pixels = (long long)rows * p->width;
+    const long long pixels = (long long)v.rows * p->width;
     if (!d_ao) {
         if ((rc = ctx->ao.d_plane.reserve((size_t)pixels * sizeof(double), ctx->stream, who))) return rc;
         d_ao = ctx->ao.d_plane.p;
@@ -490,89 +489,67 @@ extern "C" int ndt_hip_render_ao_shaded_device(ndt_hip_ctx *ctx, const ndt_rende
     return collect_ms(ctx);
 }
 
+// ndt_hip_render_ao_shaded_device into ao.d_frame (*v: sized by refuse), the plane where that entry keeps its own: ao.d_plane
+static int render_ao_shaded_own(ndt_hip_ctx *ctx, const char *who, const ndt_render_params *p, const ndt_ao_params &a, ndt_render_stats *stats, FrameView *v)
+{
+    HIP_TRY(hipSetDevice(ctx->device));
+    const int rc = ctx->ao.d_frame.reserve(v->pixels() * 4 * sizeof(double), ctx->stream, who);
+    if (rc) return rc;
+    v->d_rgba = ctx->ao.d_frame.p;
+    return ndt_hip_render_ao_shaded_device(ctx, p, &a, ctx->ao.d_frame.p, nullptr, stats);
+}
+
+// The delivering entries (the 8-bit image of those that want one: quantised into ao.d_rgba8 by the tail)
 extern "C" int ndt_hip_render_ao_shaded(ndt_hip_ctx *ctx, const ndt_render_params *p, const ndt_ao_params *ap, double *rgba, double *ao_plane,
                                         ndt_render_stats *stats)
 {
     const char *who = "ndt_hip_render_ao_shaded";
-    if (!rgba) return fail(NDT_E_INVALID, "%s: NULL argument", who);
     ndt_ao_params a;
-    int rows = 0;
-    int rc = refuse(who, ctx, p, ap, true, &a, &rows);
+    FrameView v;
+    int rc = refuse(who, ctx, p, ap, rgba, true, &a, &v);
     if (rc) return rc;
-    HIP_TRY(hipSetDevice(ctx->device));
-    AoState &ao = ctx->ao;
-    const size_t pixels = (size_t)rows * (size_t)p->width;
-    if ((rc = ao.d_frame.reserve(pixels * 4 * sizeof(double), ctx->stream, who))) return rc;
-    if ((rc = ao.d_plane.reserve(pixels * sizeof(double), ctx->stream, who))) return rc;
-    if ((rc = ndt_hip_render_ao_shaded_device(ctx, p, &a, ao.d_frame.p, ao.d_plane.p, stats))) return rc;
-    HIP_TRY(hipMemcpyAsync(rgba, ao.d_frame.p, pixels * 4 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    if (ao_plane) HIP_TRY(hipMemcpyAsync(ao_plane, ao.d_plane.p, pixels * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    return NDT_OK;
+    if ((rc = render_ao_shaded_own(ctx, who, p, a, stats, &v))) return rc;
+    // (the plane is no frame: its copy stays here, in front of the frame's on the same stream)
+    if (ao_plane) HIP_TRY(hipMemcpyAsync(ao_plane, ctx->ao.d_plane.p, v.pixels() * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    return deliver_doubles(ctx, v, rgba, nullptr);
 }
 
 extern "C" int ndt_hip_render_ao_shaded_rgba8(ndt_hip_ctx *ctx, const ndt_render_params *p, const ndt_ao_params *ap, uint8_t *rgba8,
                                               ndt_render_stats *stats)
 {
     const char *who = "ndt_hip_render_ao_shaded_rgba8";
-    if (!rgba8) return fail(NDT_E_INVALID, "%s: NULL argument", who);
     ndt_ao_params a;
-    int rows = 0;
-    int rc = refuse(who, ctx, p, ap, true, &a, &rows);
+    FrameView v;
+    int rc = refuse(who, ctx, p, ap, rgba8, true, &a, &v);
     if (rc) return rc;
-    HIP_TRY(hipSetDevice(ctx->device));
-    AoState &ao = ctx->ao;
-    const size_t pixels = (size_t)rows * (size_t)p->width;
-    if ((rc = ao.d_frame.reserve(pixels * 4 * sizeof(double), ctx->stream, who))) return rc;
-    if ((rc = ao.d_rgba8.reserve(pixels * 4, ctx->stream, who))) return rc;
-    if ((rc = ndt_hip_render_ao_shaded_device(ctx, p, &a, ao.d_frame.p, nullptr, stats))) return rc;
-    if ((rc = ndt_hip_quantize_device(ctx, ao.d_frame.p, ao.d_rgba8.p, (int64_t)pixels))) return rc;
-    HIP_TRY(hipMemcpyAsync(rgba8, ao.d_rgba8.p, pixels * 4, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    return NDT_OK;
+    if ((rc = render_ao_shaded_own(ctx, who, p, a, stats, &v))) return rc;
+    return deliver_rgba8(ctx, who, v, ctx->ao.d_rgba8, rgba8);
 }
 
 extern "C" int ndt_hip_render_ao_shaded_png(ndt_hip_ctx *ctx, const ndt_render_params *p, const ndt_ao_params *ap, uint8_t *png, int64_t cap,
                                             ndt_png_stats *stats, ndt_render_stats *render_stats)
 {
     const char *who = "ndt_hip_render_ao_shaded_png";
-    if (!png) return fail(NDT_E_INVALID, "%s: NULL argument", who);
     ndt_ao_params a;
-    int rows = 0;
-    int rc = refuse(who, ctx, p, ap, true, &a, &rows);
+    FrameView v;
+    int rc = refuse(who, ctx, p, ap, png, true, &a, &v);
     if (rc) return rc;
-    if (ndt_hip_png_bound(p->width, rows) < 0)
-        return fail(NDT_E_INVALID, "%s: the filtered stream of a %d x %d image exceeds 2^31 - 1 bytes", who, p->width, rows);
-    HIP_TRY(hipSetDevice(ctx->device));
-    AoState &ao = ctx->ao;
-    const size_t pixels = (size_t)rows * (size_t)p->width;
-    if ((rc = ao.d_frame.reserve(pixels * 4 * sizeof(double), ctx->stream, who))) return rc;
-    if ((rc = ao.d_rgba8.reserve(pixels * 4, ctx->stream, who))) return rc;
-    if ((rc = ndt_hip_render_ao_shaded_device(ctx, p, &a, ao.d_frame.p, nullptr, render_stats))) return rc;
-    if ((rc = ndt_hip_quantize_device(ctx, ao.d_frame.p, ao.d_rgba8.p, (int64_t)pixels))) return rc;
-    return ndt_hip_encode_png_device(ctx, ao.d_rgba8.p, p->width, rows, png, cap, stats);
+    if ((rc = refuse_png(who, p->width, v.rows, 4))) return rc;
+    if ((rc = render_ao_shaded_own(ctx, who, p, a, render_stats, &v))) return rc;
+    return deliver_png(ctx, who, v, ctx->ao.d_rgba8, png, cap, stats);
 }
 
 extern "C" int ndt_hip_render_ao_shaded_jpeg(ndt_hip_ctx *ctx, const ndt_render_params *p, const ndt_ao_params *ap, const ndt_jpeg_params *jp,
                                              uint8_t *jpg, int64_t cap, ndt_jpeg_stats *stats, ndt_render_stats *render_stats)
 {
     const char *who = "ndt_hip_render_ao_shaded_jpeg";
-    if (!jpg) return fail(NDT_E_INVALID, "%s: NULL argument", who);
     ndt_ao_params a;
-    int rows = 0;
-    int rc = refuse(who, ctx, p, ap, true, &a, &rows);
+    FrameView v;
+    int rc = refuse(who, ctx, p, ap, jpg, true, &a, &v);
     if (rc) return rc;
-    if (ndt_hip_jpeg_bound(p->width, rows, jp) < 0)
-        return fail(NDT_E_INVALID, "%s: no JPEG of %d x %d with these parameters (a side above 65535, a quality outside 0 .. 100, a sampling outside 0 .. 1 or a reserved word set)",
-                    who, p->width, rows);
-    HIP_TRY(hipSetDevice(ctx->device));
-    AoState &ao = ctx->ao;
-    const size_t pixels = (size_t)rows * (size_t)p->width;
-    if ((rc = ao.d_frame.reserve(pixels * 4 * sizeof(double), ctx->stream, who))) return rc;
-    if ((rc = ao.d_rgba8.reserve(pixels * 4, ctx->stream, who))) return rc;
-    if ((rc = ndt_hip_render_ao_shaded_device(ctx, p, &a, ao.d_frame.p, nullptr, render_stats))) return rc;
-    if ((rc = ndt_hip_quantize_device(ctx, ao.d_frame.p, ao.d_rgba8.p, (int64_t)pixels))) return rc;
-    return ndt_hip_encode_jpeg_device(ctx, ao.d_rgba8.p, p->width, rows, jp, jpg, cap, stats);
+    if ((rc = refuse_jpeg(who, p->width, v.rows, jp))) return rc;
+    if ((rc = render_ao_shaded_own(ctx, who, p, a, render_stats, &v))) return rc;
+    return deliver_jpeg(ctx, who, v, ctx->ao.d_rgba8, jp, jpg, cap, stats);
 }
 
 extern "C" int ndt_hip_render_exr_ao(ndt_hip_ctx *ctx, const ndt_render_params *p, const ndt_exr_params *ep, int32_t with_depth, int32_t features,
@@ -580,30 +557,25 @@ extern "C" int ndt_hip_render_exr_ao(ndt_hip_ctx *ctx, const ndt_render_params *
 {
     const char *who = "ndt_hip_render_exr_ao";
     if (stats) *stats = ndt_exr_stats{};
-    if (!out) return fail(NDT_E_INVALID, "%s: NULL argument", who);
     ndt_ao_params a;
-    int rows = 0;
-    int rc = refuse(who, ctx, p, ap, true, &a, &rows);
+    FrameView v;
+    int rc = refuse(who, ctx, p, ap, out, true, &a, &v);
     if (rc) return rc;
     if (cap < 0) return fail(NDT_E_INVALID, "%s: cap %lld", who, (long long)cap);
-    if (ndt_hip_exr_ao_bound(p->width, rows, ep, with_depth, ctx->dims, features) < 0)
+    if (ndt_hip_exr_ao_bound(p->width, v.rows, ep, with_depth, ctx->dims, features) < 0)
         return fail(NDT_E_INVALID, "%s: no EXR of %d x %d with feature mask %d (id 1, position 2, normal 4, or 0) and these parameters (a pixel type other than 0, 1, 2, or samples beyond 2^31 - 1 bytes)",
-                    who, p->width, rows, features);
-    HIP_TRY(hipSetDevice(ctx->device));
-    const size_t pixels = (size_t)p->width * (size_t)rows, img_bytes = pixels * 4 * sizeof(double);
-    if ((rc = ctx->d_out.reserve(img_bytes + (with_depth ? pixels * sizeof(double) : 0), ctx->stream, who))) return rc;
-    if ((rc = ctx->ao.d_plane.reserve(pixels * sizeof(double), ctx->stream, who))) return rc;
-    void *d_depth = with_depth ? (void *)(ctx->d_out.as<char>() + img_bytes) : nullptr;
-    if ((rc = ndt_hip_render_depth_device(ctx, p, ctx->d_out.p, d_depth, render_stats))) return rc;
+                    who, p->width, v.rows, features);
+    if ((rc = render_plain_own(ctx, who, p, with_depth != 0, render_stats, &v))) return rc;
+    if ((rc = ctx->ao.d_plane.reserve(v.pixels() * sizeof(double), ctx->stream, who))) return rc;
     ndt_feature_planes planes;
     if ((rc = features_then_ao(ctx, who, p, a, ctx->ao.d_plane.as<double>(), nullptr, &planes))) return rc;
     ctx->ao.launches += ctx->features.launches;
     // (strength 0: the colour keeps the bits of the file without AO, whatever they are)
     if (a.strength != 0) {
-        if ((rc = apply(ctx, ctx->d_out.p, ctx->ao.d_plane.p, (long long)pixels, a.strength, ctx->d_out.p))) return rc;
+        if ((rc = apply(ctx, ctx->d_out.p, ctx->ao.d_plane.p, (long long)v.pixels(), a.strength, ctx->d_out.p))) return rc;
         ++ctx->ao.launches;
     }
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     if ((rc = collect_ms(ctx))) return rc;
-    return exr_encode_ao_device(ctx, who, ctx->d_out.p, d_depth, &planes, ctx->ao.d_plane.p, ctx->dims, features, p->width, rows, ep, out, cap, stats);
+    return exr_encode_ao_device(ctx, who, v.d_rgba, v.d_depth, &planes, ctx->ao.d_plane.p, ctx->dims, features, p->width, v.rows, ep, out, cap, stats);
 }

@@ -300,8 +300,7 @@ extern "C" int ndt_hip_apng_begin(ndt_hip_ctx *ctx, int32_t width, int32_t rows,
 {
     if (!ctx) return fail(NDT_E_INVALID, "ndt_hip_apng_begin: NULL argument");
     if (width < 1 || rows < 1) return fail(NDT_E_INVALID, "ndt_hip_apng_begin: a canvas of %d x %d pixels", width, rows);
-    if (ndt_hip_png_bound(width, rows) < 0)
-        return fail(NDT_E_INVALID, "ndt_hip_apng_begin: the filtered stream of a %d x %d image exceeds 2^31 - 1 bytes", width, rows);
+    if (int rc = refuse_png("ndt_hip_apng_begin", width, rows, 4)) return rc;
     if (n_frames < 1) return fail(NDT_E_INVALID, "ndt_hip_apng_begin: n_frames %d: an animation has at least one frame", n_frames);
     if (delay_den < 1) return fail(NDT_E_INVALID, "ndt_hip_apng_begin: delay_den %d: the delay's denominator is at least 1", delay_den);
     if (delay_num < 0 || delay_num > 65535 || delay_den > 65535)

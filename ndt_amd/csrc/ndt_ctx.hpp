@@ -7,7 +7,8 @@
 //   ndt_probe.hip    what the diagnostics of a profiled pass print (stream / shade / exit probes, NDT_PHASE_TIMING)
 //   ndt_aa.hip       Whitted's recursive anti-aliasing on top of render_pass
 //   ndt_sampled.hip  -n samples > 1, lens, area lights on top of render_pass
-//   ndt_render.hip   ndt_hip_render*: argument checks and the choice between the three
+//   ndt_render.hip   ndt_hip_render*: argument checks and the choice between the three; and where every frame staged on the device is
+//                    delivered (FrameView below): the file formats' refusals and the tails.  The stage files below produce
 //   ndt_multi.hip    one frame over several contexts / devices
 //   ndt_fit.hip      ndt_hip_fit_spheres: the bounding-sphere fits of a frame (batched Nelder-Mead), kernel and launcher
 //   ndt_kd.hip       ndt_hip_build_kdtree: the kd-tree of a frame's item boxes, level by level; kernels, launcher and C ABI
@@ -381,6 +382,38 @@ int features_own(ndt_hip_ctx *ctx, const char *who, const ndt_render_params *p, 
 
 // ndt_depth.hip
 void free_depth(ndt_hip_ctx *ctx);
+
+// ndt_render.hip: delivery.  A stage (the plain render, ndt_ssaa.hip, ndt_denoise.hip, ndt_ao.hip) produces a frame into buffers of
+// its own and names it; a tail takes it to the sink.  An entry is: the stage's refusal, the sink's refusal, produce, one tail.
+#pragma GCC visibility push(hidden)     // (the library's dynamic symbol table stays as it was)
+struct FrameView {
+    const void *d_rgba;         // rows x width x 4 doubles, complete or queued on the context's stream
+    const void *d_depth;        // rows x width doubles of map, or nullptr
+    const void *d_rgba8;        // the 8-bit image where the producer has written it already (the last k_ssaa_fold), else nullptr
+    int32_t width, rows;
+    size_t pixels() const { return (size_t)rows * (size_t)width; }
+};
+// the plain frame (and its map) into ctx->d_out; v->rows = 0: no pixels, nothing made, the render call's word on `p` comes back
+int render_plain_own(ndt_hip_ctx *ctx, const char *who, const ndt_render_params *p, bool want_depth, ndt_render_stats *stats, FrameView *v);
+// what a file sink refuses before the render: a shard without rows, then a size beyond the format's bound (PNG: bpp 4, 8, 2)
+int refuse_empty_shard(const char *who, int rows);
+int refuse_png(const char *who, int32_t width, int32_t rows, int bpp);
+int refuse_jpeg(const char *who, int32_t width, int32_t rows, const ndt_jpeg_params *jp);
+int refuse_exr(const char *who, ndt_hip_ctx *ctx, const ndt_render_params *p, const ndt_exr_params *ep, int with_depth, uint8_t *out, int *rows);
+// The tails: each returns when the sink has its bytes.  The DeviceBuffers are the calling stage's own and stay so: a tail reserves
+// and fills them (stage8 only where v.d_rgba8 is not set).  stage_depth8 / depth_png given: the map too, as bytes or as a file
+int deliver_doubles(ndt_hip_ctx *ctx, const FrameView &v, double *rgba, double *depth);
+int deliver_rgba8(ndt_hip_ctx *ctx, const char *who, FrameView v, DeviceBuffer &stage8, uint8_t *rgba8, DeviceBuffer *stage_depth8 = nullptr,
+                  uint8_t *depth8 = nullptr, double *range_out = nullptr);
+int deliver_png(ndt_hip_ctx *ctx, const char *who, FrameView v, DeviceBuffer &stage8, uint8_t *png, int64_t cap, ndt_png_stats *stats,
+                DeviceBuffer *stage_depth8 = nullptr, uint8_t *depth_png = nullptr, int64_t depth_cap = 0, uint8_t *depth8 = nullptr,
+                double *range_out = nullptr);
+int deliver_png16(ndt_hip_ctx *ctx, const char *who, const FrameView &v, DeviceBuffer &stage16, DeviceBuffer &stage_grey16, uint8_t *png,
+                  int64_t cap, uint8_t *depth_png, int64_t depth_cap, ndt_png_stats *stats, double *range_out);
+int deliver_jpeg(ndt_hip_ctx *ctx, const char *who, FrameView v, DeviceBuffer &stage8, const ndt_jpeg_params *jp, uint8_t *jpg,
+                 int64_t cap, ndt_jpeg_stats *stats);
+int deliver_exr(ndt_hip_ctx *ctx, const FrameView &v, const ndt_exr_params *ep, uint8_t *out, int64_t cap, ndt_exr_stats *stats);
+#pragma GCC visibility pop
 
 // ndt_ssaa.hip
 void free_ssaa(ndt_hip_ctx *ctx);

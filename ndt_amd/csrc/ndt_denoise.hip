@@ -184,11 +184,12 @@ int collect_ms(ndt_hip_ctx *ctx)
     return NDT_OK;
 }
 
-// what every whole-frame call refuses, before any device work; *d the parameters in force, *rows the frame's
+// what every whole-frame call refuses, before any device work; *d the parameters in force, *v the frame's width and rows
 int refuse(const char *who, ndt_hip_ctx *ctx, const ndt_render_params *p, const ndt_denoise_params *dp, const void *out, ndt_denoise_params *d,
-           int *rows)
+           FrameView *v)
 {
     if (!ctx || !p || !out) return fail(NDT_E_INVALID, "%s: NULL argument", who);
+    *v = FrameView{ nullptr, nullptr, nullptr, p->width, 0 };
     *d = params_of(dp);
     int rc = check_params(who, *d);
     if (rc) return rc;
@@ -202,7 +203,7 @@ int refuse(const char *who, ndt_hip_ctx *ctx, const ndt_render_params *p, const 
     if (p->samples < 1) return fail(NDT_E_INVALID, "%s: samples=%d", who, p->samples);
     ndt_render_params q = *p;
     q.samples = 1;
-    return features_check(who, ctx, &q, rows);
+    return features_check(who, ctx, &q, &v->rows);
 }
 
 // The denoised frame of checked arguments in d_rgba (device, aligned to 16 bytes): the frame `p` asks for into the context's frame
@@ -229,19 +230,14 @@ int render_denoised(const char *who, ndt_hip_ctx *ctx, const ndt_render_params *
     return collect_ms(ctx);
 }
 
-// ... into the context's own buffer dn.d_out, and its 8-bit image into dn.d_rgba8 when wanted (queued behind it, not synchronised)
-int render_denoised_own(const char *who, ndt_hip_ctx *ctx, const ndt_render_params *p, const ndt_denoise_params &d, int rows, bool want_rgba8,
-                        ndt_render_stats *stats)
+// ... into the context's own buffer dn.d_out (*v: sized by refuse)
+int render_denoised_own(const char *who, ndt_hip_ctx *ctx, const ndt_render_params *p, const ndt_denoise_params &d, ndt_render_stats *stats, FrameView *v)
 {
     HIP_TRY(hipSetDevice(ctx->device));
-    DenoiseState &dn = ctx->denoise;
-    const size_t pixels = (size_t)rows * (size_t)p->width;
-    int rc;
-    if ((rc = dn.d_out.reserve(pixels * 4 * sizeof(double), ctx->stream, who))) return rc;
-    if (want_rgba8 && (rc = dn.d_rgba8.reserve(pixels * 4, ctx->stream, who))) return rc;
-    if ((rc = render_denoised(who, ctx, p, d, rows, dn.d_out.p, stats))) return rc;
-    if (want_rgba8 && (rc = ndt_hip_quantize_device(ctx, dn.d_out.p, dn.d_rgba8.p, (int64_t)pixels))) return rc;
-    return NDT_OK;
+    const int rc = ctx->denoise.d_out.reserve(v->pixels() * 4 * sizeof(double), ctx->stream, who);
+    if (rc) return rc;
+    v->d_rgba = ctx->denoise.d_out.p;
+    return render_denoised(who, ctx, p, d, v->rows, ctx->denoise.d_out.p, stats);
 }
 
 } // namespace
@@ -292,25 +288,24 @@ extern "C" int ndt_hip_render_denoised_device(ndt_hip_ctx *ctx, const ndt_render
 {
     const char *who = "ndt_hip_render_denoised_device";
     ndt_denoise_params d;
-    int rows = 0;
-    int rc = refuse(who, ctx, p, dp, d_rgba, &d, &rows);
+    FrameView v;
+    int rc = refuse(who, ctx, p, dp, d_rgba, &d, &v);
     if (rc) return rc;
     if (((uintptr_t)d_rgba & 15u) != 0) return fail(NDT_E_INVALID, "%s: misaligned: the image must be aligned to 16 bytes", who);
-    return render_denoised(who, ctx, p, d, rows, d_rgba, stats);
+    return render_denoised(who, ctx, p, d, v.rows, d_rgba, stats);
 }
 
+// The delivering entries (the 8-bit image of those that want one: quantised into dn.d_rgba8 by the tail)
 extern "C" int ndt_hip_render_denoised(ndt_hip_ctx *ctx, const ndt_render_params *p, const ndt_denoise_params *dp, double *rgba,
                                        ndt_render_stats *stats)
 {
     const char *who = "ndt_hip_render_denoised";
     ndt_denoise_params d;
-    int rows = 0;
-    int rc = refuse(who, ctx, p, dp, rgba, &d, &rows);
+    FrameView v;
+    int rc = refuse(who, ctx, p, dp, rgba, &d, &v);
     if (rc) return rc;
-    if ((rc = render_denoised_own(who, ctx, p, d, rows, false, stats))) return rc;
-    HIP_TRY(hipMemcpyAsync(rgba, ctx->denoise.d_out.p, (size_t)rows * (size_t)p->width * 4 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    return NDT_OK;
+    if ((rc = render_denoised_own(who, ctx, p, d, stats, &v))) return rc;
+    return deliver_doubles(ctx, v, rgba, nullptr);
 }
 
 extern "C" int ndt_hip_render_denoised_rgba8(ndt_hip_ctx *ctx, const ndt_render_params *p, const ndt_denoise_params *dp, uint8_t *rgba8,
@@ -318,13 +313,11 @@ extern "C" int ndt_hip_render_denoised_rgba8(ndt_hip_ctx *ctx, const ndt_render_
 {
     const char *who = "ndt_hip_render_denoised_rgba8";
     ndt_denoise_params d;
-    int rows = 0;
-    int rc = refuse(who, ctx, p, dp, rgba8, &d, &rows);
+    FrameView v;
+    int rc = refuse(who, ctx, p, dp, rgba8, &d, &v);
     if (rc) return rc;
-    if ((rc = render_denoised_own(who, ctx, p, d, rows, true, stats))) return rc;
-    HIP_TRY(hipMemcpyAsync(rgba8, ctx->denoise.d_rgba8.p, (size_t)rows * (size_t)p->width * 4, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    return NDT_OK;
+    if ((rc = render_denoised_own(who, ctx, p, d, stats, &v))) return rc;
+    return deliver_rgba8(ctx, who, v, ctx->denoise.d_rgba8, rgba8);
 }
 
 extern "C" int ndt_hip_render_denoised_png(ndt_hip_ctx *ctx, const ndt_render_params *p, const ndt_denoise_params *dp, uint8_t *png, int64_t cap,
@@ -332,13 +325,12 @@ extern "C" int ndt_hip_render_denoised_png(ndt_hip_ctx *ctx, const ndt_render_pa
 {
     const char *who = "ndt_hip_render_denoised_png";
     ndt_denoise_params d;
-    int rows = 0;
-    int rc = refuse(who, ctx, p, dp, png, &d, &rows);
+    FrameView v;
+    int rc = refuse(who, ctx, p, dp, png, &d, &v);
     if (rc) return rc;
-    if (ndt_hip_png_bound(p->width, rows) < 0)
-        return fail(NDT_E_INVALID, "%s: the filtered stream of a %d x %d image exceeds 2^31 - 1 bytes", who, p->width, rows);
-    if ((rc = render_denoised_own(who, ctx, p, d, rows, true, render_stats))) return rc;
-    return ndt_hip_encode_png_device(ctx, ctx->denoise.d_rgba8.p, p->width, rows, png, cap, stats);
+    if ((rc = refuse_png(who, p->width, v.rows, 4))) return rc;
+    if ((rc = render_denoised_own(who, ctx, p, d, render_stats, &v))) return rc;
+    return deliver_png(ctx, who, v, ctx->denoise.d_rgba8, png, cap, stats);
 }
 
 extern "C" int ndt_hip_render_denoised_jpeg(ndt_hip_ctx *ctx, const ndt_render_params *p, const ndt_denoise_params *dp, const ndt_jpeg_params *jp,
@@ -346,14 +338,12 @@ extern "C" int ndt_hip_render_denoised_jpeg(ndt_hip_ctx *ctx, const ndt_render_p
 {
     const char *who = "ndt_hip_render_denoised_jpeg";
     ndt_denoise_params d;
-    int rows = 0;
-    int rc = refuse(who, ctx, p, dp, jpg, &d, &rows);
+    FrameView v;
+    int rc = refuse(who, ctx, p, dp, jpg, &d, &v);
     if (rc) return rc;
-    if (ndt_hip_jpeg_bound(p->width, rows, jp) < 0)
-        return fail(NDT_E_INVALID, "%s: no JPEG of %d x %d with these parameters (a side above 65535, a quality outside 0 .. 100, a sampling outside 0 .. 1 or a reserved word set)",
-                    who, p->width, rows);
-    if ((rc = render_denoised_own(who, ctx, p, d, rows, true, render_stats))) return rc;
-    return ndt_hip_encode_jpeg_device(ctx, ctx->denoise.d_rgba8.p, p->width, rows, jp, jpg, cap, stats);
+    if ((rc = refuse_jpeg(who, p->width, v.rows, jp))) return rc;
+    if ((rc = render_denoised_own(who, ctx, p, d, render_stats, &v))) return rc;
+    return deliver_jpeg(ctx, who, v, ctx->denoise.d_rgba8, jp, jpg, cap, stats);
 }
 
 extern "C" int ndt_hip_render_denoised_exr(ndt_hip_ctx *ctx, const ndt_render_params *p, const ndt_denoise_params *dp, const ndt_exr_params *ep,
@@ -362,12 +352,12 @@ extern "C" int ndt_hip_render_denoised_exr(ndt_hip_ctx *ctx, const ndt_render_pa
     const char *who = "ndt_hip_render_denoised_exr";
     if (stats) *stats = ndt_exr_stats{};
     ndt_denoise_params d;
-    int rows = 0;
-    int rc = refuse(who, ctx, p, dp, out, &d, &rows);
+    FrameView v;
+    int rc = refuse(who, ctx, p, dp, out, &d, &v);
     if (rc) return rc;
-    if (ndt_hip_exr_bound(p->width, rows, ep, 0) < 0)
+    if (ndt_hip_exr_bound(p->width, v.rows, ep, 0) < 0)
         return fail(NDT_E_INVALID, "%s: no EXR of %d x %d with these parameters (a pixel type other than 0, 1, 2, or samples beyond 2^31 - 1 bytes)", who,
-                    p->width, rows);
-    if ((rc = render_denoised_own(who, ctx, p, d, rows, false, render_stats))) return rc;
-    return ndt_hip_encode_exr_device(ctx, ctx->denoise.d_out.p, nullptr, p->width, rows, ep, out, cap, stats);
+                    p->width, v.rows);
+    if ((rc = render_denoised_own(who, ctx, p, d, render_stats, &v))) return rc;
+    return deliver_exr(ctx, v, ep, out, cap, stats);
 }

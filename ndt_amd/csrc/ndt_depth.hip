@@ -132,40 +132,6 @@ __global__ void __launch_bounds__(DEPTH_FINISH_LANES) k_depth_finish(const doubl
     }
 }
 
-// ndt_hip_render_depth_device into the context's buffers, then both images in HBM: at 8 bits ds.d_rgba8 (the quantised image)
-// and ds.d_depth8 (the finished map), at 16 ds.d_rgba16 and ds.d_grey16.  *pixels = 0: the shard has no rows (nothing was made).
-int render_both(ndt_hip_ctx *ctx, const ndt_render_params *p, bool sixteen, double *range_out, ndt_render_stats *stats, int *rows_out,
-                size_t *pixels_out)
-{
-    HIP_TRY(hipSetDevice(ctx->device));
-    const int rows = ndt_hip_shard_rows(p->height, p->row_begin, p->row_step);
-    const size_t pixels = (size_t)(rows > 0 ? rows : 0) * (size_t)(p->width > 0 ? p->width : 0);
-    *rows_out = rows;
-    *pixels_out = pixels;
-    if (range_out) range_out[0] = range_out[1] = 0.0;
-    // (a frame without pixels: the render call says what is wrong with it, or that nothing is)
-    if (pixels == 0) return ndt_hip_render_depth_device(ctx, p, (void *)ctx, nullptr, stats);
-    const size_t img_bytes = pixels * 4 * sizeof(double), bytes = img_bytes + img_bytes / 4;       // the map sits behind the image
-    DepthState &ds = ctx->depth;
-    int rc;
-    if ((rc = ctx->d_out.reserve(bytes, ctx->stream, "ndt_hip_render_*_depth"))) return rc;
-    if (sixteen) {
-        if ((rc = ds.d_rgba16.reserve(pixels * 8, ctx->stream, "ndt_hip_render_*_depth"))) return rc;
-        if ((rc = ds.d_grey16.reserve((pixels * 2 + 3) & ~(size_t)3, ctx->stream, "ndt_hip_render_*_depth"))) return rc;
-    } else {
-        if ((rc = ds.d_rgba8.reserve(pixels * 4, ctx->stream, "ndt_hip_render_*_depth"))) return rc;
-        if ((rc = ds.d_depth8.reserve(pixels * 4, ctx->stream, "ndt_hip_render_*_depth"))) return rc;
-    }
-    void *d_depth = ctx->d_out.as<char>() + img_bytes;
-    if ((rc = ndt_hip_render_depth_device(ctx, p, ctx->d_out.p, d_depth, stats))) return rc;
-    if (sixteen) {
-        if ((rc = ndt_hip_depth_grey16_device(ctx, d_depth, (int64_t)pixels, ds.d_grey16.p, range_out))) return rc;
-        return ndt_hip_quantize16_device(ctx, ctx->d_out.p, ds.d_rgba16.p, (int64_t)pixels);
-    }
-    if ((rc = ndt_hip_depth_rgba8_device(ctx, d_depth, (int64_t)pixels, ds.d_depth8.p, range_out))) return rc;
-    return ndt_hip_quantize_device(ctx, ctx->d_out.p, ds.d_rgba8.p, (int64_t)pixels);
-}
-
 // the two launches over a map of n_pixels doubles; `who` names the entry point in errors
 int finish_map(ndt_hip_ctx *ctx, const char *who, bool sixteen, const void *d_depth, int64_t n_pixels, void *d_out, double *range_out)
 {
@@ -242,18 +208,17 @@ extern "C" int ndt_hip_depth_grey16_device(ndt_hip_ctx *ctx, const void *d_depth
 extern "C" int ndt_hip_depth_launches(ndt_hip_ctx *ctx) { return ctx ? ctx->depth.launches : 0; }
 extern "C" double ndt_hip_depth_ms(ndt_hip_ctx *ctx) { return ctx ? ctx->depth.finish_ms : 0.0; }
 
+static const char WHO[] = "ndt_hip_render_*_depth";     // below: the plain frame and its map into ctx->d_out, then a tail of ndt_render.hip
+
 extern "C" int ndt_hip_render_rgba8_depth(ndt_hip_ctx *ctx, const ndt_render_params *p, uint8_t *rgba8, uint8_t *depth8, double *range_out,
                                           ndt_render_stats *stats)
 {
     if (!ctx || !p || !rgba8 || !depth8) return fail(NDT_E_INVALID, "ndt_hip_render_rgba8_depth: NULL argument");
-    int rows = 0;
-    size_t pixels = 0;
-    int rc = render_both(ctx, p, false, range_out, stats, &rows, &pixels);
-    if (rc || pixels == 0) return rc;
-    HIP_TRY(hipMemcpyAsync(rgba8, ctx->depth.d_rgba8.p, pixels * 4, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(depth8, ctx->depth.d_depth8.p, pixels * 4, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    return NDT_OK;
+    if (range_out) range_out[0] = range_out[1] = 0.0;
+    FrameView v;
+    const int rc = render_plain_own(ctx, WHO, p, true, stats, &v);
+    if (rc || v.rows == 0) return rc;
+    return deliver_rgba8(ctx, WHO, v, ctx->depth.d_rgba8, rgba8, &ctx->depth.d_depth8, depth8, range_out);
 }
 
 extern "C" int ndt_hip_render_png_depth(ndt_hip_ctx *ctx, const ndt_render_params *p, uint8_t *png, int64_t cap, uint8_t *depth_png,
@@ -264,20 +229,13 @@ extern "C" int ndt_hip_render_png_depth(ndt_hip_ctx *ctx, const ndt_render_param
     if ((depth_png != nullptr) == (depth8 != nullptr))
         return fail(NDT_E_INVALID, "ndt_hip_render_png_depth: the map goes to depth_png or to depth8: one of the two");
     if (p->width < 1 || p->height < 1 || p->row_step < 1 || p->row_begin < 0) return fail(NDT_E_INVALID, "bad geometry");
-    if (ndt_hip_shard_rows(p->height, p->row_begin, p->row_step) < 1) return fail(NDT_E_INVALID, "ndt_hip_render_png_depth: the shard has no rows");
-    if (ndt_hip_png_bound(p->width, ndt_hip_shard_rows(p->height, p->row_begin, p->row_step)) < 0)
-        return fail(NDT_E_INVALID, "ndt_hip_render_png_depth: the filtered stream of a %d x %d image exceeds 2^31 - 1 bytes", p->width,
-                    ndt_hip_shard_rows(p->height, p->row_begin, p->row_step));
-    if (stats) stats[0] = stats[1] = ndt_png_stats{};
-    int rows = 0;
-    size_t pixels = 0;
-    int rc = render_both(ctx, p, false, range_out, render_stats, &rows, &pixels);
+    int rc = refuse_png("ndt_hip_render_png_depth", p->width, ndt_hip_shard_rows(p->height, p->row_begin, p->row_step), 4);
     if (rc) return rc;
-    if ((rc = ndt_hip_encode_png_device(ctx, ctx->depth.d_rgba8.p, p->width, rows, png, cap, stats ? &stats[0] : nullptr))) return rc;
-    if (depth_png) return ndt_hip_encode_png_device(ctx, ctx->depth.d_depth8.p, p->width, rows, depth_png, depth_cap, stats ? &stats[1] : nullptr);
-    HIP_TRY(hipMemcpyAsync(depth8, ctx->depth.d_depth8.p, pixels * 4, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    return NDT_OK;
+    if (stats) stats[0] = stats[1] = ndt_png_stats{};
+    if (range_out) range_out[0] = range_out[1] = 0.0;
+    FrameView v;
+    if ((rc = render_plain_own(ctx, WHO, p, true, render_stats, &v))) return rc;
+    return deliver_png(ctx, WHO, v, ctx->depth.d_rgba8, png, cap, stats, &ctx->depth.d_depth8, depth_png, depth_cap, depth8, range_out);
 }
 
 extern "C" int ndt_hip_render_png16_depth(ndt_hip_ctx *ctx, const ndt_render_params *p, uint8_t *png, int64_t cap, uint8_t *depth_png,
@@ -286,15 +244,11 @@ extern "C" int ndt_hip_render_png16_depth(ndt_hip_ctx *ctx, const ndt_render_par
     if (!ctx || !p || !png || !depth_png) return fail(NDT_E_INVALID, "ndt_hip_render_png16_depth: NULL argument");
     if (p->width < 1 || p->height < 1 || p->row_step < 1 || p->row_begin < 0)
         return fail(NDT_E_INVALID, "ndt_hip_render_png16_depth: bad geometry: %d x %d, rows %d by %d", p->width, p->height, p->row_begin, p->row_step);
-    const int shard = ndt_hip_shard_rows(p->height, p->row_begin, p->row_step);
-    if (shard < 1) return fail(NDT_E_INVALID, "ndt_hip_render_png16_depth: the shard has no rows");
-    if (ndt_hip_png16_bound(p->width, shard, 4) < 0)
-        return fail(NDT_E_INVALID, "ndt_hip_render_png16_depth: the filtered stream of a %d x %d image exceeds 2^31 - 1 bytes", p->width, shard);
-    if (stats) stats[0] = stats[1] = ndt_png_stats{};
-    int rows = 0;
-    size_t pixels = 0;
-    int rc = render_both(ctx, p, true, range_out, render_stats, &rows, &pixels);
+    int rc = refuse_png("ndt_hip_render_png16_depth", p->width, ndt_hip_shard_rows(p->height, p->row_begin, p->row_step), 8);
     if (rc) return rc;
-    if ((rc = ndt_hip_encode_png16_device(ctx, ctx->depth.d_rgba16.p, p->width, rows, 4, png, cap, stats ? &stats[0] : nullptr))) return rc;
-    return ndt_hip_encode_png16_device(ctx, ctx->depth.d_grey16.p, p->width, rows, 1, depth_png, depth_cap, stats ? &stats[1] : nullptr);
+    if (stats) stats[0] = stats[1] = ndt_png_stats{};
+    if (range_out) range_out[0] = range_out[1] = 0.0;
+    FrameView v;
+    if ((rc = render_plain_own(ctx, WHO, p, true, render_stats, &v))) return rc;
+    return deliver_png16(ctx, WHO, v, ctx->depth.d_rgba16, ctx->depth.d_grey16, png, cap, depth_png, depth_cap, stats, range_out);
 }

@@ -552,22 +552,6 @@ int encode_device(ndt_hip_ctx *ctx, const char *who, const void *d_rgba, const v
     return NDT_OK;
 }
 
-// what the render entries check before any device work; *rows: the shard's
-int check_render(const char *who, ndt_hip_ctx *ctx, const ndt_render_params *p, const ndt_exr_params *ep, int with_depth, uint8_t *out, int *rows)
-{
-    if (!ctx || !p || !out) return fail(NDT_E_INVALID, "%s: NULL argument", who);
-    if (p->width < 1 || p->height < 1 || p->row_step < 1 || p->row_begin < 0)
-        return fail(NDT_E_INVALID, "%s: bad geometry: %d x %d, rows %d by %d", who, p->width, p->height, p->row_begin, p->row_step);
-    *rows = ndt_hip_shard_rows(p->height, p->row_begin, p->row_step);
-    if (*rows < 1) return fail(NDT_E_INVALID, "%s: the shard has no rows", who);
-    const int pixel_type = pixel_type_of(ep);
-    if (pixel_type < 0) return fail(NDT_E_INVALID, "%s: pixel type %d: 1 is half, 2 float (0: half)", who, ep->pixel_type);
-    ExrLayout L;
-    if (!layout_of(p->width, *rows, pixel_type, with_depth != 0, L))
-        return fail(NDT_E_INVALID, "%s: the samples of a %d x %d image exceed 2^31 - 1 bytes", who, p->width, *rows);
-    return NDT_OK;
-}
-
 // the frame (K = 0: plain; K >= 1: supersampled K x K) in doubles in ctx->d_out, its map behind it if wanted, then the file of those
 // features != 0: behind the render the feature pass of the plain frame, on the same stream, and its planes as channels
 int render_file(const char *who, ndt_hip_ctx *ctx, const ndt_render_params *p, int32_t K, const ndt_exr_params *ep, int32_t with_depth,
@@ -575,7 +559,7 @@ int render_file(const char *who, ndt_hip_ctx *ctx, const ndt_render_params *p, i
 {
     if (stats) *stats = ndt_exr_stats{};
     int rows = 0;
-    int rc = check_render(who, ctx, p, ep, with_depth, out, &rows);
+    int rc = refuse_exr(who, ctx, p, ep, with_depth, out, &rows);
     if (rc) return rc;
     if (features) {
         if ((features & ~EXR_ALL_FEATURES) != 0) return fail(NDT_E_INVALID, "%s: feature mask %d: id 1, position 2, normal 4", who, features);
@@ -601,6 +585,22 @@ int render_file(const char *who, ndt_hip_ctx *ctx, const ndt_render_params *p, i
 }
 
 } // namespace
+
+// what the render entries check before any device work; *rows: the shard's
+int ndt_impl::refuse_exr(const char *who, ndt_hip_ctx *ctx, const ndt_render_params *p, const ndt_exr_params *ep, int with_depth, uint8_t *out, int *rows)
+{
+    if (!ctx || !p || !out) return fail(NDT_E_INVALID, "%s: NULL argument", who);
+    if (p->width < 1 || p->height < 1 || p->row_step < 1 || p->row_begin < 0)
+        return fail(NDT_E_INVALID, "%s: bad geometry: %d x %d, rows %d by %d", who, p->width, p->height, p->row_begin, p->row_step);
+    *rows = ndt_hip_shard_rows(p->height, p->row_begin, p->row_step);
+    if (*rows < 1) return refuse_empty_shard(who, *rows);
+    const int pixel_type = pixel_type_of(ep);
+    if (pixel_type < 0) return fail(NDT_E_INVALID, "%s: pixel type %d: 1 is half, 2 float (0: half)", who, ep->pixel_type);
+    ExrLayout L;
+    if (!layout_of(p->width, *rows, pixel_type, with_depth != 0, L))
+        return fail(NDT_E_INVALID, "%s: the samples of a %d x %d image exceed 2^31 - 1 bytes", who, p->width, *rows);
+    return NDT_OK;
+}
 
 void ndt_impl::free_exr(ndt_hip_ctx *ctx)
 {

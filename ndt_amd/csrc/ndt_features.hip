@@ -87,7 +87,7 @@ int ndt_impl::features_check(const char *who, ndt_hip_ctx *ctx, const ndt_render
     if (p->stereo != NDT_STEREO_MONO && !ctx->have_eyes)
         return fail(NDT_E_INVALID, "%s: stereo needs leftEye / rightEye (camera.h:60-61) in the flat scene", who);
     *rows = ndt_hip_shard_rows(p->height, p->row_begin, p->row_step);
-    if (*rows < 1) return fail(NDT_E_INVALID, "%s: the shard has no rows", who);
+    if (*rows < 1) return refuse_empty_shard(who, *rows);
     const long long n_primary = (long long)((p->width + 7) / 8) * ((*rows + 7) / 8) * 64;
     if (n_primary > 0x3fffffffLL) return fail(NDT_E_UNSUPPORTED, "%s: image too large for one call", who);
     return NDT_OK;

@@ -652,10 +652,9 @@ extern "C" int ndt_hip_render_jpeg(ndt_hip_ctx *ctx, const ndt_render_params *p,
     if (!ctx || !p || !jpg) return fail(NDT_E_INVALID, "ndt_hip_render_jpeg: NULL argument");
     if (p->width < 1 || p->height < 1 || p->row_step < 1 || p->row_begin < 0) return fail(NDT_E_INVALID, "bad geometry");
     const int rows = ndt_hip_shard_rows(p->height, p->row_begin, p->row_step);
-    if (rows < 1) return fail(NDT_E_INVALID, "ndt_hip_render_jpeg: the shard has no rows");
     JpegGeom g;
     int rc;
-    if ((rc = geometry("ndt_hip_render_jpeg", p->width, rows, jp, &g))) return rc;
+    if ((rc = refuse_empty_shard("ndt_hip_render_jpeg", rows)) || (rc = geometry("ndt_hip_render_jpeg", p->width, rows, jp, &g))) return rc;
     HIP_TRY(hipSetDevice(ctx->device));
     if ((rc = ctx->jpeg.d_rgba8.reserve((size_t)p->width * (size_t)rows * 4, ctx->stream, "ndt_hip_render_jpeg"))) return rc;
     ndt_hip_ctx *one[1] = { ctx };

@@ -413,16 +413,15 @@ int encode_device(ndt_hip_ctx *ctx, const char *who, const void *d_image, int32_
 {
     if (!ctx || !d_image || !png) return fail(NDT_E_INVALID, "%s: NULL argument", who);
     if (width < 1 || rows < 1) return fail(NDT_E_INVALID, "%s: a %d x %d image", who, width, rows);
-    if (stream_bytes(width, rows, f.bpp) < 0)
-        return fail(NDT_E_INVALID, "%s: the filtered stream of a %d x %d image exceeds 2^31 - 1 bytes", who, width, rows);
+    int rc = refuse_png(who, width, rows, f.bpp);
+    if (rc) return rc;
     if (cap < 0) return fail(NDT_E_INVALID, "%s: cap %lld", who, (long long)cap);
     if (((uintptr_t)d_image & (uintptr_t)(f.bpp - 1)) != 0) return fail(NDT_E_INVALID, "%s: the image is not aligned to its %d-byte pixels", who, f.bpp);
     const auto t0 = std::chrono::steady_clock::now();
     PngInfo info;
     int n_chunks = 0;
     long long bound = 0;
-    int rc = make_file(ctx, who, d_image, width, rows, f, info, n_chunks, bound);
-    if (rc) return rc;
+    if ((rc = make_file(ctx, who, d_image, width, rows, f, info, n_chunks, bound))) return rc;
     PngState &ps = ctx->png;
     hipStream_t s = ctx->stream;
     if (stats) {
@@ -453,12 +452,11 @@ int upload_image(ndt_hip_ctx *ctx, const char *who, const void *image, int32_t w
 {
     if (!ctx || !image) return fail(NDT_E_INVALID, "%s: NULL argument", who);
     if (width < 1 || rows < 1) return fail(NDT_E_INVALID, "%s: a %d x %d image", who, width, rows);
-    if (stream_bytes(width, rows, f.bpp) < 0)
-        return fail(NDT_E_INVALID, "%s: the filtered stream of a %d x %d image exceeds 2^31 - 1 bytes", who, width, rows);
+    int rc = refuse_png(who, width, rows, f.bpp);
+    if (rc) return rc;
     HIP_TRY(hipSetDevice(ctx->device));
     const size_t bytes = (size_t)width * (size_t)rows * (size_t)f.bpp;
-    int rc = ctx->png.d_rgba8.reserve(bytes, ctx->stream, who);
-    if (rc) return rc;
+    if ((rc = ctx->png.d_rgba8.reserve(bytes, ctx->stream, who))) return rc;
     HIP_TRY(hipMemcpyAsync(ctx->png.d_rgba8.p, image, bytes, hipMemcpyHostToDevice, ctx->stream));
     return NDT_OK;
 }
@@ -569,12 +567,10 @@ extern "C" int ndt_hip_render_png(ndt_hip_ctx *ctx, const ndt_render_params *p, 
     if (!ctx || !p || !png) return fail(NDT_E_INVALID, "ndt_hip_render_png: NULL argument");
     if (p->width < 1 || p->height < 1 || p->row_step < 1 || p->row_begin < 0) return fail(NDT_E_INVALID, "bad geometry");
     const int rows = ndt_hip_shard_rows(p->height, p->row_begin, p->row_step);
-    if (rows < 1) return fail(NDT_E_INVALID, "ndt_hip_render_png: the shard has no rows");
-    if (stream_bytes(p->width, rows) < 0)
-        return fail(NDT_E_INVALID, "ndt_hip_render_png: the filtered stream of a %d x %d image exceeds 2^31 - 1 bytes", p->width, rows);
-    HIP_TRY(hipSetDevice(ctx->device));
-    int rc = ctx->png.d_rgba8.reserve((size_t)p->width * (size_t)rows * 4, ctx->stream, "ndt_hip_render_png");
+    int rc = refuse_png("ndt_hip_render_png", p->width, rows, 4);
     if (rc) return rc;
+    HIP_TRY(hipSetDevice(ctx->device));
+    if ((rc = ctx->png.d_rgba8.reserve((size_t)p->width * (size_t)rows * 4, ctx->stream, "ndt_hip_render_png"))) return rc;
     ndt_hip_ctx *one[1] = { ctx };
     if ((rc = ndt_hip_render_multi_device(one, 1, p, NDT_IMAGE_RGBA8, ctx->png.d_rgba8.p, render_stats))) return rc;
     return ndt_hip_encode_png_device(ctx, ctx->png.d_rgba8.p, p->width, rows, png, cap, stats);
@@ -586,17 +582,13 @@ extern "C" int ndt_hip_render_png16(ndt_hip_ctx *ctx, const ndt_render_params *p
     if (!ctx || !p || !png) return fail(NDT_E_INVALID, "ndt_hip_render_png16: NULL argument");
     if (p->width < 1 || p->height < 1 || p->row_step < 1 || p->row_begin < 0)
         return fail(NDT_E_INVALID, "ndt_hip_render_png16: bad geometry: %d x %d, rows %d by %d", p->width, p->height, p->row_begin, p->row_step);
-    const int rows = ndt_hip_shard_rows(p->height, p->row_begin, p->row_step);
-    if (rows < 1) return fail(NDT_E_INVALID, "ndt_hip_render_png16: the shard has no rows");
-    if (stream_bytes(p->width, rows, 8) < 0)
-        return fail(NDT_E_INVALID, "ndt_hip_render_png16: the filtered stream of a %d x %d image exceeds 2^31 - 1 bytes", p->width, rows);
-    HIP_TRY(hipSetDevice(ctx->device));
-    // the frame in doubles where ndt_hip_render leaves it, its 16-bit samples beside the encoder's buffers
-    const size_t pixels = (size_t)p->width * (size_t)rows;
-    int rc = ctx->d_out.reserve(pixels * 4 * sizeof(double), ctx->stream, "ndt_hip_render_png16");
+    int rc = refuse_png("ndt_hip_render_png16", p->width, ndt_hip_shard_rows(p->height, p->row_begin, p->row_step), 8);
     if (rc) return rc;
-    if ((rc = ctx->png.d_rgba16.reserve(pixels * 8, ctx->stream, "ndt_hip_render_png16"))) return rc;
-    if ((rc = ndt_hip_render_device(ctx, p, ctx->d_out.p, render_stats))) return rc;
-    if ((rc = ndt_hip_quantize16_device(ctx, ctx->d_out.p, ctx->png.d_rgba16.p, (int64_t)pixels))) return rc;
-    return encode_device(ctx, "ndt_hip_render_png16", ctx->png.d_rgba16.p, p->width, rows, PNG_RGBA16, png, cap, stats);
+    // the frame in doubles where ndt_hip_render leaves it, its 16-bit samples beside the encoder's buffers (the encoder under this
+    // entry's own name: not deliver_png16)
+    FrameView v;
+    if ((rc = render_plain_own(ctx, "ndt_hip_render_png16", p, false, render_stats, &v))) return rc;
+    if ((rc = ctx->png.d_rgba16.reserve(v.pixels() * 8, ctx->stream, "ndt_hip_render_png16"))) return rc;
+    if ((rc = ndt_hip_quantize16_device(ctx, v.d_rgba, ctx->png.d_rgba16.p, (int64_t)v.pixels()))) return rc;
+    return encode_device(ctx, "ndt_hip_render_png16", ctx->png.d_rgba16.p, v.width, v.rows, PNG_RGBA16, png, cap, stats);
 }

@@ -1,5 +1,5 @@
 // ndt_render.hip -- ndt_hip_render*: render_image (ndt.c:900) behind the C ABI: argument checks, and the choice between
-// the deterministic pass, recursive anti-aliasing and the sampled paths.
+// the deterministic pass, recursive anti-aliasing and the sampled paths; and the delivery of frames staged on the device (FrameView).
 #include "ndt_ctx.hpp"
 
 // true anaglyph (ndt.c:643-647): red = luminance of the left eye's colour, blue = of the right eye's
@@ -135,18 +135,113 @@ extern "C" int ndt_hip_render(ndt_hip_ctx *ctx, const ndt_render_params *p, doub
 extern "C" int ndt_hip_render_depth(ndt_hip_ctx *ctx, const ndt_render_params *p, double *rgba, double *depth, ndt_render_stats *stats)
 {
     if (!ctx || !p || !rgba) return fail(NDT_E_INVALID, "NULL argument");
+    FrameView v;
+    const int rc = render_plain_own(ctx, "ndt_hip_render", p, depth != nullptr, stats, &v);
+    if (rc || v.rows == 0) return rc;
+    return deliver_doubles(ctx, v, rgba, depth);
+}
+
+int ndt_impl::render_plain_own(ndt_hip_ctx *ctx, const char *who, const ndt_render_params *p, bool want_depth, ndt_render_stats *stats, FrameView *v)
+{
     HIP_TRY(hipSetDevice(ctx->device));
-    const int rows = ndt_hip_shard_rows(p->height, p->row_begin, p->row_step);
-    const size_t img_bytes = (size_t)rows * (size_t)(p->width > 0 ? p->width : 0) * 4 * sizeof(double);
-    const size_t bytes = img_bytes + (depth ? img_bytes / 4 : 0);      // the depth map sits behind the image
-    if (img_bytes == 0) return ndt_hip_render_depth_device(ctx, p, (void *)rgba, nullptr, stats);
-    int rc = ctx->d_out.reserve(bytes, ctx->stream, "ndt_hip_render");
+    *v = FrameView{ nullptr, nullptr, nullptr, p->width, p->width > 0 ? ndt_hip_shard_rows(p->height, p->row_begin, p->row_step) : 0 };
+    if (v->rows == 0) return ndt_hip_render_depth_device(ctx, p, (void *)ctx, nullptr, stats);
+    const size_t img_bytes = v->pixels() * 4 * sizeof(double);
+    const int rc = ctx->d_out.reserve(img_bytes + (want_depth ? img_bytes / 4 : 0), ctx->stream, who);      // the map sits behind the image
     if (rc) return rc;
-    void *d_depth = depth ? (void *)(ctx->d_out.as<char>() + img_bytes) : nullptr;
-    if ((rc = ndt_hip_render_depth_device(ctx, p, ctx->d_out.p, d_depth, stats))) return rc;
-    HIP_TRY(hipMemcpyAsync(rgba, ctx->d_out.p, img_bytes, hipMemcpyDeviceToHost, ctx->stream));
-    if (depth) HIP_TRY(hipMemcpyAsync(depth, d_depth, img_bytes / 4, hipMemcpyDeviceToHost, ctx->stream));
+    v->d_rgba = ctx->d_out.p;
+    if (want_depth) v->d_depth = ctx->d_out.as<char>() + img_bytes;
+    return ndt_hip_render_depth_device(ctx, p, ctx->d_out.p, (void *)v->d_depth, stats);
+}
+
+int ndt_impl::refuse_empty_shard(const char *who, int rows) { return rows < 1 ? fail(NDT_E_INVALID, "%s: the shard has no rows", who) : NDT_OK; }
+
+int ndt_impl::refuse_png(const char *who, int32_t width, int32_t rows, int bpp)
+{
+    if (rows < 1) return refuse_empty_shard(who, rows);
+    if ((bpp == 4 ? ndt_hip_png_bound(width, rows) : ndt_hip_png16_bound(width, rows, bpp == 8 ? 4 : 1)) < 0)
+        return fail(NDT_E_INVALID, "%s: the filtered stream of a %d x %d image exceeds 2^31 - 1 bytes", who, width, rows);
+    return NDT_OK;
+}
+
+int ndt_impl::refuse_jpeg(const char *who, int32_t width, int32_t rows, const ndt_jpeg_params *jp)
+{
+    if (rows < 1) return refuse_empty_shard(who, rows);
+    if (ndt_hip_jpeg_bound(width, rows, jp) < 0)
+        return fail(NDT_E_INVALID, "%s: no JPEG of %d x %d with these parameters (a side above 65535, a quality outside 0 .. 100, a sampling outside 0 .. 1 or a reserved word set)",
+                    who, width, rows);
+    return NDT_OK;
+}
+
+// v.d_rgba8 becomes the frame's 8-bit image -- the producer's, or quantised into stage8 -- behind, where the sink takes the map, the
+// finished 8-bit map in *stage_depth8 and its range in range_out.  Queued, not synchronised.
+static int images8(ndt_hip_ctx *ctx, const char *who, FrameView &v, DeviceBuffer &stage8, DeviceBuffer *stage_depth8, double *range_out)
+{
+    int rc;
+    if (stage_depth8) {
+        if ((rc = stage_depth8->reserve(v.pixels() * 4, ctx->stream, who))) return rc;
+        if ((rc = ndt_hip_depth_rgba8_device(ctx, v.d_depth, (int64_t)v.pixels(), stage_depth8->p, range_out))) return rc;
+    }
+    if (v.d_rgba8) return NDT_OK;
+    if ((rc = stage8.reserve(v.pixels() * 4, ctx->stream, who))) return rc;
+    v.d_rgba8 = stage8.p;
+    return ndt_hip_quantize_device(ctx, v.d_rgba, stage8.p, (int64_t)v.pixels());
+}
+
+int ndt_impl::deliver_doubles(ndt_hip_ctx *ctx, const FrameView &v, double *rgba, double *depth)
+{
+    const size_t img_bytes = v.pixels() * 4 * sizeof(double);
+    HIP_TRY(hipMemcpyAsync(rgba, v.d_rgba, img_bytes, hipMemcpyDeviceToHost, ctx->stream));
+    if (depth) HIP_TRY(hipMemcpyAsync(depth, v.d_depth, img_bytes / 4, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     return NDT_OK;
 }
 
+int ndt_impl::deliver_rgba8(ndt_hip_ctx *ctx, const char *who, FrameView v, DeviceBuffer &stage8, uint8_t *rgba8, DeviceBuffer *stage_depth8,
+                            uint8_t *depth8, double *range_out)
+{
+    const int rc = images8(ctx, who, v, stage8, stage_depth8, range_out);
+    if (rc) return rc;
+    HIP_TRY(hipMemcpyAsync(rgba8, v.d_rgba8, v.pixels() * 4, hipMemcpyDeviceToHost, ctx->stream));
+    if (stage_depth8) HIP_TRY(hipMemcpyAsync(depth8, stage_depth8->p, v.pixels() * 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return NDT_OK;
+}
+
+int ndt_impl::deliver_png(ndt_hip_ctx *ctx, const char *who, FrameView v, DeviceBuffer &stage8, uint8_t *png, int64_t cap, ndt_png_stats *stats,
+                          DeviceBuffer *stage_depth8, uint8_t *depth_png, int64_t depth_cap, uint8_t *depth8, double *range_out)
+{
+    int rc = images8(ctx, who, v, stage8, stage_depth8, range_out);
+    if (rc) return rc;
+    if ((rc = ndt_hip_encode_png_device(ctx, v.d_rgba8, v.width, v.rows, png, cap, stats)) || !stage_depth8) return rc;
+    if (depth_png) return ndt_hip_encode_png_device(ctx, stage_depth8->p, v.width, v.rows, depth_png, depth_cap, stats ? &stats[1] : nullptr);
+    HIP_TRY(hipMemcpyAsync(depth8, stage_depth8->p, v.pixels() * 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return NDT_OK;
+}
+
+int ndt_impl::deliver_png16(ndt_hip_ctx *ctx, const char *who, const FrameView &v, DeviceBuffer &stage16, DeviceBuffer &stage_grey16,
+                            uint8_t *png, int64_t cap, uint8_t *depth_png, int64_t depth_cap, ndt_png_stats *stats, double *range_out)
+{
+    int rc = stage16.reserve(v.pixels() * 8, ctx->stream, who);
+    if (rc) return rc;
+    if ((rc = ndt_hip_quantize16_device(ctx, v.d_rgba, stage16.p, (int64_t)v.pixels()))) return rc;
+    if (depth_png) {
+        if ((rc = stage_grey16.reserve((v.pixels() * 2 + 3) & ~(size_t)3, ctx->stream, who))) return rc;
+        if ((rc = ndt_hip_depth_grey16_device(ctx, v.d_depth, (int64_t)v.pixels(), stage_grey16.p, range_out))) return rc;
+    }
+    if ((rc = ndt_hip_encode_png16_device(ctx, stage16.p, v.width, v.rows, 4, png, cap, stats)) || !depth_png) return rc;
+    return ndt_hip_encode_png16_device(ctx, stage_grey16.p, v.width, v.rows, 1, depth_png, depth_cap, stats ? &stats[1] : nullptr);
+}
+
+int ndt_impl::deliver_jpeg(ndt_hip_ctx *ctx, const char *who, FrameView v, DeviceBuffer &stage8, const ndt_jpeg_params *jp, uint8_t *jpg,
+                           int64_t cap, ndt_jpeg_stats *stats)
+{
+    const int rc = images8(ctx, who, v, stage8, nullptr, nullptr);
+    return rc ? rc : ndt_hip_encode_jpeg_device(ctx, v.d_rgba8, v.width, v.rows, jp, jpg, cap, stats);
+}
+
+int ndt_impl::deliver_exr(ndt_hip_ctx *ctx, const FrameView &v, const ndt_exr_params *ep, uint8_t *out, int64_t cap, ndt_exr_stats *stats)
+{
+    return ndt_hip_encode_exr_device(ctx, v.d_rgba, v.d_depth, v.width, v.rows, ep, out, cap, stats);
+}

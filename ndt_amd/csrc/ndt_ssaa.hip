@@ -199,21 +199,18 @@ int render_ssaa(ndt_hip_ctx *ctx, const ndt_render_params *p, int K, void *d_rgb
     return NDT_OK;
 }
 
-// the frame into the context's own buffers: ss.d_acc (doubles, the map behind them when wanted) and ss.d_rgba8
-int render_ssaa_own(ndt_hip_ctx *ctx, const ndt_render_params *p, int K, bool want_depth, bool want_rgba8, ndt_render_stats *stats, int *rows_out,
-                    size_t *pixels_out)
+// the frame into the context's own buffers, named by *v: ss.d_acc (doubles, the map behind them when wanted) and ss.d_rgba8
+int render_ssaa_own(ndt_hip_ctx *ctx, const ndt_render_params *p, int K, bool want_depth, bool want_rgba8, ndt_render_stats *stats, FrameView *v)
 {
     HIP_TRY(hipSetDevice(ctx->device));
     SsaaState &ss = ctx->ssaa;
-    const int rows = ndt_hip_shard_rows(p->height, p->row_begin, p->row_step);
-    const size_t pixels = (size_t)rows * (size_t)p->width;
-    *rows_out = rows;
-    *pixels_out = pixels;
-    const size_t img_bytes = pixels * 4 * sizeof(double);
+    *v = FrameView{ nullptr, nullptr, nullptr, p->width, ndt_hip_shard_rows(p->height, p->row_begin, p->row_step) };
+    const size_t pixels = v->pixels(), img_bytes = pixels * 4 * sizeof(double);
     int rc;
     if ((rc = ss.d_acc.reserve((img_bytes ? img_bytes : 32) + (want_depth ? img_bytes / 4 : 0), ctx->stream, "ndt_hip_render_ssaa*"))) return rc;
     if (want_rgba8 && (rc = ss.d_rgba8.reserve(pixels ? pixels * 4 : 4, ctx->stream, "ndt_hip_render_ssaa*"))) return rc;
-    return render_ssaa(ctx, p, K, ss.d_acc.p, want_depth ? (void *)(ss.d_acc.as<char>() + img_bytes) : nullptr, want_rgba8 ? ss.d_rgba8.p : nullptr, stats);
+    *v = FrameView{ ss.d_acc.p, want_depth ? ss.d_acc.as<char>() + img_bytes : nullptr, want_rgba8 ? ss.d_rgba8.p : nullptr, v->width, v->rows };
+    return render_ssaa(ctx, p, K, ss.d_acc.p, (void *)v->d_depth, (void *)v->d_rgba8, stats);
 }
 
 } // namespace
@@ -263,30 +260,23 @@ extern "C" int ndt_hip_render_ssaa_device(ndt_hip_ctx *ctx, const ndt_render_par
     return render_ssaa(ctx, p, K, d_rgba, d_depth, nullptr, stats);
 }
 
+// The delivering entries (a shard without rows: the host-memory sinks have nothing to write, the file sinks refuse it)
 extern "C" int ndt_hip_render_ssaa(ndt_hip_ctx *ctx, const ndt_render_params *p, int32_t K, double *rgba, double *depth, ndt_render_stats *stats)
 {
     int rc = refuse("ndt_hip_render_ssaa", ctx, p, K, rgba);
     if (rc) return rc;
-    int rows = 0;
-    size_t pixels = 0;
-    if ((rc = render_ssaa_own(ctx, p, K, depth != nullptr, false, stats, &rows, &pixels)) || pixels == 0) return rc;
-    const size_t img_bytes = pixels * 4 * sizeof(double);
-    HIP_TRY(hipMemcpyAsync(rgba, ctx->ssaa.d_acc.p, img_bytes, hipMemcpyDeviceToHost, ctx->stream));
-    if (depth) HIP_TRY(hipMemcpyAsync(depth, ctx->ssaa.d_acc.as<char>() + img_bytes, img_bytes / 4, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    return NDT_OK;
+    FrameView v;
+    if ((rc = render_ssaa_own(ctx, p, K, depth != nullptr, false, stats, &v)) || v.rows == 0) return rc;
+    return deliver_doubles(ctx, v, rgba, depth);
 }
 
 extern "C" int ndt_hip_render_ssaa_rgba8(ndt_hip_ctx *ctx, const ndt_render_params *p, int32_t K, uint8_t *rgba8, ndt_render_stats *stats)
 {
     int rc = refuse("ndt_hip_render_ssaa_rgba8", ctx, p, K, rgba8);
     if (rc) return rc;
-    int rows = 0;
-    size_t pixels = 0;
-    if ((rc = render_ssaa_own(ctx, p, K, false, true, stats, &rows, &pixels)) || pixels == 0) return rc;
-    HIP_TRY(hipMemcpyAsync(rgba8, ctx->ssaa.d_rgba8.p, pixels * 4, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    return NDT_OK;
+    FrameView v;
+    if ((rc = render_ssaa_own(ctx, p, K, false, true, stats, &v)) || v.rows == 0) return rc;
+    return deliver_rgba8(ctx, "ndt_hip_render_ssaa_rgba8", v, ctx->ssaa.d_rgba8, rgba8);
 }
 
 int ndt_impl::render_ssaa_rgba8_own(ndt_hip_ctx *ctx, const char *who, const ndt_render_params *p, int K, ndt_render_stats *stats,
@@ -294,61 +284,47 @@ int ndt_impl::render_ssaa_rgba8_own(ndt_hip_ctx *ctx, const char *who, const ndt
 {
     int rc = refuse(who, ctx, p, K, d_rgba8);
     if (rc) return rc;
-    int rows = 0;
-    size_t pixels = 0;
-    if ((rc = render_ssaa_own(ctx, p, K, false, true, stats, &rows, &pixels))) return rc;
-    *d_rgba8 = ctx->ssaa.d_rgba8.p;
+    FrameView v;
+    if ((rc = render_ssaa_own(ctx, p, K, false, true, stats, &v))) return rc;
+    *d_rgba8 = v.d_rgba8;
     return NDT_OK;
 }
 
 extern "C" int ndt_hip_render_ssaa_png(ndt_hip_ctx *ctx, const ndt_render_params *p, int32_t K, uint8_t *png, int64_t cap, ndt_png_stats *stats,
                                        ndt_render_stats *render_stats)
 {
-    int rc = refuse("ndt_hip_render_ssaa_png", ctx, p, K, png);
+    const char *who = "ndt_hip_render_ssaa_png";
+    int rc = refuse(who, ctx, p, K, png);
     if (rc) return rc;
-    const int shard = ndt_hip_shard_rows(p->height, p->row_begin, p->row_step);
-    if (shard < 1) return fail(NDT_E_INVALID, "ndt_hip_render_ssaa_png: the shard has no rows");
-    if (ndt_hip_png_bound(p->width, shard) < 0)
-        return fail(NDT_E_INVALID, "ndt_hip_render_ssaa_png: the filtered stream of a %d x %d image exceeds 2^31 - 1 bytes", p->width, shard);
-    int rows = 0;
-    size_t pixels = 0;
-    if ((rc = render_ssaa_own(ctx, p, K, false, true, render_stats, &rows, &pixels))) return rc;
-    return ndt_hip_encode_png_device(ctx, ctx->ssaa.d_rgba8.p, p->width, rows, png, cap, stats);
+    if ((rc = refuse_png(who, p->width, ndt_hip_shard_rows(p->height, p->row_begin, p->row_step), 4))) return rc;
+    FrameView v;
+    if ((rc = render_ssaa_own(ctx, p, K, false, true, render_stats, &v))) return rc;
+    return deliver_png(ctx, who, v, ctx->ssaa.d_rgba8, png, cap, stats);
 }
 
 extern "C" int ndt_hip_render_ssaa_jpeg(ndt_hip_ctx *ctx, const ndt_render_params *p, int32_t K, const ndt_jpeg_params *jp, uint8_t *jpg,
                                         int64_t cap, ndt_jpeg_stats *stats, ndt_render_stats *render_stats)
 {
-    int rc = refuse("ndt_hip_render_ssaa_jpeg", ctx, p, K, jpg);
+    const char *who = "ndt_hip_render_ssaa_jpeg";
+    int rc = refuse(who, ctx, p, K, jpg);
     if (rc) return rc;
-    const int shard = ndt_hip_shard_rows(p->height, p->row_begin, p->row_step);
-    if (shard < 1) return fail(NDT_E_INVALID, "ndt_hip_render_ssaa_jpeg: the shard has no rows");
-    if (ndt_hip_jpeg_bound(p->width, shard, jp) < 0)
-        return fail(NDT_E_INVALID, "ndt_hip_render_ssaa_jpeg: no JPEG of %d x %d with these parameters (a side above 65535, a quality outside 0 .. 100, a sampling outside 0 .. 1 or a reserved word set)",
-                    p->width, shard);
-    int rows = 0;
-    size_t pixels = 0;
-    if ((rc = render_ssaa_own(ctx, p, K, false, true, render_stats, &rows, &pixels))) return rc;
-    return ndt_hip_encode_jpeg_device(ctx, ctx->ssaa.d_rgba8.p, p->width, rows, jp, jpg, cap, stats);
+    if ((rc = refuse_jpeg(who, p->width, ndt_hip_shard_rows(p->height, p->row_begin, p->row_step), jp))) return rc;
+    FrameView v;
+    if ((rc = render_ssaa_own(ctx, p, K, false, true, render_stats, &v))) return rc;
+    return deliver_jpeg(ctx, who, v, ctx->ssaa.d_rgba8, jp, jpg, cap, stats);
 }
 
 extern "C" int ndt_hip_render_ssaa_rgba8_depth(ndt_hip_ctx *ctx, const ndt_render_params *p, int32_t K, uint8_t *rgba8, uint8_t *depth8,
                                                double *range_out, ndt_render_stats *stats)
 {
-    int rc = refuse("ndt_hip_render_ssaa_rgba8_depth", ctx, p, K, rgba8);
+    const char *who = "ndt_hip_render_ssaa_rgba8_depth";
+    int rc = refuse(who, ctx, p, K, rgba8);
     if (rc) return rc;
-    if (!depth8) return fail(NDT_E_INVALID, "ndt_hip_render_ssaa_rgba8_depth: NULL argument");
-    int rows = 0;
-    size_t pixels = 0;
+    if (!depth8) return fail(NDT_E_INVALID, "%s: NULL argument", who);
     if (range_out) range_out[0] = range_out[1] = 0.0;
-    if ((rc = render_ssaa_own(ctx, p, K, true, true, stats, &rows, &pixels)) || pixels == 0) return rc;
-    SsaaState &ss = ctx->ssaa;
-    if ((rc = ss.d_depth8.reserve(pixels * 4, ctx->stream, "ndt_hip_render_ssaa_rgba8_depth"))) return rc;
-    if ((rc = ndt_hip_depth_rgba8_device(ctx, ss.d_acc.as<char>() + pixels * 4 * sizeof(double), (int64_t)pixels, ss.d_depth8.p, range_out))) return rc;
-    HIP_TRY(hipMemcpyAsync(rgba8, ss.d_rgba8.p, pixels * 4, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(depth8, ss.d_depth8.p, pixels * 4, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    return NDT_OK;
+    FrameView v;
+    if ((rc = render_ssaa_own(ctx, p, K, true, true, stats, &v)) || v.rows == 0) return rc;
+    return deliver_rgba8(ctx, who, v, ctx->ssaa.d_rgba8, rgba8, &ctx->ssaa.d_depth8, depth8, range_out);
 }
 
 // the 16-bit files: the finished accumulator through ndt_hip_quantize16_device (one launch behind the last fold, which is left as
@@ -358,24 +334,11 @@ static int ssaa_png16(const char *who, ndt_hip_ctx *ctx, const ndt_render_params
 {
     int rc = refuse(who, ctx, p, K, png);
     if (rc) return rc;
-    const int shard = ndt_hip_shard_rows(p->height, p->row_begin, p->row_step);
-    if (shard < 1) return fail(NDT_E_INVALID, "%s: the shard has no rows", who);
-    if (ndt_hip_png16_bound(p->width, shard, 4) < 0)
-        return fail(NDT_E_INVALID, "%s: the filtered stream of a %d x %d image exceeds 2^31 - 1 bytes", who, p->width, shard);
+    if ((rc = refuse_png(who, p->width, ndt_hip_shard_rows(p->height, p->row_begin, p->row_step), 8))) return rc;
     if (range_out) range_out[0] = range_out[1] = 0.0;
-    int rows = 0;
-    size_t pixels = 0;
-    if ((rc = render_ssaa_own(ctx, p, K, depth_png != nullptr, false, render_stats, &rows, &pixels))) return rc;
-    SsaaState &ss = ctx->ssaa;
-    if ((rc = ss.d_rgba16.reserve(pixels * 8, ctx->stream, who))) return rc;
-    if ((rc = ndt_hip_quantize16_device(ctx, ss.d_acc.p, ss.d_rgba16.p, (int64_t)pixels))) return rc;
-    if (depth_png) {
-        if ((rc = ss.d_grey16.reserve((pixels * 2 + 3) & ~(size_t)3, ctx->stream, who))) return rc;
-        if ((rc = ndt_hip_depth_grey16_device(ctx, ss.d_acc.as<char>() + pixels * 4 * sizeof(double), (int64_t)pixels, ss.d_grey16.p, range_out))) return rc;
-    }
-    if ((rc = ndt_hip_encode_png16_device(ctx, ss.d_rgba16.p, p->width, rows, 4, png, cap, stats))) return rc;
-    if (!depth_png) return NDT_OK;
-    return ndt_hip_encode_png16_device(ctx, ss.d_grey16.p, p->width, rows, 1, depth_png, depth_cap, stats ? &stats[1] : nullptr);
+    FrameView v;
+    if ((rc = render_ssaa_own(ctx, p, K, depth_png != nullptr, false, render_stats, &v))) return rc;
+    return deliver_png16(ctx, who, v, ctx->ssaa.d_rgba16, ctx->ssaa.d_grey16, png, cap, depth_png, depth_cap, stats, range_out);
 }
 
 extern "C" int ndt_hip_render_ssaa_png16(ndt_hip_ctx *ctx, const ndt_render_params *p, int32_t K, uint8_t *png, int64_t cap, ndt_png_stats *stats,

@@ -882,44 +882,45 @@ class NdtHip:
         "device": left at raw device pointer `d_rgba_ptr`, returns the stats; "rgba8": the (rows, width, 4) uint8 image;
         "png" / "jpeg" / "exr": the file's bytes (self.png_stats / jpeg_stats / exr_stats keep the record) -- each with the stats."""
         p = self.params(width, height, depth, **kw)
-        rows = shard_rows(height, p.row_begin, p.row_step)
         dp = denoise_params(iterations, sigma_colour, sigma_plane, normal_power_log2)
+        return self._staged_sink("ndt_hip_render_denoised", (self.ctx, C.byref(p), C.byref(dp)), sink, (None, "device", "rgba8", "png", "jpeg", "exr"),
+                                 shard_rows(height, p.row_begin, p.row_step), width, device=(d_rgba_ptr,), quality=quality, sampling=sampling,
+                                 pixel=pixel, cap=cap)
+
+    def _staged_sink(self, stem, head, sink, sinks, rows, width, device=(), extra=(), quality=95, sampling="420", pixel="half", cap=None):
+        """The sink ladder of the entries that stage a frame on the device -- <stem>, <stem>_device, _rgba8, _png, _jpeg, _exr, each
+        called with `head` in front: allocates the output, keeps the file's record in self.png_stats / jpeg_stats / exr_stats, slices
+        the file.  sinks: those `stem` has; device: the raw device pointers of "device"; extra: further host arrays of sink None,
+        returned behind the image.  Every answer ends with the RenderStats."""
+        if sink not in sinks:
+            raise ValueError("sink %r is none of %s" % (sink, ", ".join(repr(name) for name in sinks)))
         st = RenderStats()
         if sink is None:
             out = np.zeros((rows, width, 4), dtype=np.float64)
-            self._check(self.lib.ndt_hip_render_denoised(self.ctx, C.byref(p), C.byref(dp), out.ctypes.data, C.byref(st)))
-            return out, st
+            self._check(getattr(self.lib, stem)(*head, out.ctypes.data, *[a.ctypes.data for a in extra], C.byref(st)))
+            return (out,) + tuple(extra) + (st,)
         if sink == "device":
-            self._check(self.lib.ndt_hip_render_denoised_device(self.ctx, C.byref(p), C.byref(dp), C.c_void_p(d_rgba_ptr), C.byref(st)))
+            self._check(getattr(self.lib, stem + "_device")(*head, *[C.c_void_p(d) if d else None for d in device], C.byref(st)))
             return st
         if sink == "rgba8":
             out = np.zeros((rows, width, 4), dtype=np.uint8)
-            self._check(self.lib.ndt_hip_render_denoised_rgba8(self.ctx, C.byref(p), C.byref(dp), out.ctypes.data, C.byref(st)))
+            self._check(getattr(self.lib, stem + "_rgba8")(*head, out.ctypes.data, C.byref(st)))
             return out, st
         if sink == "png":
-            cap = png_bound(width, rows) if cap is None else int(cap)
-            out = np.zeros(max(cap, 1), dtype=np.uint8)
-            self.png_stats = PngStats()
-            self._check(self.lib.ndt_hip_render_denoised_png(self.ctx, C.byref(p), C.byref(dp), out.ctypes.data, cap, C.byref(self.png_stats),
-                                                             C.byref(st)))
-            return out[:self.png_stats.png_bytes].tobytes(), st
-        if sink == "jpeg":
+            params, bound, size, stats = (), lambda: png_bound(width, rows), "png_bytes", PngStats()
+            self.png_stats = stats
+        elif sink == "jpeg":
             jp = jpeg_params(quality, sampling)
-            cap = jpeg_bound(width, rows, quality, sampling) if cap is None else int(cap)
-            out = np.zeros(max(cap, 1), dtype=np.uint8)
-            self.jpeg_stats = JpegStats()
-            self._check(self.lib.ndt_hip_render_denoised_jpeg(self.ctx, C.byref(p), C.byref(dp), C.byref(jp), out.ctypes.data, cap,
-                                                              C.byref(self.jpeg_stats), C.byref(st)))
-            return out[:self.jpeg_stats.jpeg_bytes].tobytes(), st
-        if sink == "exr":
+            params, bound, size, stats = (C.byref(jp),), lambda: jpeg_bound(width, rows, quality, sampling), "jpeg_bytes", JpegStats()
+            self.jpeg_stats = stats
+        else:
             ep = exr_params(pixel)
-            cap = exr_bound(width, rows, pixel) if cap is None else int(cap)
-            out = np.zeros(max(cap, 1), dtype=np.uint8)
-            self.exr_stats = ExrStats()
-            self._check(self.lib.ndt_hip_render_denoised_exr(self.ctx, C.byref(p), C.byref(dp), C.byref(ep), out.ctypes.data, cap,
-                                                             C.byref(self.exr_stats), C.byref(st)))
-            return out[:self.exr_stats.file_bytes].tobytes(), st
-        raise ValueError("sink %r is none of None, 'device', 'rgba8', 'png', 'jpeg', 'exr'" % (sink,))
+            params, bound, size, stats = (C.byref(ep),), lambda: exr_bound(width, rows, pixel), "file_bytes", ExrStats()
+            self.exr_stats = stats
+        cap = bound() if cap is None else int(cap)
+        out = np.zeros(max(cap, 1), dtype=np.uint8)
+        self._check(getattr(self.lib, stem + "_" + sink)(*head, *params, out.ctypes.data, cap, C.byref(stats), C.byref(st)))
+        return out[:getattr(stats, size)].tobytes(), st
 
     def render_ao(self, width, height, depth, samples=16, radius=0.0, seed=0, dirs=False, frame_samples=1, **kw):
         """ndt_hip_render_ao: the ambient occlusion of the frame render(**kw) gives -- for every pixel the cosine-weighted share of
@@ -973,35 +974,9 @@ class NdtHip:
         p = self.params(width, height, depth, samples=frame_samples, **kw)
         rows = shard_rows(height, p.row_begin, p.row_step)
         ap = ao_params(samples, radius, seed, strength)
-        st = RenderStats()
-        if sink is None:
-            out, plane = np.zeros((rows, width, 4), dtype=np.float64), np.zeros((rows, width), dtype=np.float64)
-            self._check(self.lib.ndt_hip_render_ao_shaded(self.ctx, C.byref(p), C.byref(ap), out.ctypes.data, plane.ctypes.data, C.byref(st)))
-            return out, plane, st
-        if sink == "device":
-            self._check(self.lib.ndt_hip_render_ao_shaded_device(self.ctx, C.byref(p), C.byref(ap), C.c_void_p(d_rgba_ptr),
-                                                                 C.c_void_p(d_ao_ptr) if d_ao_ptr else None, C.byref(st)))
-            return st
-        if sink == "rgba8":
-            out = np.zeros((rows, width, 4), dtype=np.uint8)
-            self._check(self.lib.ndt_hip_render_ao_shaded_rgba8(self.ctx, C.byref(p), C.byref(ap), out.ctypes.data, C.byref(st)))
-            return out, st
-        if sink == "png":
-            cap = png_bound(width, rows) if cap is None else int(cap)
-            out = np.zeros(max(cap, 1), dtype=np.uint8)
-            self.png_stats = PngStats()
-            self._check(self.lib.ndt_hip_render_ao_shaded_png(self.ctx, C.byref(p), C.byref(ap), out.ctypes.data, cap, C.byref(self.png_stats),
-                                                              C.byref(st)))
-            return out[:self.png_stats.png_bytes].tobytes(), st
-        if sink == "jpeg":
-            jp = jpeg_params(quality, sampling)
-            cap = jpeg_bound(width, rows, quality, sampling) if cap is None else int(cap)
-            out = np.zeros(max(cap, 1), dtype=np.uint8)
-            self.jpeg_stats = JpegStats()
-            self._check(self.lib.ndt_hip_render_ao_shaded_jpeg(self.ctx, C.byref(p), C.byref(ap), C.byref(jp), out.ctypes.data, cap,
-                                                               C.byref(self.jpeg_stats), C.byref(st)))
-            return out[:self.jpeg_stats.jpeg_bytes].tobytes(), st
-        raise ValueError("sink %r is none of None, 'device', 'rgba8', 'png', 'jpeg'" % (sink,))
+        plane = (np.zeros((rows, width), dtype=np.float64),) if sink is None else ()
+        return self._staged_sink("ndt_hip_render_ao_shaded", (self.ctx, C.byref(p), C.byref(ap)), sink, (None, "device", "rgba8", "png", "jpeg"),
+                                 rows, width, device=(d_rgba_ptr, d_ao_ptr), extra=plane, quality=quality, sampling=sampling, cap=cap)
 
     def apng_begin(self, width, rows, n_frames, delay_num=1, delay_den=24, n_plays=0):
         """ndt_hip_apng_begin: opens the context's animated-PNG session: n_frames frames of width x rows pixels are to come, each
@@ -1178,32 +1153,18 @@ class NdtHip:
     def render_ssaa_rgba8(self, width, height, depth, ssaa, **kw):
         """ndt_hip_render_ssaa_rgba8: the supersampled frame as the bytes the reference stores: ((rows, width, 4) uint8, stats)."""
         p, rows = self._ssaa_params(width, height, depth, kw)
-        out = np.zeros((rows, width, 4), dtype=np.uint8)
-        st = RenderStats()
-        self._check(self.lib.ndt_hip_render_ssaa_rgba8(self.ctx, C.byref(p), int(ssaa), out.ctypes.data, C.byref(st)))
-        return out, st
+        return self._staged_sink("ndt_hip_render_ssaa", (self.ctx, C.byref(p), int(ssaa)), "rgba8", ("rgba8",), rows, width)
 
     def render_ssaa_png(self, width, height, depth, ssaa, **kw):
         """ndt_hip_render_ssaa_png: ... as a PNG file made on the device: (the file's bytes, stats); self.png_stats keeps the record."""
         p, rows = self._ssaa_params(width, height, depth, kw)
-        cap = png_bound(width, rows)
-        out = np.zeros(cap, dtype=np.uint8)
-        st = RenderStats()
-        self.png_stats = PngStats()
-        self._check(self.lib.ndt_hip_render_ssaa_png(self.ctx, C.byref(p), int(ssaa), out.ctypes.data, cap, C.byref(self.png_stats), C.byref(st)))
-        return out[:self.png_stats.png_bytes].tobytes(), st
+        return self._staged_sink("ndt_hip_render_ssaa", (self.ctx, C.byref(p), int(ssaa)), "png", ("png",), rows, width)
 
     def render_ssaa_jpeg(self, width, height, depth, ssaa, quality=95, sampling="420", **kw):
         """ndt_hip_render_ssaa_jpeg: ... as a JPEG file made on the device: (the file's bytes, stats); self.jpeg_stats keeps the record."""
         p, rows = self._ssaa_params(width, height, depth, kw)
-        jp = jpeg_params(quality, sampling)
-        cap = jpeg_bound(width, rows, quality, sampling)
-        out = np.zeros(cap, dtype=np.uint8)
-        st = RenderStats()
-        self.jpeg_stats = JpegStats()
-        self._check(self.lib.ndt_hip_render_ssaa_jpeg(self.ctx, C.byref(p), int(ssaa), C.byref(jp), out.ctypes.data, cap,
-                                                      C.byref(self.jpeg_stats), C.byref(st)))
-        return out[:self.jpeg_stats.jpeg_bytes].tobytes(), st
+        return self._staged_sink("ndt_hip_render_ssaa", (self.ctx, C.byref(p), int(ssaa)), "jpeg", ("jpeg",), rows, width, quality=quality,
+                                 sampling=sampling)
 
     def render_ssaa_rgba8_depth(self, width, height, depth, ssaa, **kw):
         """ndt_hip_render_ssaa_rgba8_depth: the supersampled frame's bytes and its map (sub-sample (0, 0)'s) finished on the device:

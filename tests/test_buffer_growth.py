@@ -93,6 +93,18 @@ SINKS = [
     Sink("render_ssaa", frames("render_ssaa", ssaa=2, depth_map=True)),
     Sink("render_ssaa_rgba8", frames("render_ssaa_rgba8", ssaa=2)),
     Sink("render_ssaa_png16", frames("render_ssaa_png16", ssaa=2, depth_map=True)),
+    Sink("render_ssaa_png", frames("render_ssaa_png", ssaa=2)),
+    Sink("render_ssaa_jpeg", frames("render_ssaa_jpeg", ssaa=2)),
+    Sink("render_ssaa_rgba8_depth", frames("render_ssaa_rgba8_depth", ssaa=2)),
+    Sink("render_ssaa_exr", frames("render_ssaa_exr", ssaa=2, depth_map=True)),
+    Sink("render_exr", frames("render_exr", depth_map=True)),
+    Sink("render_denoised", frames("render_denoised")),
+    Sink("render_denoised_rgba8", frames("render_denoised", sink="rgba8")),
+    Sink("render_denoised_png", frames("render_denoised", sink="png")),
+    Sink("render_denoised_exr", frames("render_denoised", sink="exr")),
+    Sink("render_ao_shaded", frames("render_ao_shaded", samples=4)),
+    Sink("render_ao_shaded_rgba8", frames("render_ao_shaded", sink="rgba8", samples=4)),
+    Sink("render_ao_shaded_jpeg", frames("render_ao_shaded", sink="jpeg", samples=4)),
     Sink("render_aa", frames("render", aa=(AA["aa_diff"], AA["aa_depth"]))),                # the AaBuffers pool
     Sink("render_multi", multi_frame),                                                      # d_image, d_shard
     Sink("fit_spheres", fitted, scene=None, steps=[4, 64, 4]),                              # d_fit
