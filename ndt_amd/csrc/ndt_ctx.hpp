@@ -26,6 +26,8 @@
 //                    guided by the feature planes; kernel, launcher and C ABI
 //   ndt_ao.hip       ndt_hip_ao_device / ndt_hip_render_ao* / ndt_hip_render_exr_ao: ambient occlusion from the feature planes -- the
 //                    sample rays, the trace kernel as it is, the fold into a plane, the plane applied to a frame; kernels and C ABI
+//   ndt_shading.hpp  the arithmetic of apply_lights and get_ray_color on values, stated once for every kernel that shades: the
+//                    per-bounce and light-window kernels, the frame kernel (ndt_kernels.hip, ndt_stream.hpp), k_resolve (ndt_frame.hip)
 //   ndt_buffer.hpp   DeviceBuffer: the grow-only device buffers of the context and of its sinks, their one grow and free path
 #pragma once
 #include <hip/hip_runtime.h>

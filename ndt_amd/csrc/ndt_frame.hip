@@ -3,6 +3,7 @@
 // such pass; recursive anti-aliasing and the sampled paths call it once per level / round.
 #include "ndt_ctx.hpp"
 #include "ndt_finish.hpp"
+#include "ndt_shading.hpp"
 #include <stddef.h>
 
 static void free_stream_args(ndt_hip_ctx *ctx)
@@ -248,37 +249,24 @@ __global__ void k_stream_done(Workspace ws, StreamArgs sa, unsigned long long *d
 }
 
 // Bottom-up combine of one bounce: get_ray_color's blend of its own colour with the colours
-// its reflection / refraction children returned (ndt.c:402-429), in the reference's order.
+// its reflection / refraction children returned (blend_children, ndt_shading.hpp), with plain accesses.
 __device__ __forceinline__ void resolve_node(const double *blob, const SceneDesc &sd, const Workspace &ws, int specular, long long g)
 {
     if (ws.depth_left[g] <= 0) return;
     const int obj = ws.hit_obj[g];
     if (obj < 0) return;                        // background node: colour and count already final
-    const int mw = sd.off_mat + 8 * obj;
-    const double hitr[3] = { blob[mw + 3], blob[mw + 4], blob[mw + 5] };
+    const Surface sf = surface_of(blob, sd, obj, specular);
     double c[3] = { ws.clr[0 * ws.cap + g], ws.clr[1 * ws.cap + g], ws.clr[2 * ws.cap + g] };
     int cnt = ws.count[g];
-    const int refl = ws.child_refl[g];
-    if (refl != -1) {
-        double ref[3] = { 0.0, 0.0, 0.0 };
-        if (refl >= 0) {
-            ref[0] = ws.clr[0 * ws.cap + refl]; ref[1] = ws.clr[1 * ws.cap + refl]; ref[2] = ws.clr[2 * ws.cap + refl];
-            cnt += ws.count[refl];
-        }
-        for (int k = 0; k < 3; ++k) {
-            if (specular) c[k] = (1 - hitr[k]) * (c[k]) + (hitr[k]) * ref[k];     // ndt.c:405-407
-            else c[k] += hitr[k] * ref[k];                                         // ndt.c:411-413
+    const int child[2] = { ws.child_refl[g], ws.child_refr[g] };
+    double ref[2][3] = { { 0.0, 0.0, 0.0 }, { 0.0, 0.0, 0.0 } };        // (a child that was cut off, -2: black)
+    for (int j = 0; j < 2; ++j) {
+        if (child[j] >= 0) {
+            for (int k = 0; k < 3; ++k) ref[j][k] = ws.clr[k * ws.cap + child[j]];
+            cnt += ws.count[child[j]];
         }
     }
-    const int refr = ws.child_refr[g];
-    if (refr != -1) {
-        double ref[3] = { 0.0, 0.0, 0.0 };
-        if (refr >= 0) {
-            ref[0] = ws.clr[0 * ws.cap + refr]; ref[1] = ws.clr[1 * ws.cap + refr]; ref[2] = ws.clr[2 * ws.cap + refr];
-            cnt += ws.count[refr];
-        }
-        for (int k = 0; k < 3; ++k) c[k] += (1.0 - hitr[k]) * ref[k];              // ndt.c:426-428
-    }
+    blend_children(c, sf.refl, specular, child[0] != -1, ref[0], child[1] != -1, ref[1]);
     ws.clr[0 * ws.cap + g] = c[0];
     ws.clr[1 * ws.cap + g] = c[1];
     ws.clr[2 * ws.cap + g] = c[2];

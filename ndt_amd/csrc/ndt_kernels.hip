@@ -7,9 +7,10 @@
 //   k_trace        trace_kd (object.c:683) for every node of the bounce       -> (object, primitive)
 //   k_shade_emit   first half of apply_lights (ndt.c:71-259): hit point, same-side test,
 //                  spot cone, one shadow ray per light that passes            -> shadow queue
-//   k_trace        trace_kd for the shadow queue (dist_limit per ray)
-//   k_shade_finish second half of apply_lights (ndt.c:217-310) + the reflect / refract spawn
-//                  of get_ray_color (ndt.c:381-430)                           -> next bounce
+//                  + the reflect / refract spawn of get_ray_color (ndt.c:381-430)  -> next bounce
+//   k_trace        trace_kd for the shadow queue (dist_limit per ray) and for the next bounce's nodes
+//   k_shade_finish second half of apply_lights (ndt.c:217-310)                -> the node's own colour
+// (the arithmetic of both halves and of the spawn: ndt_shading.hpp)
 #if NDT_DIMS <= 5 && !defined(NDT_OUTLINE_SMALL)
 // inlined libm for the small vectors, out of line from 6-D on (ndt_device.hpp, NDT_LIBM)
 #define NDT_INLINE_LIBM 1
@@ -22,6 +23,7 @@
 #define NDT_SHADE_INLINE_ISECT 1
 #endif
 #include "ndt_kernels.hpp"
+#include "ndt_shading.hpp"
 #include <hip/hip_ext.h>
 #include <stdlib.h>
 #include <map>
@@ -1066,6 +1068,35 @@ NDT_DEV bool light_setup(const double *blob, const SceneDesc &sd, int li, const 
     return true;
 }
 
+// The two steps of a node's shadow rays that shade_emit_node and window_emit_node share (li_base: where the light window
+// starts in the whole list).  The third, the walk that stores the fired rays, stands in both: as one function it cost
+// k_shade_emit of 6-D six registers, 127 -> 133, and with them its fourth wavefront per SIMD (profiles/shading_once.md).
+// Which lights fire for this hit (ndt.c:113-208): one shadow ray per light that passes the same-side / cone tests.
+NDT_DEV unsigned long long emit_fire_mask(const double *blob, const SceneDesc &sd, const double (&src)[N], const double (&hit)[N],
+                                          const double (&nrm)[N], unsigned long long node_key, int li_base)
+{
+    unsigned long long fire = 0ull;
+    for (int li = 0; li < sd.n_lights; ++li) {
+        int type;
+        double lgt_pos[N], rev_light[N], light_vec[N], so[N];
+        ShadowSetup ss;
+        if (light_setup(blob, sd, li, src, hit, nrm, type, lgt_pos, rev_light, light_vec, so, ss, node_key, li_base)) fire |= 1ull << li;
+    }
+    return fire;
+}
+// Lane s learns how many lanes fire segment s's light.  (Every lane of a wavefront that has a shaded node calls.)
+NDT_DEV int emit_segment_votes(const double *blob, const SceneDesc &sd, unsigned long long fire)
+{
+    const int lane = __lane_id();
+    int my_total = 0, seg = 0;
+    for (int li = 0; li < sd.n_lights; ++li) {
+        if (blob_int(blob, light_word(sd, li), 0) == NDT_LIGHT_AMBIENT_) continue;     // wave-uniform
+        const unsigned long long vote = __ballot((fire >> li) & 1ull);
+        if (lane == seg) my_total = __popcll(vote);
+        ++seg;
+    }
+    return my_total;
+}
 // What the wavefronts of one shade_emit workgroup reserve together: every wavefront adds its wants here (LDS atomics,
 // which also hand it its offset inside the workgroup's share), ONE wavefront turns the sums into global reservations, and
 // the bases come back through LDS.  A global counter takes ~150 returning atomics per us; with a reservation per wavefront
@@ -1131,75 +1162,25 @@ NDT_DEV void shade_emit_node(const double *blob, const SceneDesc &sd, const Work
     // segments go out as ONE atomic instruction (lane s reserves for segment s), so a wavefront
     // waits for a single atomic round trip however many lights there are.
     const int lane = __lane_id();
-    unsigned long long fire = 0ull;
     const unsigned long long node_key = (rg.sample_keys && in_range) ? ws.rng_key[g] : 0ull;    // stochastic renders only
     NDT_SEC(0);
-    if (shaded) {
-        for (int li = 0; li < sd.n_lights; ++li) {
-            int type;
-            double lgt_pos[N], rev_light[N], light_vec[N], so[N];
-            ShadowSetup ss;
-            if (light_setup(blob, sd, li, src, hit, nrm, type, lgt_pos, rev_light, light_vec, so, ss, node_key)) fire |= 1ull << li;
-        }
-    }
+    const unsigned long long fire = shaded ? emit_fire_mask(blob, sd, src, hit, nrm, node_key, 0) : 0ull;
     NDT_SEC(1);
-    // lane s learns how many lanes fire segment s's light, and which light that is
-    int my_total = 0, seg = 0;
-    if (live) {
-        for (int li = 0; li < sd.n_lights; ++li) {
-            if (blob_int(blob, light_word(sd, li), 0) == NDT_LIGHT_AMBIENT_) continue;     // wave-uniform
-            const unsigned long long vote = __ballot((fire >> li) & 1ull);
-            if (lane == seg) my_total = __popcll(vote);
-            ++seg;
-        }
-    }
+    const int my_total = live ? emit_segment_votes(blob, sd, fire) : 0;
     if (shaded) ws.sh_mask[g] = fire;
     NDT_SEC(2);
     // get_ray_color, ndt.c:381-430: spawn reflection / refraction.  The children depend on the
     // hit only, not on the lighting, so they are created here -- before the shadow rays of this
     // bounce are traced -- and the host traces them in the SAME launch as those shadow rays.
-    bool want_refl = false, want_refr = false;
-    double refl_ray[N], refr_ray[N];
-    double refl_frac = 0, refr_frac = 0;
-    int depth_next = 0;
+    Children<N> ch;
     if (shaded) {
-        const int mw = sd.off_mat + 8 * obj;
-        const double refl_r = blob[mw + 3], refl_g = blob[mw + 4], refl_b = blob[mw + 5];
-        const bool transparent = blob[mw + 7] != 0.0;
-        const double frac = ws.frac[g];
-        depth_next = dl - 1;
-        const double gb2 = (refl_g > refl_b) ? refl_g : refl_b;
-        const double contrib = (refl_r > gb2) ? refl_r : gb2;
-        int c_refl = -1, c_refr = -1;
-        if (contrib > 0 && (refl_r != 0.0 || refl_g != 0.0 || refl_b != 0.0)) {
-            refl_frac = contrib * frac;
-            // child cut-offs (ndt.c:336-341) return black without tracing
-            if (refl_frac < (1.0 / 512.0) || depth_next <= 0) {
-                c_refl = -2;
-            } else {
-                v_reflect<N>(look, nrm, refl_ray, 1.0);
-                v_unitize<N>(refl_ray);
-                want_refl = true;
-            }
-        }
-        if (transparent) {
-            refr_frac = (1 - contrib) * frac;
-            if (refr_frac < (1.0 / 512.0) || depth_next <= 0) {
-                c_refr = -2;
-            } else {
-                double nrm_u[N];                                    // vectNd_refract unitizes the normal it is given (vectNd.c:155);
-                v_copy<N>(nrm_u, nrm);                              // the shadow rays below still need the original
-                v_refract<N>(look, nrm_u, refr_ray, blob[mw + 6]);
-                v_unitize<N>(refr_ray);
-                want_refr = true;
-            }
-        }
-        ws.child_refl[g] = c_refl;
-        ws.child_refr[g] = c_refr;
+        ch = children_of<N>(look, nrm, surface_of(blob, sd, obj, rg.specular), ws.frac[g], dl);
+        ws.child_refl[g] = ch.c_refl;
+        ws.child_refr[g] = ch.c_refr;
     }
     // Compact the children of this wavefront into the next bounce: one reservation per
     // wavefront, reflection rays first and refraction rays after them.
-    const unsigned long long v_refl = __ballot(want_refl), v_refr = __ballot(want_refr);
+    const unsigned long long v_refl = __ballot(ch.want_refl), v_refr = __ballot(ch.want_refr);
     const int n_refl = __popcll(v_refl), total = n_refl + __popcll(v_refr);
     // the workgroup's reservations: wants in, one wavefront asks the global counters, bases out
     int my_off = 0, wave_off = 0;
@@ -1217,16 +1198,16 @@ NDT_DEV void shade_emit_node(const double *blob, const SceneDesc &sd, const Work
     if (total > 0 && (long long)base + total > ws.cap) {
         // node pool overflow: flag it (the host renders the frame again with a larger pool), spawn nothing
         if (lane == 0) atomicOr(&ws.counters[2], 1);
-        want_refl = false;
-        want_refr = false;
+        ch.want_refl = false;
+        ch.want_refr = false;
     }
     const unsigned long long below = (1ull << lane) - 1ull;
-    if (want_refl) {
+    if (ch.want_refl) {
         const long long c = (long long)base + __popcll(v_refl & below);
         store_soa<N>(ws.ray_o, ws.cap, c, hit);
-        store_soa<N>(ws.ray_v, ws.cap, c, refl_ray);
-        ws.frac[c] = refl_frac;
-        ws.depth_left[c] = depth_next;
+        store_soa<N>(ws.ray_v, ws.cap, c, ch.refl_ray);
+        ws.frac[c] = ch.refl_frac;
+        ws.depth_left[c] = ch.depth_next;
         ws.child_refl[c] = -1;
         ws.child_refr[c] = -1;
         ws.count[c] = 0;
@@ -1234,12 +1215,12 @@ NDT_DEV void shade_emit_node(const double *blob, const SceneDesc &sd, const Work
         if (rg.sample_keys) ws.rng_key[c] = ndt_rng_mix(node_key ^ 0x1ull);
         ws.child_refl[g] = (int)c;
     }
-    if (want_refr) {
+    if (ch.want_refr) {
         const long long c = (long long)base + n_refl + __popcll(v_refr & below);
         store_soa<N>(ws.ray_o, ws.cap, c, hit);
-        store_soa<N>(ws.ray_v, ws.cap, c, refr_ray);
-        ws.frac[c] = refr_frac;
-        ws.depth_left[c] = depth_next;
+        store_soa<N>(ws.ray_v, ws.cap, c, ch.refr_ray);
+        ws.frac[c] = ch.refr_frac;
+        ws.depth_left[c] = ch.depth_next;
         ws.child_refl[c] = -1;
         ws.child_refr[c] = -1;
         ws.count[c] = 0;
@@ -1248,10 +1229,10 @@ NDT_DEV void shade_emit_node(const double *blob, const SceneDesc &sd, const Work
         ws.child_refr[g] = (int)c;
     }
     NDT_SEC(3);
-    // shadow rays into their segments
+    // shadow rays into their segments (window_emit_node holds the same walk: see emit_fire_mask)
     // (every lane walking only the lights it fires -- as the frame kernel does, ndt_stream.hpp -- was measured here: the
     // 1080p frames 2-4 % slower; these launches are throughput-bound and the shuffles cost more than the idle iterations)
-    seg = 0;
+    int seg = 0;
     for (int li = 0; live && li < sd.n_lights; ++li) {
         const int list_type = blob_int(blob, light_word(sd, li), 0);        // (wave-uniform)
         if (list_type == NDT_LIGHT_AMBIENT_) continue;
@@ -1270,13 +1251,8 @@ NDT_DEV void shade_emit_node(const double *blob, const SceneDesc &sd, const Work
             const long long slot = (long long)seg * lr.seg_stride + idx;
             ws.sh_idx[(long long)seg * ws.cap + g] = idx;
             if (!origin_known) store_soa<N>(ws.so, ws.sh_cap, slot, so);
-            // point/spot: from the light along light_vec (ndt.c:211); directional: from the
-            // nudged hit point along rev_light (ndt.c:238)
-            // (one store of a selected VALUE: two stores from different local arrays make the compiler pick the array
-            // through a pointer, which puts both in scratch)
             double dir[N];
-#pragma unroll
-            for (int c = 0; c < N; ++c) dir[c] = (type == NDT_LIGHT_DIRECTIONAL_) ? rev_light[c] : light_vec[c];
+            shadow_dir<N>(type, rev_light, light_vec, dir);
             store_soa<N>(ws.sv, ws.sh_cap, slot, dir);
             ws.slim[slot] = ss.dist_limit;
         }
@@ -1369,25 +1345,11 @@ NDT_DEV void shade_finish_node(const double *blob, const SceneDesc &sd, const Wo
         }
         // the hit point and normal trace_kd would have returned, as in shade_emit: same function, same operands, same bits
         isect_full(blob, &sd, prim_in, src, look, hit, nrm);
-        const int mw = sd.off_mat + 8 * obj;
-        const double hit_r = blob[mw], hit_g = blob[mw + 1], hit_b = blob[mw + 2];
-        const double refl_r = blob[mw + 3], refl_g = blob[mw + 4], refl_b = blob[mw + 5];
-        const bool transparent = blob[mw + 7] != 0.0;
-        double hitr_r = 0.0, hitr_g = 0.0, hitr_b = 0.0;
-        if (rg.specular) {
-            hitr_r = refl_r; hitr_g = refl_g; hitr_b = refl_b;
-        }
+        const Surface sf = surface_of(blob, sd, obj, rg.specular);
         // apply_lights, ndt.c:88-92: scn->ambient first
-        double cr, cg, cb;
-        if (CONT) {
-            cr = ws.clr[0 * ws.cap + g];
-            cg = ws.clr[1 * ws.cap + g];
-            cb = ws.clr[2 * ws.cap + g];
-        } else {
-            cr = hit_r * blob[sd.off_cam + 4 * N + 1];
-            cg = hit_g * blob[sd.off_cam + 4 * N + 2];
-            cb = hit_b * blob[sd.off_cam + 4 * N + 3];
-        }
+        double c[3];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) c[k] = CONT ? ws.clr[k * ws.cap + g] : sf.colour[k] * blob[sd.off_cam + 4 * N + 1 + k];
         int n_shadow = 0;
         // Every lane walks ITS lights -- the ones that fired a shadow ray for this hit, and the ambient ones, in the list's
         // order (the sums below are taken in that order, ndt.c:98) -- not the whole list: on the benchmark scene a hit fires
@@ -1396,86 +1358,36 @@ NDT_DEV void shade_finish_node(const double *blob, const SceneDesc &sd, const Wo
             const int li = __ffsll((long long)todo) - 1;
             const int w = light_word(sd, li);
             const int ltype = blob_int(blob, w, 0);
-            const double lr_ = blob[w + 1], lg_ = blob[w + 2], lb_ = blob[w + 3];
-            if (ltype == NDT_LIGHT_AMBIENT_) {              // ndt.c:106-111
-                cr += hit_r * lr_;
-                cg += hit_g * lg_;
-                cb += hit_b * lb_;
+            const double light[3] = { blob[w + 1], blob[w + 2], blob[w + 3] };
+            if (ltype == NDT_LIGHT_AMBIENT_) {
+                ambient_term(sf, light, c);
             } else {
-            // (if / else and one `lit`, no `continue`: every early continue of a divergent loop is a flag the compiler carries round it)
-            const int seg = __popcll(~ambient & ((1ull << li) - 1ull));         // its segment of the shadow queue
-            const long long slot = (long long)seg * lr.seg_stride + ws.sh_idx[(long long)seg * ws.cap + g];
-            int type;
-            double lgt_pos[N], rev_light[N], light_vec[N], so[N], light_hit_normal[N];
-            ShadowSetup ss;
-            light_setup(blob, sd, li, src, hit, nrm, type, lgt_pos, rev_light, light_vec, so, ss,
-                        rg.sample_keys ? ws.rng_key[g] : 0ull, li_base);
-            const int sobj = (li == li_first) ? sobj_first : ws.sobj[slot];
-            const int sprim = (li == li_first) ? sprim_first : ws.sprim[slot];
-            ++n_shadow;
-            bool lit;
-            if (type == NDT_LIGHT_DIRECTIONAL_) {
-                lit = sobj < 0;                             // anything at all shadows it, ndt.c:246
-                v_copy<N>(light_hit_normal, nrm);           // ndt.c:252-254
-            } else {
-                lit = sobj == obj;                          // ndt.c:217
-                if (lit) {
-                    double light_hit[N];
-                    isect_full(blob, &sd, sprim, so, light_vec, light_hit, light_hit_normal);
-                    const double dist = v_dist<N>(hit, light_hit);
-                    lit = !(dist > NDT_EPS);                // ndt.c:225
-                }
-            }
-            if (lit) {
-            double angle = v_angle<N>(nrm, light_vec);      // ndt.c:263
-            if (angle > NDT_PI / 2.0) angle = NDT_PI - angle;
-            const double light_scale = nd_cos(angle) / ss.ldist2;
-            if (!transparent) {
-                cr += hit_r * lr_ * light_scale;
-                cg += hit_g * lg_ * light_scale;
-                cb += hit_b * lb_ * light_scale;
-            }
-            if (rg.specular) {                              // ndt.c:276-310
-                double light_ref[N], rev_look[N];
-                v_reflect<N>(light_vec, light_hit_normal, light_ref, 0.5);
-                v_unitize<N>(light_ref);
-                v_scale<N>(look, -1, rev_look);
-                v_unitize<N>(rev_look);
-                double rv = v_dot<N>(light_ref, rev_look);
-                rv = (0 > rv) ? 0 : rv;                     // MAX(0,rv), image.h:31
-                const double rvn = nd_pow(rv, 50.0);
-                const double gb = (lg_ > lb_) ? lg_ : lb_;
-                const double max_light = (lr_ > gb) ? lr_ : gb;
-                cr += hitr_r * lr_ / max_light * rvn;
-                cg += hitr_g * lg_ / max_light * rvn;
-                cb += hitr_b * lb_ / max_light * rvn;
-            }
-            }
+                // (if / else and one `lit`, no `continue`: every early continue of a divergent loop is a flag the compiler carries round it)
+                const int seg = __popcll(~ambient & ((1ull << li) - 1ull));         // its segment of the shadow queue
+                const long long slot = (long long)seg * lr.seg_stride + ws.sh_idx[(long long)seg * ws.cap + g];
+                int type;
+                double lgt_pos[N], rev_light[N], light_vec[N], so[N], light_hit_normal[N];
+                ShadowSetup ss;
+                light_setup(blob, sd, li, src, hit, nrm, type, lgt_pos, rev_light, light_vec, so, ss,
+                            rg.sample_keys ? ws.rng_key[g] : 0ull, li_base);
+                const int sobj = (li == li_first) ? sobj_first : ws.sobj[slot];
+                const int sprim = (li == li_first) ? sprim_first : ws.sprim[slot];
+                ++n_shadow;
+                const bool lit = shadow_lit<N>(type, obj, sobj, sprim, hit, nrm, so, light_vec, light_hit_normal,
+                                               [&](int prim, const double (&o)[N], const double (&v)[N], double (&lh)[N], double (&ln)[N]) {
+                                                   isect_full(blob, &sd, prim, o, v, lh, ln);
+                                               });
+                if (lit) light_term<N>(sf, rg.specular, look, nrm, light_vec, light_hit_normal, ss.ldist2, light, c);
             }
         }
         if (resolve_here) {
             // The deepest bounce of the frame: its nodes have no child nodes (a child there was cut off, -2: black, ndt.c:336-341),
-            // so get_ray_color's blend (ndt.c:402-429; ndt_frame.hip:resolve_node, same operations) needs nothing but this node
-            const double hitr[3] = { refl_r, refl_g, refl_b };
-            double c[3] = { cr, cg, cb };
-            if (ws.child_refl[g] != -1) {
-                const double ref = 0.0;
-#pragma unroll
-                for (int k = 0; k < 3; ++k) {
-                    if (rg.specular) c[k] = (1 - hitr[k]) * (c[k]) + (hitr[k]) * ref;       // ndt.c:405-407
-                    else c[k] += hitr[k] * ref;                                             // ndt.c:411-413
-                }
-            }
-            if (ws.child_refr[g] != -1) {
-                const double ref = 0.0;
-#pragma unroll
-                for (int k = 0; k < 3; ++k) c[k] += (1.0 - hitr[k]) * ref;                  // ndt.c:426-428
-            }
-            cr = c[0]; cg = c[1]; cb = c[2];
+            // so get_ray_color's blend needs nothing but this node
+            const double black[3] = { 0.0, 0.0, 0.0 };
+            blend_children(c, sf.refl, rg.specular, ws.child_refl[g] != -1, black, ws.child_refr[g] != -1, black);
         }
-        ws.clr[0 * ws.cap + g] = cr;
-        ws.clr[1 * ws.cap + g] = cg;
-        ws.clr[2 * ws.cap + g] = cb;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) ws.clr[k * ws.cap + g] = c[k];
         ws.count[g] = (CONT ? ws.count[g] : 1) + n_shadow;
 
     }
@@ -1527,25 +1439,9 @@ NDT_DEV void window_emit_node(const double *blob, const SceneDesc &sd, const Wor
     }
     const bool live = __ballot(shaded) != 0ull;
     const int lane = __lane_id();
-    unsigned long long fire = 0ull;
     const unsigned long long node_key = (rg.sample_keys && in_range) ? ws.rng_key[g] : 0ull;
-    if (shaded && room) {
-        for (int li = 0; li < sd.n_lights; ++li) {
-            int type;
-            double lgt_pos[N], rev_light[N], light_vec[N], so[N];
-            ShadowSetup ss;
-            if (light_setup(blob, sd, li, src, hit, nrm, type, lgt_pos, rev_light, light_vec, so, ss, node_key, li_base)) fire |= 1ull << li;
-        }
-    }
-    int my_total = 0, seg = 0;
-    if (live) {
-        for (int li = 0; li < sd.n_lights; ++li) {
-            if (blob_int(blob, light_word(sd, li), 0) == NDT_LIGHT_AMBIENT_) continue;     // wave-uniform
-            const unsigned long long vote = __ballot((fire >> li) & 1ull);
-            if (lane == seg) my_total = __popcll(vote);
-            ++seg;
-        }
-    }
+    const unsigned long long fire = (shaded && room) ? emit_fire_mask(blob, sd, src, hit, nrm, node_key, li_base) : 0ull;
+    const int my_total = live ? emit_segment_votes(blob, sd, fire) : 0;
     if (shaded) ws.sh_mask[g] = fire;
     int my_off = 0;
     if (my_total > 0) my_off = atomicAdd(&sh->seg_total[lane], my_total);
@@ -1560,7 +1456,8 @@ NDT_DEV void window_emit_node(const double *blob, const SceneDesc &sd, const Wor
     }
     __syncthreads();
     const int my_base = (my_total > 0) ? sh->seg_base[lane] + my_off : 0;
-    seg = 0;
+    // (the walk of shade_emit_node, with the window's place in the list)
+    int seg = 0;
     for (int li = 0; live && li < sd.n_lights; ++li) {
         const int list_type = blob_int(blob, light_word(sd, li), 0);        // (wave-uniform)
         if (list_type == NDT_LIGHT_AMBIENT_) continue;
@@ -1578,8 +1475,7 @@ NDT_DEV void window_emit_node(const double *blob, const SceneDesc &sd, const Wor
             ws.sh_idx[(long long)seg * ws.cap + g] = idx;
             if (!origin_known) store_soa<N>(ws.so, ws.sh_cap, slot, so);
             double dir[N];
-#pragma unroll
-            for (int c = 0; c < N; ++c) dir[c] = (type == NDT_LIGHT_DIRECTIONAL_) ? rev_light[c] : light_vec[c];
+            shadow_dir<N>(type, rev_light, light_vec, dir);
             store_soa<N>(ws.sv, ws.sh_cap, slot, dir);
             ws.slim[slot] = ss.dist_limit;
         }

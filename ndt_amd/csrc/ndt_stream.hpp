@@ -171,38 +171,24 @@ struct WaveStats {          // what a wavefront adds to the frame's statistics w
 
 // ------------------------------------------------------------------ the ray tree, bottom-up
 
-// get_ray_color's blend of a node's own colour with what its children returned (ndt.c:402-429): resolve_node of
-// ndt_frame.hip with coherent accesses.  `mat` is the global blob (materials are not staged in LDS).
+// get_ray_color's blend of a node's own colour with what its children returned (blend_children, ndt_shading.hpp), with
+// coherent accesses.  `mat` is the global blob (materials are not staged in LDS).
 NDT_DEV void stream_resolve(const double *mat, const SceneDesc &sd, const Workspace &ws, int specular, long long g)
 {
-    const int obj = cldi(ws.hit_obj + g);
-    const int mw = sd.off_mat + 8 * obj;
-    const double hitr[3] = { mat[mw + 3], mat[mw + 4], mat[mw + 5] };
+    const Surface sf = surface_of(mat, sd, cldi(ws.hit_obj + g), specular);
     double c[3] = { cld(ws.clr + 0 * ws.cap + g), cld(ws.clr + 1 * ws.cap + g), cld(ws.clr + 2 * ws.cap + g) };
     int cnt = cldi(ws.count + g);
-    const int refl = cldi(ws.child_refl + g);
-    if (refl != -1) {
-        double ref[3] = { 0.0, 0.0, 0.0 };
-        if (refl >= 0) {
-            ref[0] = cld(ws.clr + 0 * ws.cap + refl); ref[1] = cld(ws.clr + 1 * ws.cap + refl); ref[2] = cld(ws.clr + 2 * ws.cap + refl);
-            cnt += cldi(ws.count + refl);
-        }
+    const int child[2] = { cldi(ws.child_refl + g), cldi(ws.child_refr + g) };
+    double ref[2][3] = { { 0.0, 0.0, 0.0 }, { 0.0, 0.0, 0.0 } };        // (a child that was cut off, -2: black)
 #pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            if (specular) c[k] = (1 - hitr[k]) * (c[k]) + (hitr[k]) * ref[k];     // ndt.c:405-407
-            else c[k] += hitr[k] * ref[k];                                         // ndt.c:411-413
+    for (int j = 0; j < 2; ++j) {
+        if (child[j] >= 0) {
+#pragma unroll
+            for (int k = 0; k < 3; ++k) ref[j][k] = cld(ws.clr + k * ws.cap + child[j]);
+            cnt += cldi(ws.count + child[j]);
         }
     }
-    const int refr = cldi(ws.child_refr + g);
-    if (refr != -1) {
-        double ref[3] = { 0.0, 0.0, 0.0 };
-        if (refr >= 0) {
-            ref[0] = cld(ws.clr + 0 * ws.cap + refr); ref[1] = cld(ws.clr + 1 * ws.cap + refr); ref[2] = cld(ws.clr + 2 * ws.cap + refr);
-            cnt += cldi(ws.count + refr);
-        }
-#pragma unroll
-        for (int k = 0; k < 3; ++k) c[k] += (1.0 - hitr[k]) * ref[k];              // ndt.c:426-428
-    }
+    blend_children(c, sf.refl, specular, child[0] != -1, ref[0], child[1] != -1, ref[1]);
     cst(ws.clr + 0 * ws.cap + g, c[0]);
     cst(ws.clr + 1 * ws.cap + g, c[1]);
     cst(ws.clr + 2 * ws.cap + g, c[2]);
@@ -240,7 +226,8 @@ NDT_DEV void complete_up(const double *mat, const SceneDesc &sd, const Workspace
 
 // ------------------------------------------------------------------ lighting of one node batch
 
-// Second half of apply_lights (ndt.c:217-310) for the 64 nodes of batch nb: shade_finish_node with coherent accesses,
+// Second half of apply_lights (ndt.c:217-310) for the 64 nodes of batch nb: the functions of ndt_shading.hpp that
+// shade_finish_node calls, between coherent accesses;
 // returns whether this lane's node was lit (its colour then starts its way up the tree).  Every lane of the wavefront calls.
 NDT_DEV bool stream_light_batch(const double *blob, const double *mat, const SceneDesc &sd, const Workspace &ws, const RenderGeom &rg,
                                 const StreamArgs &sa, int nb)
@@ -256,18 +243,11 @@ NDT_DEV bool stream_light_batch(const double *blob, const double *mat, const Sce
         cload_soa<N>(ws.ray_v, g, look);
         cload_soa<N>(ws.hit_p, g, hit);
         cload_soa<N>(ws.hit_n, g, nrm);
-        const int mw = sd.off_mat + 8 * obj;
-        const double hit_r = mat[mw], hit_g = mat[mw + 1], hit_b = mat[mw + 2];
-        const double refl_r = mat[mw + 3], refl_g = mat[mw + 4], refl_b = mat[mw + 5];
-        const bool transparent = mat[mw + 7] != 0.0;
-        double hitr_r = 0.0, hitr_g = 0.0, hitr_b = 0.0;
-        if (rg.specular) {
-            hitr_r = refl_r; hitr_g = refl_g; hitr_b = refl_b;
-        }
+        const Surface sf = surface_of(mat, sd, obj, rg.specular);
         // apply_lights, ndt.c:88-92: scn->ambient first
-        double cr = hit_r * mat[sd.off_cam + 4 * N + 1];
-        double cg = hit_g * mat[sd.off_cam + 4 * N + 2];
-        double cb = hit_b * mat[sd.off_cam + 4 * N + 3];
+        double c[3];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) c[k] = sf.colour[k] * mat[sd.off_cam + 4 * N + 1 + k];
         const unsigned long long fire = cldu(ws.sh_mask + g);
         const unsigned long long key = rg.sample_keys ? cldu(ws.rng_key + g) : 0ull;
         int n_shadow = 0;
@@ -279,11 +259,9 @@ NDT_DEV bool stream_light_batch(const double *blob, const double *mat, const Sce
             const int li = __ffsll((long long)todo) - 1;
             const int w = light_word(sd, li);
             const int ltype = blob_int(mat, w, 0);
-            const double lr_ = mat[w + 1], lg_ = mat[w + 2], lb_ = mat[w + 3];
-            if (ltype == NDT_LIGHT_AMBIENT_) {              // ndt.c:106-111
-                cr += hit_r * lr_;
-                cg += hit_g * lg_;
-                cb += hit_b * lb_;
+            const double light[3] = { mat[w + 1], mat[w + 2], mat[w + 3] };
+            if (ltype == NDT_LIGHT_AMBIENT_) {
+                ambient_term(sf, light, c);
                 continue;
             }
             const int seg = __popcll(~ambient & ((1ull << li) - 1ull));
@@ -295,43 +273,16 @@ NDT_DEV bool stream_light_batch(const double *blob, const double *mat, const Sce
             const int sobj = cldi(ws.sobj + slot);
             const int sprim = cldi(ws.sprim + slot);
             ++n_shadow;
-            if (type == NDT_LIGHT_DIRECTIONAL_) {
-                if (sobj >= 0) continue;                    // anything at all shadows it, ndt.c:246
-                v_copy<N>(light_hit_normal, nrm);           // ndt.c:252-254
-            } else {
-                if (sobj != obj) continue;                  // ndt.c:217
-                double light_hit[N];
-                isect_full_stream(blob, &sd, sprim, so, light_vec, light_hit, light_hit_normal);
-                const double dist = v_dist<N>(hit, light_hit);
-                if (dist > NDT_EPS) continue;               // ndt.c:225
-            }
-            double angle = v_angle<N>(nrm, light_vec);      // ndt.c:263
-            if (angle > NDT_PI / 2.0) angle = NDT_PI - angle;
-            const double light_scale = nd_cos(angle) / ss.ldist2;
-            if (!transparent) {
-                cr += hit_r * lr_ * light_scale;
-                cg += hit_g * lg_ * light_scale;
-                cb += hit_b * lb_ * light_scale;
-            }
-            if (rg.specular) {                              // ndt.c:276-310
-                double light_ref[N], rev_look[N];
-                v_reflect<N>(light_vec, light_hit_normal, light_ref, 0.5);
-                v_unitize<N>(light_ref);
-                v_scale<N>(look, -1, rev_look);
-                v_unitize<N>(rev_look);
-                double rv = v_dot<N>(light_ref, rev_look);
-                rv = (0 > rv) ? 0 : rv;                     // MAX(0,rv), image.h:31
-                const double rvn = nd_pow(rv, 50.0);
-                const double gb = (lg_ > lb_) ? lg_ : lb_;
-                const double max_light = (lr_ > gb) ? lr_ : gb;
-                cr += hitr_r * lr_ / max_light * rvn;
-                cg += hitr_g * lg_ / max_light * rvn;
-                cb += hitr_b * lb_ / max_light * rvn;
-            }
+            if (!shadow_lit<N>(type, obj, sobj, sprim, hit, nrm, so, light_vec, light_hit_normal,
+                               [&](int prim, const double (&o)[N], const double (&v)[N], double (&lh)[N], double (&ln)[N]) {
+                                   isect_full_stream(blob, &sd, prim, o, v, lh, ln);
+                               }))
+                continue;
+            light_term<N>(sf, rg.specular, look, nrm, light_vec, light_hit_normal, ss.ldist2, light, c);
         }
-        cst(ws.clr + 0 * ws.cap + g, cr);
-        cst(ws.clr + 1 * ws.cap + g, cg);
-        cst(ws.clr + 2 * ws.cap + g, cb);
+        cst(ws.clr + 0 * ws.cap + g, c[0]);
+        cst(ws.clr + 1 * ws.cap + g, c[1]);
+        cst(ws.clr + 2 * ws.cap + g, c[2]);
         csti(ws.count + g, 1 + n_shadow);
     }
     drain();
@@ -342,7 +293,8 @@ NDT_DEV bool stream_light_batch(const double *blob, const double *mat, const Sce
 
 // What get_ray_color and apply_lights do between the closest-hit query and the shadow queries, for the 64 nodes of
 // batch nb, by the wavefront that has just traced them (src / look / obj / prim are still in its registers): hit point
-// and normal, background colour, children, shadow rays -- shade_emit_node with per-wavefront reservations (the
+// and normal, background colour, children, shadow rays -- the arithmetic shade_emit_node uses (ndt_shading.hpp), with coherent
+// stores and per-wavefront reservations (the
 // wavefronts of a persistent launch are not in step, so there is no workgroup to share a reservation with; they also
 // do not all arrive at the counters at once).  Every lane of the wavefront calls.
 
@@ -411,45 +363,10 @@ NDT_DEV void stream_shade_batch(const double *blob, const double *mat, const Sce
         my_total = __popcll(my_vote);
         if (shaded) cstu(ws.sh_mask + g, fire);
         // ---- get_ray_color, ndt.c:381-430: reflection / refraction children
-        bool want_refl = false, want_refr = false;
-        double refl_ray[N], refr_ray[N];
-        double refl_frac = 0, refr_frac = 0;
-        int depth_next = 0;
-        int c_refl = -1, c_refr = -1;
-        if (shaded) {
-            const int mw = sd.off_mat + 8 * obj;
-            const double refl_r = mat[mw + 3], refl_g = mat[mw + 4], refl_b = mat[mw + 5];
-            const bool transparent = mat[mw + 7] != 0.0;
-            const double frac = cld(ws.frac + g);
-            depth_next = depth_left - 1;
-            const double gb2 = (refl_g > refl_b) ? refl_g : refl_b;
-            const double contrib = (refl_r > gb2) ? refl_r : gb2;
-            if (contrib > 0 && (refl_r != 0.0 || refl_g != 0.0 || refl_b != 0.0)) {
-                refl_frac = contrib * frac;
-                // child cut-offs (ndt.c:336-341) return black without tracing
-                if (refl_frac < (1.0 / 512.0) || depth_next <= 0) {
-                    c_refl = -2;
-                } else {
-                    v_reflect<N>(look, nrm, refl_ray, 1.0);
-                    v_unitize<N>(refl_ray);
-                    want_refl = true;
-                }
-            }
-            if (transparent) {
-                refr_frac = (1 - contrib) * frac;
-                if (refr_frac < (1.0 / 512.0) || depth_next <= 0) {
-                    c_refr = -2;
-                } else {
-                    double nrm_u[N];                                    // vectNd_refract unitizes the normal it is given (vectNd.c:155);
-                    v_copy<N>(nrm_u, nrm);                              // the shadow rays below still need the original
-                    v_refract<N>(look, nrm_u, refr_ray, mat[mw + 6]);
-                    v_unitize<N>(refr_ray);
-                    want_refr = true;
-                }
-            }
-        }
+        Children<N> ch;
+        if (shaded) ch = children_of<N>(look, nrm, surface_of(mat, sd, obj, rg.specular), cld(ws.frac + g), depth_left);
         // ---- reservations: the children at the node tail, the shadow rays in their lights' segments
-        const unsigned long long v_refl = __ballot(want_refl), v_refr = __ballot(want_refr);
+        const unsigned long long v_refl = __ballot(ch.want_refl), v_refr = __ballot(ch.want_refr);
         const int n_refl = __popcll(v_refl), total = n_refl + __popcll(v_refr);
         int base = 0;
         if (total > 0) {
@@ -478,35 +395,35 @@ NDT_DEV void stream_shade_batch(const double *blob, const double *mat, const Sce
         if (__ballot(my_total > 0 && (long long)my_base + my_total > sa.seg_cap) != 0ull) return;
         // ---- the children
         const unsigned long long below = (1ull << lane) - 1ull;
-        if (want_refl) {
+        if (ch.want_refl) {
             const long long c = (long long)base + __popcll(v_refl & below);
             cstore_soa<N>(ws.ray_o, c, hit);
-            cstore_soa<N>(ws.ray_v, c, refl_ray);
-            cst(ws.frac + c, refl_frac);
-            csti(ws.depth_left + c, depth_next);
+            cstore_soa<N>(ws.ray_v, c, ch.refl_ray);
+            cst(ws.frac + c, ch.refl_frac);
+            csti(ws.depth_left + c, ch.depth_next);
             csti(sa.parent + c, (int)g);
             if (rg.sample_keys) cstu(ws.rng_key + c, ndt_rng_mix(node_key ^ 0x1ull));
-            c_refl = (int)c;
+            ch.c_refl = (int)c;
         }
-        if (want_refr) {
+        if (ch.want_refr) {
             const long long c = (long long)base + n_refl + __popcll(v_refr & below);
             cstore_soa<N>(ws.ray_o, c, hit);
-            cstore_soa<N>(ws.ray_v, c, refr_ray);
-            cst(ws.frac + c, refr_frac);
-            csti(ws.depth_left + c, depth_next);
+            cstore_soa<N>(ws.ray_v, c, ch.refr_ray);
+            cst(ws.frac + c, ch.refr_frac);
+            csti(ws.depth_left + c, ch.depth_next);
             csti(sa.parent + c, (int)g);
             if (rg.sample_keys) cstu(ws.rng_key + c, ndt_rng_mix(node_key ^ 0x2ull));
-            c_refr = (int)c;
+            ch.c_refr = (int)c;
         }
         if (shaded) {
-            csti(ws.child_refl + g, c_refl);
-            csti(ws.child_refr + g, c_refr);
+            csti(ws.child_refl + g, ch.c_refl);
+            csti(ws.child_refr + g, ch.c_refr);
             // what the node waits for before its colour is final: its own lighting and its children
-            csti(sa.pend + g, 1 + (c_refl >= 0 ? 1 : 0) + (c_refr >= 0 ? 1 : 0));
+            csti(sa.pend + g, 1 + (ch.c_refl >= 0 ? 1 : 0) + (ch.c_refr >= 0 ? 1 : 0));
         }
         if (total > 0) {
             // statistics: the deepest bounce that has nodes
-            int lvl = (want_refl || want_refr) ? rg.max_depth - depth_next : 0;
+            int lvl = (ch.want_refl || ch.want_refr) ? rg.max_depth - ch.depth_next : 0;
 #pragma unroll
             for (int d = 32; d > 0; d >>= 1) lvl = max(lvl, __shfl_xor(lvl, d, 64));
             stats.max_level = max(stats.max_level, lvl);
@@ -533,11 +450,8 @@ NDT_DEV void stream_shade_batch(const double *blob, const double *mat, const Sce
                 const long long slot = (long long)seg * sa.seg_cap + idx;
                 csti(ws.sh_idx + (long long)seg * ws.cap + g, idx);
                 cstore_soa<N>(ws.so, slot, so);
-                // point/spot: from the light along light_vec (ndt.c:211); directional: from the nudged hit point along
-                // rev_light (ndt.c:238) -- one store of a selected VALUE (two stores from different arrays end in scratch)
                 double dir[N];
-#pragma unroll
-                for (int c = 0; c < N; ++c) dir[c] = (type == NDT_LIGHT_DIRECTIONAL_) ? rev_light[c] : light_vec[c];
+                shadow_dir<N>(type, rev_light, light_vec, dir);
                 cstore_soa<N>(ws.sv, slot, dir);
                 cst(ws.slim + slot, ss.dist_limit);
                 csti(sa.sowner + slot, (int)g);
