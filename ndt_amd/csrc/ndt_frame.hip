@@ -382,7 +382,19 @@ static int wait_for_tag(ndt_hip_ctx *ctx, const unsigned long long *word, unsign
     return NDT_OK;
 }
 
-static long long n_pixels(const RenderGeom &rg) { return rg.samples ? (long long)rg.n_samples : (long long)rg.rows * rg.width; }
+// The primaries a pass traces: one a sample, or one a pixel -- but none for the 46 blank lines between the eyes of a frame-packed
+// image (primary_node makes no ray there, ndt.c:614-631)
+static long long n_pixels(const RenderGeom &rg)
+{
+    if (rg.samples) return (long long)rg.n_samples;
+    long long rows = rg.rows;
+    if (rg.stereo == 4)
+        for (int r = 0; r < rg.rows; ++r) {
+            const int j = rg.row_pair ? rg.row_begin + (r >> 1) * rg.row_step + (r & 1) : rg.row_begin + r * rg.row_step;
+            if (j >= 1080 && j <= 1080 + 45) rows -= 1;
+        }
+    return rows * rg.width;
+}
 
 // A profiled pass takes the frame's begin / end from the dispatch timestamps of its first and last kernel
 template <typename Kernel, typename... Args>

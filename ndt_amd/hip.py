@@ -557,7 +557,7 @@ class NdtHip:
 
     def params(self, width, height, depth, row_begin=0, row_step=1, specular=1, profile=0, aa=None, stereo=0, samples=1):
         p = RenderParams(width, height, depth, int(samples), row_begin, row_step, specular, profile)
-        p.stereo = int(stereo)      # ndt_stereo_mode: 0 mono, 1 side by side, 2 over/under, 3 anaglyph
+        p.stereo = int(stereo)      # ndt_stereo_mode: 0 mono, 1 side by side, 2 over/under, 3 anaglyph, 4 frame packing (2205 lines)
         if aa is not None:
             # Whitted's recursive anti-aliasing, `-a diff,depth` (ndt.c:655-733)
             p.recursive_aa, p.aa_diff, p.aa_depth = 1, int(aa[0]), int(aa[1])
