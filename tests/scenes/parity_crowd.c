@@ -9,7 +9,9 @@
  * Everything follows from the arguments through a small integer generator of its own.
  *
  * config: "items=K" (default 320), "seed=S" (default 1), "nohcube" (no hcube: it nests every m-face, 52 904 of them in
- * 10-D).  Without nohcube the crowd holds two hcubes up to 6-D and one above, in different mask words.
+ * 10-D), "mix=light" / "mix=spheres" (the K - 1 small objects cycle through the three types with the shortest records --
+ * sphere, hdisk, cylinder -- or are all spheres, placed the same way: 192 and 256 items within a 64 KB trace section; no
+ * hcube).  Without nohcube the crowd holds two hcubes up to 6-D and one above, in different mask words.
  * Compiled against the REFERENCE's headers by oracle/Makefile (-> oracle/_ref/scenes/parity_crowd.so).
  */
 #include <stdio.h>
@@ -69,7 +71,8 @@ int scene_setup(scene *scn, int dims, int frame, int frames, char *config)
 {
     (void)frame; (void)frames;
     const int items = config_int(config, "items=", 320);
-    const int nohcube = (config && strstr(config, "nohcube")) ? 1 : 0;
+    const int light_mix = (config && strstr(config, "mix=light")) ? 3 : (config && strstr(config, "mix=spheres")) ? 1 : 0;
+    const int nohcube = (light_mix || (config && strstr(config, "nohcube"))) ? 1 : 0;
     crowd_state = 0x9E3779B97F4A7C15ULL ^ ((unsigned long long)config_int(config, "seed=", 1) << 20) ^ (unsigned long long)dims;
     for (int i = 0; i < 4; ++i) rnd();
 
@@ -144,6 +147,7 @@ int scene_setup(scene *scn, int dims, int frame, int frames, char *config)
     /* the hcubes stand at the first hcube turns past a third and two thirds of the items: different mask words */
     static char *cycle[8] = { "sphere", "hdisk", "cylinder", "hcylinder", "orthotope", "hcube", "hfacet", "facet" };
     static char *instead[3] = { "sphere", "orthotope", "hdisk" };
+    static char *light_cycle[3] = { "sphere", "hdisk", "cylinder" };
     const int hcubes = nohcube ? 0 : dims <= 6 ? 2 : 1;
     int hcube_at[2] = { -1, -1 };
     for (int k = 0; k < hcubes; ++k) {
@@ -155,6 +159,7 @@ int scene_setup(scene *scn, int dims, int frame, int frames, char *config)
     for (int j = 1; j < items; ++j) {
         char *type = cycle[j % 8];
         if (j % 8 == 5 && j != hcube_at[0] && j != hcube_at[1]) type = instead[(j / 8) % 3];
+        if (light_mix) type = light_cycle[j % light_mix];
 
         /* the cell: items that follow each other in number stand in neighbouring cells, so a leaf's list holds runs of numbers */
         const int cell = j - 1;
