@@ -297,12 +297,13 @@ int main(int argc, char **argv)
     int stereo = atoi(arg_str(argc, argv, "--stereo", "0"));     /* stereo_mode, ndt.c:46-48 */
     int samples = atoi(arg_str(argc, argv, "--samples", "1"));   /* `-n`: > 1 draws from drand48, run with --threads 1 */
     const char *depth_out = arg_str(argc, argv, "--depth-out", NULL);
+    specular_enabled = atoi(arg_str(argc, argv, "--specular", "1")) ? 1 : 0;   /* 0: what `ndt`'s option at ndt.c:1583 does */
     scene_v2 = arg_flag(argc, argv, "--scene-v2");
     if (!objdir || !scene_so || width < 1 || height < 1) {
         fprintf(stderr, "usage: ndt_ref_shim --objects DIR --scene X.so --dims N [--frame F] [--config S] --res WxH\n"
                         "       [--threads T] [--depth L] [--scene-out F] [--fb-out F] [--rays-in F --rays-out F]\n"
                         "       [--tmp DIR] [--no-render] [--aa DIFF,DEPTH] [--yaml-out F]\n"
-                        "       [--stereo MODE] [--depth-out F] [--scene-v2] [--samples N]\n");
+                        "       [--stereo MODE] [--depth-out F] [--scene-v2] [--samples N] [--specular 0|1]\n");
         return 2;
     }
 

@@ -5,7 +5,11 @@
  * LIGHT_AMBIENT entry next to scn->ambient, finite hcylinders (flag 0), infinite cylinders
  * (flag[1] = 1), hfacets with a computed normal (flag 0), refraction with total internal
  * reflection, mirror chains that run into the 1/512 weight cut-off, and a non-unit hplane
- * normal.  This scene has all of them, for any dims >= 3.  It is compiled against the
+ * normal.  This scene has all of them, for any dims >= 3 -- as objects: how often a frame's rays take
+ * the branches thins out with the dimension (total internal reflection: 156 nodes of the zoo4d fixture,
+ * 1 of zoo9d .. zoo11d, none of zoo12d), and no reflectance here has a zero channel or a maximum other
+ * than red.  The scene whose frames are COUNTED to take every shading branch in every dimension is
+ * parity_shade.c (tests/test_shading_known_answers.py).  This one is compiled against the
  * REFERENCE's headers by oracle/Makefile (-> oracle/_ref/scenes/parity_zoo.so) to generate
  * golden fixtures from the compiled reference, and against this repository's host API in
  * tests/test_host_api.py.  config: "mirror" makes two facing planes near-perfect mirrors.
