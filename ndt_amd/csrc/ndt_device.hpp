@@ -1522,9 +1522,19 @@ NDT_DEV void cls_scan(const double *blob, const SceneDesc &sd, const VisitMask<M
 // Where the traversal stack lives.  Scratch (per-lane arrays in private memory) always works; LDS
 // (one slot per lane and level, [level][lane] so that lanes never share a bank) takes the push /
 // pop round trips out of the T phase when the workgroup's LDS has room for depth x lanes entries.
+//
+// An entry is 12 bytes, not 20: of {far child, a, tu} it holds the two that cost something to rebuild.  `tu` is the one that can
+// be derived: a pending far child's interval ends where its parent's did, and a node's `tu` is either the root interval's or
+// `tp + EPS` of the nearest ancestor at which the walk went near with both children pending (kd-tree.c:551) -- and that ancestor's
+// entry is the one directly below on the stack, because every such step leaves an entry behind (the push below is `both & alive`;
+// an entry whose `lt > tp` fails is dropped by the same test at pop time).  So a pop reads the entry and the `a` of the one below
+// it, both at once -- one LDS round trip -- and repeats the push's addition on the push's operand: the same bits.  The root's
+// `tu` stands below the first entry, in the level the stack has to spare (kd_depth + 1 levels, at most kd_depth - 1 entries), so
+// the read of "the entry below" never leaves the lane's stack.  (POP == 0, the variants whose registers did not take the change:
+// {parent, tu}, and the far child and `a` are recomputed from the parent's record -- a second, dependent round trip.)
 struct KdStackLds {
-    double *tu;         // already offset by the lane: element d at [d * stride]
-    int *node;          // the PARENT of the pending far child: its split plane gives `a` back exactly (12 bytes per entry, not 20)
+    double *t;          // already offset by the lane: element d at [d * stride].  `a` of the entry ([-stride]: the root's tu); POP == 0: tu
+    int *node;          // the pending far child; POP == 0: its PARENT, whose split plane gives `a` back exactly
     int stride;
 };
 
@@ -1535,11 +1545,13 @@ struct KdStackLds {
 // LAZY_INV (the per-bounce trace kernel): the inverse directions are made where a ray enters the tree, behind the root box test
 // -- a ray that misses the box, the sky, is finished there and never reads them: N divisions of about 12 instructions.  Same
 // inv_of, same values.  (The frame kernel keeps them in front: moving them moved its spills.)
-template <int N, int MW, bool LSTACK = false, bool UNI = false, bool LAZY_INV = false>
+// POP (LSTACK only): the stack entry is {far child, a} and a pop derives `tu` from the entry below (KdStackLds above).
+// LEAF_SETS (item sets, MW == 1): a node's item set is read where the record says leaf, not at every node (below).
+template <int N, int MW, bool LSTACK = false, bool UNI = false, bool LAZY_INV = false, bool POP = false, bool LEAF_SETS = false>
 NDT_DEV void trace_kd(const double *blob, const SceneDesc &sd, VisitMask<MW> &mask, const double (&o)[N],
                       const double (&v)[N], double dist_limit, int &out_obj, int &out_prim
 #ifdef NDT_PHASE_TIMING
-                      , unsigned long long (&ph)[8], unsigned int (&cnt)[8], unsigned int (&occ)[8]
+                      , unsigned long long (&ph)[8], unsigned int (&cnt)[12], unsigned int (&occ)[8]
 #endif
                       , KdStackLds ls = KdStackLds{}, ClsLds cl = ClsLds{}, const bool has_ray = true, double *box_slot = nullptr)
 {
@@ -1586,6 +1598,7 @@ NDT_DEV void trace_kd(const double *blob, const SceneDesc &sd, VisitMask<MW> &ma
     // traversal state
     int st_node[LSTACK ? 1 : NDT_KD_STACK];
     double st_a[LSTACK ? 1 : NDT_KD_STACK], st_tu[LSTACK ? 1 : NDT_KD_STACK];
+    static_assert(LSTACK || !POP, "POP is a layout of the LDS stack");
     int sp = 0;
     int node = 0;
     double ntl = 0, ntu = 0;
@@ -1699,6 +1712,7 @@ NDT_DEV void trace_kd(const double *blob, const SceneDesc &sd, VisitMask<MW> &ma
                 node = 0;
                 ntl = tl;
                 ntu = tu;
+                if (POP) ls.t[-ls.stride] = tu;     // below the first entry: what a pop from an otherwise empty stack takes for `tu`
                 st = 1;
             }
         }
@@ -1716,12 +1730,23 @@ NDT_DEV void trace_kd(const double *blob, const SceneDesc &sd, VisitMask<MW> &ma
                     } else {
                         // (LDS stack: sp counts in entries' distance, ls.stride -- no multiplication per push and pop)
                         sp -= LSTACK ? ls.stride : 1;
+                        NDT_COUNT(6);
+#ifdef NDT_PHASE_TIMING
+                        cnt[8] += (__lane_id() == __ffsll((long long)__ballot(1)) - 1);     // T iterations that run this path
+#endif
                         double a;
-                        if (LSTACK) {
+                        if (POP) {
+                            // the entry is the far child and its gate; `tu` is what the push's `ntu = tp + EPS` made of the entry
+                            // below, or the root's: all reads are independent (one round trip), nothing is recomputed
+                            node = ls.node[sp];
+                            a = ls.t[sp];
+                            const double below = ls.t[sp - ls.stride];
+                            ntu = sp == 0 ? below : below + NDT_EPS;
+                        } else if (LSTACK) {
                             // the entry names the parent; tp and the far child are recomputed from its record
                             // with the operations of the push (same operands, same result)
                             const int parent = ls.node[sp];
-                            ntu = ls.tu[sp];
+                            ntu = ls.t[sp];
                             const ndt_v2d prec = blob_pair(blob, sd.off_kd + 2 * parent);
                             const long long pw0 = __double_as_longlong(prec.x);
                             const int pdim = (int)(pw0 & 0xffffffffll);
@@ -1736,6 +1761,9 @@ NDT_DEV void trace_kd(const double *blob, const SceneDesc &sd, VisitMask<MW> &ma
                         ntl = a - NDT_EPS;
                         // `*t_ptr > tp` (kd-tree.c:552), evaluated now that the near subtree is done; `tu < 0` (kd-tree.c:490)
                         st = ((lt > a) & !(ntu < 0.0)) ? 1 : 0;
+#ifdef NDT_PHASE_TIMING
+                        cnt[7] += (st == 0);                                // popped and dropped
+#endif
                     }
                 } else if (ntu < 0.0) {
                     st = 0;                                             // kd-tree.c:490
@@ -1745,8 +1773,12 @@ NDT_DEV void trace_kd(const double *blob, const SceneDesc &sd, VisitMask<MW> &ma
                     ndt_v2d rec = blob_pair(blob, sd.off_kd + 2 * node);
                     // BITS: the items below this node that the ray has not visited yet.  None left: nothing in this subtree can
                     // change the ray's state any more (its leaves would scan nothing), so the walk does not enter it.
+                    // LEAF_SETS: that test prunes 0.15 % of the node visits of the benchmark frame and costs every inner visit an LDS
+                    // read, two and-nots, a 64-bit compare and a branch.  The set is read at the leaves, where it is the list; an
+                    // exhausted subtree is walked to leaves that scan nothing: the same answers.
                     unsigned long long below = ~0ull;
-                    if (BITS) {
+                    constexpr bool SETS_AT_LEAVES = BITS && LEAF_SETS;
+                    if (BITS && !SETS_AT_LEAVES) {
                         double ns = blob[sd.off_nset + node];
 #ifndef NDT_NO_T_HOIST
                         // both reads in flight before the test of `below` (the compiler sinks the record's read behind it otherwise:
@@ -1762,7 +1794,8 @@ NDT_DEV void trace_kd(const double *blob, const SceneDesc &sd, VisitMask<MW> &ma
                     } else if (dim < 0) {
                         // leaf: trace() over its items (kd-tree.c:497-519)
                         if (BITS) {
-                            st = 2;
+                            if (SETS_AT_LEAVES) below = (unsigned long long)__double_as_longlong(blob[sd.off_nset + node]) & ~mask.w[0];
+                            st = (SETS_AT_LEAVES && below == 0ull) ? 0 : 2;
                             cand = below;
                         } else {
                             const long long w1 = __double_as_longlong(rec.y);
@@ -1788,8 +1821,13 @@ NDT_DEV void trace_kd(const double *blob, const SceneDesc &sd, VisitMask<MW> &ma
                         const bool near_only = (ntu < tp - NDT_EPS) & alive;                // near, same interval
                         const bool far_only = !near_only & (ntl > tp + NDT_EPS) & alive;    // far, same interval
                         const bool both = !near_only & !far_only;
-                        if (both & (lt > tp)) {
-                            if (LSTACK) { ls.node[sp] = node; ls.tu[sp] = ntu; }
+                        // POP: every step that tightens `ntu` below leaves its entry, so that a pop finds the `tp` its `tu` was made
+                        // of in the entry below; one that fails `lt > tp` already is dropped by that test when it is popped.
+                        // (`alive` holds at every visit: `lt` changes in leaves only, a child visited from its parent has the
+                        // parent's `ntl`, and a popped one is visited only with lt > a > a - EPS.  Kept as the reference has it.)
+                        if (POP ? (both & alive) : (both & (lt > tp))) {
+                            if (POP) { ls.node[sp] = far; ls.t[sp] = tp; }
+                            else if (LSTACK) { ls.node[sp] = node; ls.t[sp] = ntu; }
                             else { st_node[sp] = far; st_a[sp] = tp; st_tu[sp] = ntu; }
                             sp += LSTACK ? ls.stride : 1;               // far: (tp-EPS, tu), gate tp
                         }

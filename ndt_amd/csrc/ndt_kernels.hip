@@ -378,6 +378,38 @@ constexpr int trace_head_steps(int n, int mw, bool lstack, bool prim)
     return 7;
 }
 #endif
+// Which of round 16's two changes to the tree walk a variant of k_trace takes: 1 the traversal stack holds {far child, a} and a
+// pop needs no parent record (trace_kd's POP; ndt_device.hpp:KdStackLds has the argument; LDS stacks), 2 the item set of a node is
+// read at the leaves only (LEAF_SETS; the item-set tier).  The same gate as above: only where the kernel spills no more vector
+// registers and keeps its wavefronts per SIMD (profiles/r16_walk_settings.txt has every variant of N = 3 .. 12 under every
+// setting, profiles/r16_kernel_resources.txt the table as built); a variant that takes neither is the round 14 kernel instruction
+// for instruction.  -DNDT_POP_STEP=0 .. 3 (make walk0 .. walk3) puts one setting in place of the table.
+constexpr int trace_walk_mask(int mw, bool lstack) { return (lstack ? 1 : 0) | (mw == 1 ? 2 : 0); }
+#ifdef NDT_POP_STEP
+constexpr int trace_walk_steps(int, int mw, bool lstack, bool) { return (NDT_POP_STEP) & trace_walk_mask(mw, lstack); }     // (experiments: one setting everywhere)
+#else
+constexpr int trace_walk_steps(int n, int mw, bool lstack, bool prim)
+{
+    // the setting of most steps that spills no more than the parent (3, else 1, else 2), read off the table's four columns.
+    // columns: <1, true, true, false>, <1, true, true, true>, <4, true, true, false>, <4, true, true, true>, <1, true, false, false>,
+    // <1, true, false, true>; the other variants have neither an LDS stack nor item sets
+    constexpr int take[10][6] = {
+        { 3, 3, 1, 1, 2, 2 },     //  3-D
+        { 3, 3, 0, 1, 2, 2 },     //  4-D
+        { 2, 2, 1, 0, 2, 2 },     //  5-D
+        { 3, 2, 0, 0, 0, 2 },     //  6-D
+        { 0, 0, 0, 1, 2, 2 },     //  7-D
+        { 3, 0, 1, 0, 2, 2 },     //  8-D
+        { 2, 2, 0, 1, 2, 2 },     //  9-D
+        { 3, 2, 0, 0, 2, 2 },     // 10-D
+        { 2, 2, 0, 1, 2, 2 },     // 11-D
+        { 2, 2, 0, 0, 2, 2 },     // 12-D
+    };
+    const int col = lstack ? (mw == 1 ? 0 : 2) + (prim ? 1 : 0) : 4 + (prim ? 1 : 0);
+    if (n < 3 || n > 12 || (mw != 1 && !(mw == 4 && lstack))) return 0;
+    return take[n - 3][col] & trace_walk_mask(mw, lstack);
+}
+#endif
 NDT_DEV KernargBytes karg_here()
 {
     KernargBytes p = (KernargBytes)__builtin_amdgcn_kernarg_segment_ptr();
@@ -433,6 +465,8 @@ __global__ void __launch_bounds__(MW == 0 ? NDT_TRACE_T1_MAX_BLOCK : NDT_TRACE_M
 {
     constexpr int STEPS = trace_head_steps(N, MW, LSTACK, PRIM);
     constexpr bool KARG = (STEPS & 1) != 0, SEG_ONCE = (STEPS & 2) != 0, LAZY = (STEPS & 4) != 0;
+    constexpr int WALK = trace_walk_steps(N, MW, LSTACK, PRIM);
+    constexpr bool POP = (WALK & 1) != 0, LEAF_SETS = (WALK & 2) != 0;
     extern __shared__ __attribute__((aligned(16))) double lds_blob[];
     const double *blob = gblob;
     if (LDS) {
@@ -452,11 +486,12 @@ __global__ void __launch_bounds__(MW == 0 ? NDT_TRACE_T1_MAX_BLOCK : NDT_TRACE_M
     }
     KdStackLds kstack{};
     if (LSTACK) {
-        // behind the scene: [kd_depth][lanes] of tu (doubles) and parent node (ints)
+        // behind the scene: [kd_depth + 1][lanes] of doubles, then of ints.  POP: the root's tu in level 0, the entries' `a` from
+        // level 1 on (a root-to-leaf path leaves at most kd_depth - 1 entries) and their far children; else the entries' tu and parents
         double *base = lds_blob + ((sd.trace_words + 1) & ~1);
         const int depth = sd.kd_depth + 1;
         kstack.stride = blockDim.x;
-        kstack.tu = base + threadIdx.x;
+        kstack.t = base + threadIdx.x + (POP ? blockDim.x : 0);
         kstack.node = (int *)(base + (size_t)depth * blockDim.x) + threadIdx.x;
     }
     VisitMask<MW> mask;
@@ -483,6 +518,7 @@ __global__ void __launch_bounds__(MW == 0 ? NDT_TRACE_T1_MAX_BLOCK : NDT_TRACE_M
     // the end of the kernel, so that the counters' atomics do not sit inside the phases they measure
     unsigned long long ph[8] = { 0, 0, 0, 0, 0, 0, 0, 0 };      // T, G, I, list end, -, prologue, outside trace_kd, -
     unsigned long long acc[24];                                  // [0..6] per-ray counts + rays, [8..13] / [16..21] loop occupancy
+    unsigned long long pops[3] = { 0, 0, 0 };                    // stack pops, pops that drop their entry, T iterations with a pop in them
     for (int i = 0; i < 24; ++i) acc[i] = 0ull;
     unsigned long long out_last = __builtin_readcyclecounter();
     unsigned long long batch_mark = 0;
@@ -696,7 +732,7 @@ __global__ void __launch_bounds__(MW == 0 ? NDT_TRACE_T1_MAX_BLOCK : NDT_TRACE_M
         const double lim = (live && part.lim) ? part.lim[g] : -1.0;
         int obj, prim;
 #ifdef NDT_PHASE_TIMING
-        unsigned int cnt[8] = { 0, 0, 0, 0, 0, 0, 0, 0 };
+        unsigned int cnt[12] = { 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0 };
         unsigned int occ[8] = { 0, 0, 0, 0, 0, 0, 0, 0 };
         ph[6] += __builtin_readcyclecounter() - out_last;
         batch_mark = wall_clock64();
@@ -704,7 +740,7 @@ __global__ void __launch_bounds__(MW == 0 ? NDT_TRACE_T1_MAX_BLOCK : NDT_TRACE_M
             obj = (o[0] + v[0] + lim > 1e300) ? 0 : -1;     // keeps the loads alive
             prim = -1;
         } else
-        trace_kd<N, MW, LSTACK, MW == 0, LAZY>(blob, sd, mask, o, v, lim, obj, prim, ph, cnt, occ, kstack, cls, live, box_slot);
+        trace_kd<N, MW, LSTACK, MW == 0, LAZY, POP, LEAF_SETS>(blob, sd, mask, o, v, lim, obj, prim, ph, cnt, occ, kstack, cls, live, box_slot);
         out_last = __builtin_readcyclecounter();
         if (ws.dbg && lane == __ffsll((long long)__ballot(1)) - 1) {
             // duration of this batch inside trace_kd: slowest batch of the launch (dbg[40 + is_shadow])
@@ -720,6 +756,7 @@ __global__ void __launch_bounds__(MW == 0 ? NDT_TRACE_T1_MAX_BLOCK : NDT_TRACE_M
                 for (int i = 0; i < 8; ++i) acc[(in_seg ? 16 : 8) + i] += occ[i];
             for (int i = 0; i < 6; ++i) acc[i] += cnt[i];
             acc[6] += 1ull;
+            for (int i = 0; i < 3; ++i) pops[i] += cnt[6 + i];
             if (ws.dbg) {
                 // per-ray maxima: node visits, gates, intersections; and the same summed over the slowest lane's wave
                 unsigned int nv = cnt[0], ng = cnt[1] + cnt[3], ni = cnt[2] + cnt[4];
@@ -745,7 +782,7 @@ __global__ void __launch_bounds__(MW == 0 ? NDT_TRACE_T1_MAX_BLOCK : NDT_TRACE_M
             prim = -1;
         } else
 #endif
-        trace_kd<N, MW, LSTACK, MW == 0, LAZY>(blob, sd, mask, o, v, lim, obj, prim, kstack, cls, live, box_slot);
+        trace_kd<N, MW, LSTACK, MW == 0, LAZY, POP, LEAF_SETS>(blob, sd, mask, o, v, lim, obj, prim, kstack, cls, live, box_slot);
 #endif
 #ifdef NDT_TRACE_SKIP_KNOB
         if (job.skip_trace == 2 && obj == -1) live = false;
@@ -778,6 +815,11 @@ __global__ void __launch_bounds__(MW == 0 ? NDT_TRACE_T1_MAX_BLOCK : NDT_TRACE_M
             unsigned long long x = acc[i];
             for (int d = 32; d > 0; d >>= 1) x += __shfl_xor(x, d, 64);
             if (lane == 0 && x) atomicAdd(&ws.dbg[8 + i], x);
+        }
+        for (int i = 0; i < 3; ++i) {
+            unsigned long long x = pops[i];
+            for (int d = 32; d > 0; d >>= 1) x += __shfl_xor(x, d, 64);
+            if (lane == 0 && x) atomicAdd(&ws.dbg[60 + i], x);
         }
         if (lane == 0) {
             for (int i = 0; i < 4; ++i) atomicAdd(&ws.dbg[i], ph[i]);

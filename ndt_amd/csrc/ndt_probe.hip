@@ -167,6 +167,9 @@ void ndt_impl::print_phase_timing(const unsigned long long *dbg)
         fprintf(stderr, "ndt_hip:    coherent leaf scan: fetching windows %llu, boxes / gates of the windows %llu (its intersections are in I)\n", d[32], d[7]);
     fprintf(stderr, "ndt_hip: per-ray counts over %llu rays: node visits %llu, face gates %llu (pass %llu), item gates %llu (pass %llu), isect hits %llu\n",
             d[14], d[8], d[9], d[10], d[11], d[12], d[13]);
+    if (d[60])
+        fprintf(stderr, "ndt_hip: traversal stack over %llu rays: pops %llu, of them dropped at once %llu; T iterations with a pop in them %llu (of %llu)\n",
+                d[14], d[60], d[61], d[62], d[16] + d[24]);
     fprintf(stderr, "ndt_hip: batch time inside trace_kd (100 MHz wall clock): closest max %.1f us mean %.1f us, shadow max %.1f us mean %.1f us\n",
             d[40] / 100.0, d[44] ? d[42] / 100.0 / d[44] : 0.0, d[41] / 100.0, d[45] ? d[43] / 100.0 / d[45] : 0.0);
     fprintf(stderr, "ndt_hip: per-ray maxima: %llu node visits, %llu gates, %llu intersections; per-batch maxima: %llu T, %llu G, %llu I iterations\n",

@@ -585,7 +585,7 @@ __global__ void __launch_bounds__(NDT_STREAM_MAX_BLOCK) k_frame_stream(const dou
         double *base = lds_blob + ((sd.trace_words + 1) & ~1);
         const int depth = sd.kd_depth + 1;
         kstack.stride = blockDim.x;
-        kstack.tu = base + threadIdx.x;
+        kstack.t = base + threadIdx.x;
         kstack.node = (int *)(base + (size_t)depth * blockDim.x) + threadIdx.x;
     }
     VisitMask<MW> mask;
@@ -701,7 +701,7 @@ __global__ void __launch_bounds__(NDT_STREAM_MAX_BLOCK) k_frame_stream(const dou
 #ifdef NDT_PHASE_TIMING
                 {   // (diagnostic build: the phase stamps of the per-bounce trace kernel are not collected here)
                     unsigned long long ph[8] = {};
-                    unsigned int cnt[8] = {}, occ[8] = {};
+                    unsigned int cnt[12] = {}, occ[8] = {};
                     trace_kd<N, MW, LSTACK>(blob, sd, mask, o, v, lim, obj, prim, ph, cnt, occ, kstack, ClsLds{}, true, box_slot);
                 }
 #else
