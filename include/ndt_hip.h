@@ -707,6 +707,74 @@ int ndt_hip_render_denoised_exr(ndt_hip_ctx *ctx, const ndt_render_params *p, co
 int ndt_hip_denoise_launches(ndt_hip_ctx *ctx);
 double ndt_hip_denoise_ms(ndt_hip_ctx *ctx);
 
+/* The sample moments of a frame: beside the frame, what the adaptive loop of the stochastic paths (samples > 1, area lights)
+ * consumed for every pixel -- the input of the variance-guided denoiser below.
+ *   rgba    what ndt_hip_render_device gives for `p`, bit for bit
+ *   count   [rows * width] int32: the samples the loop consumed for the pixel
+ *   sum_sq  [3][rows * width] doubles: for c = r, g, b, 0.0 and then sum_sq_c = sum_sq_c + l_c * l_c for the colour l of each
+ *           consumed sample, in the order consumed
+ * A frame that does not go through the loop (samples == 1 on a scene without area lights) has count = 1 and sum_sq_c = rgba_c *
+ * rgba_c, from one small launch.  Option "sample_cap" bounds count.  NDT_E_UNSUPPORTED with the cause in the error text, before any
+ * device work and with nothing written: recursive_aa, NDT_STEREO_ANAGLYPH, NDT_STEREO_HIDEF.  Row shards and NDT_STEREO_SIDE_SIDE /
+ * OVER_UNDER work.  _device: device memory (count aligned to 4 bytes, sum_sq to 8); the other: host memory.  Synchronous. */
+int ndt_hip_render_moments_device(ndt_hip_ctx *ctx, const ndt_render_params *p, void *d_rgba, void *d_count, void *d_sum_sq,
+                                  ndt_render_stats *stats);
+int ndt_hip_render_moments(ndt_hip_ctx *ctx, const ndt_render_params *p, double *rgba, int32_t *count, double *sum_sq,
+                           ndt_render_stats *stats);
+
+/* The variance of every pixel's mean, summed over r, g, b, from the moments (kernel k_sample_variance: one lane a pixel, one launch;
+ * device memory; synchronous).  Defined to the bit, for n = count[p]: n < 2 gives 0.0.  Otherwise v = 0 and, for c = r, g, b in
+ * turn:  m = rgba[p][c];  e = sum_sq[c][p] / (double)n - m * m;  e = e > 0 ? e : 0.0;  v = v + e / (double)(n - 1).
+ * variance[p] = v, [rows * width] doubles: in the units of the filter's squared colour distance. */
+int ndt_hip_sample_variance_device(ndt_hip_ctx *ctx, const void *d_rgba, const void *d_count, const void *d_sum_sq, int32_t width,
+                                   int32_t rows, void *d_variance);
+
+/* The variance-guided denoiser (`ndt_hip --vdenoise`): the a-trous filter above with the width of its colour weight taken from the
+ * frame, pixel by pixel, and the variance carried through the iterations.  It filters where the frame is noisy; where it has
+ * converged it copies the pixel bit for bit.  Defined to the bit.  Inputs: those of ndt_hip_denoise_device, and variance =
+ * [rows * width] doubles.  Iteration it = 0 .. iterations - 1 has step s = 1 << it, reads (cur, vcur) and writes (next, vnext);
+ * k2 = k_colour * k_colour and inv_p = 1.0 / (sigma_plane * sigma_plane) are host doubles.  For pixel p = (y, x) with me = id[p]:
+ *   me == 0: next[p] and vnext[p] are cur[p] and vcur[p], bit for bit.
+ *   the local variance, at distance 1 whatever the step: gn = 0, gd = 0; r = (y + b - 1, x + a - 1) for b outer, a inner over
+ *       0 .. 2, g = G[b] * G[a], G = {1/4, 1/2, 1/4}; r is skipped when it lies outside the image or id[r] != me, otherwise
+ *       gn = gn + g * vcur[r];  gd = gd + g.   sp = k2 * (gn / gd).
+ *   !(sp > 0) -- zero, negative or a NaN: next[p] and vnext[p] are copied bit for bit: the pixel has converged.
+ *   otherwise the 25 taps of the definition above in the same order: h, wn, wp as there, cc on `cur`, and
+ *       wc = 1.0 / (1.0 + cc / sp);  w = ((h * wn) * wp) * wc, the tap skipped unless w > 0; the centre always taken with w = h.
+ *       a taken tap, the centre too: num[c] = num[c] + w * cur[q][c] for the four channels, then den = den + w, then
+ *       vn = vn + (w * w) * vcur[q].   Finally next[p][c] = num[c] / den and vnext[p] = vn / (den * den).
+ * Only + - * / and comparisons on doubles, none contracted.
+ *   ndt_hip_vdenoise_device          the filter alone on the context's device memory: arguments, alignments and the in-place rule of
+ *                                    ndt_hip_denoise_device; d_variance and d_variance_out aligned to 8 bytes, d_variance_out may be
+ *                                    NULL (the last plane is dropped) or d_variance.  One launch an iteration; synchronous
+ *   ndt_hip_render_vdenoised_device  on the context's one stream: ndt_hip_render_moments_device for `p`; the feature pass of a copy of
+ *                                    `p` whose samples is 1; k_sample_variance; the iterations into d_rgba (aligned to 16)
+ *   ndt_hip_render_vdenoised         the same into host memory;  _rgba8 / _png / _jpeg / _exr: as ndt_hip_render_denoised's
+ * ndt_hip_denoise_launches / ndt_hip_denoise_ms report the context's last call of either filter: 4 + 1 + iterations launches after
+ * a frame rendered here, iterations after ndt_hip_vdenoise_device.  vp == NULL: the defaults.  Refusals: those of the denoiser
+ * above, and what the moments refuse.  None falls back. */
+typedef struct ndt_vdenoise_params {
+    int32_t iterations;             /* 1 .. 6; default 4 */
+    int32_t normal_power_log2;      /* 0 .. 8; default 5 */
+    double  k_colour;               /* finite, > 0; default 4.0: the colour weight halves at k_colour local standard deviations */
+    double  sigma_plane;            /* finite, > 0; default 0.25 */
+} ndt_vdenoise_params;
+int ndt_hip_vdenoise_device(ndt_hip_ctx *ctx, const void *d_rgba_in, const ndt_feature_planes *d_planes, const void *d_variance,
+                            int32_t dims, int32_t width, int32_t rows, const ndt_vdenoise_params *vp, void *d_rgba_out,
+                            void *d_variance_out);
+int ndt_hip_render_vdenoised_device(ndt_hip_ctx *ctx, const ndt_render_params *p, const ndt_vdenoise_params *vp, void *d_rgba,
+                                    ndt_render_stats *stats);
+int ndt_hip_render_vdenoised(ndt_hip_ctx *ctx, const ndt_render_params *p, const ndt_vdenoise_params *vp, double *rgba,
+                             ndt_render_stats *stats);
+int ndt_hip_render_vdenoised_rgba8(ndt_hip_ctx *ctx, const ndt_render_params *p, const ndt_vdenoise_params *vp, uint8_t *rgba8,
+                                   ndt_render_stats *stats);
+int ndt_hip_render_vdenoised_png(ndt_hip_ctx *ctx, const ndt_render_params *p, const ndt_vdenoise_params *vp, uint8_t *png, int64_t cap,
+                                 ndt_png_stats *stats, ndt_render_stats *render_stats);
+int ndt_hip_render_vdenoised_jpeg(ndt_hip_ctx *ctx, const ndt_render_params *p, const ndt_vdenoise_params *vp, const ndt_jpeg_params *jp,
+                                  uint8_t *jpg, int64_t cap, ndt_jpeg_stats *stats, ndt_render_stats *render_stats);
+int ndt_hip_render_vdenoised_exr(ndt_hip_ctx *ctx, const ndt_render_params *p, const ndt_vdenoise_params *vp, const ndt_exr_params *ep,
+                                 uint8_t *out, int64_t cap, ndt_exr_stats *stats, ndt_render_stats *render_stats);
+
 /* Ambient occlusion of a frame on the device (`ndt_hip --ao`): how open the surface a pixel shows is to its surroundings, in all N
  * coordinates -- geometry only, from the planes of ndt_hip_render_features.  One stage between the render and the sink, as the
  * denoiser is.  Inputs, of the rows `p` selects: id = [rows * width] int32; position, normal, ray_v = [dims][rows * width] doubles, the
@@ -808,8 +876,8 @@ int ndt_hip_render_multi(ndt_hip_ctx *const *ctxs, int32_t n_ctx, const ndt_rend
 enum ndt_multi_path { NDT_MULTI_NONE = 0, NDT_MULTI_LOCAL = 1, NDT_MULTI_PEER = 2, NDT_MULTI_STAGED = 3 };
 int ndt_hip_multi_path_taken(ndt_hip_ctx *ctx);
 
-/* Switches of a context.  None changes an image; they choose between equivalent ways of producing it, or turn diagnostics
- * on.  The same names, upper-cased behind NDT_HIP_ (NDT_HIP_PIPELINE, NDT_HIP_DEBUG_LEVELS ...), are read from the
+/* Switches of a context.  None but "sample_seed" and "sample_cap" changes an image; they choose between equivalent ways of
+ * producing it, or turn diagnostics on.  The same names, upper-cased behind NDT_HIP_ (NDT_HIP_PIPELINE, NDT_HIP_DEBUG_LEVELS ...), are read from the
  * environment ONCE, when the context is created; nothing on the render or upload path looks at the environment.
  *   "pipeline"        0 auto, 1 levels (one trace launch + shade launches per bounce), 2 stream (the whole ray tree in
  *                     one persistent launch) -- DESIGN.md section 3; the environment takes the words
@@ -835,6 +903,11 @@ int ndt_hip_multi_path_taken(ndt_hip_ctx *ctx);
  *                                the slab; 0: the slab only (tests prove every value neutral)
  *   "sample_seed"     stochastic renders (-n > 1, area lights): which set of counter-based random streams the samples draw
  *                     from (0, the default, and any other value give images that are independent draws of one distribution)
+ *   "sample_cap"      stochastic renders: 0 (default) no cap -- `samples` is a lower bound, a pixel goes on sampling while its running
+ *                     mean moves by more than 1/256; C >= 1: no pixel takes more than C samples and no pass renders past them
+ *                     (C <= samples: exactly C a pixel, one pass, aa_samples = C x pixels).  It names no stream: sample r of a pixel
+ *                     is the same sample with and without a cap.  Wherever the loop runs: samples > 1, area lights, the list renders
+ *                     of recursive_aa, both eyes of an anaglyph.  A negative value: NDT_E_INVALID
  *   "multi_path"      ndt_hip_render_multi: 0 auto (stores on the same device, peer stores over xGMI, a staged copy where
  *                     there is no peer access), 1 never staged, 2 always staged -- also between contexts of one device
  *   "light_overlap"   per-bounce pipeline, one light window: 1 (default) the lighting of every bounce but the deepest runs

@@ -61,7 +61,7 @@ extern "C" int ndt_hip_create(int device, ndt_hip_ctx **out)
     ctx->device = device;
     {
         // the environment is read here, once: nothing on the render or upload path looks at it
-        static const char *const names[] = { "stream_below", "stream_below_list", "hull_box", "face_box", "face_tree", "face_groups", "item_sets", "gate_prepass", "gate_prepass_below", "item_boxes", "leaf_history", "leaf_scan", "leaf_scan_group", "multi_path", "sample_seed", "stream_fused", "fuse_primaries", "light_overlap", "early_pixels", "light_window", "ao_batch", "debug_levels",
+        static const char *const names[] = { "stream_below", "stream_below_list", "hull_box", "face_box", "face_tree", "face_groups", "item_sets", "gate_prepass", "gate_prepass_below", "item_boxes", "leaf_history", "leaf_scan", "leaf_scan_group", "multi_path", "sample_seed", "sample_cap", "stream_fused", "fuse_primaries", "light_overlap", "early_pixels", "light_window", "ao_batch", "debug_levels",
                                              "exit_probe", "shade_probe", "stream_probe", "test_small_pool" };
         const char *pl = getenv("NDT_HIP_PIPELINE");
         if (pl) (void)ndt_hip_set_option(ctx, "pipeline", !strcmp(pl, "levels") ? 1 : !strcmp(pl, "stream") ? 2 : 0);
@@ -124,6 +124,7 @@ extern "C" int ndt_hip_destroy(ndt_hip_ctx *ctx)
     for (DeviceBuffer &slot : ctx->pool2) slot.release();
     ctx->d_blob.release();
     ctx->d_out.release();
+    ctx->d_moments.release();
     ctx->d_fit.release();
     free_kd(ctx);
     free_png(ctx);
@@ -166,6 +167,10 @@ extern "C" int ndt_hip_set_option(ndt_hip_ctx *ctx, const char *name, int64_t va
     else if (!strcmp(name, "gate_prepass_below")) ctx->gate_prepass_below = value;
     else if (!strcmp(name, "gate_prepass")) ctx->gate_prepass = value < 0 ? 0 : value > 2 ? 2 : (int)value;
     else if (!strcmp(name, "sample_seed")) ctx->sample_seed = value;
+    else if (!strcmp(name, "sample_cap")) {
+        if (value < 0) return fail(NDT_E_INVALID, "sample_cap %lld (0 no cap, or the most samples a pixel takes)", (long long)value);
+        ctx->sample_cap = value > 10000 ? 10000 : (int)value;       // (the loop ends at 10000 samples by itself)
+    }
     else if (!strcmp(name, "leaf_scan")) ctx->leaf_scan = on;
     else if (!strcmp(name, "leaf_scan_group")) ctx->leaf_scan_group = value < 1 ? 1 : value > 64 ? 64 : (int)value;
     else if (!strcmp(name, "leaf_history")) ctx->leaf_history = value < 0 ? 0 : value > 4 ? 4 : (int)value;

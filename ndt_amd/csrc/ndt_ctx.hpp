@@ -6,7 +6,7 @@
 //   ndt_frame.hip    workspace + one pass of the ray pipeline over a set of primaries (render_pass)
 //   ndt_probe.hip    what the diagnostics of a profiled pass print (stream / shade / exit probes, NDT_PHASE_TIMING)
 //   ndt_aa.hip       Whitted's recursive anti-aliasing on top of render_pass
-//   ndt_sampled.hip  -n samples > 1, lens, area lights on top of render_pass
+//   ndt_sampled.hip  -n samples > 1, lens, area lights on top of render_pass; option "sample_cap" and the sample moments of a frame
 //   ndt_render.hip   ndt_hip_render*: argument checks and the choice between the three; and where every frame staged on the device is
 //                    delivered (FrameView below): the file formats' refusals and the tails.  The stage files below produce
 //   ndt_multi.hip    one frame over several contexts / devices
@@ -23,7 +23,8 @@
 //   ndt_depth.hip    ndt_hip_depth_rgba8_device / ndt_hip_render_*_depth: the depth map of `-z` normalised and quantised on the device
 //   ndt_ssaa.hip     ndt_hip_ssaa_fold_device / ndt_hip_render_ssaa*: K x K supersampling, K ordinary renders folded on the device
 //   ndt_denoise.hip  ndt_hip_denoise_device / ndt_hip_render_denoised*: the edge-avoiding a-trous filter over the double framebuffer,
-//                    guided by the feature planes; kernel, launcher and C ABI
+//                    guided by the feature planes; kernel, launcher and C ABI.  And ndt_hip_sample_variance_device / ndt_hip_vdenoise_device /
+//                    ndt_hip_render_vdenoised*: the same filter with the colour weight's width taken from the frame's sample moments
 //   ndt_ao.hip       ndt_hip_ao_device / ndt_hip_render_ao* / ndt_hip_render_exr_ao: ambient occlusion from the feature planes -- the
 //                    sample rays, the trace kernel as it is, the fold into a plane, the plane applied to a frame; kernels and C ABI
 //   ndt_shading.hpp  the arithmetic of apply_lights and get_ray_color on values, stated once for every kernel that shades: the
@@ -144,13 +145,15 @@ struct SsaaState {
     double fold_ms = 0.0;           // their summed device time
 };
 
-// ndt_hip_denoise_device, ndt_hip_render_denoised* (ndt_denoise.hip): grow-only device buffers, reused by the next frame
+// ndt_hip_denoise_device, ndt_hip_render_denoised*, ndt_hip_vdenoise_device, ndt_hip_render_vdenoised* (ndt_denoise.hip): grow-only device buffers, reused by the next frame
 struct DenoiseState {
     DeviceBuffer d_ping, d_pong;    // what the iterations between the first image and the last one write: rows x width x 4 doubles each
+    DeviceBuffer d_vping, d_vpong;  // ndt_hip_vdenoise_device, ndt_hip_render_vdenoised*: the same for the variance plane, rows x width doubles each
+    DeviceBuffer d_moments, d_variance;     // ndt_hip_render_vdenoised*: the frame's sums of squares with its counts behind them; its variance plane
     DeviceBuffer d_frame;           // ndt_hip_render_denoised*: the frame as rendered
     DeviceBuffer d_out, d_rgba8;    // ... denoised, for the calls that deliver to host memory or as a file, and its 8-bit image
     hipEvent_t ev[12] = {};         // around every iteration's launch
-    int launches = 0;               // kernel launches of the last call: the feature pass's and the iterations'
+    int launches = 0;               // kernel launches of the last call of either filter: the feature pass's, k_sample_variance and the iterations'
     int iterations = 0;             // iterations of the last call
     double ms = 0.0;                // their summed device time
 };
@@ -279,6 +282,8 @@ struct ndt_hip_ctx {
     DeviceBuffer d_stage;
     hipStream_t stage_stream = nullptr;
     int stage_device = 0;
+    int sample_cap = 0;             // option "sample_cap": the adaptive loop of the stochastic paths stops at this many samples a pixel (0: no cap)
+    DeviceBuffer d_moments;         // ndt_hip_render_moments: the sums of squares and, behind them, the counts, before they are delivered
     long long sample_seed = 0;      // option "sample_seed": selects the set of random streams of the stochastic paths (0: the default set)
     int multi_path = 0;             // option "multi_path": 0 auto, 1 never staged, 2 always staged
     int multi_path_taken = 0;       // ndt_multi_path of the last multi-context frame (ndt_hip_multi_path_taken)
@@ -397,6 +402,8 @@ struct FrameView {
 };
 // the plain frame (and its map) into ctx->d_out; v->rows = 0: no pixels, nothing made, the render call's word on `p` comes back
 int render_plain_own(ndt_hip_ctx *ctx, const char *who, const ndt_render_params *p, bool want_depth, ndt_render_stats *stats, FrameView *v);
+// what ndt_hip_render_moments* refuse under the name `who`, before any device work: recursive_aa, anaglyph, frame packing
+int moments_refuse(const char *who, const ndt_render_params *p);
 // what a file sink refuses before the render: a shard without rows, then a size beyond the format's bound (PNG: bpp 4, 8, 2)
 int refuse_empty_shard(const char *who, int rows);
 int refuse_png(const char *who, int32_t width, int32_t rows, int bpp);
@@ -433,7 +440,13 @@ void free_ao(ndt_hip_ctx *ctx);
 int render_antialiased(ndt_hip_ctx *ctx, const ndt_render_params *p, void *d_rgba, ndt_render_stats &total, void *d_depth = nullptr);
 // ndt_render.hip: true anaglyph (ndt.c:643-647) of two eye images, n_pixels x rgba each
 void launch_anaglyph(hipStream_t s, const double *left, const double *right, double *out, long long n_pixels);
-int render_sampled(ndt_hip_ctx *ctx, const ndt_render_params *p, void *d_rgba, ndt_render_stats &total, void *d_depth = nullptr);
+// mo (ndt_hip_render_moments*; not for an anaglyph): where the loop also leaves what it consumed -- device memory
+struct SampleMoments {
+    void *d_count;              // [n_pixels] int32: samples consumed
+    void *d_sum_sq;             // [3][n_pixels] doubles: the sums of their squared r, g, b
+};
+int render_sampled(ndt_hip_ctx *ctx, const ndt_render_params *p, void *d_rgba, ndt_render_stats &total, void *d_depth = nullptr,
+                   const SampleMoments *mo = nullptr);
 // get_pixel_color's adaptive loop (ndt.c:488-568) for a LIST of image positions (2 doubles each, pixels of an img_w x img_h
 // image): the samples of a stochastic anti-aliased render (a lens, area lights).  No jitter (ndt.c:505: not in this mode).
 struct SampledList {

@@ -20,8 +20,17 @@ void ndt_impl::launch_anaglyph(hipStream_t s, const double *left, const double *
     hipLaunchKernelGGL(k_anaglyph, dim3((unsigned)((n_pixels + 255) / 256)), dim3(256), 0, s, left, right, out, n_pixels);
 }
 
-extern "C" int ndt_hip_render_depth_device(ndt_hip_ctx *ctx, const ndt_render_params *p, void *d_rgba, void *d_depth,
-                                           ndt_render_stats *stats)
+// The moments of a frame that does not go through the sampled loop: one sample a pixel, the pixel itself
+__global__ void k_moments_single(const double *rgba, int *count, double *sum_sq, long long n_pixels)
+{
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n_pixels) return;
+    count[i] = 1;
+    for (int c = 0; c < 3; ++c) sum_sq[c * n_pixels + i] = rgba[4 * i + c] * rgba[4 * i + c];
+}
+
+// ndt_hip_render_depth_device; mo (ndt_hip_render_moments*, whose refusals the caller has made): the frame's sample moments too
+static int render_frame(ndt_hip_ctx *ctx, const ndt_render_params *p, void *d_rgba, void *d_depth, ndt_render_stats *stats, const SampleMoments *mo)
 {
     if (!ctx || !p || !d_rgba) return fail(NDT_E_INVALID, "NULL argument");
     if (!ctx->have_scene) return fail(NDT_E_STATE, "no scene uploaded");
@@ -58,6 +67,7 @@ extern "C" int ndt_hip_render_depth_device(ndt_hip_ctx *ctx, const ndt_render_pa
         // get_ray_color returns black without tracing (ndt.c:340); averages of black are black
         launch_fill_black(s, (double *)d_rgba, n_pixels);
         if (d_depth) HIP_TRY(hipMemsetAsync(d_depth, 0, (size_t)n_pixels * sizeof(double), s));
+        if (mo) hipLaunchKernelGGL(k_moments_single, dim3((unsigned)((n_pixels + 255) / 256)), dim3(256), 0, s, (const double *)d_rgba, (int *)mo->d_count, (double *)mo->d_sum_sq, n_pixels);
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipStreamSynchronize(s));
         if (stats) *stats = st;
@@ -68,7 +78,7 @@ extern "C" int ndt_hip_render_depth_device(ndt_hip_ctx *ctx, const ndt_render_pa
     if (p->recursive_aa) {
         rc = render_antialiased(ctx, p, d_rgba, st, d_depth);
     } else if (stochastic) {
-        rc = render_sampled(ctx, p, d_rgba, st, d_depth);
+        rc = render_sampled(ctx, p, d_rgba, st, d_depth, mo);
     } else {
         RenderGeom rg{};
         rg.width = p->width;
@@ -116,9 +126,64 @@ extern "C" int ndt_hip_render_depth_device(ndt_hip_ctx *ctx, const ndt_render_pa
             }
             rc = render_pass(ctx, rg, p->profile != 0, d_rgba, st, d_depth);
         }
+        if (!rc && mo) {
+            // no sampled loop, no such state: one sample a pixel, the pixel itself
+            hipLaunchKernelGGL(k_moments_single, dim3((unsigned)((n_pixels + 255) / 256)), dim3(256), 0, s, (const double *)d_rgba, (int *)mo->d_count, (double *)mo->d_sum_sq, n_pixels);
+            HIP_TRY(hipGetLastError());
+            HIP_TRY(hipStreamSynchronize(s));
+        }
     }
     if (rc) return rc;
     if (stats) *stats = st;
+    return NDT_OK;
+}
+
+extern "C" int ndt_hip_render_depth_device(ndt_hip_ctx *ctx, const ndt_render_params *p, void *d_rgba, void *d_depth,
+                                           ndt_render_stats *stats)
+{
+    return render_frame(ctx, p, d_rgba, d_depth, stats, nullptr);
+}
+
+int ndt_impl::moments_refuse(const char *who, const ndt_render_params *p)
+{
+    if (p->recursive_aa)
+        return fail(NDT_E_UNSUPPORTED, "%s: no sample moments of a recursive_aa frame: its pixels are averages of corner samples, not of the loop's samples", who);
+    if (p->stereo == NDT_STEREO_ANAGLYPH) return fail(NDT_E_UNSUPPORTED, "%s: no sample moments of an NDT_STEREO_ANAGLYPH frame: a pixel mixes two loops", who);
+    if (p->stereo == NDT_STEREO_HIDEF) return fail(NDT_E_UNSUPPORTED, "%s: no sample moments of an NDT_STEREO_HIDEF (frame-packed) frame", who);
+    return NDT_OK;
+}
+
+extern "C" int ndt_hip_render_moments_device(ndt_hip_ctx *ctx, const ndt_render_params *p, void *d_rgba, void *d_count, void *d_sum_sq,
+                                             ndt_render_stats *stats)
+{
+    const char *who = "ndt_hip_render_moments_device";
+    if (!ctx || !p || !d_rgba || !d_count || !d_sum_sq) return fail(NDT_E_INVALID, "%s: NULL argument", who);
+    if (((uintptr_t)d_count & 3u) != 0 || ((uintptr_t)d_sum_sq & 7u) != 0) return fail(NDT_E_INVALID, "%s: misaligned: the counts to 4 bytes, the sums to 8", who);
+    const int rc = moments_refuse(who, p);
+    if (rc) return rc;
+    const SampleMoments mo{ d_count, d_sum_sq };
+    return render_frame(ctx, p, d_rgba, nullptr, stats, &mo);
+}
+
+extern "C" int ndt_hip_render_moments(ndt_hip_ctx *ctx, const ndt_render_params *p, double *rgba, int32_t *count, double *sum_sq,
+                                      ndt_render_stats *stats)
+{
+    const char *who = "ndt_hip_render_moments";
+    if (!ctx || !p || !rgba || !count || !sum_sq) return fail(NDT_E_INVALID, "%s: NULL argument", who);
+    int rc = moments_refuse(who, p);
+    if (rc) return rc;
+    HIP_TRY(hipSetDevice(ctx->device));
+    const int rows = p->width > 0 && p->height > 0 && p->row_step > 0 && p->row_begin >= 0 ? ndt_hip_shard_rows(p->height, p->row_begin, p->row_step) : 0;
+    if (rows == 0) return render_frame(ctx, p, (void *)ctx, nullptr, stats, nullptr);      // no pixels: the render call's word on `p`
+    const size_t pixels = (size_t)rows * (size_t)p->width;
+    if ((rc = ctx->d_out.reserve(pixels * 4 * sizeof(double), ctx->stream, who))) return rc;
+    if ((rc = ctx->d_moments.reserve(pixels * (3 * sizeof(double) + sizeof(int32_t)), ctx->stream, who))) return rc;
+    const SampleMoments mo{ ctx->d_moments.as<char>() + pixels * 3 * sizeof(double), ctx->d_moments.p };
+    if ((rc = render_frame(ctx, p, ctx->d_out.p, nullptr, stats, &mo))) return rc;
+    HIP_TRY(hipMemcpyAsync(rgba, ctx->d_out.p, pixels * 4 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(count, mo.d_count, pixels * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(sum_sq, mo.d_sum_sq, pixels * 3 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
     return NDT_OK;
 }
 

@@ -69,9 +69,12 @@ __global__ void k_ns_samples(const int *active, int n_active, int per, int width
 // sdepth: a depth-map render -- every sample overwrites the pixel's depth (get_ray_color, ndt.c:362-373), so the LAST sample the
 // loop takes leaves its value.  blank_from / blank_to: image rows of a frame-packed image that stay black (ndt.c:625-627: no
 // sample is taken there)
+// cap (option "sample_cap"; 0: none): the loop also ends once `cap` samples are consumed -- with 0 every decision is the one above.
+// sq (or nullptr: nothing is loaded or stored): 3 doubles a pixel, the sum of the squares of the r, g, b of every consumed sample, in
+// the order consumed (ndt_hip_render_moments*)
 __global__ void k_ns_accumulate(const int *active, int n_active, int per, const double *colours, const double *sdepth, unsigned int round0,
                                 int min_samples, int width, int row_begin, int row_step, int blank_from, int blank_to, double *acc,
-                                int *taken, int *next, int *next_count)
+                                int *taken, int *next, int *next_count, int cap, double *sq)
 {
     const int a = blockIdx.x * blockDim.x + threadIdx.x;
     const bool in_range = a < n_active;
@@ -98,10 +101,16 @@ __global__ void k_ns_accumulate(const int *active, int n_active, int per, const 
             clr_diff = (dr > gb) ? dr : gb;
         }
         t[0] += l[0]; t[1] += l[1]; t[2] += l[2]; t[3] += l[3];
+        if (sq) {
+            double *q = sq + 3ll * pix;
+            q[0] = q[0] + l[0] * l[0];
+            q[1] = q[1] + l[1] * l[1];
+            q[2] = q[2] + l[2] * l[2];
+        }
         if (sdepth) t[5] = sdepth[(long long)a * per + r];
         ++used;
         const int done = i + 1;
-        go_on = done < min_samples || (done < 10000 && clr_diff > 1.0 / 256.0);
+        go_on = (done < min_samples || (done < 10000 && clr_diff > 1.0 / 256.0)) && (cap == 0 || done < cap);
     }
     if (in_range) {
         t[4] = clr_diff;
@@ -111,10 +120,11 @@ __global__ void k_ns_accumulate(const int *active, int n_active, int per, const 
     if (go_on) next[slot] = pix;
 }
 
-__global__ void k_ns_init(double *acc, int *active, int *taken, long long n_pixels)
+__global__ void k_ns_init(double *acc, int *active, int *taken, long long n_pixels, double *sq)
 {
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n_pixels) return;
+    if (sq) sq[3 * i] = sq[3 * i + 1] = sq[3 * i + 2] = 0.0;
     double *t = acc + 6 * i;
     t[0] = t[1] = t[2] = t[3] = 0.0;
     t[4] = 256.0;
@@ -145,13 +155,24 @@ __global__ void k_ns_finish(const double *acc, const int *taken, double *rgba, d
     }
 }
 
+// ndt_hip_render_moments*: what the loop kept of every pixel beside its mean -- the samples it consumed and, as planes [3][n_pixels],
+// the sums of their squares
+__global__ void k_ns_finish_moments(const int *taken, const double *sq, int *count, double *sum_sq, long long n_pixels)
+{
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n_pixels) return;
+    count[i] = taken[i];
+    for (int c = 0; c < 3; ++c) sum_sq[c * n_pixels + i] = sq[3 * i + c];
+}
+
 // One eye's image (or the whole image, for the modes that split it by position).  eye: 0 left, 1 centre, 2 right; stereo: what
 // the ray pipeline is told (0 for the two passes of an anaglyph); salt: the two eyes of an anaglyph draw from different streams,
 // as the reference's two get_pixel_color calls draw different numbers (ndt.c:639-640).
 // (sl: the positions of a list render instead of the image's pixels -- the samples of an anti-aliased render, which calls this
 // from inside its own pass and so hands out the scratch of the nested pool)
+// (mo: the frame's sample moments too, into device memory -- the image's pixels only)
 static int render_sampled_eye(ndt_hip_ctx *ctx, const ndt_render_params *p, int eye, int stereo, unsigned long long salt, void *d_rgba,
-                              ndt_render_stats &total, void *d_depth, const SampledList *sl = nullptr)
+                              ndt_render_stats &total, void *d_depth, const SampledList *sl = nullptr, const SampleMoments *mo = nullptr)
 {
     hipStream_t s = ctx->stream;
     const int W = sl ? sl->img_w : p->width, H = sl ? sl->img_h : p->height;
@@ -164,7 +185,9 @@ static int render_sampled_eye(ndt_hip_ctx *ctx, const ndt_render_params *p, int 
     double *acc = nullptr, *samples = nullptr, *colours = nullptr;
     unsigned long long *keys = nullptr;
     int *list[2] = { nullptr, nullptr }, *taken = nullptr, *counter = nullptr;
-    double *sdepth = nullptr;
+    double *sdepth = nullptr, *sq = nullptr;
+    // option "sample_cap": no pixel takes more samples than this, and no pass renders past it (0: none)
+    const unsigned int cap = (unsigned int)ctx->sample_cap;
     // frame packing: 1080 lines left eye, 45 blank, 1080 right eye (ndt.c:614-631)
     const int blank_from = (stereo == NDT_STEREO_HIDEF && !sl) ? 1080 : 1, blank_to = (stereo == NDT_STEREO_HIDEF && !sl) ? 1080 + 45 : 0;
     if ((rc = buf.get(&acc, (size_t)n_pixels * 6))) return rc;
@@ -172,15 +195,16 @@ static int render_sampled_eye(ndt_hip_ctx *ctx, const ndt_render_params *p, int 
     if ((rc = buf.get(&list[1], (size_t)n_pixels))) return rc;
     if ((rc = buf.get(&taken, (size_t)n_pixels))) return rc;
     if ((rc = buf.get(&counter, 1))) return rc;
+    if (mo && (rc = buf.get(&sq, (size_t)n_pixels * 3))) return rc;
     const unsigned g_all = (unsigned)((n_pixels + 255) / 256);
-    hipLaunchKernelGGL(k_ns_init, dim3(g_all), dim3(256), 0, s, acc, list[0], taken, n_pixels);
+    hipLaunchKernelGGL(k_ns_init, dim3(g_all), dim3(256), 0, s, acc, list[0], taken, n_pixels, sq);
     int n_active = (int)n_pixels;
     // samples per pixel and pass: the first `samples` are certain to be needed; after that the loop may stop at
     // any sample, so passes speculate further ahead the fewer pixels are left (about 4 M primaries per pass)
     const long long per_pass = 4ll << 20;
     size_t cap_samples = 0;
     int flip = 0;
-    for (unsigned int round = 0; n_active > 0 && round < 10000;) {
+    for (unsigned int round = 0; n_active > 0 && round < 10000 && (cap == 0 || round < cap);) {
         long long per = round < (unsigned int)p->samples ? (long long)p->samples - round : per_pass / n_active;
         if (per > per_pass / n_active) per = per_pass / n_active;
         // ... but never more than have been taken already: the waste stays below a factor of two
@@ -188,6 +212,7 @@ static int render_sampled_eye(ndt_hip_ctx *ctx, const ndt_render_params *p, int 
         if (per < 1) per = 1;
         if (per > 64) per = 64;
         if (round + per > 10000) per = 10000 - round;
+        if (cap != 0 && round + per > cap) per = cap - round;
         const long long n_s = (long long)n_active * per;
         if ((size_t)n_s > cap_samples) {
             cap_samples = (size_t)n_s;
@@ -221,7 +246,7 @@ static int render_sampled_eye(ndt_hip_ctx *ctx, const ndt_render_params *p, int 
         add_stats(total, st);
         HIP_TRY(hipMemsetAsync(counter, 0, sizeof(int), s));
         hipLaunchKernelGGL(k_ns_accumulate, dim3((unsigned)((n_active + 1023) / 1024)), dim3(1024), 0, s, list[flip], n_active, (int)per, colours, d_depth ? sdepth : nullptr,
-                           round, p->samples, W, p->row_begin, p->row_step, blank_from, blank_to, acc, taken, list[flip ^ 1], counter);
+                           round, p->samples, W, p->row_begin, p->row_step, blank_from, blank_to, acc, taken, list[flip ^ 1], counter, (int)cap, sq);
         HIP_TRY(hipMemcpyAsync(&n_active, counter, sizeof(int), hipMemcpyDeviceToHost, s));
         HIP_TRY(hipStreamSynchronize(s));
         flip ^= 1;
@@ -231,6 +256,8 @@ static int render_sampled_eye(ndt_hip_ctx *ctx, const ndt_render_params *p, int 
     if ((rc = buf.get(&used_total, 1))) return rc;
     HIP_TRY(hipMemsetAsync(used_total, 0, sizeof(unsigned long long), s));
     hipLaunchKernelGGL(k_ns_finish, dim3((unsigned)((n_pixels + 1023) / 1024)), dim3(1024), 0, s, acc, taken, (double *)d_rgba, (double *)d_depth, n_pixels, used_total);
+    if (mo)
+        hipLaunchKernelGGL(k_ns_finish_moments, dim3(g_all), dim3(256), 0, s, taken, sq, (int *)mo->d_count, (double *)mo->d_sum_sq, n_pixels);
     HIP_TRY(hipMemcpyAsync(&used_host, used_total, sizeof(used_host), hipMemcpyDeviceToHost, s));
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(s));
@@ -244,9 +271,10 @@ int ndt_impl::render_sampled_list(ndt_hip_ctx *ctx, const ndt_render_params *p, 
     return render_sampled_eye(ctx, p, eye, stereo, salt, d_rgba, total, nullptr, &sl);
 }
 
-int ndt_impl::render_sampled(ndt_hip_ctx *ctx, const ndt_render_params *p, void *d_rgba, ndt_render_stats &total, void *d_depth)
+int ndt_impl::render_sampled(ndt_hip_ctx *ctx, const ndt_render_params *p, void *d_rgba, ndt_render_stats &total, void *d_depth,
+                             const SampleMoments *mo)
 {
-    if (p->stereo != NDT_STEREO_ANAGLYPH) return render_sampled_eye(ctx, p, 1, p->stereo, 0ull, d_rgba, total, d_depth);
+    if (p->stereo != NDT_STEREO_ANAGLYPH) return render_sampled_eye(ctx, p, 1, p->stereo, 0ull, d_rgba, total, d_depth, nullptr, mo);
     // anaglyph (ndt.c:636-647): every pixel runs get_pixel_color for the left eye, then for the right; the depth map is the left's
     const int rows = ndt_hip_shard_rows(p->height, p->row_begin, p->row_step);
     const long long n_pixels = (long long)rows * p->width;

@@ -37,6 +37,9 @@ API_SYMBOLS = [
     "ndt_hip_encode_exr_features_device", "ndt_hip_render_exr_features", "ndt_hip_render_ssaa_exr_features",
     "ndt_hip_denoise_device", "ndt_hip_render_denoised_device", "ndt_hip_render_denoised", "ndt_hip_render_denoised_rgba8",
     "ndt_hip_render_denoised_png", "ndt_hip_render_denoised_jpeg", "ndt_hip_render_denoised_exr", "ndt_hip_denoise_launches", "ndt_hip_denoise_ms",
+    "ndt_hip_render_moments_device", "ndt_hip_render_moments", "ndt_hip_sample_variance_device", "ndt_hip_vdenoise_device",
+    "ndt_hip_render_vdenoised_device", "ndt_hip_render_vdenoised", "ndt_hip_render_vdenoised_rgba8", "ndt_hip_render_vdenoised_png",
+    "ndt_hip_render_vdenoised_jpeg", "ndt_hip_render_vdenoised_exr",
     "ndt_hip_ao_device", "ndt_hip_render_ao_device", "ndt_hip_render_ao", "ndt_hip_ao_apply_device", "ndt_hip_render_ao_shaded_device",
     "ndt_hip_render_ao_shaded", "ndt_hip_render_ao_shaded_rgba8", "ndt_hip_render_ao_shaded_png", "ndt_hip_render_ao_shaded_jpeg",
     "ndt_hip_exr_ao_bound", "ndt_hip_encode_exr_ao_device", "ndt_hip_render_exr_ao", "ndt_hip_ao_launches", "ndt_hip_ao_ms",
@@ -197,6 +200,18 @@ def load_library():
         lib.ndt_hip_denoise_launches.argtypes = [C.c_void_p]
         lib.ndt_hip_denoise_ms.argtypes = [C.c_void_p]
         lib.ndt_hip_denoise_ms.restype = C.c_double
+    if hasattr(lib, "ndt_hip_vdenoise_device"):     # (likewise)
+        lib.ndt_hip_render_moments_device.argtypes = [C.c_void_p] * 6
+        lib.ndt_hip_render_moments.argtypes = [C.c_void_p] * 6
+        lib.ndt_hip_sample_variance_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]
+        lib.ndt_hip_vdenoise_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p,
+                                                C.c_void_p, C.c_void_p]
+        lib.ndt_hip_render_vdenoised_device.argtypes = [C.c_void_p] * 5
+        lib.ndt_hip_render_vdenoised.argtypes = [C.c_void_p] * 5
+        lib.ndt_hip_render_vdenoised_rgba8.argtypes = [C.c_void_p] * 5
+        lib.ndt_hip_render_vdenoised_png.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
+        lib.ndt_hip_render_vdenoised_jpeg.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
+        lib.ndt_hip_render_vdenoised_exr.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
     if hasattr(lib, "ndt_hip_ao_device"):           # (likewise)
         lib.ndt_hip_ao_device.argtypes = [C.c_void_p] * 6
         lib.ndt_hip_render_ao_device.argtypes = [C.c_void_p] * 6
@@ -323,6 +338,16 @@ class DenoiseParams(C.Structure):
 def denoise_params(iterations=4, sigma_colour=0.25, sigma_plane=0.25, normal_power_log2=5):
     """The ndt_denoise_params of these values (the defaults are the library's); the library checks their ranges."""
     return DenoiseParams(int(iterations), int(normal_power_log2), float(sigma_colour), float(sigma_plane))
+
+
+class VDenoiseParams(C.Structure):
+    """ndt_vdenoise_params: iterations 1 .. 6, normal_power_log2 0 .. 8, k_colour and sigma_plane finite and above 0"""
+    _fields_ = [("iterations", C.c_int32), ("normal_power_log2", C.c_int32), ("k_colour", C.c_double), ("sigma_plane", C.c_double)]
+
+
+def vdenoise_params(iterations=4, k_colour=4.0, sigma_plane=0.25, normal_power_log2=5):
+    """The ndt_vdenoise_params of these values (the defaults are the library's); the library checks their ranges."""
+    return VDenoiseParams(int(iterations), int(normal_power_log2), float(k_colour), float(sigma_plane))
 
 
 class AoParams(C.Structure):
@@ -884,6 +909,48 @@ class NdtHip:
         p = self.params(width, height, depth, **kw)
         dp = denoise_params(iterations, sigma_colour, sigma_plane, normal_power_log2)
         return self._staged_sink("ndt_hip_render_denoised", (self.ctx, C.byref(p), C.byref(dp)), sink, (None, "device", "rgba8", "png", "jpeg", "exr"),
+                                 shard_rows(height, p.row_begin, p.row_step), width, device=(d_rgba_ptr,), quality=quality, sampling=sampling,
+                                 pixel=pixel, cap=cap)
+
+    def render_moments(self, width, height, depth, **kw):
+        """ndt_hip_render_moments: the frame render(**kw) gives, bit for bit, and what the adaptive loop consumed for it: returns
+        ((rows, width, 4) float64, count (rows, width) int32 -- the samples of every pixel --, sum_sq (3, rows, width) float64 -- the
+        sums of their squared r, g, b --, RenderStats).  Option "sample_cap" bounds the counts."""
+        p = self.params(width, height, depth, **kw)
+        rows = shard_rows(height, p.row_begin, p.row_step)
+        out = np.zeros((rows, width, 4), dtype=np.float64)
+        count = np.zeros((rows, width), dtype=np.int32)
+        sum_sq = np.zeros((3, rows, width), dtype=np.float64)
+        st = RenderStats()
+        self._check(self.lib.ndt_hip_render_moments(self.ctx, C.byref(p), out.ctypes.data, count.ctypes.data, sum_sq.ctypes.data, C.byref(st)))
+        return out, count, sum_sq, st
+
+    def sample_variance(self, d_rgba_ptr, d_count_ptr, d_sum_sq_ptr, width, rows, d_variance_ptr):
+        """ndt_hip_sample_variance_device: the variance of every pixel's mean, summed over r, g, b, from the moments at raw device
+        pointers, into rows * width doubles at `d_variance_ptr`."""
+        self._check(self.lib.ndt_hip_sample_variance_device(self.ctx, C.c_void_p(d_rgba_ptr), C.c_void_p(d_count_ptr), C.c_void_p(d_sum_sq_ptr),
+                                                            int(width), int(rows), C.c_void_p(d_variance_ptr)))
+
+    def vdenoise(self, d_rgba_in_ptr, d_planes, d_variance_ptr, dims, width, rows, d_rgba_out_ptr=None, d_variance_out_ptr=None, **vd):
+        """ndt_hip_vdenoise_device: the variance-guided a-trous filter alone, on rows x width x 4 device doubles at `d_rgba_in_ptr` and
+        the rows x width variance plane at `d_variance_ptr`, guided by the device planes `d_planes` names, into `d_rgba_out_ptr`
+        (default: in place) and, unless None, the propagated plane into `d_variance_out_ptr`.  vd: iterations, k_colour, sigma_plane,
+        normal_power_log2."""
+        vp = vdenoise_params(**vd)
+        planes = FeaturePlanes(d_planes.get("id"), d_planes.get("position"), d_planes.get("normal"), None, None)
+        out = d_rgba_in_ptr if d_rgba_out_ptr is None else d_rgba_out_ptr
+        self._check(self.lib.ndt_hip_vdenoise_device(self.ctx, C.c_void_p(d_rgba_in_ptr), C.byref(planes), C.c_void_p(d_variance_ptr), int(dims),
+                                                     int(width), int(rows), C.byref(vp), C.c_void_p(out),
+                                                     C.c_void_p(d_variance_out_ptr) if d_variance_out_ptr else None))
+
+    def render_vdenoised(self, width, height, depth, sink=None, iterations=4, k_colour=4.0, sigma_plane=0.25, normal_power_log2=5,
+                         d_rgba_ptr=None, quality=95, sampling="420", pixel="half", cap=None, **kw):
+        """ndt_hip_render_vdenoised*: the frame render(**kw) gives, denoised on the device by the variance-guided a-trous filter: the
+        width of its colour weight comes from the sample moments of the frame itself, pixel by pixel.  Sinks and answers as
+        render_denoised's; denoise_launches() is 5 + iterations afterwards."""
+        p = self.params(width, height, depth, **kw)
+        vp = vdenoise_params(iterations, k_colour, sigma_plane, normal_power_log2)
+        return self._staged_sink("ndt_hip_render_vdenoised", (self.ctx, C.byref(p), C.byref(vp)), sink, (None, "device", "rgba8", "png", "jpeg", "exr"),
                                  shard_rows(height, p.row_begin, p.row_step), width, device=(d_rgba_ptr,), quality=quality, sampling=sampling,
                                  pixel=pixel, cap=cap)
 

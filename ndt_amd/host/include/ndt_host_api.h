@@ -453,6 +453,14 @@ typedef struct ndt_frame_request {
     int ao_samples;
     double ao_radius, ao_strength;
     unsigned long long ao_seed;
+    /* `--sample-cap C`: option "sample_cap" of every context of the thread (include/ndt_hip.h) -- no pixel takes more than C samples;
+     * 0 = no cap, `samples` is a lower bound */
+    int sample_cap;
+    /* `--vdenoise`: the frame denoised on the GPU by the variance-guided a-trous filter of ndt_hip_render_vdenoised*, which takes the
+     * width of its colour weight from the frame's own sample moments.  The four are ndt_vdenoise_params'; vdenoise_iterations 0 = off.
+     * It goes with what denoise_iterations goes with, is refused with what that is refused with, and with denoise_iterations itself */
+    int vdenoise_iterations, vdenoise_normal_power_log2;
+    double vdenoise_k_colour, vdenoise_sigma_plane;
 } ndt_frame_request;
 /* Everything that arrives is malloc'ed by the library and freed by ndt_frame_free; what was not asked for stays NULL. */
 typedef struct ndt_frame {
@@ -464,7 +472,7 @@ typedef struct ndt_frame {
     /* host milliseconds of the frame's device work beside the render: making the file or files, finishing the map, the folds of --ssaa */
     double file_ms, depth_ms, ssaa_ms;
     int feature_channels, feature_launches;     /* exr_features: the channels it added to the file, and the kernel launches of the feature pass */
-    int denoise_launches;                       /* denoise_iterations: kernel launches of the feature pass and the iterations */
+    int denoise_launches;                       /* denoise_iterations, vdenoise_iterations: kernel launches of the feature pass (and k_sample_variance) and the iterations */
     double denoise_ms;                          /* ... and the iterations' summed device time */
     int ao_launches;                            /* ao_samples: kernel launches of the feature pass, the occlusion pass and the apply */
     double ao_ms;                               /* ... and the device time of the occlusion pass */
@@ -475,7 +483,7 @@ typedef struct ndt_frame {
  * as 8-bit pixels, and a PNG or JPEG file is then encoded from those on the first context; a frame with a map is rendered by one
  * context whatever was set, and a 16-bit PNG, an OpenEXR file or an animated PNG frame over several contexts is refused.  What the
  * device did is said on stdout: `compressed PNG of B bytes on GPU D in L launches` (`16-bit PNG`, `depth PNG`, `16-bit depth PNG`),
- * `encoded JPEG of ...`, `encoded EXR of ...`, `added K feature channels on GPU D in L launches`, `finished depth map [lo, hi] on GPU D in L launches`, `supersampled KxK on GPU D in L launches`, `denoised in K iterations on GPU D in L launches`, `ambient occlusion of K samples on GPU D in L launches`, `animated PNG frame
+ * `encoded JPEG of ...`, `encoded EXR of ...`, `added K feature channels on GPU D in L launches`, `finished depth map [lo, hi] on GPU D in L launches`, `supersampled KxK on GPU D in L launches`, `denoised in K iterations on GPU D in L launches`, `variance-guided denoise in K iterations on GPU D in L launches`, `ambient occlusion of K samples on GPU D in L launches`, `animated PNG frame
  * K: w x h at x,y (B bytes) on GPU D in L launches`. */
 int ndt_render_frame(scene *scn, const ndt_frame_request *request, ndt_frame *out);
 /* safe on a zeroed or a half-filled frame; leaves it zeroed */

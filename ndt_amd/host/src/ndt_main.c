@@ -35,6 +35,11 @@
  * each) and `--denoise-normal E` (0 .. 8, default 5) set its three weights.  With the default stored PNG, --png [--deflate gpu],
  * --jpeg, --exr, --raw, -n, -j, --fit gpu and --kd gpu; not with -a, -m other than mono, -g N > 1, --ssaa above 1, --apng, --png16,
  * -z or --exr-aov.
+ * `--sample-cap C` (1 .. 10000) makes -n an exact count where C <= n: no pixel takes more than C samples (without it a pixel samples
+ * on while its mean moves by more than 1/256).  `--vdenoise [K]` (1 .. 6 iterations, default 4) is the same stage with the width
+ * of the colour weight taken from the frame's own samples, pixel by pixel (ndt_hip_render_vdenoised*): it filters where the frame is
+ * noisy and copies a pixel that has converged; `--vdenoise-colour X` (above 0, default 4: standard deviations), `--vdenoise-plane X`
+ * and `--vdenoise-normal E` as above.  It goes with and without what --denoise does, and not with --denoise.
  * `--ao [K]` (1 .. 256 samples, default 16) shades every frame by its ambient occlusion, found on the GPU between the render and the
  * sink: from the N-D hit point of every pixel's primary ray K rays over the hemisphere of the N-D normal there, and the colour
  * multiplied by the cosine-weighted share of them that get away (ndt_hip_render_ao_shaded*); `--ao-radius R` (finite, 0 or above;
@@ -443,6 +448,11 @@ int main(int argc, char **argv)
     int denoise_normal = 5; /* --denoise-normal E: the normals' dot product squared E times, 0 .. 8 */
     double denoise_colour = 0.25, denoise_plane = 0.25;     /* --denoise-colour X, --denoise-plane X: sigma_colour, sigma_plane, above 0 */
     const char *denoise_tuned = NULL;       /* the first --denoise-* flag given */
+    int vdenoise = 0;       /* --vdenoise [K]: every frame denoised on the GPU by K iterations of the variance-guided a-trous filter, 1 .. 6 (default 4); 0: off */
+    int vdenoise_normal = 5;    /* --vdenoise-normal E, 0 .. 8 */
+    double vdenoise_colour = 4.0, vdenoise_plane = 0.25;    /* --vdenoise-colour X, --vdenoise-plane X: k_colour, sigma_plane, above 0 */
+    const char *vdenoise_tuned = NULL;      /* the first --vdenoise-* flag given */
+    int sample_cap = 0;     /* --sample-cap C: no pixel takes more than C samples (option "sample_cap"); 0: no cap, -n is a lower bound */
     int ao = 0;             /* --ao [K]: every frame shaded by its ambient occlusion of K samples a pixel, found on the GPU, 1 .. 256 (default 16); 0: off */
     double ao_radius = 0.0, ao_strength = 1.0;      /* --ao-radius R: finite, 0 (any hit occludes) or above; --ao-strength S: 0 .. 1 */
     unsigned long long ao_seed = 0;                 /* --ao-seed X */
@@ -462,6 +472,9 @@ int main(int argc, char **argv)
                                         { "denoise-plane", required_argument, NULL, 1020 }, { "denoise-normal", required_argument, NULL, 1021 },
                                         { "ao", optional_argument, NULL, 1022 }, { "ao-radius", required_argument, NULL, 1023 },
                                         { "ao-strength", required_argument, NULL, 1024 }, { "ao-seed", required_argument, NULL, 1025 },
+                                        { "vdenoise", optional_argument, NULL, 1026 }, { "vdenoise-colour", required_argument, NULL, 1027 },
+                                        { "vdenoise-plane", required_argument, NULL, 1028 }, { "vdenoise-normal", required_argument, NULL, 1029 },
+                                        { "sample-cap", required_argument, NULL, 1030 },
                                         { NULL, 0, NULL, 0 } };
     int ch;
     while ((ch = getopt_long(argc, argv, "a:d:g:r:f:j:l:m:3:n:ps:t:u:o:zh", longopts, NULL)) != -1) {
@@ -678,10 +691,63 @@ int main(int argc, char **argv)
             if (!ao_tuned) ao_tuned = "--ao-seed";
             break;
         }
+        case 1026: {
+            /* --vdenoise, --vdenoise=K or --vdenoise K: a following word that starts with a digit is the count */
+            const char *arg = optarg;
+            if (!arg && optind < argc && argv[optind][0] >= '0' && argv[optind][0] <= '9') arg = argv[optind++];
+            vdenoise = 4;
+            if (arg) {
+                char *end = NULL;
+                const long k = strtol(arg, &end, 10);
+                if (end == arg || *end || k < 1 || k > 6) {
+                    fprintf(stderr, "%s: --vdenoise takes 1 .. 6 iterations, not '%s'\n", argv[0], arg);
+                    return 1;
+                }
+                vdenoise = (int)k;
+            }
+            break;
+        }
+        case 1027:
+        case 1028: {
+            char *end = NULL;
+            const double x = strtod(optarg, &end);
+            const char *flag = ch == 1027 ? "--vdenoise-colour" : "--vdenoise-plane";
+            if (end == optarg || *end || !(x > 0) || !isfinite(x)) {
+                fprintf(stderr, "%s: %s takes a finite number above 0, not '%s'\n", argv[0], flag, optarg);
+                return 1;
+            }
+            if (ch == 1027) vdenoise_colour = x;
+            else vdenoise_plane = x;
+            if (!vdenoise_tuned) vdenoise_tuned = flag;
+            break;
+        }
+        case 1029: {
+            char *end = NULL;
+            const long e = strtol(optarg, &end, 10);
+            if (end == optarg || *end || e < 0 || e > 8) {
+                fprintf(stderr, "%s: --vdenoise-normal takes 0 .. 8, not '%s'\n", argv[0], optarg);
+                return 1;
+            }
+            vdenoise_normal = (int)e;
+            if (!vdenoise_tuned) vdenoise_tuned = "--vdenoise-normal";
+            break;
+        }
+        case 1030: {
+            char *end = NULL;
+            const long c = strtol(optarg, &end, 10);
+            if (end == optarg || *end || c < 1 || c > 10000) {
+                fprintf(stderr, "%s: --sample-cap takes 1 .. 10000 samples a pixel, not '%s'\n", argv[0], optarg);
+                return 1;
+            }
+            sample_cap = (int)c;
+            break;
+        }
         default:
             fprintf(stderr, "usage: %s -s scene.so|builtin:yaml [-d dims] [-r WxH|1080p|4k] [-f last|first:last[:total]] [-l depth]\n"
                             "          [-a diff,depth] [-n samples] [-m s|o|a|m] [-p] [-z] [-j frames_in_flight] [-g gpus_per_frame] [-u config] [--dump-scene file.ndtscene] [--raw file.f64] [--png [--deflate stored|gpu]] [--jpeg [--jpeg-quality 1..100] [--jpeg-sampling 420|444]] [--fit host|gpu] [--kd host|gpu] [--depth host|gpu [--depth-png]] [--ssaa 1..8] [--png16] [--apng [--apng-fps 1..1000]] [--exr [--exr-pixel half|float] [--exr-aov id,position,normal|all]]\n"
                             "          [--denoise [1..6] [--denoise-colour X] [--denoise-plane X] [--denoise-normal 0..8]]: every frame denoised on the GPU, with the stored PNG, --png [--deflate gpu], --jpeg, --exr, --raw, -n, -j, --fit gpu, --kd gpu; refused with -a, -m s|o|a|h, -g N > 1, --ssaa above 1, --apng, --png16, -z, --exr-aov\n"
+                            "          [--sample-cap C]: no pixel takes more than C samples (without it -n is a lower bound: a pixel samples on while its mean moves by more than 1/256)\n"
+                            "          [--vdenoise [1..6] [--vdenoise-colour X] [--vdenoise-plane X] [--vdenoise-normal 0..8]]: every frame denoised on the GPU by the variance-guided filter, which takes the width of its colour weight from the frame's own samples (best with -n K --sample-cap K); goes with and is refused with what --denoise is, and with --denoise\n"
                             "          [--ao [1..256] [--ao-radius R] [--ao-strength 0..1] [--ao-seed X]]: every frame shaded by its ambient occlusion, found on the GPU, with the PPM, --png [--deflate gpu], --jpeg, --raw, --exr [-z] [--exr-aov ...] (which gets the channel AO), -n, -m s|o, -j, --fit gpu, --kd gpu; refused with -a, -m a|h, -g N > 1, --ssaa above 1, --apng, --png16, --denoise, --depth gpu, -z without --exr\n", argv[0]);
             return ch == 'h' ? 0 : 1;
         }
@@ -716,8 +782,8 @@ int main(int argc, char **argv)
                 apng ? "--apng" : "--png16");
         return 1;
     }
-    if (ao && denoise) {
-        fprintf(stderr, "%s: --ao with --denoise: one stage stands between the render and the sink: take one\n", argv[0]);
+    if (ao && (denoise || vdenoise)) {
+        fprintf(stderr, "%s: --ao with %s: one stage stands between the render and the sink: take one\n", argv[0], denoise ? "--denoise" : "--vdenoise");
         return 1;
     }
     if (ao && depth_gpu) {
@@ -732,34 +798,45 @@ int main(int argc, char **argv)
         fprintf(stderr, "%s: %s sets a weight of the denoiser: it needs --denoise\n", argv[0], denoise_tuned);
         return 1;
     }
-    if (denoise && aa_depth >= 0) {
-        fprintf(stderr, "%s: --denoise with -a: an anti-aliased pixel is an average of corner samples, and the denoiser's guides are one primary ray's: take -n\n", argv[0]);
+    if (vdenoise_tuned && !vdenoise) {
+        fprintf(stderr, "%s: %s sets a weight of the variance-guided denoiser: it needs --vdenoise\n", argv[0], vdenoise_tuned);
         return 1;
     }
-    if (denoise && stereo != 0) {
-        fprintf(stderr, "%s: --denoise with -m %s: a stencil must not cross the seam between two eyes; that is not built: take -m m\n", argv[0],
+    if (vdenoise && denoise) {
+        fprintf(stderr, "%s: --vdenoise with --denoise: one stage stands between the render and the sink: take one\n", argv[0]);
+        return 1;
+    }
+    /* what either denoiser is refused with, under the name of the one asked for */
+    const char *dn = vdenoise ? "--vdenoise" : "--denoise";
+    const int filtered = denoise || vdenoise;
+    if (filtered && aa_depth >= 0) {
+        fprintf(stderr, "%s: %s with -a: an anti-aliased pixel is an average of corner samples, and the denoiser's guides are one primary ray's: take -n\n", argv[0], dn);
+        return 1;
+    }
+    if (filtered && stereo != 0) {
+        fprintf(stderr, "%s: %s with -m %s: a stencil must not cross the seam between two eyes; that is not built: take -m m\n", argv[0], dn,
                 stereo == 1 ? "s" : stereo == 2 ? "o" : stereo == 3 ? "a" : "h");
         return 1;
     }
-    if (denoise && gpus > 1) {
-        fprintf(stderr, "%s: --denoise with -g %d: a cyclic row shard has no neighbouring rows to filter over: take -g 1 (or -j)\n", argv[0], gpus);
+    if (filtered && gpus > 1) {
+        fprintf(stderr, "%s: %s with -g %d: a cyclic row shard has no neighbouring rows to filter over: take -g 1 (or -j)\n", argv[0], dn, gpus);
         return 1;
     }
-    if (denoise && ssaa > 1) {
-        fprintf(stderr, "%s: --denoise with --ssaa %d: the guides are the plain frame's, not a supersampled one's: take one\n", argv[0], ssaa);
+    if (filtered && ssaa > 1) {
+        fprintf(stderr, "%s: %s with --ssaa %d: the guides are the plain frame's, not a supersampled one's: take one\n", argv[0], dn, ssaa);
         return 1;
     }
-    if (denoise && (apng || png16)) {
-        fprintf(stderr, "%s: --denoise with %s: the denoised frame leaves as a PPM, --png, --jpeg, --exr or --raw: take one of those\n", argv[0],
+    if (filtered && (apng || png16)) {
+        fprintf(stderr, "%s: %s with %s: the denoised frame leaves as a PPM, --png, --jpeg, --exr or --raw: take one of those\n", argv[0], dn,
                 apng ? "--apng" : "--png16");
         return 1;
     }
-    if (denoise && want_depth) {
-        fprintf(stderr, "%s: --denoise with -z: no depth map is made beside a denoised frame: take one\n", argv[0]);
+    if (filtered && want_depth) {
+        fprintf(stderr, "%s: %s with -z: no depth map is made beside a denoised frame: take one\n", argv[0], dn);
         return 1;
     }
-    if (denoise && exr_aov_given) {
-        fprintf(stderr, "%s: --denoise with --exr-aov: the denoised file carries colour only: take one\n", argv[0]);
+    if (filtered && exr_aov_given) {
+        fprintf(stderr, "%s: %s with --exr-aov: the denoised file carries colour only: take one\n", argv[0], dn);
         return 1;
     }
     if (exr_pixel && !exr) {
@@ -908,6 +985,9 @@ int main(int argc, char **argv)
     frame_request.exr_features = exr_aov;
     frame_request.denoise_iterations = denoise; frame_request.denoise_normal_power_log2 = denoise_normal;
     frame_request.denoise_sigma_colour = denoise_colour; frame_request.denoise_sigma_plane = denoise_plane;
+    frame_request.sample_cap = sample_cap;
+    frame_request.vdenoise_iterations = vdenoise; frame_request.vdenoise_normal_power_log2 = vdenoise_normal;
+    frame_request.vdenoise_k_colour = vdenoise_colour; frame_request.vdenoise_sigma_plane = vdenoise_plane;
     frame_request.ao_samples = ao; frame_request.ao_radius = ao_radius; frame_request.ao_strength = ao_strength; frame_request.ao_seed = ao_seed;
     frame_request.colour = exr ? NDT_COLOUR_EXR : apng ? NDT_COLOUR_APNG : png16 ? NDT_COLOUR_PNG16 : want_f64 ? NDT_COLOUR_F64
                          : file_kind != NDT_COLOUR_F64 ? file_kind : NDT_COLOUR_RGBA8;

@@ -11,12 +11,14 @@ static __thread int g_n_ctx = 0;            /* contexts that exist */
 static __thread int g_want_ctx = 1;         /* contexts a frame is spread over */
 static __thread int g_first_device = 0;
 static __thread int g_paths_said = 0;
+static __thread int g_sample_cap = 0;       /* the "sample_cap" the thread's contexts were last given */
 
 static void drop_contexts(void)
 {
     for (int k = 0; k < g_n_ctx; ++k) ndt_hip_destroy(g_ctx[k]);
     g_n_ctx = 0;
     g_paths_said = 0;
+    g_sample_cap = 0;
 }
 
 void ndt_render_use_device(int device)
@@ -557,18 +559,33 @@ static ndt_denoise_params denoise_params_of(const ndt_frame_request *rq)
     return dp;
 }
 
-/* what a denoised frame does not go with, by name, before the scene is flattened or a device asked for */
+static ndt_vdenoise_params vdenoise_params_of(const ndt_frame_request *rq)
+{
+    ndt_vdenoise_params vp;
+    memset(&vp, 0, sizeof(vp));
+    vp.iterations = rq->vdenoise_iterations;
+    vp.normal_power_log2 = rq->vdenoise_normal_power_log2;
+    vp.k_colour = rq->vdenoise_k_colour;
+    vp.sigma_plane = rq->vdenoise_sigma_plane;
+    return vp;
+}
+
+/* what a denoised frame does not go with, by name, before the scene is flattened or a device asked for (either filter) */
 static int denoise_refused(const ndt_frame_request *rq)
 {
     const char *why = NULL;
-    if (rq->aa_depth >= 0 && rq->aa_diff < 256) why = "recursive anti-aliasing (aa_depth >= 0): its pixels are averages of corner samples";
+    const int variance = rq->vdenoise_iterations != 0;
+    if (variance && rq->denoise_iterations != 0) why = "denoise_iterations: one stage stands between the render and the sink";
+    else if (rq->aa_depth >= 0 && rq->aa_diff < 256) why = "recursive anti-aliasing (aa_depth >= 0): its pixels are averages of corner samples";
     else if (rq->stereo != 0) why = "a stereo mode: a stencil must not cross the seam between two eyes";
     else if (rq->ssaa != 1) why = "ssaa above 1: the guides are the plain frame's";
     else if (rq->map != NDT_MAP_NONE) why = "a depth map";
     else if (rq->exr_features) why = "exr_features";
     else if (rq->colour == NDT_COLOUR_PNG16 || rq->colour == NDT_COLOUR_APNG) why = "a 16-bit or an animated PNG";
     else if (g_want_ctx > 1) why = "a frame spread over several GPU contexts: a cyclic row shard has no neighbouring rows";
-    if (why) fprintf(stderr, "ndt_render_frame: denoise_iterations %d with %s: not built; there is no fallback\n", rq->denoise_iterations, why);
+    if (why)
+        fprintf(stderr, "ndt_render_frame: %s %d with %s: not built; there is no fallback\n", variance ? "vdenoise_iterations" : "denoise_iterations",
+                variance ? rq->vdenoise_iterations : rq->denoise_iterations, why);
     return why != NULL;
 }
 
@@ -577,13 +594,16 @@ static int frame_denoised(const ndt_render_params *p, const ndt_frame_request *r
     const int width = p->width, height = p->height;
     const size_t n = (size_t)width * (size_t)height;
     const ndt_denoise_params dp = denoise_params_of(rq);
+    const ndt_vdenoise_params vp = vdenoise_params_of(rq);
+    const int variance = rq->vdenoise_iterations != 0;      /* the variance-guided filter: the same sinks through ndt_hip_render_vdenoised* */
     int ok;
     if (rq->colour == NDT_COLOUR_F64) {
         if (!(f->rgba = (double *)malloc(n * 4 * sizeof(double)))) return out_of_memory();
-        ok = ndt_hip_render_denoised(g_ctx[0], p, &dp, f->rgba, NULL) == NDT_OK;
+        ok = (variance ? ndt_hip_render_vdenoised(g_ctx[0], p, &vp, f->rgba, NULL) : ndt_hip_render_denoised(g_ctx[0], p, &dp, f->rgba, NULL)) == NDT_OK;
     } else if (rq->colour == NDT_COLOUR_RGBA8) {
         if (!(f->rgba8 = (unsigned char *)malloc(n * 4))) return out_of_memory();
-        ok = ndt_hip_render_denoised_rgba8(g_ctx[0], p, &dp, f->rgba8, NULL) == NDT_OK;
+        ok = (variance ? ndt_hip_render_vdenoised_rgba8(g_ctx[0], p, &vp, f->rgba8, NULL)
+                       : ndt_hip_render_denoised_rgba8(g_ctx[0], p, &dp, f->rgba8, NULL)) == NDT_OK;
     } else if (rq->colour == NDT_COLOUR_EXR) {
         ndt_exr_params ep;
         ndt_exr_stats es;
@@ -595,7 +615,8 @@ static int frame_denoised(const ndt_render_params *p, const ndt_frame_request *r
             fprintf(stderr, "ndt_render_frame: no OpenEXR file of %d x %d with pixel type %d\n", width, height, rq->exr_pixel);
             return 0;
         }
-        if (!(ok = ndt_hip_render_denoised_exr(g_ctx[0], p, &dp, &ep, f->file, cap, &es, NULL) == NDT_OK)) return 0;
+        if (!(ok = (variance ? ndt_hip_render_vdenoised_exr(g_ctx[0], p, &vp, &ep, f->file, cap, &es, NULL)
+                             : ndt_hip_render_denoised_exr(g_ctx[0], p, &dp, &ep, f->file, cap, &es, NULL)) == NDT_OK)) return 0;
         f->file_bytes = es.file_bytes;
         f->file_ms = es.ms;
         printf("encoded EXR of %lld bytes on GPU %d in %d launches\n", (long long)es.file_bytes, ndt_hip_device(g_ctx[0]), es.launches);
@@ -611,8 +632,12 @@ static int frame_denoised(const ndt_render_params *p, const ndt_frame_request *r
             else fprintf(stderr, "ndt_render_frame: no JPEG of %d x %d at quality %d, sampling %d\n", width, height, jp.quality, jp.sampling);
             return 0;
         }
-        ok = (png ? ndt_hip_render_denoised_png(g_ctx[0], p, &dp, f->file, cap, &ps, NULL)
-                  : ndt_hip_render_denoised_jpeg(g_ctx[0], p, &dp, &jp, f->file, cap, &js, NULL)) == NDT_OK;
+        if (variance)
+            ok = (png ? ndt_hip_render_vdenoised_png(g_ctx[0], p, &vp, f->file, cap, &ps, NULL)
+                      : ndt_hip_render_vdenoised_jpeg(g_ctx[0], p, &vp, &jp, f->file, cap, &js, NULL)) == NDT_OK;
+        else
+            ok = (png ? ndt_hip_render_denoised_png(g_ctx[0], p, &dp, f->file, cap, &ps, NULL)
+                      : ndt_hip_render_denoised_jpeg(g_ctx[0], p, &dp, &jp, f->file, cap, &js, NULL)) == NDT_OK;
         if (!ok) return 0;
         f->file_bytes = png ? ps.png_bytes : js.jpeg_bytes;
         f->file_ms = png ? ps.encode_ms : js.encode_ms;
@@ -622,7 +647,8 @@ static int frame_denoised(const ndt_render_params *p, const ndt_frame_request *r
     if (!ok) return 0;
     f->denoise_launches = ndt_hip_denoise_launches(g_ctx[0]);
     f->denoise_ms = ndt_hip_denoise_ms(g_ctx[0]);
-    printf("denoised in %d iterations on GPU %d in %d launches\n", dp.iterations, ndt_hip_device(g_ctx[0]), f->denoise_launches);
+    if (variance) printf("variance-guided denoise in %d iterations on GPU %d in %d launches\n", vp.iterations, ndt_hip_device(g_ctx[0]), f->denoise_launches);
+    else printf("denoised in %d iterations on GPU %d in %d launches\n", dp.iterations, ndt_hip_device(g_ctx[0]), f->denoise_launches);
     return 1;
 }
 
@@ -650,6 +676,7 @@ static int ao_refused(const ndt_frame_request *rq)
     else if (rq->map != NDT_MAP_NONE && rq->map != NDT_MAP_EXR_Z) why = "a depth map that is not the Z channel of the OpenEXR file";
     else if (rq->colour == NDT_COLOUR_PNG16 || rq->colour == NDT_COLOUR_APNG) why = "a 16-bit or an animated PNG";
     else if (rq->denoise_iterations != 0) why = "denoise_iterations: one stage stands between the render and the sink";
+    else if (rq->vdenoise_iterations != 0) why = "vdenoise_iterations: one stage stands between the render and the sink";
     else if (g_want_ctx > 1) why = "a frame spread over several GPU contexts";
     else if (rq->ao_samples < 1 || rq->ao_samples > 256) why = "a sample count outside 1 .. 256";
     if (why) fprintf(stderr, "ndt_render_frame: ao_samples %d with %s: not built; there is no fallback\n", rq->ao_samples, why);
@@ -749,7 +776,11 @@ int ndt_render_frame(scene *scn, const ndt_frame_request *rq, ndt_frame *f)
         fprintf(stderr, "ndt_render_frame: exr_features are channels of the OpenEXR file: colour (%s) has none\n", colour_kinds[rq->colour].name);
         return 0;
     }
-    if (rq->denoise_iterations != 0 && denoise_refused(rq)) return 0;
+    if ((rq->denoise_iterations != 0 || rq->vdenoise_iterations != 0) && denoise_refused(rq)) return 0;
+    if (rq->sample_cap < 0) {
+        fprintf(stderr, "ndt_render_frame: sample_cap %d: 0 for no cap, or the most samples a pixel takes\n", rq->sample_cap);
+        return 0;
+    }
     if (rq->ao_samples != 0 && ao_refused(rq)) return 0;
     /* 1. the scene: flattened, uploaded to every context of the thread (the pthread fan-out of ndt.c:949-975 is the GPU's job now;
      * `threads` fits the scene's bounding spheres in parallel) */
@@ -765,6 +796,11 @@ int ndt_render_frame(scene *scn, const ndt_frame_request *rq, ndt_frame *f)
     int ok = have_contexts();
     for (int k = 0; ok && k < g_n_ctx; ++k)
         if (ndt_hip_upload_scene(g_ctx[k], &fb.fs) != NDT_OK) ok = 0;
+    if (ok && rq->sample_cap != g_sample_cap) {     /* (a thread that never asks for a cap leaves its contexts as they were created) */
+        for (int k = 0; ok && k < g_n_ctx; ++k)
+            if (ndt_hip_set_option(g_ctx[k], "sample_cap", rq->sample_cap) != NDT_OK) ok = 0;
+        if (ok) g_sample_cap = rq->sample_cap;
+    }
     if (timing) clock_gettime(CLOCK_MONOTONIC, &ts2);
     const int map8 = rq->map == NDT_MAP_DEPTH8 || rq->map == NDT_MAP_PNG;
     if (ok) {
@@ -779,7 +815,7 @@ int ndt_render_frame(scene *scn, const ndt_frame_request *rq, ndt_frame *f)
             p.aa_depth = rq->aa_depth;
         }
         /* 2. and 3. colour and map in the forms asked for: one device call makes both, so the routine is chosen by the pair */
-        if (rq->denoise_iterations != 0) ok = frame_denoised(&p, rq, f);
+        if (rq->denoise_iterations != 0 || rq->vdenoise_iterations != 0) ok = frame_denoised(&p, rq, f);
         else if (rq->ao_samples != 0) ok = frame_ao(&p, rq, f, fb.fs.dims);
         else if (rq->colour == NDT_COLOUR_EXR) ok = frame_exr(&p, rq, f, fb.fs.dims);
         else if (rq->colour == NDT_COLOUR_APNG) ok = frame_apng(&p, rq, f);
