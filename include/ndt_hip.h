@@ -983,6 +983,42 @@ int ndt_hip_hcube_face_groups(const ndt_flat_scene *scene, int32_t object, doubl
  * Returns the number of boxed items (0: none), <0 on NDT_E_*. */
 int ndt_hip_item_boxes(const ndt_flat_scene *scene, double *frame, double *rows, uint8_t *has);
 
+/* What upload accepts.  Host only (no GPU, no context): NDT_OK, or the code ndt_hip_upload_scene would refuse `scene` with and
+ * its message in ndt_hip_last_error().  ndt_hip_upload_scene calls this first and builds nothing for a scene it refuses; a
+ * refused upload (or one that fails later, on the device) leaves the context WITHOUT a scene -- the one it held is gone, every
+ * render answers NDT_E_STATE until an upload succeeds -- and nothing of the refused scene stays behind in it.
+ *
+ * The rules, tried in this order; the first one broken is the answer.  NDT_E_INVALID unless marked [U] = NDT_E_UNSUPPORTED.
+ * "A vector range (off, k)" is k vectors at vecs + off: off >= 0, k >= 0, off + k * dims <= n_vecs.  A message about an object,
+ * a kd node or a light names it: "object 7: ...", "kd node 3: ...", "light 2: ...".
+ *   1. abi_version == NDT_HIP_ABI_VERSION; [U] NDT_MIN_DIMS <= dims <= NDT_MAX_DIMS; [U] 0 <= cam_type <= 2; cam_type != 0
+ *      needs cam_local_x_off, cam_local_y_off, cam_local_z_off >= 0.
+ *   2. Counts: n_lights, n_objects, n_items, n_kd_nodes, n_leaf_refs, n_inf, n_vecs, n_sizes, n_flags, n_obj_refs >= 0 (the message
+ *      names the count); [U] n_lights <= NDT_MAX_LIGHTS; n_items <= n_objects.  A count says how many entries of its array may be read: the library
+ *      reads none beyond it and cannot know of a count larger than the memory behind the pointer.
+ *   3. An array with a positive count is not NULL: vecs, sizes, flags, obj_refs, lights, objects, kd_nodes, leaf_refs, inf_refs.
+ *   4. The kd-tree, when n_kd_nodes > 0, walked from node 0 (level 1), a node, then its left subtree, then its right one; nodes
+ *      the walk does not reach are not read.  [U] No node stands deeper than level 40 (the traversal stack; the walk itself goes
+ *      no deeper).  No node is reached twice (reported as that node).  Interior node (dim >= 0): dim < dims; left and right are
+ *      node indices, 0 <= . < n_kd_nodes (reported as the node that holds the index).  Leaf (dim < 0): num >= 0, first >= 0,
+ *      first + num <= n_leaf_refs, and every listed entry is an item, 0 <= . < n_items.
+ *   5. Every entry of inf_refs is an item.
+ *   6. Every object, in order: [U] 0 <= type < NDT_OBJ_TYPE_COUNT; (bounds_center_off, 1), (pos_off, n_pos) and (dir_off, n_dir)
+ *      are vector ranges; n_size >= 0, size_off >= 0, size_off + n_size <= n_sizes; the same for n_flag, flag_off and n_flags;
+ *      then what its plugin reads: sphere 1 pos, 1 size; hplane 1 pos, 1 dir; hdisk 1 pos, 1 dir, 1 size; cylinder 2 pos, 1 size;
+ *      hcylinder dims - 1 pos, 1 size; orthotope 1 pos, 1 flag and 0 <= flags[flag_off] <= min(n_dir, dims); hfacet 3 pos, 1 flag,
+ *      and 3 dir when flags[flag_off] != 0; facet 3 pos, 1 dir; hcube: [U] n_obj >= 1 (the faces add_faces makes, hcube.c:34),
+ *      obj_off >= 0, obj_off + n_obj <= n_obj_refs, every child an object index, 0 <= . < n_objects, of an object that is no
+ *      hcube.  n_obj / obj_off of other types and `parent` are not read.
+ *   7. (bb_lower_off, 1) and (bb_upper_off, 1) are vector ranges.
+ *   8. Every light, in order: 0 <= type <= NDT_LIGHT_RECT; DISK / RECT: (area_off, 2); POINT / SPOT / DISK / RECT: (pos_off, 1);
+ *      DIRECTIONAL / SPOT: (dir_off, 1) are vector ranges.  Offsets a type does not use are not read.
+ *   9. The camera: (cam_pos_off, 1), (cam_img_orig_off, 1), (cam_dir_x_off, 1), (cam_dir_y_off, 1), and each of cam_left_eye_off,
+ *      cam_right_eye_off, cam_local_x_off, cam_local_y_off, cam_local_z_off that is >= 0 (negative: the scene has none).
+ * A NULL `scene` is refused with NDT_E_INVALID like any other, by either entry, and costs the context its scene as well.
+ * Reals are not judged.  Scenes with no light, no kd node, no infinite object, no item or no object at all pass. */
+int ndt_hip_check_scene(const ndt_flat_scene *scene);
+
 /* The stream the context launches on (a hipStream_t, created hipStreamNonBlocking: nothing the caller queues on the NULL
  * stream or any other is ordered against it implicitly), for callers that time with their own events or order other work
  * against it. */

@@ -211,30 +211,35 @@ extern "C" int ndt_hip_synchronize(ndt_hip_ctx *ctx)
     return NDT_OK;
 }
 
-extern "C" int ndt_hip_upload_scene(ndt_hip_ctx *ctx, const ndt_flat_scene *fs)
+// The context as it is before its first upload, as far as a scene goes (ndt_ctx.hpp).  The device buffers stay: they are grow-only
+// and hold nothing a render reads without a scene.
+void ndt_impl::drop_scene(ndt_hip_ctx *ctx)
 {
-    if (!ctx || !fs) return fail(NDT_E_INVALID, "NULL argument");
-    if (fs->abi_version != NDT_HIP_ABI_VERSION) return fail(NDT_E_INVALID, "scene ABI %d, library ABI %d", fs->abi_version, NDT_HIP_ABI_VERSION);
-    if (fs->dims < NDT_MIN_DIMS || fs->dims > NDT_MAX_DIMS)
-        return fail(NDT_E_UNSUPPORTED, "%d dimensions: kernels are built for %d..%d", fs->dims, NDT_MIN_DIMS, NDT_MAX_DIMS);
-    if (fs->cam_type < 0 || fs->cam_type > 2) return fail(NDT_E_UNSUPPORTED, "camera type %d", fs->cam_type);
-    if (fs->cam_type != 0 && (fs->cam_local_x_off < 0 || fs->cam_local_y_off < 0 || fs->cam_local_z_off < 0))
-        return fail(NDT_E_INVALID, "VR / panorama cameras need the local axes (camera.h:69-71) in the flat scene");
-    if (fs->n_lights < 0 || fs->n_lights > NDT_MAX_LIGHTS) return fail(NDT_E_UNSUPPORTED, "%d lights (max %d)", fs->n_lights, NDT_MAX_LIGHTS);
-    if (fs->n_objects < 0 || fs->n_items < 0 || fs->n_items > fs->n_objects) return fail(NDT_E_INVALID, "object counts");
-    if (fs->n_kd_nodes < 0 || fs->n_inf < 0 || fs->n_leaf_refs < 0) return fail(NDT_E_INVALID, "kd-tree counts");
-    if (fs->n_objects > 0 && !fs->objects) return fail(NDT_E_INVALID, "objects is NULL");
-    if (fs->n_lights > 0 && !fs->lights) return fail(NDT_E_INVALID, "lights is NULL");
-    if (!fs->vecs) return fail(NDT_E_INVALID, "vecs is NULL");
-    HIP_TRY(hipSetDevice(ctx->device));
     ctx->have_scene = false;
-    int rc = build_blob(ctx, fs);
-    if (rc) return rc;
+    ctx->kt = nullptr;
+    ctx->dims = 0;
+    ctx->aperture_radius = 0.0;
+    ctx->cam_type = 0;
+    ctx->have_eyes = ctx->have_local_axes = false;
+    ctx->has_area_lights = false;
+    ctx->sd = SceneDesc{};
+    ctx->blob.clear();
+    ctx->tier = 0;
+    ctx->n_shadow_lights = 0;
+    ctx->light_types.clear();
+    ctx->windows.clear();
+}
+
+// What follows the check on a scene it passed; a failure in here is the device's (NDT_E_DEVICE, NDT_E_NOMEM).
+static int upload_checked(ndt_hip_ctx *ctx, const ndt_flat_scene *fs, const SceneFacts &facts)
+{
+    HIP_TRY(hipSetDevice(ctx->device));
+    build_blob(ctx, fs, facts);
     ctx->dims = fs->dims;
     ctx->kt = table_for(fs->dims);
     if (!ctx->kt) return fail(NDT_E_UNSUPPORTED, "no kernels for %d dimensions", fs->dims);
     HIP_TRY(sync_streams(ctx));          // (the lighting kernels read the blob too)
-    if ((rc = ctx->d_blob.reserve(ctx->blob.size() * sizeof(double), ctx->stream, "ndt_hip_upload_scene"))) return rc;
+    if (int rc = ctx->d_blob.reserve(ctx->blob.size() * sizeof(double), ctx->stream, "ndt_hip_upload_scene")) return rc;
     HIP_TRY(hipMemcpyAsync(ctx->d_blob.p, ctx->blob.data(), ctx->blob.size() * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     ctx->aperture_radius = fs->cam_aperture_radius;
@@ -244,6 +249,17 @@ extern "C" int ndt_hip_upload_scene(ndt_hip_ctx *ctx, const ndt_flat_scene *fs)
                 ctx->dims, ctx->sd.n_items, ctx->sd.n_objects, ctx->sd.n_kd_nodes, ctx->sd.kd_depth, ctx->sd.trace_words, ctx->sd.trace_words / 128,
                 ctx->sd.total_words, ctx->tier, ctx->sd.mask_words);
     return NDT_OK;
+}
+
+extern "C" int ndt_hip_upload_scene(ndt_hip_ctx *ctx, const ndt_flat_scene *fs)
+{
+    if (!ctx) return fail(NDT_E_INVALID, "NULL argument");
+    // whatever comes of it -- a NULL scene too -- the scene the context held is gone (include/ndt_hip.h "What upload accepts")
+    drop_scene(ctx);
+    SceneFacts facts;
+    int rc = check_scene(fs, &facts);        // (refuses a NULL scene)
+    if (rc == NDT_OK && (rc = upload_checked(ctx, fs, facts)) != NDT_OK) drop_scene(ctx);
+    return rc;
 }
 
 // pixel_d2c, image.h:36-39

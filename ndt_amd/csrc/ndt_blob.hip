@@ -177,11 +177,15 @@ bool vec_ok(const ndt_flat_scene *fs, int64_t off, int64_t count)
 
 } // namespace
 
-// Renumber the kd-tree in preorder (left child = parent + 1) and check it is a tree.
+// ------------------------------------------------------------------ what upload accepts (include/ndt_hip.h, rules 1 .. 9)
+
+// Rule 4: the kd nodes in preorder (left child = parent + 1), checked to be a tree of at most NDT_KD_STACK levels on the way
+// down -- the recursion is as deep as the deepest node it accepts, plus the one it refuses.
 static int kd_preorder(const ndt_flat_scene *fs, int node, int depth, std::vector<int> &order, std::vector<char> &seen,
                        int &max_depth)
 {
-    if (node < 0 || node >= fs->n_kd_nodes) return fail(NDT_E_INVALID, "kd node index %d out of range", node);
+    if (depth > NDT_KD_STACK)
+        return fail(NDT_E_UNSUPPORTED, "kd node %d: depth %d exceeds the traversal stack (%d)", node, depth, NDT_KD_STACK);
     if (seen[node]) return fail(NDT_E_INVALID, "kd node %d reached twice", node);
     seen[node] = 1;
     order.push_back(node);
@@ -189,20 +193,121 @@ static int kd_preorder(const ndt_flat_scene *fs, int node, int depth, std::vecto
     const ndt_flat_kdnode &k = fs->kd_nodes[node];
     if (k.dim >= 0) {
         if (k.dim >= fs->dims) return fail(NDT_E_INVALID, "kd node %d splits dimension %d of a %d-D scene", node, k.dim, fs->dims);
-        int rc = kd_preorder(fs, k.left, depth + 1, order, seen, max_depth);
-        if (rc) return rc;
-        rc = kd_preorder(fs, k.right, depth + 1, order, seen, max_depth);
-        if (rc) return rc;
+        const int child[2] = { k.left, k.right };
+        for (int c : child) {
+            if (c < 0 || c >= fs->n_kd_nodes) return fail(NDT_E_INVALID, "kd node %d: child index %d out of range (%d nodes)", node, c, fs->n_kd_nodes);
+            if (int rc = kd_preorder(fs, c, depth + 1, order, seen, max_depth)) return rc;
+        }
     } else {
         if (k.num < 0 || k.first < 0 || (int64_t)k.first + k.num > fs->n_leaf_refs)
-            return fail(NDT_E_INVALID, "kd leaf %d item range out of bounds", node);
+            return fail(NDT_E_INVALID, "kd node %d: leaf item range out of bounds", node);
         for (int i = 0; i < k.num; ++i) {
             int id = fs->leaf_refs[k.first + i];
-            if (id < 0 || id >= fs->n_items) return fail(NDT_E_INVALID, "kd leaf %d lists object %d (n_items %d)", node, id, fs->n_items);
+            if (id < 0 || id >= fs->n_items) return fail(NDT_E_INVALID, "kd node %d: leaf lists object %d (n_items %d)", node, id, fs->n_items);
         }
     }
     return NDT_OK;
 }
+
+int ndt_impl::check_scene(const ndt_flat_scene *fs, SceneFacts *facts)
+{
+    if (!fs) return fail(NDT_E_INVALID, "NULL argument");
+    // 1
+    if (fs->abi_version != NDT_HIP_ABI_VERSION) return fail(NDT_E_INVALID, "scene ABI %d, library ABI %d", fs->abi_version, NDT_HIP_ABI_VERSION);
+    if (fs->dims < NDT_MIN_DIMS || fs->dims > NDT_MAX_DIMS)
+        return fail(NDT_E_UNSUPPORTED, "%d dimensions: kernels are built for %d..%d", fs->dims, NDT_MIN_DIMS, NDT_MAX_DIMS);
+    if (fs->cam_type < 0 || fs->cam_type > 2) return fail(NDT_E_UNSUPPORTED, "camera type %d", fs->cam_type);
+    if (fs->cam_type != 0 && (fs->cam_local_x_off < 0 || fs->cam_local_y_off < 0 || fs->cam_local_z_off < 0))
+        return fail(NDT_E_INVALID, "VR / panorama cameras need the local axes (camera.h:69-71) in the flat scene");
+    // 2
+    const struct { const char *name; int64_t value; } counts[] = {
+        { "n_lights", fs->n_lights }, { "n_objects", fs->n_objects }, { "n_items", fs->n_items }, { "n_kd_nodes", fs->n_kd_nodes },
+        { "n_leaf_refs", fs->n_leaf_refs }, { "n_inf", fs->n_inf }, { "n_vecs", fs->n_vecs }, { "n_sizes", fs->n_sizes },
+        { "n_flags", fs->n_flags }, { "n_obj_refs", fs->n_obj_refs } };
+    for (const auto &c : counts)
+        if (c.value < 0) return fail(NDT_E_INVALID, "%s %lld: a count is not negative", c.name, (long long)c.value);
+    if (fs->n_lights > NDT_MAX_LIGHTS) return fail(NDT_E_UNSUPPORTED, "%d lights (max %d)", fs->n_lights, NDT_MAX_LIGHTS);
+    if (fs->n_items > fs->n_objects) return fail(NDT_E_INVALID, "n_items %d of %d objects", fs->n_items, fs->n_objects);
+    // 3
+    if (fs->n_vecs > 0 && !fs->vecs) return fail(NDT_E_INVALID, "vecs is NULL");
+    if (fs->n_sizes > 0 && !fs->sizes) return fail(NDT_E_INVALID, "sizes is NULL");
+    if (fs->n_flags > 0 && !fs->flags) return fail(NDT_E_INVALID, "flags is NULL");
+    if (fs->n_obj_refs > 0 && !fs->obj_refs) return fail(NDT_E_INVALID, "obj_refs is NULL");
+    if (fs->n_lights > 0 && !fs->lights) return fail(NDT_E_INVALID, "lights is NULL");
+    if (fs->n_objects > 0 && !fs->objects) return fail(NDT_E_INVALID, "objects is NULL");
+    if (fs->n_kd_nodes > 0 && !fs->kd_nodes) return fail(NDT_E_INVALID, "kd_nodes is NULL");
+    if (fs->n_leaf_refs > 0 && !fs->leaf_refs) return fail(NDT_E_INVALID, "leaf_refs is NULL");
+    if (fs->n_inf > 0 && !fs->inf_refs) return fail(NDT_E_INVALID, "inf_refs is NULL");
+    // 4
+    SceneFacts mine;
+    SceneFacts &f = facts ? *facts : mine;
+    f.kd_order.clear();
+    f.kd_depth = 0;
+    if (fs->n_kd_nodes > 0) {
+        std::vector<char> seen((size_t)fs->n_kd_nodes, 0);
+        if (int rc = kd_preorder(fs, 0, 1, f.kd_order, seen, f.kd_depth)) return rc;
+    }
+    // 5
+    for (int i = 0; i < fs->n_inf; ++i)
+        if (fs->inf_refs[i] < 0 || fs->inf_refs[i] >= fs->n_items)
+            return fail(NDT_E_INVALID, "infinite list entry %d names object %d (n_items %d)", i, fs->inf_refs[i], fs->n_items);
+    // 6
+    const int n = fs->dims;
+    for (int i = 0; i < fs->n_objects; ++i) {
+        const ndt_flat_object &o = fs->objects[i];
+        if (o.type < 0 || o.type >= NDT_OBJ_TYPE_COUNT) return fail(NDT_E_UNSUPPORTED, "object %d: unknown type %d", i, o.type);
+        if (!vec_ok(fs, o.bounds_center_off, 1)) return fail(NDT_E_INVALID, "object %d: bounds centre out of range", i);
+        if (!vec_ok(fs, o.pos_off, o.n_pos) || !vec_ok(fs, o.dir_off, o.n_dir)) return fail(NDT_E_INVALID, "object %d: vector range", i);
+        if (o.n_size < 0 || o.size_off < 0 || (int64_t)o.size_off + o.n_size > fs->n_sizes) return fail(NDT_E_INVALID, "object %d: size range", i);
+        if (o.n_flag < 0 || o.flag_off < 0 || (int64_t)o.flag_off + o.n_flag > fs->n_flags) return fail(NDT_E_INVALID, "object %d: flag range", i);
+        const char *need = nullptr;         // what the plugin's prepare() reads (build_blob's switch)
+        switch (o.type) {
+        case NDT_OBJ_SPHERE: if (o.n_pos < 1 || o.n_size < 1) need = "sphere needs 1 pos, 1 size"; break;
+        case NDT_OBJ_HPLANE: if (o.n_pos < 1 || o.n_dir < 1) need = "hplane needs 1 pos, 1 dir"; break;
+        case NDT_OBJ_HDISK: if (o.n_pos < 1 || o.n_dir < 1 || o.n_size < 1) need = "hdisk needs 1 pos, 1 dir, 1 size"; break;
+        case NDT_OBJ_CYLINDER: if (o.n_pos < 2 || o.n_size < 1) need = "cylinder needs 2 pos, 1 size"; break;
+        case NDT_OBJ_HCYLINDER: if (o.n_pos < n - 1 || o.n_size < 1) need = "hcylinder needs dims-1 pos, 1 size"; break;
+        case NDT_OBJ_ORTHOTOPE:
+            if (o.n_flag < 1 || o.n_pos < 1) need = "orthotope needs 1 pos, 1 flag";
+            else if (fs->flags[o.flag_off] < 0 || fs->flags[o.flag_off] > o.n_dir || fs->flags[o.flag_off] > n) need = "orthotope flag[0] vs directions";
+            break;
+        case NDT_OBJ_HFACET:
+            if (o.n_pos < 3 || o.n_flag < 1) need = "hfacet needs 3 pos, 1 flag";
+            else if (fs->flags[o.flag_off] && o.n_dir < 3) need = "hfacet with vertex normals needs 3 dir";
+            break;
+        case NDT_OBJ_FACET: if (o.n_pos < 3 || o.n_dir < 1) need = "facet needs 3 pos, 1 dir"; break;
+        case NDT_OBJ_HCUBE:
+            if (o.n_obj < 1) return fail(NDT_E_UNSUPPORTED, "object %d: hcube without faces (supply add_faces output)", i);
+            if (o.obj_off < 0 || (int64_t)o.obj_off + o.n_obj > fs->n_obj_refs) return fail(NDT_E_INVALID, "object %d: child range", i);
+            for (int k = 0; k < o.n_obj; ++k) {
+                const int c = fs->obj_refs[o.obj_off + k];
+                if (c < 0 || c >= fs->n_objects || fs->objects[c].type == NDT_OBJ_HCUBE)
+                    return fail(NDT_E_INVALID, "object %d: bad nested primitive %d", i, c);
+            }
+            break;
+        }
+        if (need) return fail(NDT_E_INVALID, "object %d: %s", i, need);
+    }
+    // 7
+    if (!vec_ok(fs, fs->bb_lower_off, 1) || !vec_ok(fs, fs->bb_upper_off, 1)) return fail(NDT_E_INVALID, "root box out of range");
+    // 8
+    for (int i = 0; i < fs->n_lights; ++i) {
+        const ndt_flat_light &l = fs->lights[i];
+        if (l.type < 0 || l.type > NDT_LIGHT_RECT) return fail(NDT_E_INVALID, "light %d: type %d", i, l.type);
+        const bool area = l.type == NDT_LIGHT_DISK || l.type == NDT_LIGHT_RECT;
+        if (area && !vec_ok(fs, l.area_off, 2)) return fail(NDT_E_INVALID, "light %d: area lights need u1 / v1 (scene.c:182-195) in the flat scene", i);
+        if ((l.type == NDT_LIGHT_POINT || l.type == NDT_LIGHT_SPOT || area) && !vec_ok(fs, l.pos_off, 1)) return fail(NDT_E_INVALID, "light %d: position missing", i);
+        if ((l.type == NDT_LIGHT_DIRECTIONAL || l.type == NDT_LIGHT_SPOT) && !vec_ok(fs, l.dir_off, 1)) return fail(NDT_E_INVALID, "light %d: direction missing", i);
+    }
+    // 9
+    const int32_t cam[9] = { fs->cam_pos_off, fs->cam_img_orig_off, fs->cam_dir_x_off, fs->cam_dir_y_off, fs->cam_left_eye_off,
+                             fs->cam_right_eye_off, fs->cam_local_x_off, fs->cam_local_y_off, fs->cam_local_z_off };
+    for (int k = 0; k < 9; ++k)
+        if ((k < 4 || cam[k] >= 0) && !vec_ok(fs, cam[k], 1)) return fail(NDT_E_INVALID, "camera vectors out of range");
+    return NDT_OK;
+}
+
+extern "C" int ndt_hip_check_scene(const ndt_flat_scene *fs) { return check_scene(fs, nullptr); }
 
 // Hull box of an hcube: an oriented box that contains every point the faces' intersect() can
 // return.  NOT part of the reference's algorithm -- an exactness-preserving cull, like the
@@ -761,7 +866,7 @@ extern "C" int ndt_hip_item_boxes(const ndt_flat_scene *fs, double *frame_out, d
     return n;
 }
 
-int ndt_impl::build_blob(ndt_hip_ctx *ctx, const ndt_flat_scene *fs)
+void ndt_impl::build_blob(ndt_hip_ctx *ctx, const ndt_flat_scene *fs, const SceneFacts &facts)
 {
     const int n = fs->dims;
     BlobBuilder b;
@@ -774,26 +879,18 @@ int ndt_impl::build_blob(ndt_hip_ctx *ctx, const ndt_flat_scene *fs)
     sd.mask_words = (fs->n_items + 63) / 64;
     if (sd.mask_words < 1) sd.mask_words = 1;
 
-    // ---- kd nodes, preorder
-    std::vector<int> order;
-    std::vector<char> seen((size_t)(fs->n_kd_nodes > 0 ? fs->n_kd_nodes : 1), 0);
-    int max_depth = 0;
-    if (fs->n_kd_nodes > 0) {
-        int rc = kd_preorder(fs, 0, 1, order, seen, max_depth);
-        if (rc) return rc;
-        if (max_depth > NDT_KD_STACK)
-            return fail(NDT_E_UNSUPPORTED, "kd-tree depth %d exceeds the traversal stack (%d)", max_depth, NDT_KD_STACK);
-    }
-    sd.kd_depth = max_depth;
+    // ---- kd nodes, preorder (check_scene)
+    const std::vector<int> &order = facts.kd_order;
+    sd.kd_depth = facts.kd_depth;
     // Item sets (ndt_device.hpp:trace_kd): with at most 64 items and every list ascending in item number -- the reference's
     // kd builder keeps the scene's object order in every leaf -- a leaf record carries its items as a 64-bit set.  Any other
     // scene of up to 256 items takes the kernels with a four-word mask, which read the lists.
     bool item_sets = sd.mask_words == 1 && ctx->item_sets;
     if (item_sets) {
-        for (int i = 0; i < fs->n_kd_nodes && item_sets; ++i) {
-            const ndt_flat_kdnode &k = fs->kd_nodes[i];
+        // (the nodes of the tree: one the walk from the root does not reach is not checked, and not read)
+        for (size_t i = 0; i < order.size() && item_sets; ++i) {
+            const ndt_flat_kdnode &k = fs->kd_nodes[order[i]];
             if (k.dim >= 0) continue;
-            if (k.num < 0 || k.first < 0 || (int64_t)k.first + k.num > fs->n_leaf_refs) return fail(NDT_E_INVALID, "kd leaf %d: item range", i);
             for (int j = 0; j < k.num; ++j) {
                 const int id = fs->leaf_refs[k.first + j];
                 if (id < 0 || id >= 64 || (j > 0 && id <= fs->leaf_refs[k.first + j - 1])) item_sets = false;
@@ -810,7 +907,6 @@ int ndt_impl::build_blob(ndt_hip_ctx *ctx, const ndt_flat_scene *fs)
     for (size_t i = 0; i < order.size(); ++i) {
         const ndt_flat_kdnode &k = fs->kd_nodes[order[i]];
         if (k.dim >= 0) {
-            if (new_index[k.left] != (int)i + 1) return fail(NDT_E_INVALID, "internal: preorder numbering");
             b.push_ints(k.dim, new_index[k.right]);
             b.push(k.boundary);
         } else {
@@ -835,11 +931,7 @@ int ndt_impl::build_blob(ndt_hip_ctx *ctx, const ndt_flat_scene *fs)
     std::vector<int> ref_patch;
     sd.off_leaf = b.push_ref_list(leaf_list, ref_patch);
     std::vector<int> inf_list;
-    for (int i = 0; i < fs->n_inf; ++i) {
-        int id = fs->inf_refs[i];
-        if (id < 0 || id >= fs->n_items) return fail(NDT_E_INVALID, "infinite list names object %d (n_items %d)", id, fs->n_items);
-        inf_list.push_back(id);
-    }
+    for (int i = 0; i < fs->n_inf; ++i) inf_list.push_back(fs->inf_refs[i]);
     sd.off_inf = b.push_ref_list(inf_list, ref_patch);
 
     // ---- object headers (filled after params are placed), bounding spheres, root box
@@ -851,12 +943,10 @@ int ndt_impl::build_blob(ndt_hip_ctx *ctx, const ndt_flat_scene *fs)
     sd.off_bs = b.words();
     for (int i = 0; i < fs->n_objects; ++i) {
         const ndt_flat_object &o = fs->objects[i];
-        if (!vec_ok(fs, o.bounds_center_off, 1)) return fail(NDT_E_INVALID, "object %d: bounds centre out of range", i);
         b.push_vec(fs->vecs + o.bounds_center_off, n);
         b.push(o.bounds_radius);
         b.push(o.bounds_radius * o.bounds_radius);      // bounding.c:22
     }
-    if (!vec_ok(fs, fs->bb_lower_off, 1) || !vec_ok(fs, fs->bb_upper_off, 1)) return fail(NDT_E_INVALID, "root box out of range");
     sd.off_bb = b.push_vec(fs->vecs + fs->bb_lower_off, n);
     b.push_vec(fs->vecs + fs->bb_upper_off, n);
 
@@ -866,16 +956,8 @@ int ndt_impl::build_blob(ndt_hip_ctx *ctx, const ndt_flat_scene *fs)
     for (int i = 0; i < fs->n_objects; ++i) {
         const ndt_flat_object &o = fs->objects[i];
         child_first[i] = (int)child_list.size();
-        if (o.type == NDT_OBJ_HCUBE) {
-            if (o.n_obj < 1) return fail(NDT_E_UNSUPPORTED, "object %d: hcube without faces (supply add_faces output)", i);
-            if (o.obj_off < 0 || (int64_t)o.obj_off + o.n_obj > fs->n_obj_refs) return fail(NDT_E_INVALID, "object %d: child range", i);
-            for (int k = 0; k < o.n_obj; ++k) {
-                int c = fs->obj_refs[o.obj_off + k];
-                if (c < 0 || c >= fs->n_objects || fs->objects[c].type == NDT_OBJ_HCUBE)
-                    return fail(NDT_E_INVALID, "object %d: bad nested primitive %d", i, c);
-                child_list.push_back(c);
-            }
-        }
+        if (o.type == NDT_OBJ_HCUBE)
+            for (int k = 0; k < o.n_obj; ++k) child_list.push_back(fs->obj_refs[o.obj_off + k]);
     }
     sd.off_child = b.push_ref_list(child_list, ref_patch);
 
@@ -889,10 +971,6 @@ int ndt_impl::build_blob(ndt_hip_ctx *ctx, const ndt_flat_scene *fs)
     sd.off_params = b.words();
     for (int i = 0; i < fs->n_objects; ++i) {
         const ndt_flat_object &o = fs->objects[i];
-        if (o.type < 0 || o.type >= NDT_OBJ_TYPE_COUNT) return fail(NDT_E_UNSUPPORTED, "object %d: unknown type %d", i, o.type);
-        if (!vec_ok(fs, o.pos_off, o.n_pos) || !vec_ok(fs, o.dir_off, o.n_dir)) return fail(NDT_E_INVALID, "object %d: vector range", i);
-        if (o.n_size < 0 || o.size_off < 0 || (int64_t)o.size_off + o.n_size > fs->n_sizes) return fail(NDT_E_INVALID, "object %d: size range", i);
-        if (o.n_flag < 0 || o.flag_off < 0 || (int64_t)o.flag_off + o.n_flag > fs->n_flags) return fail(NDT_E_INVALID, "object %d: flag range", i);
         const double *pos = fs->vecs + o.pos_off;
         const double *dir = fs->vecs + o.dir_off;
         const double *size = fs->sizes + o.size_off;
@@ -904,25 +982,19 @@ int ndt_impl::build_blob(ndt_hip_ctx *ctx, const ndt_flat_scene *fs)
         int aux0 = 0, aux1 = 0;
         const int p = b.words() - sd.off_params;
         double tmp[NDT_MAX_DIMS], ax[NDT_MAX_DIMS];
-        auto need = [&](bool ok, const char *what) -> int {
-            return ok ? NDT_OK : fail(NDT_E_INVALID, "object %d: %s", i, what);
-        };
-        int rc = NDT_OK;
+        // (what every case reads of pos / dir / size / flag is there: check_scene, rule 6)
         switch (o.type) {
         case NDT_OBJ_SPHERE:        // sphere.c:18-32 (pow(r,2.0) == r*r)
-            if ((rc = need(o.n_pos >= 1 && o.n_size >= 1, "sphere needs 1 pos, 1 size"))) return rc;
             b.push_vec(pos, n);
             b.push(size[0] * size[0]);
             break;
         case NDT_OBJ_HPLANE:
         case NDT_OBJ_HDISK:
-            if ((rc = need(o.n_pos >= 1 && o.n_dir >= 1 && (o.type == NDT_OBJ_HPLANE || o.n_size >= 1), "hplane/hdisk parameters"))) return rc;
             b.push_vec(pos, n);
             b.push_vec(dir, n);
             b.push(o.type == NDT_OBJ_HDISK ? size[0] : 0.0);
             break;
         case NDT_OBJ_CYLINDER: {    // cylinder.c:22-40
-            if ((rc = need(o.n_pos >= 2 && o.n_size >= 1, "cylinder needs 2 pos, 1 size"))) return rc;
             h_sub(pos + n, pos, ax, n);
             h_unitize(ax, n);
             b.push_vec(pos, n);
@@ -936,7 +1008,6 @@ int ndt_impl::build_blob(ndt_hip_ctx *ctx, const ndt_flat_scene *fs)
         }
         case NDT_OBJ_HCYLINDER: {   // hcylinder.c:23-54
             const int m = n - 2;
-            if ((rc = need(o.n_pos >= n - 1 && o.n_size >= 1, "hcylinder needs dims-1 pos, 1 size"))) return rc;
             b.push_vec(pos, n);
             b.push(size[0]);
             for (int k = 0; k < m; ++k) {
@@ -952,9 +1023,7 @@ int ndt_impl::build_blob(ndt_hip_ctx *ctx, const ndt_flat_scene *fs)
             break;
         }
         case NDT_OBJ_ORTHOTOPE: {   // orthotope.c:23-54
-            if ((rc = need(o.n_flag >= 1 && o.n_pos >= 1, "orthotope needs 1 pos, 1 flag"))) return rc;
             const int m = flag[0];
-            if ((rc = need(m >= 0 && m <= o.n_dir && m <= n, "orthotope flag[0] vs directions"))) return rc;
             b.push_vec(pos, n);
             b.push(0.0);
             for (int k = 0; k < m; ++k) {
@@ -1017,8 +1086,6 @@ int ndt_impl::build_blob(ndt_hip_ctx *ctx, const ndt_flat_scene *fs)
             break;
         }
         case NDT_OBJ_HFACET: {      // hfacet.c:43-87 + the ray-invariant dots of get_barycentric (hfacet.c:176-181)
-            if ((rc = need(o.n_pos >= 3 && o.n_flag >= 1, "hfacet needs 3 pos, 1 flag"))) return rc;
-            if ((rc = need(!flag[0] || o.n_dir >= 3, "hfacet with vertex normals needs 3 dir"))) return rc;
             double edge[3][NDT_MAX_DIMS], uedge0[NDT_MAX_DIMS], perp[NDT_MAX_DIMS];
             for (int k = 0; k < 3; ++k) h_sub(pos + ((k + 1) % 3) * n, pos + k * n, edge[k], n);
             memcpy(uedge0, edge[0], n * sizeof(double));
@@ -1045,7 +1112,6 @@ int ndt_impl::build_blob(ndt_hip_ctx *ctx, const ndt_flat_scene *fs)
             break;
         }
         case NDT_OBJ_FACET: {       // facet.c:42-83
-            if ((rc = need(o.n_pos >= 3 && o.n_dir >= 1, "facet needs 3 pos, 1 dir"))) return rc;
             double edge0[NDT_MAX_DIMS], edge1[NDT_MAX_DIMS], b0[NDT_MAX_DIMS], b1[NDT_MAX_DIMS], angle[3];
             for (int k = 0; k < 3; ++k)
                 angle[k] = h_angle3(pos + ((k + 2) % 3) * n, pos + k * n, pos + ((k + 1) % 3) * n, n);
@@ -1106,14 +1172,10 @@ int ndt_impl::build_blob(ndt_hip_ctx *ctx, const ndt_flat_scene *fs)
     for (int i = 0; i < fs->n_lights; ++i) {
         const ndt_flat_light &l = fs->lights[i];
         double zero[NDT_MAX_DIMS] = { 0 };
-        if (l.type < 0 || l.type > NDT_LIGHT_RECT) return fail(NDT_E_INVALID, "light %d: type %d", i, l.type);
         const bool area = l.type == NDT_LIGHT_DISK || l.type == NDT_LIGHT_RECT;
-        if (area && !vec_ok(fs, l.area_off, 2)) return fail(NDT_E_INVALID, "light %d: area lights need u1 / v1 (scene.c:182-195) in the flat scene", i);
         if (area) has_area_lights = true;
         const bool want_pos = l.type == NDT_LIGHT_POINT || l.type == NDT_LIGHT_SPOT || area;
         const bool want_dir = l.type == NDT_LIGHT_DIRECTIONAL || l.type == NDT_LIGHT_SPOT;
-        if (want_pos && !vec_ok(fs, l.pos_off, 1)) return fail(NDT_E_INVALID, "light %d: position missing", i);
-        if (want_dir && !vec_ok(fs, l.dir_off, 1)) return fail(NDT_E_INVALID, "light %d: direction missing", i);
         if (l.type == NDT_LIGHT_AMBIENT && i < 64) sd.ambient_bits |= 1ull << i;
         b.push_ints(l.type, 0);
         b.push(l.red); b.push(l.green); b.push(l.blue);
@@ -1125,9 +1187,6 @@ int ndt_impl::build_blob(ndt_hip_ctx *ctx, const ndt_flat_scene *fs)
         b.push_vec(area ? fs->vecs + l.area_off + n : zero, n);     // v1
     }
     ctx->has_area_lights = has_area_lights;
-    if (!vec_ok(fs, fs->cam_pos_off, 1) || !vec_ok(fs, fs->cam_img_orig_off, 1) || !vec_ok(fs, fs->cam_dir_x_off, 1) ||
-        !vec_ok(fs, fs->cam_dir_y_off, 1))
-        return fail(NDT_E_INVALID, "camera vectors out of range");
     sd.off_cam = b.push_vec(fs->vecs + fs->cam_pos_off, n);
     b.push_vec(fs->vecs + fs->cam_img_orig_off, n);
     b.push_vec(fs->vecs + fs->cam_dir_x_off, n);
@@ -1144,7 +1203,6 @@ int ndt_impl::build_blob(ndt_hip_ctx *ctx, const ndt_flat_scene *fs)
         b.push(fs->cam_h_fov);
         b.push(fs->cam_v_fov);
         for (int k = 0; k < 5; ++k) {
-            if (offs[k] >= 0 && !vec_ok(fs, offs[k], 1)) return fail(NDT_E_INVALID, "camera vectors out of range");
             if (offs[k] >= 0) b.push_vec(fs->vecs + offs[k], n);
             else for (int c = 0; c < n; ++c) b.push(0.0);
         }
@@ -1230,7 +1288,6 @@ int ndt_impl::build_blob(ndt_hip_ctx *ctx, const ndt_flat_scene *fs)
     ctx->light_types.resize(fs->n_lights);
     for (int i = 0; i < fs->n_lights; ++i) ctx->light_types[i] = fs->lights[i].type;
     light_windows(ctx);         // (sets n_shadow_lights: the non-ambient lights of the largest window)
-    return NDT_OK;
 }
 
 void ndt_impl::light_windows(ndt_hip_ctx *ctx)

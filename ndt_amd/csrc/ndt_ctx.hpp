@@ -317,7 +317,17 @@ void hcube_face_tree(const HullFaces &hf, int n, std::vector<double> &rows, std:
 void hcube_face_groups(const HullFaces &hf, const std::vector<double> &hull_rows, int n, std::vector<double> &clusters, std::vector<int> &table,
                        std::vector<int> &face_set, std::vector<int> &members);
 bool scene_item_boxes(const ndt_flat_scene *fs, int n, std::vector<double> &frame, std::vector<double> &rows, std::vector<char> &has);
-int build_blob(ndt_hip_ctx *ctx, const ndt_flat_scene *fs);
+// What check_scene learns on its way and build_blob needs: the kd nodes in preorder and the tree's depth (root = level 1).
+struct SceneFacts {
+    std::vector<int> kd_order;
+    int kd_depth = 0;
+};
+// Every structural rule of include/ndt_hip.h "What upload accepts", stated once (ndt_hip_check_scene, ndt_hip_upload_scene).
+int check_scene(const ndt_flat_scene *fs, SceneFacts *facts);
+// Lays out a scene check_scene passed; what it decides depends on the context's options alone, and it cannot fail.
+void build_blob(ndt_hip_ctx *ctx, const ndt_flat_scene *fs, const SceneFacts &facts);
+// The context without a scene: have_scene false and every field an upload derives from a scene back at its initial value.
+void drop_scene(ndt_hip_ctx *ctx);
 // splits the uploaded scene's lights into windows of ctx->light_window entries; sets ctx->windows and ctx->n_shadow_lights
 void light_windows(ndt_hip_ctx *ctx);
 // the scene description `sd` with its light section narrowed to window k

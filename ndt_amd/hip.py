@@ -9,7 +9,7 @@ import os
 
 import numpy as np
 
-from .flat_scene import RenderParams, RenderStats, shard_rows
+from .flat_scene import NDT_E_STATE, RenderParams, RenderStats, shard_rows
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("NDT_HIP_LIB") or os.path.join(_HERE, "libndt_hip.so")
@@ -21,7 +21,7 @@ API_SYMBOLS = [
     "ndt_hip_synchronize", "ndt_hip_last_error", "ndt_hip_abi_version", "ndt_hip_hcube_hull_box", "ndt_hip_hcube_face_boxes", "ndt_hip_hcube_face_boxes_all", "ndt_hip_hcube_face_tree", "ndt_hip_hcube_face_groups",
     "ndt_hip_render_depth_device", "ndt_hip_render_depth", "ndt_hip_render_rgba8", "ndt_hip_render_multi_device",
     "ndt_hip_render_multi", "ndt_hip_device_count", "ndt_hip_device", "ndt_hip_set_option", "ndt_hip_multi_path_taken",
-    "ndt_hip_item_boxes", "ndt_hip_render_rgba8_async", "ndt_hip_render_rgba8_wait",
+    "ndt_hip_item_boxes", "ndt_hip_check_scene", "ndt_hip_render_rgba8_async", "ndt_hip_render_rgba8_wait",
     "ndt_hip_fit_spheres", "ndt_hip_fit_launches",
     "ndt_hip_build_kdtree", "ndt_hip_kdtree_fetch", "ndt_hip_kd_launches",
     "ndt_hip_png_bound", "ndt_hip_encode_png_device", "ndt_hip_encode_png", "ndt_hip_render_png",
@@ -106,6 +106,8 @@ def load_library():
     lib.ndt_hip_device.argtypes = [C.c_void_p]
     lib.ndt_hip_multi_path_taken.argtypes = [C.c_void_p]
     lib.ndt_hip_item_boxes.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    if hasattr(lib, "ndt_hip_check_scene"):         # (absent from earlier builds, which profiles/ab_libs.sh loads to compare)
+        lib.ndt_hip_check_scene.argtypes = [C.c_void_p]
     lib.ndt_hip_render_rgba8_async.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.ndt_hip_render_rgba8_wait.argtypes = [C.c_void_p]
     lib.ndt_hip_set_option.argtypes = [C.c_void_p, C.c_char_p, C.c_int64]
@@ -475,6 +477,15 @@ def item_boxes(fs):
     return frame, rows[:n], has[:n].astype(bool)
 
 
+def check_scene(fs):
+    """ndt_hip_check_scene: what ndt_hip_upload_scene accepts (host only, no GPU, no context).  Returns None for a scene upload
+    would take and raises NdtHipError with upload's code and message for one it would refuse."""
+    lib = load_library()
+    rc = lib.ndt_hip_check_scene(fs.byref())
+    if rc != 0:
+        raise NdtHipError(rc, (lib.ndt_hip_last_error() or b"").decode())
+
+
 def hcube_face_boxes(fs, obj):
     """The boxes of the single faces of hcube `obj` in its hull box's frame (host only, no GPU), for an hcube of any number of
     faces: (centre[F,N], half[F,N], possible[F] bool) or None when the hcube gets no face boxes."""
@@ -577,8 +588,15 @@ class NdtHip:
         return int(self.lib.ndt_hip_multi_path_taken(self.ctx))
 
     def upload_scene(self, fs):
+        self.scene = None        # (a refused upload leaves the context without a scene: include/ndt_hip.h "What upload accepts")
         self._check(self.lib.ndt_hip_upload_scene(self.ctx, fs.byref()))
         self.scene = fs          # keep the arrays alive; also gives dims
+
+    def _dims(self):
+        """Dimensions of the uploaded scene; without one, the error the library itself gives a call out of order."""
+        if self.scene is None:
+            raise NdtHipError(NDT_E_STATE, "no scene uploaded")
+        return self.scene.dims
 
     def params(self, width, height, depth, row_begin=0, row_step=1, specular=1, profile=0, aa=None, stereo=0, samples=1):
         p = RenderParams(width, height, depth, int(samples), row_begin, row_step, specular, profile)
@@ -808,7 +826,7 @@ class NdtHip:
         ep = exr_params(pixel)
         if ao is not None and ao is not False:
             ap = ao_params(**({} if ao is True else dict(ao)))
-            cap = exr_ao_bound(width, rows, self.scene.dims, features, pixel, depth_map) if cap is None else int(cap)
+            cap = exr_ao_bound(width, rows, self._dims(), features, pixel, depth_map) if cap is None else int(cap)
             out = np.zeros(max(cap, 1), dtype=np.uint8)
             st = RenderStats()
             self.exr_stats = ExrStats()
@@ -817,7 +835,7 @@ class NdtHip:
                                                        C.byref(self.exr_stats), C.byref(st)))
             return out[:self.exr_stats.file_bytes].tobytes(), st
         if cap is None:
-            cap = exr_features_bound(width, rows, self.scene.dims, features, pixel, depth_map) if features else exr_bound(width, rows, pixel, depth_map)
+            cap = exr_features_bound(width, rows, self._dims(), features, pixel, depth_map) if features else exr_bound(width, rows, pixel, depth_map)
         out = np.zeros(int(cap), dtype=np.uint8)
         st = RenderStats()
         self.exr_stats = ExrStats()
@@ -834,7 +852,7 @@ class NdtHip:
         self.exr_stats keeps the record.  features: ndt_hip_render_ssaa_exr_features, the plain frame's feature channels beside it."""
         p, rows = self._ssaa_params(width, height, depth, kw)
         ep = exr_params(pixel)
-        cap = exr_features_bound(width, rows, self.scene.dims, features, pixel, depth_map) if features else exr_bound(width, rows, pixel, depth_map)
+        cap = exr_features_bound(width, rows, self._dims(), features, pixel, depth_map) if features else exr_bound(width, rows, pixel, depth_map)
         out = np.zeros(cap, dtype=np.uint8)
         st = RenderStats()
         self.exr_stats = ExrStats()
@@ -854,7 +872,7 @@ class NdtHip:
         (row shards, stereo 1 / 2); frames without one primary ray a pixel (aa, samples > 1, anaglyph) are refused."""
         p = self.params(width, height, depth, **kw)
         rows = shard_rows(height, p.row_begin, p.row_step)
-        d = self.scene.dims
+        d = self._dims()
         out = {"id": np.zeros((rows, width), dtype=np.int32), "position": np.zeros((d, rows, width)), "normal": np.zeros((d, rows, width))}
         if rays:
             out["ray_o"], out["ray_v"] = np.zeros((d, rows, width)), np.zeros((d, rows, width))
@@ -1000,7 +1018,7 @@ class NdtHip:
         rows = shard_rows(height, p.row_begin, p.row_step)
         ap = ao_params(samples, radius, seed)
         plane = np.zeros((rows, width), dtype=np.float64)
-        used = np.zeros((max(int(samples), 0), self.scene.dims, rows, width), dtype=np.float64) if dirs else None
+        used = np.zeros((max(int(samples), 0), self._dims(), rows, width), dtype=np.float64) if dirs else None
         st = RenderStats()
         self._check(self.lib.ndt_hip_render_ao(self.ctx, C.byref(p), C.byref(ap), plane.ctypes.data, used.ctypes.data if dirs else None,
                                                C.byref(st)))
@@ -1288,7 +1306,7 @@ class NdtHip:
 
     def trace_rays(self, rays):
         """Batch of trace_kd queries; rays: (n, 2*dims+1) = o, v, dist_limit per row."""
-        d = self.scene.dims
+        d = self._dims()
         n = rays.shape[0]
         o = np.ascontiguousarray(rays[:, :d], dtype=np.float64)
         v = np.ascontiguousarray(rays[:, d:2 * d], dtype=np.float64)
